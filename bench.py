@@ -5,6 +5,8 @@
                                                           clock has settled; any K / W works)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N                              (no launcher: bench.py starts the N ranks itself, _self_launch)
+    python bench.py --full                                (the headline and every figure listed below beside it)
+    python bench.py --dump-outputs DIR                    (also writes what the last timed step returned, as .npy)
 
 One "step" = one pass of the whole hot path (fpc_detect: network, exp-softmax,
 depth-to-space, threshold, greedy NMS, sort, border crop, descriptor sampling) over
@@ -13,7 +15,11 @@ one batch of 32 synthetic 640x480 frames that is already resident in HBM
 (weak scaling; configs[2] = 256 frames over 8 GPUs); the only collective is the
 start-up broadcast of the packed weights.  Prints ONE JSON line on rank 0.
 
-What the line holds besides the contract's fields:
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the cheap facts of
+the set-up (`create`, `weights_broadcast_ms`, `keypoints_per_frame`, ...).  Its timed region carries no HIP events.
+
+With --full the line also holds, from HIP events in the timed steps and passes of their own after
+them:
   roofline          the dominant kernel symbol of the step against its roof, `frac` <= 1 by construction:
                     bound "mfma" (fp32 workloads): achieved = FLOPs the matrix cores EXECUTED per launch (padding
                     included, a Winograd 3x3 at its reduced count) / the launch's duration / the fp32 matrix peak.
@@ -32,6 +38,12 @@ What the line holds besides the contract's fields:
   cpu_baseline      SURVEY 8(d): the torch.nn.functional CPU restatement of the path (oracle/torch_cpu.py + the C
                     oracle's post-processing) on this host: the MEDIAN of three passes over 100 frames (min / max
                     beside it), one thread and batch 32 as side figures; bounded.
+  also              single_context, latency_b1, host_fed, other_workloads, the other fp32 modes, layer_ms_*; the
+                    --no-* options drop single passes of a --full run.
+
+--dump-outputs DIR (rank 0): what Engine.detect would have returned for the timed path's last step -- per frame the
+keypoints' (x, y), confidences, descriptors and candidate counts -- as float32 / float64 .npy files, at most 64 MB in
+all (dump_outputs).  Frames and checkpoint are seeded: the same arguments give the same inputs on every run and build.
 """
 import argparse
 import csv
@@ -610,6 +622,37 @@ def bind_cpu_threads(world):
     return n
 
 
+DUMP_BYTES = 64 << 20
+DUMP_DESC_ROWS = 32768      # a seeded sample of the descriptor rows: all of them are 65 MB for 32 VGA frames
+
+
+def dump_outputs(path, eng, n):
+    """--dump-outputs: the last step's results as a caller of the path receives them (Engine.fetch, which is what
+    Engine.detect returns), the frames' keypoints concatenated in frame order:
+      keypoints_per_frame [n], candidates_per_frame [n]     float32
+      keypoints_xy [K,2] (x, y pixels), keypoints_conf [K]  float32
+      descriptor_rows [S]                                   float64: the rows of `descriptors`, sorted; all K when
+                                                            K <= DUMP_DESC_ROWS, else a sample drawn with seed 0
+      descriptors [S,D]                                     float32 (not written when the descriptor head is off)"""
+    res = eng.fetch(n)
+    out = {"keypoints_per_frame": np.array([len(r[1]) for r in res], np.float32),
+           "candidates_per_frame": np.array([r[3] for r in res], np.float32),
+           "keypoints_xy": np.concatenate([r[0] for r in res]).astype(np.float32),
+           "keypoints_conf": np.concatenate([r[1] for r in res]).astype(np.float32)}
+    if res[0][2] is not None:
+        desc = np.concatenate([r[2] for r in res])
+        k = desc.shape[0]
+        rows = np.arange(k) if k <= DUMP_DESC_ROWS else np.sort(np.random.default_rng(0).choice(k, DUMP_DESC_ROWS, replace=False))
+        out["descriptor_rows"] = rows.astype(np.float64)
+        out["descriptors"] = np.ascontiguousarray(desc[rows], np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -645,7 +688,18 @@ def main():
     ap.add_argument("--only-timed", action="store_true", help="the timed region and nothing else (profiling runs)")
     ap.add_argument("--no-other-workloads", action="store_true",
                     help="skip the bounded passes of BASELINE.json configs[3] / configs[4] reported beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline (HIP events in the timed region, roofline, steady state, "
+                         "one context, latency, the other fp32 modes, configs[3] / configs[4], host-fed rates, CPU "
+                         "baseline); without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step returned (rank 0's batch) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_serial_pass = args.no_host_fed = args.no_alt_pass = True
+        args.no_steady_state = args.no_latency = args.no_other_workloads = args.no_timing_events = True
     if args.only_timed:
         args.no_cpu_baseline = args.no_serial_pass = args.no_host_fed = args.no_alt_pass = True
         args.no_steady_state = args.no_latency = args.no_other_workloads = True
@@ -779,6 +833,8 @@ def main():
     for e_ in engs:
         e_.set_timing(False)
     dt, value_all, per_rank = aggregate_over_ranks(world, my_dt, dt, bcast_ms, args.steps, BATCH)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engs[(args.steps - 1) % len(engs)], BATCH)
 
     # steady state: the same loop for >= 2 s (the K timed steps of the contract last well under DVFS settling time)
     steady = None
@@ -796,7 +852,7 @@ def main():
 
     single = rank == 0 and world == 1
     single_ctx = None
-    if args.contexts > 1 and not args.only_timed:
+    if args.contexts > 1 and args.full and not args.only_timed:
         # the same loop on ONE context with the library's default plan (every rank; not part of `value`)
         e0 = Engine(H, W, max_batch=BATCH, **kw1)
         e0.import_packed(eng.export_packed())

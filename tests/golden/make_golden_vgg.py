@@ -4,10 +4,11 @@ parameters and frames.  The network is the reference's source compiled unmodifie
 libtorch (oracle/Makefile.ref -> oracle/_ref/ref_vgg_forward); this script only writes its input files,
 runs it, and stores what it returns.  Run in the build container (needs /root/reference):
 
-    make -C oracle -f Makefile.ref && python tests/golden/make_golden_vgg.py
+    make -C oracle -f Makefile.ref && python tests/golden/make_golden_vgg.py [48x64]
 
   f7_vgg_32x48.npz  : logits [1,65,4,6] and desc [1,256,4,6] in full, for a 32x48 frame
   f7_vgg_qvga.npz   : strided probes of both maps for a 240x320 frame + checksums
+  f7_vgg_48x64.npz  : logits [1,65,6,8] and desc [1,256,6,8] in full, for a 48x64 frame (argument 48x64: this one alone)
   f7_vgg_names.txt  : SPModel's named_parameters() (name + shape) as the binary prints them
 """
 import os
@@ -57,7 +58,17 @@ def gray(seed, h, w):
     return synth.make_batch(seed, 1, h, w, gray=True)[:, :1].copy()
 
 
-if __name__ == "__main__":
+def write_48x64():
+    """f7_vgg_48x64.npz: the case tests/test_oracle_vs_golden.py also runs the binary on where it is built."""
+    point, desc, _ = run_reference(synth.make_vgg_state_dict(77, 2.5), gray(505, 48, 64))
+    np.savez(os.path.join(HERE, "f7_vgg_48x64.npz"), seed_weights=77, dustbin_bias=2.5, seed_frame=505, h=48, w=64,
+             logits=point, desc=desc)
+    print("F7 48x64", point.shape, desc.shape)
+
+
+if __name__ == "__main__" and sys.argv[1:] == ["48x64"]:
+    write_48x64()
+elif __name__ == "__main__":
     sd = synth.make_vgg_state_dict(31, 3.0)
     fr = gray(400, 32, 48)
     point, desc, names = run_reference(sd, fr)
@@ -76,3 +87,4 @@ if __name__ == "__main__":
              logits_probe=point.ravel()[::7].copy(), desc_probe=desc.ravel()[::11].copy(),
              logits_sum=float(point.astype(np.float64).sum()), desc_abs_sum=float(np.abs(desc).astype(np.float64).sum()))
     print("F7 qvga", point.shape, "logit range", float(point.min()), float(point.max()))
+    write_48x64()

@@ -179,24 +179,27 @@ def test_f7_vgg_network_against_the_reference_binary_outputs(golden_dir):
 
 
 def test_vgg_oracle_against_live_reference_binary(golden_dir):
-    """Where oracle/_ref/ref_vgg_forward exists (built from /root/reference by oracle/Makefile.ref), run the
-    reference itself on a fresh seed and compare."""
+    """The reference itself on a seed of its own (fixture F7 48x64: what oracle/_ref/ref_vgg_forward returned for it)
+    against the oracle; where that binary is built (oracle/Makefile.ref) and runs, also its output of now."""
     import importlib.util
+    g = np.load(os.path.join(golden_dir, "f7_vgg_48x64.npz"))
+    sd = synth.make_vgg_state_dict(int(g["seed_weights"]), float(g["dustbin_bias"]))
+    fr = _gray(int(g["seed_frame"]), int(g["h"]), int(g["w"]))
+    refs = [(g["logits"], g["desc"])]
     binpath = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "ref_vgg_forward")
-    if not os.path.exists(binpath):
-        pytest.skip("oracle/_ref/ref_vgg_forward not built")
-    specm = importlib.util.spec_from_file_location("make_golden_vgg", os.path.join(golden_dir, "make_golden_vgg.py"))
-    mg = importlib.util.module_from_spec(specm)
-    specm.loader.exec_module(mg)
-    sd = synth.make_vgg_state_dict(77, 2.5)
-    fr = _gray(505, 48, 64)
-    try:
-        point, dref, _ = mg.run_reference(sd, fr)
-    except Exception as exc:  # e.g. libtorch missing on the machine running the tests
-        pytest.skip("reference binary did not run: %r" % (exc,))
+    if os.path.exists(binpath):
+        specm = importlib.util.spec_from_file_location("make_golden_vgg", os.path.join(golden_dir, "make_golden_vgg.py"))
+        mg = importlib.util.module_from_spec(specm)
+        specm.loader.exec_module(mg)
+        try:
+            point, dref, _ = mg.run_reference(sd, fr)
+            refs.append((point, dref))
+        except Exception:  # e.g. libtorch missing on the machine running the tests: the stored outputs still hold
+            pass
     prob, desc, logits = oracle.vgg_forward(fr, sd, arch.vgg_state_dict_spec())
-    np.testing.assert_allclose(logits, point, rtol=0, atol=2e-5)
-    np.testing.assert_allclose(desc, dref, rtol=0, atol=2e-6)
+    for point, dref in refs:
+        np.testing.assert_allclose(logits, point, rtol=0, atol=2e-5)
+        np.testing.assert_allclose(desc, dref, rtol=0, atol=2e-6)
 
 
 def _f3b_cases(golden_dir):
