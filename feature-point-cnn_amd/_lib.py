@@ -28,6 +28,7 @@ SYMBOLS = [
     "fpc_detect_u8", "fpc_u8_staging", "fpc_homography_adaptation", "fpc_detect_u8_resized",
     "fpc_sample_descriptors", "fpc_plan_hash", "fpc_broadcast_weights", "fpc_read_activation",
     "fpc_pack_layout_revision", "fpc_check_guards", "fpc_stream_report", "fpc_output_range",
+    "fpc_match_frames", "fpc_first_within_frames",
 ]
 
 ABI_VERSION = 4
@@ -139,6 +140,8 @@ def load():
     l.fpc_output_range.argtypes = [vp, ci, vp, vp, vp]
     l.fpc_match.argtypes = [vp, vp, ci, vp, ci, ci, ctypes.c_float, vp, vp]
     l.fpc_first_within.argtypes = [vp, vp, ci, vp, ci, ctypes.c_float, vp]
+    l.fpc_match_frames.argtypes = [vp, ci, ci, vp, vp, ci, ctypes.c_float, ctypes.c_float, vp, vp]
+    l.fpc_first_within_frames.argtypes = [vp, ci, vp, vp, ctypes.c_float, vp]
     l.fpc_sample_descriptors.argtypes = [vp, vp, vp, ci, vp]
     l.fpc_read_activation.argtypes = [vp, ctypes.c_char_p, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     l.fpc_plan_hash.argtypes = [vp]

@@ -33,6 +33,7 @@
 #include "kernels_misc.h"
 #include "queue_map.h"
 #include "match.h"
+#include "match_frames.h"
 #include "homography.h"
 #include "weights.h"
 
@@ -556,6 +557,12 @@ struct fpc_ctx {
   unsigned long long* sort_scratch;
   int32_t* nms_aux = nullptr;  // [B][NMS_AUX_INTS] (kernels_misc.h: nms_chunk_sort_kernel)
   unsigned long long *rowbest, *colbest;  // descriptor matching workspace, `cap` entries each
+  // batched matching (fpc_match_frames / fpc_first_within_frames): norms [(B + 1)][cap], top-2 [B][cap][2],
+  // column minima [B][cap] -- carved behind the buffers above (null where descriptors are off)
+  float* mf_norms = nullptr;
+  unsigned long long *mf_top2 = nullptr, *mf_colbest = nullptr;
+  int pts_n = 0;                     // frames of the last call that produced keypoints (fpc_detect*, fpc_get_points)
+  bool pts_desc = false;             // ... and whether it sampled their descriptors
 
   float* u8stage = nullptr;          // fpc_detect_u8: converted frames [B,cin,H,W], allocated on first use
   char* ha_ws = nullptr;             // fpc_homography_adaptation: workspace, allocated on first use
@@ -1348,6 +1355,8 @@ static int build_vgg_plan(fpc_ctx* c) {
   const size_t o_sort = cv.take<unsigned long long>((size_t)B * c->sort_cap);
   const size_t o_aux = cv.take<int32_t>((size_t)B * NMS_AUX_INTS);
   const size_t o_rowbest = cv.take<unsigned long long>(c->cap), o_colbest = cv.take<unsigned long long>(c->cap);
+  const size_t o_mfn = cv.take<float>((size_t)(B + 1) * c->cap), o_mft = cv.take<unsigned long long>((size_t)B * c->cap * 2);
+  const size_t o_mfc = cv.take<unsigned long long>((size_t)B * c->cap);
   cv.finish();
   c->slab_bytes = cv.off;
   if (hipMalloc((void**)&c->slab, c->slab_bytes) != hipSuccess) {
@@ -1373,6 +1382,9 @@ static int build_vgg_plan(fpc_ctx* c) {
   c->nms_aux = reinterpret_cast<int32_t*>(c->slab + o_aux);
   c->rowbest = reinterpret_cast<unsigned long long*>(c->slab + o_rowbest);
   c->colbest = reinterpret_cast<unsigned long long*>(c->slab + o_colbest);
+  c->mf_norms = F(o_mfn);
+  c->mf_top2 = reinterpret_cast<unsigned long long*>(c->slab + o_mft);
+  c->mf_colbest = reinterpret_cast<unsigned long long*>(c->slab + o_mfc);
 
   size_t bo = BLOB_HEADER_FLOATS;
   c->ops.clear();
@@ -1560,6 +1572,9 @@ static int build_plan(fpc_ctx* c) {
   const size_t o_sort = cv.take<unsigned long long>((size_t)B * c->sort_cap);
   const size_t o_aux = cv.take<int32_t>((size_t)B * NMS_AUX_INTS);
   const size_t o_rowbest = cv.take<unsigned long long>(c->cap), o_colbest = cv.take<unsigned long long>(c->cap);
+  const size_t o_mfn = cv.take<float>(de ? (size_t)(B + 1) * c->cap : 64);
+  const size_t o_mft = cv.take<unsigned long long>(de ? (size_t)B * c->cap * 2 : 64);
+  const size_t o_mfc = cv.take<unsigned long long>(de ? (size_t)B * c->cap : 64);
   cv.finish();
   c->slab_bytes = cv.off;
   if (hipMalloc((void**)&c->slab, c->slab_bytes) != hipSuccess) {
@@ -1589,6 +1604,9 @@ static int build_plan(fpc_ctx* c) {
   c->nms_aux = reinterpret_cast<int32_t*>(c->slab + o_aux);
   c->rowbest = reinterpret_cast<unsigned long long*>(c->slab + o_rowbest);
   c->colbest = reinterpret_cast<unsigned long long*>(c->slab + o_colbest);
+  c->mf_norms = F(o_mfn);
+  c->mf_top2 = reinterpret_cast<unsigned long long*>(c->slab + o_mft);
+  c->mf_colbest = reinterpret_cast<unsigned long long*>(c->slab + o_mfc);
 
   // ---- ops
   size_t bo = BLOB_HEADER_FLOATS;  // blob offset in floats (the tag of the packed format comes first)
@@ -3579,7 +3597,13 @@ int fpc_detect(fpc_ctx* c, const float* frames, int n) {
   HIPCHECK(hipSetDevice(c->cfg.device));
   const bool de = c->cfg.descriptor_enabled != 0;
   if (c->split_f16) HIPCHECK(hipMemsetAsync(c->status + 1, 0, sizeof(int32_t), c->stream));
-  return for_each_sub(c, n, [&](const Sub& sb) { run_path(c, frames, sb, de, 1); });
+  c->pts_n = 0;
+  const int rc = for_each_sub(c, n, [&](const Sub& sb) { run_path(c, frames, sb, de, 1); });
+  if (rc == FPC_OK) {
+    c->pts_n = n;
+    c->pts_desc = de;
+  }
+  return rc;
 }
 
 int fpc_detect_u8(fpc_ctx* c, const uint8_t* frames, int n, int layout) {
@@ -3717,6 +3741,8 @@ int fpc_get_points(fpc_ctx* c, const float* prob, const float* desc_nchw, int n)
     run_desc(c, all, c->desc_in_nhwc);
   }
   HIPCHECK(hipGetLastError());
+  c->pts_n = n;
+  c->pts_desc = desc_nchw && c->cfg.descriptor_enabled;
   return FPC_OK;
 }
 
@@ -3774,6 +3800,55 @@ int fpc_first_within(fpc_ctx* c, const float* key, int nk, const float* cur, int
   a.q = key; a.t = cur; a.nq = nk; a.nt = nc; a.D = c->D; a.rowbest = nullptr; a.colbest = nullptr; a.first = ws; a.tol2 = tolerance * tolerance;
   hipLaunchKernelGGL(match_gemm_kernel, dim3((nk + 127) / 128, (nc + 127) / 128), dim3(256), 0, c->stream, a);
   hipLaunchKernelGGL(first_finalize_kernel, dim3((nk + 255) / 256), dim3(256), 0, c->stream, ws, nk, first);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+// fpc_match_frames / fpc_first_within_frames: checks shared by both (include/fpc.h)
+static int match_frames_check(fpc_ctx* c, int n, const float* key, const int32_t* nkey) {
+  if (!c->cfg.descriptor_enabled || !c->pts_desc || n < 1 || n > c->pts_n || n > c->B) return FPC_E_INVALID;
+  if (key && (!nkey || (reinterpret_cast<uintptr_t>(key) & 15))) return FPC_E_INVALID;   // rows are read as float4
+  return FPC_OK;
+}
+
+static MatchFramesArgs match_frames_args(fpc_ctx* c, int n, const float* key, const int32_t* nkey) {
+  MatchFramesArgs a{};
+  a.desc = c->desc_out; a.count = c->count; a.key = key; a.nkey = key ? nkey : nullptr;
+  a.n = n; a.cap = c->cap; a.D = c->D;
+  a.norms = c->mf_norms; a.top2 = c->mf_top2; a.colbest = c->mf_colbest;
+  return a;
+}
+
+int fpc_match_frames(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey, int cross_check,
+                     float max_dist, float ratio, int32_t* match, float* dist) {
+  if (!c || !match || (pairing != FPC_PAIR_KEY && pairing != FPC_PAIR_PREVIOUS) || !(max_dist >= 0.f) ||
+      !(ratio >= 0.f && ratio <= 1.f) || (pairing == FPC_PAIR_KEY && !key))
+    return FPC_E_INVALID;
+  if (int rc = match_frames_check(c, n, key, nkey)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  MatchFramesArgs a = match_frames_args(c, n, key, nkey);
+  a.pairing = pairing;
+  a.cross_check = cross_check != 0;
+  if (a.cross_check)
+    HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * n * c->cap, c->stream));
+  hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, n + 1), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(match_frames_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, n), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(match_frames_finalize_kernel, dim3((c->cap + 255) / 256, n), dim3(256), 0, c->stream, a, max_dist,
+                     ratio, match, dist);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_first_within_frames(fpc_ctx* c, int n, const float* key, const int32_t* nkey, float tolerance, int32_t* first) {
+  if (!c || !first || !key || !nkey || !(tolerance >= 0.f)) return FPC_E_INVALID;
+  if (int rc = match_frames_check(c, n, key, nkey)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  MatchFramesArgs a = match_frames_args(c, n, key, nkey);
+  a.first_mode = 1;
+  a.tol2 = tolerance * tolerance;
+  a.first = first;
+  hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, n + 1), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(match_frames_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, n), dim3(256), 0, c->stream, a);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }

@@ -390,6 +390,102 @@ class Engine:
         self.sync()
         return out.cpu().numpy()
 
+    # -- the same rules over the last detect's batch, on the device (fpc_match_frames / fpc_first_within_frames) ----
+    PAIRINGS = {"key": 0, "previous": 1}     # FPC_PAIR_KEY / FPC_PAIR_PREVIOUS (include/fpc.h)
+
+    def _results_view(self):
+        """(desc [B,cap,D], count [B]) aliasing the library's device results (fpc_results)."""
+        cap, dd, b = self.capacity, self.desc_dim, self.max_batch
+        desc = torch.as_tensor(_DevArray(self._res.desc, b * cap * dd * 4), device=self.torch_device)
+        count = torch.as_tensor(_DevArray(self._res.count, b * 4), device=self.torch_device)
+        return desc.view(torch.float32).view(b, cap, dd), count.view(torch.int32)
+
+    def keep_frame(self, f):
+        """A device copy of frame f's descriptors [cap,D] and of its device count [1] (int32), ordered on the ctx stream
+        behind the last detect: the next call's key, with no host round trip."""
+        if not self.descriptor_enabled or not 0 <= f < self.max_batch:
+            raise ValueError("keep_frame needs descriptors and 0 <= f < max_batch")
+        desc, count = self._results_view()
+        with torch.cuda.stream(self.torch_stream()):
+            return desc[f].clone(), count[f:f + 1].clone()
+
+    def _key(self, key):
+        """key -> (descriptors, device count) on the device, or (None, None).  A (desc, count) pair (keep_frame) is
+        used as it is; a host array or tensor [k,D] is uploaded together with a device count k."""
+        if key is None:
+            return None, None
+        if isinstance(key, tuple):
+            d, c = key
+            if d.device != self.torch_device or d.dtype != torch.float32 or d.dim() != 2 or d.shape[1] != self.desc_dim \
+                    or c.device != self.torch_device or c.dtype != torch.int32:
+                raise ValueError("a (desc, count) key must be device tensors float32 [k,%d] and int32 [1]" % self.desc_dim)
+            return d.contiguous(), c
+        d = self._desc(key)
+        return d, torch.tensor([d.shape[0]], dtype=torch.int32, device=self.torch_device)
+
+    def _enqueue(self, call):
+        """Runs `call` on the ctx stream ordered after the caller's current torch stream (and the caller's stream after
+        it): GPU-side waits only, no host synchronisation."""
+        cur, st = torch.cuda.current_stream(self.torch_device), self.torch_stream()
+        st.wait_stream(cur)
+        call()
+        cur.wait_stream(st)
+
+    def match_frames_async(self, n, key=None, pairing="key", cross_check=True, max_dist=0.0, ratio=0.0):
+        """fpc_match_frames: every frame of the last detect against the key set ("key") or its predecessor in the batch
+        ("previous"; frame 0 against the key, or nothing without one) -> (match int32 [n,cap], dist float32 [n,cap]) on
+        the device; rows past a frame's count are -1.  Does not synchronise."""
+        if pairing not in self.PAIRINGS:
+            raise ValueError("pairing must be one of %s, got %r" % (sorted(self.PAIRINGS), pairing))
+        kd, kc = self._key(key)
+        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
+        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device)
+
+        def call():
+            _lib.check(self._l.fpc_match_frames(self._ctx, n, self.PAIRINGS[pairing],
+                                                kd.data_ptr() if kd is not None else None,
+                                                kc.data_ptr() if kc is not None else None, int(bool(cross_check)),
+                                                float(max_dist), float(ratio), m.data_ptr(), d.data_ptr()),
+                       "fpc_match_frames")
+        self._enqueue(call)
+        if kd is not None:      # (the caching allocator must not hand the key's memory out before the ctx stream read it)
+            kd.record_stream(self.torch_stream())
+            kc.record_stream(self.torch_stream())
+        return m, d
+
+    def _frame_counts(self, n):
+        return self._results_view()[1][:n].cpu().numpy()
+
+    def match_frames(self, n, key=None, pairing="key", cross_check=True, max_dist=0.0, ratio=0.0):
+        """match_frames_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        m, d = self.match_frames_async(n, key, pairing, cross_check, max_dist, ratio)
+        self.sync()
+        cnt = self._frame_counts(n)
+        m, d = m.cpu().numpy(), d.cpu().numpy()
+        return [(m[f, :cnt[f]].copy(), d[f, :cnt[f]].copy()) for f in range(n)]
+
+    def first_within_frames_async(self, n, key, tolerance=0.8):
+        """fpc_first_within_frames -> int32 [n,cap] on the device: per key row, the first row of frame f closer than
+        `tolerance`, or -1 (rows past the key's count: -1).  Does not synchronise."""
+        kd, kc = self._key(key)
+        if kd is None:
+            raise ValueError("first_within_frames needs a key set")
+        out = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
+        self._enqueue(lambda: _lib.check(self._l.fpc_first_within_frames(self._ctx, n, kd.data_ptr(), kc.data_ptr(),
+                                                                         float(tolerance), out.data_ptr()),
+                                         "fpc_first_within_frames"))
+        kd.record_stream(self.torch_stream())
+        kc.record_stream(self.torch_stream())
+        return out, kc
+
+    def first_within_frames(self, n, key, tolerance=0.8):
+        """SearchKeyFrameCorrespondence for every frame of the last detect: per frame int32 [nkey]."""
+        out, kc = self.first_within_frames_async(n, key, tolerance)
+        self.sync()
+        nk = min(max(int(kc.cpu()[0]), 0), self.capacity)
+        out = out.cpu().numpy()
+        return [out[f, :nk].copy() for f in range(n)]
+
     # -- timing ----------------------------------------------------------------------
     def check_guards(self):
         """Contexts created with plan_flags=["guard_zones"] (a test facility): waits for the device and returns the number

@@ -250,6 +250,20 @@ def get_best_correspondences(stop_features, features, engine):
     return features[keep], match[keep]
 
 
+def get_best_correspondences_batch(stop_features, engine, n):
+    """get_best_correspondences for every frame of the engine's last detect, in one fpc_match_frames call against the
+    stop frame's descriptors -> per frame (rows [x, y, confidence, descriptor] of that frame that found a mutual nearest
+    neighbour, their indices into `stop_features`)."""
+    matches = engine.match_frames(n, key=np.ascontiguousarray(stop_features[:, 3:], np.float32), pairing="key",
+                                  cross_check=True)
+    out = []
+    for (xy, conf, desc, _), (match, _) in zip(engine.fetch(n, with_desc=True), matches):
+        features = np.hstack((_points_array(xy, conf).T, desc))
+        keep = np.flatnonzero(match >= 0)
+        out.append((features[keep], match[keep]))
+    return out
+
+
 def _points_array(xy, conf):
     pts = np.zeros((3, len(conf)))
     pts[0], pts[1], pts[2] = xy[:, 0], xy[:, 1], conf

@@ -356,6 +356,35 @@ int fpc_match(fpc_ctx* ctx, const float* q_dev, int nq, const float* t_dev, int 
 int fpc_first_within(fpc_ctx* ctx, const float* key_dev, int nk, const float* cur_dev, int nc,
                      float tolerance, int32_t* first_dev);
 
+/* --- the same two rules over a whole batch, straight from the device results -----------------------------------------
+ * Frame f's query set is desc[f][0 .. count[f]) of fpc_results, from the last call that produced keypoints with
+ * descriptors (fpc_detect, fpc_detect_u8*, fpc_get_points with a descriptor map); count[f] is read on the device.
+ * FPC_E_INVALID when n exceeds that call's n, when it produced no descriptors, or with descriptor_enabled = 0.
+ * Train set of frame f:  FPC_PAIR_KEY -- the key set;  FPC_PAIR_PREVIOUS -- frame f-1 of the same results for f >= 1;
+ * frame 0 against the key set, or against nothing when key_dev is NULL (frame-to-frame tracking over a video batch).
+ * Key set: key_dev [nkey][D] fp32 (D = desc_dim: 128, 256 for FPC_ARCH_VGG; 16-byte aligned), *nkey_dev an int32 in
+ * device memory, read on the device and clamped to [0, cap] -- a frame kept from the previous call can be the key
+ * without a host round trip.  nkey_dev is required whenever key_dev is given.
+ *
+ * fpc_match_frames: for every row i < count[f], exactly fpc_match(frame f, train(f), cross_check, max_dist); with
+ * ratio > 0 also Lowe's test d1 < ratio * d2, d2 the distance to the second-nearest train row in (d^2, index) order
+ * (fewer than two train rows: the test fails).  Enabled conditions are ANDed; dist = d1 as in fpc_match.  A row with
+ * no train rows: match -1, dist +inf; rows count[f] <= i < cap: match -1 (dist +inf).  match_dev [n][cap],
+ * dist_dev [n][cap] (may be NULL), cap = fpc_results().capacity.
+ * FPC_E_INVALID also for a NULL ctx / output, a bad pairing, ratio outside [0, 1], max_dist < 0, a NULL key_dev with
+ * FPC_PAIR_KEY.
+ *
+ * fpc_first_within_frames: for every key row j < nkey, fpc_first_within(key, frame f): the first row of frame f closer
+ * than `tolerance`, or -1.  first_dev [n][cap]; rows j >= nkey get -1.  key_dev / nkey_dev required; tolerance >= 0.
+ *
+ * Both: asynchronous on the ctx stream (no host synchronisation, no device-to-host copy; may be enqueued right after
+ * fpc_detect and before the next one), deterministic (bit-identical outputs on repeated calls). */
+enum { FPC_PAIR_KEY = 0, FPC_PAIR_PREVIOUS = 1 };
+int fpc_match_frames(fpc_ctx* ctx, int n, int pairing, const float* key_dev, const int32_t* nkey_dev,
+                     int cross_check, float max_dist, float ratio, int32_t* match_dev, float* dist_dev);
+int fpc_first_within_frames(fpc_ctx* ctx, int n, const float* key_dev, const int32_t* nkey_dev,
+                            float tolerance, int32_t* first_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
