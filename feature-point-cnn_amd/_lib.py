@@ -29,6 +29,7 @@ SYMBOLS = [
     "fpc_sample_descriptors", "fpc_plan_hash", "fpc_broadcast_weights", "fpc_read_activation",
     "fpc_pack_layout_revision", "fpc_check_guards", "fpc_stream_report", "fpc_output_range",
     "fpc_match_frames", "fpc_first_within_frames",
+    "fpc_default_ransac_params", "fpc_ransac_homography", "fpc_homography_frames",
 ]
 
 ABI_VERSION = 4
@@ -70,6 +71,12 @@ class FpcStreamReport(ctypes.Structure):
                 ("process_probe_launches", ctypes.c_int), ("process_inconclusive_rounds", ctypes.c_int),
                 ("process_probe_ms", ctypes.c_float), ("create_probe_rounds", ctypes.c_int),
                 ("create_placement_ms", ctypes.c_float), ("process_registered_streams", ctypes.c_int)]
+
+
+class FpcRansacParams(ctypes.Structure):
+    """fpc_ransac_params (include/fpc.h)."""
+    _fields_ = [("iterations", ctypes.c_int), ("reproj_threshold", ctypes.c_float), ("seed", ctypes.c_uint32),
+                ("refits", ctypes.c_int), ("min_inliers", ctypes.c_int)]
 
 
 class FpcError(RuntimeError):
@@ -142,6 +149,10 @@ def load():
     l.fpc_first_within.argtypes = [vp, vp, ci, vp, ci, ctypes.c_float, vp]
     l.fpc_match_frames.argtypes = [vp, ci, ci, vp, vp, ci, ctypes.c_float, ctypes.c_float, vp, vp]
     l.fpc_first_within_frames.argtypes = [vp, ci, vp, vp, ctypes.c_float, vp]
+    rp = ctypes.POINTER(FpcRansacParams)
+    l.fpc_default_ransac_params.argtypes = [rp]
+    l.fpc_ransac_homography.argtypes = [vp, ci, vp, vp, vp, ci, rp, vp, vp, vp]
+    l.fpc_homography_frames.argtypes = [vp, ci, ci, vp, vp, vp, rp, vp, vp, vp]
     l.fpc_sample_descriptors.argtypes = [vp, vp, vp, ci, vp]
     l.fpc_read_activation.argtypes = [vp, ctypes.c_char_p, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     l.fpc_plan_hash.argtypes = [vp]

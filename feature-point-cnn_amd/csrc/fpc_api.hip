@@ -34,6 +34,7 @@
 #include "queue_map.h"
 #include "match.h"
 #include "match_frames.h"
+#include "ransac_homography.h"
 #include "homography.h"
 #include "weights.h"
 
@@ -561,6 +562,11 @@ struct fpc_ctx {
   // column minima [B][cap] -- carved behind the buffers above (null where descriptors are off)
   float* mf_norms = nullptr;
   unsigned long long *mf_top2 = nullptr, *mf_colbest = nullptr;
+  // RANSAC homographies (fpc_ransac_homography / fpc_homography_frames): pair lists [B][cap] of 16-byte records, the mask
+  // row of every pair [B][cap], pair counts [B], best keys [B] -- carved with or without descriptors
+  float4* hf_pairs = nullptr;
+  int32_t *hf_row = nullptr, *hf_np = nullptr;
+  unsigned long long* hf_best = nullptr;
   int pts_n = 0;                     // frames of the last call that produced keypoints (fpc_detect*, fpc_get_points)
   bool pts_desc = false;             // ... and whether it sampled their descriptors
 
@@ -1357,6 +1363,8 @@ static int build_vgg_plan(fpc_ctx* c) {
   const size_t o_rowbest = cv.take<unsigned long long>(c->cap), o_colbest = cv.take<unsigned long long>(c->cap);
   const size_t o_mfn = cv.take<float>((size_t)(B + 1) * c->cap), o_mft = cv.take<unsigned long long>((size_t)B * c->cap * 2);
   const size_t o_mfc = cv.take<unsigned long long>((size_t)B * c->cap);
+  const size_t o_hfp = cv.take<float4>((size_t)B * c->cap), o_hfr = cv.take<int32_t>((size_t)B * c->cap);
+  const size_t o_hfn = cv.take<int32_t>(B), o_hfb = cv.take<unsigned long long>(B);
   cv.finish();
   c->slab_bytes = cv.off;
   if (hipMalloc((void**)&c->slab, c->slab_bytes) != hipSuccess) {
@@ -1385,6 +1393,10 @@ static int build_vgg_plan(fpc_ctx* c) {
   c->mf_norms = F(o_mfn);
   c->mf_top2 = reinterpret_cast<unsigned long long*>(c->slab + o_mft);
   c->mf_colbest = reinterpret_cast<unsigned long long*>(c->slab + o_mfc);
+  c->hf_pairs = reinterpret_cast<float4*>(c->slab + o_hfp);
+  c->hf_row = reinterpret_cast<int32_t*>(c->slab + o_hfr);
+  c->hf_np = reinterpret_cast<int32_t*>(c->slab + o_hfn);
+  c->hf_best = reinterpret_cast<unsigned long long*>(c->slab + o_hfb);
 
   size_t bo = BLOB_HEADER_FLOATS;
   c->ops.clear();
@@ -1575,6 +1587,8 @@ static int build_plan(fpc_ctx* c) {
   const size_t o_mfn = cv.take<float>(de ? (size_t)(B + 1) * c->cap : 64);
   const size_t o_mft = cv.take<unsigned long long>(de ? (size_t)B * c->cap * 2 : 64);
   const size_t o_mfc = cv.take<unsigned long long>(de ? (size_t)B * c->cap : 64);
+  const size_t o_hfp = cv.take<float4>((size_t)B * c->cap), o_hfr = cv.take<int32_t>((size_t)B * c->cap);
+  const size_t o_hfn = cv.take<int32_t>(B), o_hfb = cv.take<unsigned long long>(B);
   cv.finish();
   c->slab_bytes = cv.off;
   if (hipMalloc((void**)&c->slab, c->slab_bytes) != hipSuccess) {
@@ -1607,6 +1621,10 @@ static int build_plan(fpc_ctx* c) {
   c->mf_norms = F(o_mfn);
   c->mf_top2 = reinterpret_cast<unsigned long long*>(c->slab + o_mft);
   c->mf_colbest = reinterpret_cast<unsigned long long*>(c->slab + o_mfc);
+  c->hf_pairs = reinterpret_cast<float4*>(c->slab + o_hfp);
+  c->hf_row = reinterpret_cast<int32_t*>(c->slab + o_hfr);
+  c->hf_np = reinterpret_cast<int32_t*>(c->slab + o_hfn);
+  c->hf_best = reinterpret_cast<unsigned long long*>(c->slab + o_hfb);
 
   // ---- ops
   size_t bo = BLOB_HEADER_FLOATS;  // blob offset in floats (the tag of the packed format comes first)
@@ -3849,6 +3867,64 @@ int fpc_first_within_frames(fpc_ctx* c, int n, const float* key, const int32_t* 
   a.first = first;
   hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, n + 1), dim3(256), 0, c->stream, a);
   hipLaunchKernelGGL(match_frames_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, n), dim3(256), 0, c->stream, a);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_default_ransac_params(fpc_ransac_params* p) {
+  if (!p) return FPC_E_INVALID;
+  p->iterations = 1024;
+  p->reproj_threshold = 3.0f;
+  p->seed = 0;
+  p->refits = 2;
+  p->min_inliers = 8;
+  return FPC_OK;
+}
+
+static bool ransac_params_ok(const fpc_ransac_params* p) {
+  return p && p->iterations >= 1 && p->iterations <= HF_MAX_ITERATIONS && p->reproj_threshold > 0.f &&
+         p->reproj_threshold < 1e18f && p->refits >= 0 && p->refits <= 4 && p->min_inliers >= 4;
+}
+
+static HfArgs ransac_args(fpc_ctx* c, int n, const fpc_ransac_params* p) {
+  HfArgs a{};
+  a.pairs = c->hf_pairs; a.row = c->hf_row; a.np = c->hf_np; a.best = c->hf_best;
+  a.cap = c->cap; a.n = n;
+  a.T = p->iterations; a.refits = p->refits; a.min_inliers = p->min_inliers;
+  a.thr = p->reproj_threshold; a.seed = p->seed;
+  return a;
+}
+
+// the kernels both entry points share, behind their pack / gather kernel
+static void ransac_launch(fpc_ctx* c, const HfArgs& a, float* H, int32_t* ninliers, uint8_t* inlier, int mstride) {
+  hipLaunchKernelGGL(ransac_score_kernel, dim3((a.T + 255) / 256, a.n), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(ransac_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, H, ninliers, inlier, mstride);
+}
+
+int fpc_ransac_homography(fpc_ctx* c, int n, const float* src_xy, const float* dst_xy, const int32_t* npairs, int stride,
+                          const fpc_ransac_params* p, float* H, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !src_xy || !dst_xy || !npairs || !H || !ninliers || !ransac_params_ok(p)) return FPC_E_INVALID;
+  if (n < 1 || n > c->B || stride < 1 || stride > c->cap) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const HfArgs a = ransac_args(c, n, p);
+  hipLaunchKernelGGL(hf_pack_kernel, dim3((stride + 255) / 256, n), dim3(256), 0, c->stream, a, src_xy, dst_xy, npairs,
+                     stride, inlier);
+  ransac_launch(c, a, H, ninliers, inlier, stride);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_homography_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy, const int32_t* nkey, const int32_t* match,
+                          const fpc_ransac_params* p, float* H, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !match || !H || !ninliers || !ransac_params_ok(p) || (pairing != FPC_PAIR_KEY && pairing != FPC_PAIR_PREVIOUS) ||
+      (pairing == FPC_PAIR_KEY && !key_xy) || (key_xy && !nkey))
+    return FPC_E_INVALID;
+  if (n < 1 || n > c->pts_n || n > c->B) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const HfArgs a = ransac_args(c, n, p);
+  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, pairing, key_xy, nkey, match,
+                     inlier);
+  ransac_launch(c, a, H, ninliers, inlier, c->cap);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }

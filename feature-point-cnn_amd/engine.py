@@ -486,6 +486,107 @@ class Engine:
         out = out.cpu().numpy()
         return [out[f, :nk].copy() for f in range(n)]
 
+    # -- geometric verification: RANSAC homographies on the device (fpc_ransac_homography / fpc_homography_frames) -----
+    def _points_view(self):
+        """(xy [B,cap,2] int32, count [B] int32) aliasing the library's device results (fpc_results)."""
+        cap, b = self.capacity, self.max_batch
+        xy = torch.as_tensor(_DevArray(self._res.xy, b * cap * 2 * 4), device=self.torch_device)
+        count = torch.as_tensor(_DevArray(self._res.count, b * 4), device=self.torch_device)
+        return xy.view(torch.int32).view(b, cap, 2), count.view(torch.int32)
+
+    def keep_frame_points(self, f):
+        """A device copy of frame f's keypoint coordinates xy [cap,2] (int32), ordered on the ctx stream behind the last
+        detect: keep_frame's companion, the key_xy of homography_frames (rows past the frame's count are never referenced
+        by a match table made against keep_frame(f))."""
+        if not 0 <= f < self.max_batch:
+            raise ValueError("keep_frame_points needs 0 <= f < max_batch")
+        with torch.cuda.stream(self.torch_stream()):
+            return self._points_view()[0][f].clone()
+
+    def _ransac_params(self, params):
+        p = _lib.FpcRansacParams()
+        _lib.check(self._l.fpc_default_ransac_params(ctypes.byref(p)), "fpc_default_ransac_params")
+        for k, v in params.items():
+            if k not in ("iterations", "reproj_threshold", "seed", "refits", "min_inliers"):
+                raise TypeError("unknown RANSAC parameter %r" % (k,))
+            setattr(p, k, v)
+        return p
+
+    def _key_xy(self, key_xy):
+        """key_xy -> (xy int32 [k,2], device count) or (None, None).  An (xy, count) pair of device tensors is used as it
+        is; a device tensor or host array [k,2] gets the device count k."""
+        if key_xy is None:
+            return None, None
+        if isinstance(key_xy, tuple):
+            xy, c = key_xy
+            if xy.device != self.torch_device or xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 \
+                    or c.device != self.torch_device or c.dtype != torch.int32:
+                raise ValueError("an (xy, count) key must be device tensors int32 [k,2] and int32 [1]")
+            return xy.contiguous(), c
+        xy = key_xy if isinstance(key_xy, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(key_xy, dtype=np.int32))
+        xy = xy.to(self.torch_device, torch.int32).contiguous()
+        if xy.dim() != 2 or xy.shape[1] != 2:
+            raise ValueError("key_xy must be [k,2]")
+        return xy, torch.tensor([xy.shape[0]], dtype=torch.int32, device=self.torch_device)
+
+    def ransac_homography_async(self, src, dst, npairs, **params):
+        """fpc_ransac_homography: src / dst float32 [n,stride,2] and npairs int32 [n] (device tensors or host arrays) ->
+        device tensors (H float32 [n,3,3] mapping src to dst with H[2,2] = 1, ninliers int32 [n], inlier bool [n,stride]);
+        a failed frame has H = 0 and no inliers.  Parameters: the fields of fpc_ransac_params.  Does not synchronise."""
+        p = self._ransac_params(params)
+        src = torch.as_tensor(src).to(self.torch_device, torch.float32).contiguous()
+        dst = torch.as_tensor(dst).to(self.torch_device, torch.float32).contiguous()
+        npairs = torch.as_tensor(npairs).to(self.torch_device, torch.int32).contiguous()
+        if src.dim() != 3 or src.shape[2] != 2 or dst.shape != src.shape or npairs.shape != (src.shape[0],):
+            raise ValueError("src and dst must be [n,stride,2] and npairs [n]")
+        n, stride = int(src.shape[0]), int(src.shape[1])
+        hm = torch.empty((n, 3, 3), dtype=torch.float32, device=self.torch_device)
+        ni = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
+        mask = torch.empty((n, stride), dtype=torch.uint8, device=self.torch_device)
+        self._enqueue(lambda: _lib.check(self._l.fpc_ransac_homography(
+            self._ctx, n, src.data_ptr(), dst.data_ptr(), npairs.data_ptr(), stride, ctypes.byref(p), hm.data_ptr(),
+            ni.data_ptr(), mask.data_ptr()), "fpc_ransac_homography"))
+        for t in (src, dst, npairs):
+            t.record_stream(self.torch_stream())
+        return hm, ni, mask.view(torch.bool)
+
+    def ransac_homography(self, src, dst, npairs, **params):
+        """ransac_homography_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,stride])."""
+        hm, ni, mask = self.ransac_homography_async(src, dst, npairs, **params)
+        self.sync()
+        return hm.cpu().numpy(), ni.cpu().numpy(), mask.cpu().numpy()
+
+    def homography_frames_async(self, n, match, key_xy=None, pairing="key", **params):
+        """fpc_homography_frames: the pairs (xy[f][i], train_xy[match[f][i]]) of every frame of the last detect, `match`
+        being match_frames_async's table (int32 [n,cap], device) for the same pairing and key, `key_xy` the key frame's
+        coordinates (keep_frame_points) -> device tensors (H [n,3,3], ninliers [n], inlier bool [n,cap] by query row).
+        Does not synchronise."""
+        if pairing not in self.PAIRINGS:
+            raise ValueError("pairing must be one of %s, got %r" % (sorted(self.PAIRINGS), pairing))
+        p = self._ransac_params(params)
+        kx, kc = self._key_xy(key_xy)
+        if match.device != self.torch_device or match.dtype != torch.int32 or tuple(match.shape) != (n, self.capacity):
+            raise ValueError("match must be a device tensor int32 [n,%d]" % self.capacity)
+        match = match.contiguous()
+        hm = torch.empty((n, 3, 3), dtype=torch.float32, device=self.torch_device)
+        ni = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
+        mask = torch.empty((n, self.capacity), dtype=torch.uint8, device=self.torch_device)
+        self._enqueue(lambda: _lib.check(self._l.fpc_homography_frames(
+            self._ctx, n, self.PAIRINGS[pairing], kx.data_ptr() if kx is not None else None,
+            kc.data_ptr() if kc is not None else None, match.data_ptr(), ctypes.byref(p), hm.data_ptr(), ni.data_ptr(),
+            mask.data_ptr()), "fpc_homography_frames"))
+        match.record_stream(self.torch_stream())
+        if kx is not None:
+            kx.record_stream(self.torch_stream())
+            kc.record_stream(self.torch_stream())
+        return hm, ni, mask.view(torch.bool)
+
+    def homography_frames(self, n, match, key_xy=None, pairing="key", **params):
+        """homography_frames_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,cap])."""
+        hm, ni, mask = self.homography_frames_async(n, match, key_xy, pairing, **params)
+        self.sync()
+        return hm.cpu().numpy(), ni.cpu().numpy(), mask.cpu().numpy()
+
     # -- timing ----------------------------------------------------------------------
     def check_guards(self):
         """Contexts created with plan_flags=["guard_zones"] (a test facility): waits for the device and returns the number

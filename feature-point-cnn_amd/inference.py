@@ -264,6 +264,26 @@ def get_best_correspondences_batch(stop_features, engine, n):
     return out
 
 
+def estimate_homographies_batch(engine, n, stop_features, cross_check=True, max_dist=0.0, ratio=0.0, **ransac_params):
+    """Geometric verification of every frame of the engine's last detect against the stop frame, on the device:
+    fpc_match_frames against the stop frame's descriptors, then fpc_homography_frames on that match table and the stop
+    frame's coordinates, with no host round trip in between -> per frame (H float32 [3,3] mapping the frame's pixels to the
+    stop frame's, all zeros when the frame failed; the rows [x, y, confidence, descriptor] of the frame that are inliers of
+    H; their indices into `stop_features`).  `ransac_params`: the fields of fpc_ransac_params."""
+    key = np.ascontiguousarray(stop_features[:, 3:], np.float32)
+    key_xy = np.ascontiguousarray(np.rint(stop_features[:, :2]), np.int32)
+    match, _ = engine.match_frames_async(n, key=key, pairing="key", cross_check=cross_check, max_dist=max_dist, ratio=ratio)
+    hm, _, mask = engine.homography_frames_async(n, match, key_xy=key_xy, pairing="key", **ransac_params)
+    engine.sync()
+    hm, mask, match = hm.cpu().numpy(), mask.cpu().numpy(), match.cpu().numpy()
+    out = []
+    for f, (xy, conf, desc, _) in enumerate(engine.fetch(n, with_desc=True)):
+        features = np.hstack((_points_array(xy, conf).T, desc))
+        keep = np.flatnonzero(mask[f, :len(conf)])
+        out.append((hm[f], features[keep], match[f, keep]))
+    return out
+
+
 def _points_array(xy, conf):
     pts = np.zeros((3, len(conf)))
     pts[0], pts[1], pts[2] = xy[:, 0], xy[:, 1], conf

@@ -385,6 +385,66 @@ int fpc_match_frames(fpc_ctx* ctx, int n, int pairing, const float* key_dev, con
 int fpc_first_within_frames(fpc_ctx* ctx, int n, const float* key_dev, const int32_t* nkey_dev,
                             float tolerance, int32_t* first_dev);
 
+/* Geometric verification: a RANSAC homography per frame from point correspondences, on the device.  The reference has
+ * only the synthesis side (python/src/homographies.py: sample_homography, warp_points, flat2mat, invert_homography); the
+ * estimation it would leave to cv2.findHomography(RANSAC), which is not available to this build: the rule below is pinned
+ * by planted homographies and by a float64 restatement (tests/test_homography_ransac.py), not against OpenCV.
+ *
+ * fpc_ransac_homography: explicit correspondences.  src_xy_dev / dst_xy_dev float32 [n][stride][2] (x, y); npairs_dev
+ * int32 [n], read on the device and clamped to [0, stride]; 1 <= stride <= fpc_results().capacity; 1 <= n <= max_batch.
+ * fpc_homography_frames: straight from the device results of the last call that produced keypoints and a match table
+ * of fpc_match_frames (same n, same pairing, same key): the pairs of frame f are (xy[f][i], train_xy[match[f][i]]) for the
+ * rows i < count[f] with 0 <= match[f][i] < the train set's row count, in ascending i (other rows are not pairs).
+ * train_xy = key_xy_dev int32 [nkey][2] with nkey_dev clamped to [0, cap] (FPC_PAIR_KEY), or xy[f-1] (FPC_PAIR_PREVIOUS;
+ * frame 0 against the key, or failing when key_xy_dev is NULL).  Needs no descriptors.
+ *
+ * Outputs: H_dev float32 [n][9], ninliers_dev int32 [n], inlier_dev uint8 [n][stride] (explicit; indexed by the pair) or
+ * [n][cap] (frames; indexed by the query row i), may be NULL.
+ *  - Direction: H is row-major with H[8] == 1 and maps a query (src) pixel (x, y, 1) to its train (dst) pixel.
+ *  - Inliers: a pair is an inlier of H when |H.src - dst|_2 < reproj_threshold (evaluated without the division, in fp64
+ *    from the fp32 H that is returned).  ninliers and inlier are those of the returned H.
+ *  - Failure: a frame with fewer than 4 pairs, with no non-degenerate sample, or with fewer than min_inliers inliers after
+ *    the last refit gets nine zeros, ninliers = 0 and an all-zero mask.  Mask entries past a frame's pair count (explicit)
+ *    or of rows that are not pairs (frames) are 0.
+ *  - Sampling: with mix(a): a ^= a >> 16; a *= 0x7feb352d; a ^= a >> 15; a *= 0x846ca68b; a ^= a >> 16 on uint32 (wrapping),
+ *    draw k = 0 .. 15 of hypothesis t of frame f over M pairs is
+ *        r = mix(seed ^ mix((f * 4096 + t) * 16 + k)) % M.
+ *    The draws are taken in order of k; a draw equal to an index already taken is skipped; the first 4 distinct indices
+ *    are the sample (in that order), and a hypothesis that has not found 4 within its 16 draws is degenerate.
+ *  - Degenerate samples: three of the 4 src or of the 4 dst points collinear (doubled triangle area below 0.5 px^2), a
+ *    non-finite H, or an H that cannot be scaled to H[8] = 1 (|h8| <= 1e-12 max|h|).  They score 0 and are never chosen.
+ *  - Scoring: the 4-point H is solved exactly in fp64 and applied in fp32; hypothesis t counts the pairs with
+ *    |(h1.p, h2.p) - w (u, v)|^2 < threshold^2 w^2 and w = h3.p of the sign it has at the sample's first point.
+ *  - Selection: the largest count; ties go to the lower t (an integer maximum: independent of execution order).
+ *  - Refit, `refits` times: the inliers of the current H (the rule under "Inliers") are translated to their centroid and
+ *    scaled to an RMS distance of sqrt(2), src and dst each (Hartley); the 8 x 8 normal equations of the rows
+ *    [x y 1 0 0 0 -ux -uy | u], [0 0 0 x y 1 -vx -vy | v] are summed in fp64 in a fixed order (no floating-point atomics)
+ *    and solved by elimination with partial pivoting; the result is denormalised, scaled to H[8] = 1 and rounded to fp32.
+ *    Fewer than 4 inliers, a point set of zero spread or a singular system keeps the previous H and ends the refits.
+ *  - Determinism: the same seed and the same inputs give bit-identical outputs, and the two entry points give
+ *    bit-identical outputs on equal pair lists.
+ *  - Execution: asynchronous on the ctx stream, no host synchronisation, no device-to-host copy; may be enqueued right
+ *    behind fpc_match_frames and before the next fpc_detect.  The workspace is the ctx's: nothing is allocated per call.
+ * FPC_E_INVALID (nothing is written): a NULL ctx / params / input / H_dev / ninliers_dev, iterations outside 1 .. 4096,
+ * reproj_threshold not > 0, refits outside 0 .. 4, min_inliers < 4, n < 1, n above max_batch (explicit) or above the
+ * frames of the last call that produced keypoints (frames), stride outside 1 .. capacity, a bad pairing, FPC_PAIR_KEY
+ * without key_xy_dev, key_xy_dev without nkey_dev. */
+typedef struct fpc_ransac_params {
+  int      iterations;        /* T hypotheses per frame, 1 .. 4096                                   */
+  float    reproj_threshold;  /* pixels, > 0                                                         */
+  uint32_t seed;              /* same seed + same inputs -> bit-identical outputs                    */
+  int      refits;            /* 0 .. 4 least-squares refits on the inlier set after the best sample */
+  int      min_inliers;       /* >= 4; fewer inliers after the last refit -> the frame fails         */
+} fpc_ransac_params;
+/* 1024 iterations, 3.0 px, seed 0, 2 refits, 8 inliers. */
+int fpc_default_ransac_params(fpc_ransac_params* params);
+int fpc_ransac_homography(fpc_ctx* ctx, int n, const float* src_xy_dev, const float* dst_xy_dev, const int32_t* npairs_dev,
+                          int stride, const fpc_ransac_params* params, float* H_dev, int32_t* ninliers_dev,
+                          uint8_t* inlier_dev);
+int fpc_homography_frames(fpc_ctx* ctx, int n, int pairing, const int32_t* key_xy_dev, const int32_t* nkey_dev,
+                          const int32_t* match_dev, const fpc_ransac_params* params, float* H_dev, int32_t* ninliers_dev,
+                          uint8_t* inlier_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
