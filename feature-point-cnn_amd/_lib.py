@@ -30,6 +30,8 @@ SYMBOLS = [
     "fpc_pack_layout_revision", "fpc_check_guards", "fpc_stream_report", "fpc_output_range",
     "fpc_match_frames", "fpc_first_within_frames",
     "fpc_default_ransac_params", "fpc_ransac_homography", "fpc_homography_frames",
+    "fpc_bank_create", "fpc_bank_destroy", "fpc_bank_get", "fpc_bank_store", "fpc_bank_store_rows", "fpc_bank_clear",
+    "fpc_match_bank", "fpc_homography_bank",
 ]
 
 ABI_VERSION = 4
@@ -77,6 +79,15 @@ class FpcRansacParams(ctypes.Structure):
     """fpc_ransac_params (include/fpc.h)."""
     _fields_ = [("iterations", ctypes.c_int), ("reproj_threshold", ctypes.c_float), ("seed", ctypes.c_uint32),
                 ("refits", ctypes.c_int), ("min_inliers", ctypes.c_int)]
+
+
+BANK_MAX_SLOTS = 1024         # include/fpc.h FPC_BANK_MAX_SLOTS
+
+
+class FpcBankView(ctypes.Structure):
+    """fpc_bank_view (include/fpc.h)."""
+    _fields_ = [("desc", ctypes.c_void_p), ("xy", ctypes.c_void_p), ("count", ctypes.c_void_p), ("slots", ctypes.c_int),
+                ("rows", ctypes.c_int), ("desc_dim", ctypes.c_int), ("chunk", ctypes.c_int), ("bytes", ctypes.c_size_t)]
 
 
 class FpcError(RuntimeError):
@@ -153,6 +164,14 @@ def load():
     l.fpc_default_ransac_params.argtypes = [rp]
     l.fpc_ransac_homography.argtypes = [vp, ci, vp, vp, vp, ci, rp, vp, vp, vp]
     l.fpc_homography_frames.argtypes = [vp, ci, ci, vp, vp, vp, rp, vp, vp, vp]
+    l.fpc_bank_create.argtypes = [vp, ci, ci]
+    l.fpc_bank_destroy.argtypes = [vp]
+    l.fpc_bank_get.argtypes = [vp, ctypes.POINTER(FpcBankView)]
+    l.fpc_bank_store.argtypes = [vp, ci, ci]
+    l.fpc_bank_store_rows.argtypes = [vp, ci, vp, vp, vp]
+    l.fpc_bank_clear.argtypes = [vp, ci]
+    l.fpc_match_bank.argtypes = [vp, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp]
+    l.fpc_homography_bank.argtypes = [vp, ci, vp, vp, rp, vp, vp, vp]
     l.fpc_sample_descriptors.argtypes = [vp, vp, vp, ci, vp]
     l.fpc_read_activation.argtypes = [vp, ctypes.c_char_p, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     l.fpc_plan_hash.argtypes = [vp]

@@ -34,6 +34,7 @@
 #include "queue_map.h"
 #include "match.h"
 #include "match_frames.h"
+#include "match_bank.h"
 #include "ransac_homography.h"
 #include "homography.h"
 #include "weights.h"
@@ -567,6 +568,12 @@ struct fpc_ctx {
   float4* hf_pairs = nullptr;
   int32_t *hf_row = nullptr, *hf_np = nullptr;
   unsigned long long* hf_best = nullptr;
+  // key-frame bank (fpc_bank_*, fpc_match_bank, fpc_homography_bank): one allocation of its own, made by fpc_bank_create --
+  // storage, per-slot norms and fpc_match_bank's workspace, carved with canary zones in a FPC_PLAN_GUARD_ZONES context
+  char* bank_slab = nullptr;
+  size_t bank_bytes = 0;
+  BankArgs bank{};
+  std::vector<std::pair<size_t, size_t>> bank_guards;          // (offset, bytes) of the canary zones in bank_slab
   int pts_n = 0;                     // frames of the last call that produced keypoints (fpc_detect*, fpc_get_points)
   bool pts_desc = false;             // ... and whether it sampled their descriptors
 
@@ -3186,6 +3193,7 @@ void fpc_destroy(fpc_ctx* c) {
     qmap::release_owner(c);
   }
   if (c->slab) hipFree(c->slab);
+  if (c->bank_slab) hipFree(c->bank_slab);
   if (c->blob) hipFree(c->blob);
   if (c->u8stage) hipFree(c->u8stage);
   if (c->ha_ws) hipFree(c->ha_ws);
@@ -3291,6 +3299,10 @@ int fpc_check_guards(fpc_ctx* c, long long* bad_words) {
   for (const auto& z : c->guards) {
     const size_t n = z.second / 4;
     guard_count_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<const uint32_t*>(c->slab + z.first), n, GUARD_PATTERN, d);
+  }
+  for (const auto& z : c->bank_guards) {      // the key-frame bank's zones (fpc_bank_create)
+    const size_t n = z.second / 4;
+    guard_count_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<const uint32_t*>(c->bank_slab + z.first), n, GUARD_PATTERN, d);
   }
   unsigned long long h = 0;
   const hipError_t e1 = hipStreamSynchronize(c->stream);
@@ -3923,7 +3935,159 @@ int fpc_homography_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy,
   HIPCHECK(hipSetDevice(c->cfg.device));
   const HfArgs a = ransac_args(c, n, p);
   hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, pairing, key_xy, nkey, match,
-                     inlier);
+                     inlier, HfBank{});
+  ransac_launch(c, a, H, ninliers, inlier, c->cap);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+// ---- key-frame bank (include/fpc.h; kernels in match_bank.h) -------------------------------------------------------------
+// fpc_match_bank's score pass keeps top-2 keys (16 B) per query row and a column minimum (8 B) per bank row for every
+// (frame, slot) pair in flight; the slots run in chunks so that this stays within BANK_WS_BUDGET (one slot at the least).
+constexpr size_t BANK_WS_BUDGET = (size_t)256 << 20;
+
+int fpc_bank_create(fpc_ctx* c, int slots, int rows) {
+  if (!c || c->bank_slab || !c->cfg.descriptor_enabled || slots < 1 || slots > FPC_BANK_MAX_SLOTS || rows < 1 || rows > c->cap)
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const size_t B = c->B, cap = c->cap, D = c->D;
+  const size_t per_slot = B * (cap * 16 + (size_t)rows * 8);
+  const int chunk = (int)std::min<size_t>(slots, std::max<size_t>(1, BANK_WS_BUDGET / per_slot));
+  Carver cv;
+  std::vector<std::pair<size_t, size_t>> zones;
+  cv.zones = &zones;
+  cv.guard = c->guard_zones ? GUARD_BYTES : 0;
+  const size_t o_desc = cv.take<float>((size_t)slots * rows * D), o_xy = cv.take<int32_t>((size_t)slots * rows * 2);
+  const size_t o_cnt = cv.take<int32_t>(slots), o_nrm = cv.take<float>((size_t)slots * rows);
+  const size_t o_top = cv.take<unsigned long long>(B * chunk * cap * 2), o_col = cv.take<unsigned long long>(B * chunk * rows);
+  const size_t o_sc = cv.take<int32_t>(B * slots), o_best = cv.take<int32_t>(B);
+  char* p = nullptr;
+  HIPCHECK(hipMalloc((void**)&p, cv.off));
+  {
+    hipError_t e = hipMemset(p, 0, cv.off);                     // every slot starts empty
+    if (e == hipSuccess) e = hipDeviceSynchronize();            // (as in fill_guards: the null stream does not order c->stream)
+    for (const auto& z : zones) {
+      const size_t n = z.second / 4;
+      guard_fill_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<uint32_t*>(p + z.first), n, GUARD_PATTERN);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) hipFree(p);
+    HIPCHECK(e);
+  }
+  c->bank_slab = p;
+  c->bank_bytes = cv.off;
+  c->bank_guards = zones;
+  BankArgs& b = c->bank;
+  b.desc = reinterpret_cast<float*>(p + o_desc);
+  b.xy = reinterpret_cast<int32_t*>(p + o_xy);
+  b.count = reinterpret_cast<int32_t*>(p + o_cnt);
+  b.norms = reinterpret_cast<float*>(p + o_nrm);
+  b.top2 = reinterpret_cast<unsigned long long*>(p + o_top);
+  b.colbest = reinterpret_cast<unsigned long long*>(p + o_col);
+  b.score = reinterpret_cast<int32_t*>(p + o_sc);
+  b.best = reinterpret_cast<int32_t*>(p + o_best);
+  b.slots = slots; b.rows = rows; b.D = c->D; b.chunk = chunk;
+  return FPC_OK;
+}
+
+int fpc_bank_destroy(fpc_ctx* c) {
+  if (!c || !c->bank_slab) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  HIPCHECK(hipStreamSynchronize(c->stream));                    // calls that still read the bank
+  HIPCHECK(hipFree(c->bank_slab));
+  c->bank_slab = nullptr;
+  c->bank_bytes = 0;
+  c->bank_guards.clear();
+  c->bank = BankArgs{};
+  return FPC_OK;
+}
+
+int fpc_bank_get(fpc_ctx* c, fpc_bank_view* out) {
+  if (!c || !out || !c->bank_slab) return FPC_E_INVALID;
+  out->desc = c->bank.desc;
+  out->xy = c->bank.xy;
+  out->count = c->bank.count;
+  out->slots = c->bank.slots;
+  out->rows = c->bank.rows;
+  out->desc_dim = c->bank.D;
+  out->chunk = c->bank.chunk;
+  out->bytes = c->bank_bytes;
+  return FPC_OK;
+}
+
+int fpc_bank_store(fpc_ctx* c, int frame, int slot) {
+  if (!c || !c->bank_slab || !c->pts_desc || frame < 0 || frame >= c->pts_n || frame >= c->B || slot < 0 ||
+      slot >= c->bank.slots)
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(bank_store_kernel, dim3((c->bank.rows + 127) / 128), dim3(256), 0, c->stream, c->bank, slot,
+                     c->desc_out + (size_t)frame * c->cap * c->D, c->xy + (size_t)frame * c->cap * 2, c->count + frame, c->cap);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_bank_store_rows(fpc_ctx* c, int slot, const float* desc, const int32_t* xy, const int32_t* n) {
+  if (!c || !c->bank_slab || slot < 0 || slot >= c->bank.slots || !desc || !xy || !n ||
+      (reinterpret_cast<uintptr_t>(desc) & 15))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(bank_store_kernel, dim3((c->bank.rows + 127) / 128), dim3(256), 0, c->stream, c->bank, slot, desc, xy, n,
+                     c->bank.rows);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_bank_clear(fpc_ctx* c, int slot) {
+  if (!c || !c->bank_slab || slot < -1 || slot >= c->bank.slots) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(bank_clear_kernel, dim3((c->bank.slots + 255) / 256), dim3(256), 0, c->stream, c->bank, slot);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_match_bank(fpc_ctx* c, int n, int cross_check, float max_dist, float ratio, int min_score, int32_t* score,
+                   int32_t* best, int32_t* match, float* dist) {
+  if (!c || !c->bank_slab || (!score && !best) || !(max_dist >= 0.f) || !(ratio >= 0.f && ratio <= 1.f) || min_score < 0)
+    return FPC_E_INVALID;
+  if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const BankArgs& b = c->bank;
+  MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
+  a.cross_check = cross_check != 0;
+  // the frames' norms, once for the score pass and the table pass (grid y = n: no key block)
+  hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, n), dim3(256), 0, c->stream, a);
+  HIPCHECK(hipMemsetAsync(b.score, 0, sizeof(int32_t) * n * b.slots, c->stream));
+  for (int s0 = 0; s0 < b.slots; s0 += b.chunk) {
+    const int ns = std::min(b.chunk, b.slots - s0);
+    if (a.cross_check)
+      HIPCHECK(hipMemsetAsync(b.colbest, 0xff, sizeof(unsigned long long) * ((size_t)(n - 1) * b.chunk + ns) * b.rows, c->stream));
+    hipLaunchKernelGGL(bank_score_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, n, ns), dim3(256), 0, c->stream, a, b, s0);
+    hipLaunchKernelGGL(bank_count_kernel, dim3((c->cap + 255) / 256, n, ns), dim3(256), 0, c->stream, a, b, s0, max_dist, ratio);
+  }
+  hipLaunchKernelGGL(bank_select_kernel, dim3(n), dim3(256), 0, c->stream, b, min_score, score, best);
+  if (match || dist) {
+    // the table of frame f against slot best[f]: fpc_match_frames' own kernels with a per-frame key
+    a.key = b.desc; a.key_slot = b.best; a.bank_norms = b.norms; a.bank_count = b.count;
+    a.bank_rows = b.rows; a.bank_slots = b.slots;
+    if (a.cross_check)
+      HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * n * c->cap, c->stream));
+    hipLaunchKernelGGL(match_frames_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, n), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(match_frames_finalize_kernel, dim3((c->cap + 255) / 256, n), dim3(256), 0, c->stream, a, max_dist,
+                       ratio, match, dist);
+  }
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_homography_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const fpc_ransac_params* p, float* H,
+                        int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->bank_slab || !slot || !match || !H || !ninliers || !ransac_params_ok(p)) return FPC_E_INVALID;
+  if (n < 1 || n > c->pts_n || n > c->B) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const HfArgs a = ransac_args(c, n, p);
+  const HfBank hb{slot, c->bank.count, c->bank.rows, c->bank.slots};
+  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
+                     (const int32_t*)nullptr, match, inlier, hb);
   ransac_launch(c, a, H, ninliers, inlier, c->cap);
   HIPCHECK(hipGetLastError());
   return FPC_OK;

@@ -17,6 +17,8 @@
 //                          Column minima for the cross check: 64-bit atomicMin on (d^2 bits, row) per frame, as in
 //                          match.h (exact, order-independent, ties to the lower row).
 //   match_frames_finalize_kernel  cross check, max_dist, ratio test; rows past count[f] -> -1.
+// The strip body (mf_strip), the row norm (mf_row_norm) and the finalize rule (mf_row_ok) are device functions that the
+// key-frame bank (match_bank.h) calls too; with MatchFramesArgs::key_slot the key is chosen per frame from that bank.
 // In first-within mode the key is the query and frame f the train set; the lowest index below the tolerance is a
 // plain minimum, and the strip's workgroup writes the output itself.
 #pragma once
@@ -41,6 +43,14 @@ struct MatchFramesArgs {
   unsigned long long* top2;     // [n][cap][2]     (d^2 bits << 32 | train index), best then second best
   unsigned long long* colbest;  // [n][cap]        (d^2 bits << 32 | query index), pre-filled with ~0
   int32_t* first;               // [n][cap]        first-within output
+  // per-frame key (fpc_match_bank's table pass, match_bank.h): with key_slot != null frame f's train set is slot
+  // key_slot[f] of a key-frame bank -- `key` is the bank's desc [slots][bank_rows][D], its norms and counts are the
+  // bank's own -- and a slot outside [0, bank_slots) is an empty train set.  Null in fpc_match_frames /
+  // fpc_first_within_frames, whose sets are the ones above.
+  const int32_t* key_slot;      // [n]  device
+  const float* bank_norms;      // [slots][bank_rows]
+  const int32_t* bank_count;    // [slots]
+  int bank_rows, bank_slots;
 };
 
 __device__ __forceinline__ int mf_clamp(int v, int cap) { return v < 0 ? 0 : v > cap ? cap : v; }
@@ -66,9 +76,27 @@ __device__ __forceinline__ MfSets mf_sets(const MatchFramesArgs& a, int f) {
   if (a.pairing == 1 && f > 0) {
     s.t = a.desc + (size_t)(f - 1) * a.cap * a.D; s.tn = a.norms + (size_t)(f - 1) * a.cap;
     s.nt = mf_clamp(a.count[f - 1], a.cap);
+  } else if (a.key_slot) {
+    const int sl = a.key_slot[f];
+    const bool in = sl >= 0 && sl < a.bank_slots;
+    s.t = a.key + (in ? (size_t)sl * a.bank_rows * a.D : 0);
+    s.tn = a.bank_norms + (in ? (size_t)sl * a.bank_rows : 0);
+    s.nt = in ? mf_clamp(a.bank_count[sl], a.bank_rows) : 0;
   } else {
     s.t = a.key; s.tn = kn; s.nt = mf_nkey(a);
   }
+  return s;
+}
+
+// lane l / l + 32 of a wave hold the two halves of one row (`row` points at float half * 4 of it): the partial sum of
+// match_gemm_kernel's qn / tn step, then one add across the halves
+__device__ __forceinline__ float mf_row_norm(const float* row, int K8) {
+  float s = 0.f;
+  for (int k8 = 0; k8 < K8; ++k8) {
+    const float4 c = *reinterpret_cast<const float4*>(row + k8 * 8);
+    s += c.x * c.x + c.y * c.y + c.z * c.z + c.w * c.w;     // match_gemm_kernel's qn / tn step
+  }
+  s += __shfl_xor(s, 32);
   return s;
 }
 
@@ -81,27 +109,21 @@ __global__ __launch_bounds__(256) void mf_norms_kernel(const MatchFramesArgs a) 
   const int r = blockIdx.x * 128 + (threadIdx.x >> 6) * 32 + (lane & 31);
   const float* base = f < a.n ? a.desc + (size_t)f * a.cap * a.D : a.key;
   const float* row = base + (size_t)min(r, nr - 1) * a.D + half * 4;
-  float s = 0.f;
-  const int K8 = a.D / 8;
-  for (int k8 = 0; k8 < K8; ++k8) {
-    const float4 c = *reinterpret_cast<const float4*>(row + k8 * 8);
-    s += c.x * c.x + c.y * c.y + c.z * c.z + c.w * c.w;     // match_gemm_kernel's qn / tn step
-  }
-  s += __shfl_xor(s, 32);
+  const float s = mf_row_norm(row, a.D / 8);
   if (half == 0 && r < nr) a.norms[(size_t)f * a.cap + r] = s;
 }
 
-// grid (ceil(cap / 64), n), 256 threads
-__global__ __launch_bounds__(256) void match_frames_kernel(const MatchFramesArgs a) {
+// One workgroup (256 threads), one 64-row strip (rows q0 ..) of one (query set, train set) pair `s`: the body of
+// match_frames_kernel, shared with the key-frame bank's score pass (match_bank.h), which runs it over a third grid
+// dimension.  top2 [..][2], colbest [..], first_out [..]: row 0 of THIS pair's tables.
+__device__ __forceinline__ void mf_strip(const MatchFramesArgs& a, const MfSets& s, int q0, unsigned long long* top2,
+                                         unsigned long long* colbest, int32_t* first_out) {
   __shared__ __attribute__((aligned(16))) float s_d2[4][64 * MF_PITCH];
   __shared__ unsigned long long s_top[4][64][2];
   __shared__ unsigned int s_first[4][64];
   __shared__ float s_qn[64];
-  const int f = blockIdx.y, q0 = blockIdx.x * MF_ROWS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = lane >> 5, l31 = lane & 31;
-  const MfSets s = mf_sets(a, f);
-  int32_t* first_out = a.first + (size_t)f * a.cap;
   if (q0 >= s.nq || s.nt == 0) {            // an empty strip, or no train rows: nothing to multiply
     if (a.first_mode && tid < MF_ROWS && q0 + tid < a.cap) first_out[q0 + tid] = -1;
     return;                                  // (arg-min mode: the finalize kernel reads nq / nt itself)
@@ -209,7 +231,7 @@ __global__ __launch_bounds__(256) void match_frames_kernel(const MatchFramesArgs
         if (i < nrow && e < best) { best = e; bi = i; }
       }
       if (tj < s.nt && bi >= 0)
-        atomicMin(a.colbest + (size_t)f * a.cap + tj, ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)(q0 + bi));
+        atomicMin(colbest + tj, ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)(q0 + bi));
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads of this tile done before the next tile overwrites it
   }
@@ -238,11 +260,31 @@ __global__ __launch_bounds__(256) void match_frames_kernel(const MatchFramesArgs
           if (v < m1) { m2 = m1; m1 = v; }
           else if (v < m2) m2 = v;
         }
-      unsigned long long* o = a.top2 + ((size_t)f * a.cap + qi) * 2;
+      unsigned long long* o = top2 + (size_t)qi * 2;
       o[0] = m1;
       o[1] = m2;
     }
   }
+}
+
+// grid (ceil(cap / 64), n), 256 threads
+__global__ __launch_bounds__(256) void match_frames_kernel(const MatchFramesArgs a) {
+  const int f = blockIdx.y;
+  mf_strip(a, mf_sets(a, f), blockIdx.x * MF_ROWS, a.top2 + (size_t)f * a.cap * 2, a.colbest + (size_t)f * a.cap,
+           a.first + (size_t)f * a.cap);
+}
+
+// Row i's fate from its top-2 keys k1, k2 and the pair's column minima (null: no cross check): cross check, max_dist,
+// ratio test, ANDed; d = the distance to the nearest train row.  Shared with the bank's score pass (match_bank.h).
+__device__ __forceinline__ bool mf_row_ok(unsigned long long k1, unsigned long long k2, int i,
+                                          const unsigned long long* colbest, float max_dist, float ratio, float& d) {
+  const int j = (int)(k1 & 0xffffffffu);
+  d = sqrtf(__uint_as_float((unsigned)(k1 >> 32)));
+  bool ok = true;
+  if (colbest) ok = (int)(colbest[j] & 0xffffffffu) == i;
+  if (ok && max_dist > 0.f) ok = d < max_dist;
+  if (ok && ratio > 0.f) ok = k2 != ~0ull && d < ratio * sqrtf(__uint_as_float((unsigned)(k2 >> 32)));
+  return ok;
 }
 
 // grid (ceil(cap / 256), n)
@@ -253,18 +295,15 @@ __global__ __launch_bounds__(256) void match_frames_finalize_kernel(const MatchF
   const MfSets s = mf_sets(a, f);
   const size_t o = (size_t)f * a.cap + i;
   if (i >= s.nq || s.nt == 0) {
-    match[o] = -1;
+    if (match) match[o] = -1;
     if (dist) dist[o] = INFINITY;
     return;
   }
-  const unsigned long long k1 = a.top2[2 * o], k2 = a.top2[2 * o + 1];
-  const int j = (int)(k1 & 0xffffffffu);
-  const float d = sqrtf(__uint_as_float((unsigned)(k1 >> 32)));
-  bool ok = true;
-  if (a.cross_check) ok = (int)(a.colbest[(size_t)f * a.cap + j] & 0xffffffffu) == i;
-  if (ok && max_dist > 0.f) ok = d < max_dist;
-  if (ok && ratio > 0.f) ok = k2 != ~0ull && d < ratio * sqrtf(__uint_as_float((unsigned)(k2 >> 32)));
-  match[o] = ok ? j : -1;
+  float d;
+  const int j = (int)(a.top2[2 * o] & 0xffffffffu);
+  const bool ok = mf_row_ok(a.top2[2 * o], a.top2[2 * o + 1], i, a.cross_check ? a.colbest + (size_t)f * a.cap : nullptr,
+                            max_dist, ratio, d);
+  if (match) match[o] = ok ? j : -1;
   if (dist) dist[o] = d;
 }
 

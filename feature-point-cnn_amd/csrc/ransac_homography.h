@@ -120,17 +120,31 @@ __global__ __launch_bounds__(256) void hf_pack_kernel(HfArgs a, const float* __r
   }
 }
 
+// fpc_homography_bank: frame f's train coordinates are slot slot[f] of a key-frame bank (xy [slots][rows][2] passed as
+// key_xy, count [slots]); a slot outside [0, slots) leaves the frame without pairs.  All null / 0 in fpc_homography_frames.
+struct HfBank {
+  const int32_t* slot;          // [n] device
+  const int32_t* count;         // [slots]
+  int rows, slots;
+};
+
 // one workgroup per frame; rows i < count[f] with 0 <= match < the train set's row count, in ascending i
 __global__ __launch_bounds__(256) void hf_gather_kernel(HfArgs a, const int32_t* __restrict__ xy, const int32_t* __restrict__ count,
                                                         int pairing, const int32_t* __restrict__ key_xy,
                                                         const int32_t* __restrict__ nkey, const int32_t* __restrict__ match,
-                                                        uint8_t* mask) {
+                                                        uint8_t* mask, const HfBank bank) {
   __shared__ int wsum[4];
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cap = a.cap;
   const int cnt = hf_clamp(count[f], cap);
   const int32_t* txy = nullptr;
   int nt = 0;
-  if (pairing == 1 && f > 0) {
+  if (bank.slot) {                            // a per-frame train table: slot bank.slot[f] of key_xy [slots][rows][2]
+    const int sl = bank.slot[f];
+    if (sl >= 0 && sl < bank.slots) {
+      txy = key_xy + (size_t)sl * bank.rows * 2;
+      nt = hf_clamp(bank.count[sl], bank.rows);
+    }
+  } else if (pairing == 1 && f > 0) {
     txy = xy + (size_t)(f - 1) * cap * 2;
     nt = hf_clamp(count[f - 1], cap);
   } else if (key_xy) {

@@ -94,6 +94,7 @@ class Engine:
                     bad = int(b.value)
             self._l.fpc_destroy(self._ctx)
             self._ctx = ctypes.c_void_p()
+            self._bank = None
             if bad:
                 raise RuntimeError("fpc_check_guards: %d canary words were overwritten -- a kernel stored outside its tensors" % bad)
 
@@ -584,6 +585,116 @@ class Engine:
     def homography_frames(self, n, match, key_xy=None, pairing="key", **params):
         """homography_frames_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,cap])."""
         hm, ni, mask = self.homography_frames_async(n, match, key_xy, pairing, **params)
+        self.sync()
+        return hm.cpu().numpy(), ni.cpu().numpy(), mask.cpu().numpy()
+
+    # -- key-frame bank: a batch against many stored key frames (fpc_bank_* / fpc_match_bank / fpc_homography_bank) -----
+    def bank_create(self, slots, rows=None):
+        """fpc_bank_create: a device-resident bank of `slots` key frames of up to `rows` keypoints each (default: the
+        capacity).  The only bank call that allocates; one bank per engine."""
+        _lib.check(self._l.fpc_bank_create(self._ctx, int(slots), int(self.capacity if rows is None else rows)),
+                   "fpc_bank_create")
+        v = _lib.FpcBankView()
+        _lib.check(self._l.fpc_bank_get(self._ctx, ctypes.byref(v)), "fpc_bank_get")
+        self._bank = v
+        return v.bytes
+
+    def bank_destroy(self):
+        _lib.check(self._l.fpc_bank_destroy(self._ctx), "fpc_bank_destroy")
+        self._bank = None
+
+    def _bank_info(self):
+        v = getattr(self, "_bank", None)
+        if v is None:
+            raise ValueError("the engine has no key-frame bank (bank_create)")
+        return v
+
+    def bank_view(self):
+        """(desc float32 [slots,rows,D], xy int32 [slots,rows,2], count int32 [slots]) aliasing the bank's device memory
+        (fpc_bank_get); `bank_info()` has the sizes."""
+        v = self._bank_info()
+        s, r, dd = v.slots, v.rows, v.desc_dim
+        desc = torch.as_tensor(_DevArray(v.desc, s * r * dd * 4), device=self.torch_device)
+        xy = torch.as_tensor(_DevArray(v.xy, s * r * 2 * 4), device=self.torch_device)
+        count = torch.as_tensor(_DevArray(v.count, s * 4), device=self.torch_device)
+        return desc.view(torch.float32).view(s, r, dd), xy.view(torch.int32).view(s, r, 2), count.view(torch.int32)
+
+    def bank_info(self):
+        """{"slots", "rows", "desc_dim", "chunk" (slots scored per pass), "bytes" (allocated, workspace included)}."""
+        v = self._bank_info()
+        return {"slots": v.slots, "rows": v.rows, "desc_dim": v.desc_dim, "chunk": v.chunk, "bytes": v.bytes}
+
+    def bank_store(self, frame, slot):
+        """fpc_bank_store: frame `frame` of the last detect into slot `slot` (its most confident `rows` keypoints), on the
+        ctx stream behind that detect.  Does not synchronise."""
+        self._enqueue(lambda: _lib.check(self._l.fpc_bank_store(self._ctx, int(frame), int(slot)), "fpc_bank_store"))
+
+    def bank_store_rows(self, slot, desc, xy):
+        """fpc_bank_store_rows: a saved key frame into slot `slot`: desc [k,D], xy [k,2] (host arrays or device tensors),
+        or device pairs (desc, count) / (xy, count) as keep_frame / keep_frame_points make them.  Does not synchronise."""
+        d, n = self._key(desc)
+        x, _ = self._key_xy(xy)
+        if d is None or x is None or x.shape[0] < d.shape[0]:
+            raise ValueError("bank_store_rows needs descriptors [k,D] and coordinates [k,2]")
+        self._enqueue(lambda: _lib.check(self._l.fpc_bank_store_rows(self._ctx, int(slot), d.data_ptr(), x.data_ptr(),
+                                                                     n.data_ptr()), "fpc_bank_store_rows"))
+        for t in (d, x, n):
+            t.record_stream(self.torch_stream())
+
+    def bank_clear(self, slot=None):
+        """fpc_bank_clear: empties slot `slot`, or every slot."""
+        s = -1 if slot is None else int(slot)
+        if s < 0 and slot is not None:
+            raise ValueError("slot must be >= 0 (None clears every slot)")
+        self._enqueue(lambda: _lib.check(self._l.fpc_bank_clear(self._ctx, s), "fpc_bank_clear"))
+
+    def match_bank_async(self, n, cross_check=True, max_dist=0.0, ratio=0.0, min_score=0, table=True):
+        """fpc_match_bank: every frame of the last detect against every slot of the bank -> device tensors (score int32
+        [n,slots], best int32 [n] (-1: no slot reached max(min_score, 1)), match int32 [n,cap], dist float32 [n,cap]) --
+        the last two are match_frames_async's table against slot best[f] (None with table=False).  Give max_dist or
+        ratio: a bare cross check does not tell slots apart (include/fpc.h).  Does not synchronise."""
+        v = self._bank_info()
+        score = torch.empty((n, v.slots), dtype=torch.int32, device=self.torch_device)
+        best = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
+        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device) if table else None
+        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device) if table else None
+        self._enqueue(lambda: _lib.check(self._l.fpc_match_bank(
+            self._ctx, n, int(bool(cross_check)), float(max_dist), float(ratio), int(min_score), score.data_ptr(),
+            best.data_ptr(), m.data_ptr() if table else None, d.data_ptr() if table else None), "fpc_match_bank"))
+        return score, best, m, d
+
+    def match_bank(self, n, cross_check=True, max_dist=0.0, ratio=0.0, min_score=0):
+        """match_bank_async, then host arrays: (score [n,slots], best [n], [(match int32 [K_f], dist float32 [K_f])])."""
+        score, best, m, d = self.match_bank_async(n, cross_check, max_dist, ratio, min_score)
+        self.sync()
+        cnt = self._frame_counts(n)
+        m, d = m.cpu().numpy(), d.cpu().numpy()
+        return score.cpu().numpy(), best.cpu().numpy(), [(m[f, :cnt[f]].copy(), d[f, :cnt[f]].copy()) for f in range(n)]
+
+    def homography_bank_async(self, n, slot, match, **params):
+        """fpc_homography_bank: homography_frames_async with frame f's key coordinates taken from bank slot slot[f] (int32
+        [n], device; normally match_bank_async's `best`) and `match` that call's table -> device tensors (H [n,3,3],
+        ninliers [n], inlier bool [n,cap]); a frame with slot -1 fails (H = 0).  Does not synchronise."""
+        self._bank_info()
+        p = self._ransac_params(params)
+        if slot.device != self.torch_device or slot.dtype != torch.int32 or tuple(slot.shape) != (n,):
+            raise ValueError("slot must be a device tensor int32 [n]")
+        if match.device != self.torch_device or match.dtype != torch.int32 or tuple(match.shape) != (n, self.capacity):
+            raise ValueError("match must be a device tensor int32 [n,%d]" % self.capacity)
+        slot, match = slot.contiguous(), match.contiguous()
+        hm = torch.empty((n, 3, 3), dtype=torch.float32, device=self.torch_device)
+        ni = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
+        mask = torch.empty((n, self.capacity), dtype=torch.uint8, device=self.torch_device)
+        self._enqueue(lambda: _lib.check(self._l.fpc_homography_bank(
+            self._ctx, n, slot.data_ptr(), match.data_ptr(), ctypes.byref(p), hm.data_ptr(), ni.data_ptr(),
+            mask.data_ptr()), "fpc_homography_bank"))
+        slot.record_stream(self.torch_stream())
+        match.record_stream(self.torch_stream())
+        return hm, ni, mask.view(torch.bool)
+
+    def homography_bank(self, n, slot, match, **params):
+        """homography_bank_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,cap])."""
+        hm, ni, mask = self.homography_bank_async(n, slot, match, **params)
         self.sync()
         return hm.cpu().numpy(), ni.cpu().numpy(), mask.cpu().numpy()
 

@@ -284,6 +284,20 @@ def estimate_homographies_batch(engine, n, stop_features, cross_check=True, max_
     return out
 
 
+def relocalise_batch(engine, n, cross_check=True, max_dist=0.7, ratio=0.0, min_score=0, **ransac_params):
+    """Which stored key frame does each frame of the engine's last detect see, and under which homography?  fpc_match_bank
+    against every slot of the engine's key-frame bank and fpc_homography_bank on the winning slot's match table, enqueued
+    back to back, one synchronisation -> per frame (slot (-1: none reached max(min_score, 1) matches), that slot's score,
+    H float32 [3,3] mapping the frame's pixels to the key frame's (zeros when the frame failed), ninliers).  max_dist
+    defaults to the reference's threshold (settings.py:6): a bare cross check does not tell key frames apart."""
+    score, best, match, _ = engine.match_bank_async(n, cross_check=cross_check, max_dist=max_dist, ratio=ratio,
+                                                    min_score=min_score)
+    hm, ni, _ = engine.homography_bank_async(n, best, match, **ransac_params)
+    engine.sync()
+    score, best, hm, ni = score.cpu().numpy(), best.cpu().numpy(), hm.cpu().numpy(), ni.cpu().numpy()
+    return [(int(best[f]), int(score[f, best[f]]) if best[f] >= 0 else 0, hm[f], int(ni[f])) for f in range(n)]
+
+
 def _points_array(xy, conf):
     pts = np.zeros((3, len(conf)))
     pts[0], pts[1], pts[2] = xy[:, 0], xy[:, 1], conf

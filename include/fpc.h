@@ -445,6 +445,81 @@ int fpc_homography_frames(fpc_ctx* ctx, int n, int pairing, const int32_t* key_x
                           const int32_t* match_dev, const fpc_ransac_params* params, float* H_dev, int32_t* ninliers_dev,
                           uint8_t* inlier_dev);
 
+/* --- key-frame bank: a batch against MANY stored key frames in one call (relocalisation, loop closure) ------------------
+ * The calls above know one key frame.  The bank keeps up to FPC_BANK_MAX_SLOTS of them on the device -- what 'k' in
+ * cpp/src/main.cc:118-123 and 's' in python/src/inference.py:57-60 store, several times over -- and fpc_match_bank answers
+ * "which stored frame does this frame see?" for a whole batch without a host round trip; fpc_homography_bank then
+ * verifies the answer geometrically.  One bank per ctx.
+ *
+ * fpc_bank_create: 1 <= slots <= FPC_BANK_MAX_SLOTS, 1 <= rows <= fpc_results().capacity; needs descriptor_enabled.  The
+ * ONLY bank call that allocates (and the only one, with fpc_bank_destroy, that synchronises): the storage below, the
+ * rows' squared norms and the workspace of fpc_match_bank -- no later bank call allocates.  Every slot starts empty.
+ * FPC_E_INVALID when the ctx already has a bank.  fpc_bank_destroy frees it (waiting for the ctx stream first);
+ * fpc_destroy frees a bank that is still alive.  In a FPC_PLAN_GUARD_ZONES context every buffer of the bank is followed by
+ * a canary zone of its own, and fpc_check_guards counts those too.
+ * fpc_bank_get: the bank as device pointers, valid until fpc_bank_destroy / fpc_destroy.  Slot s holds count[s] rows
+ * (0 = empty): desc[s][0 .. count[s]) and their pixel coordinates xy[s][..] = (x, y); rows behind count[s] are
+ * unspecified.  chunk: the slots one pass of fpc_match_bank scores together (its workspace is max_batch x chunk x
+ * capacity entries: DESIGN.md section 7); bytes: everything the bank allocated, that workspace included.
+ * fpc_bank_store: frame `frame` of the last call that produced keypoints with descriptors (as for fpc_match_frames) into
+ * slot `slot`, replacing what it held: the frame's first min(count[frame], rows) rows -- results are sorted by descending
+ * confidence, so with rows < count these are the most confident ones (the rule of cpp/src/main.cc:121-123).  count[frame]
+ * is read on the device: the call may be enqueued right behind fpc_detect.  The rows' squared norms are computed here,
+ * once, with the partial sums fpc_match_frames uses for its key, which is what makes the distances below bit-equal.
+ * fpc_bank_store_rows: the same from caller memory (a saved map): desc_dev [*n][D] fp32, 16-byte aligned, xy_dev [*n][2]
+ * int32, *n_dev an int32 in device memory, read on the device and clamped to [0, rows].
+ * fpc_bank_clear: count[slot] = 0; slot = -1 clears every slot.
+ *
+ * fpc_match_bank: the query sets are frames 0 .. n-1 of the last results, as in fpc_match_frames.
+ *  - score_dev int32 [n][slots]: score[f][s] = the number of rows i < count[f] for which
+ *    fpc_match_frames(frame f, FPC_PAIR_KEY, key = slot s, cross_check, max_dist, ratio) gives match >= 0.  An empty slot
+ *    scores 0.  Integer sums: independent of the execution order.
+ *  - best_dev int32 [n]: the slot with the largest score, ties to the LOWER slot; -1 when the largest score is below
+ *    max(min_score, 1).
+ *  - match_dev int32 [n][cap], dist_dev float [n][cap] (both may be NULL): the fpc_match_frames table of frame f against
+ *    slot best[f] -- bit-identical to what that call returns with desc[best[f]], count[best[f]] as its key (it IS that
+ *    call's kernels, with the key chosen per frame on the device).  A frame with best[f] = -1: -1 / +inf.
+ *  - score_dev or best_dev may be NULL, not both.
+ *  - WARNING: a bare cross check (max_dist = 0, ratio = 0) does not discriminate between slots.  Two UNRELATED descriptor
+ *    sets have many mutual nearest neighbours (on random unit-norm sets a large share of the smaller set), so an
+ *    unrelated slot can outscore the right one.  Give max_dist (the reference's threshold is 0.7, settings.py:6) or a
+ *    ratio (0.8), with or without the cross check; tests/test_match_bank.py shows both sides on planted data.
+ * fpc_homography_bank: fpc_homography_frames with FPC_PAIR_KEY and a per-frame key: frame f's train coordinates are the
+ * bank's xy[slot[f]] with the bank's count[slot[f]]; slot_dev int32 [n] (normally best_dev) is read on the device;
+ * match_dev is fpc_match_bank's table.  For every frame the outputs are bit-identical to fpc_homography_frames(n,
+ * FPC_PAIR_KEY, xy[slot[f]], &count[slot[f]], match, params) at the SAME frame index (the sampler hashes f).  A frame
+ * whose slot is outside [0, slots) -- best = -1 -- has no pairs and fails as under "Failure" above: nine zeros, 0 inliers,
+ * an all-zero mask.  Needs no descriptors in the results, only keypoints.
+ *
+ * All of these but create / destroy: asynchronous on the ctx stream, no host synchronisation, no device-to-host copy, no
+ * allocation; every count is read on the device; deterministic (bit-identical outputs on repeated calls).  A sequence
+ * fpc_detect, fpc_bank_store, fpc_detect, fpc_match_bank, fpc_homography_bank needs no host call in between.
+ * FPC_E_INVALID (nothing is written): a NULL ctx; no bank (or, for create, a bank already there, descriptor_enabled = 0,
+ * slots / rows out of range); slot outside [0, slots) (clear: [-1, slots)); frame outside the frames of the last call
+ * that produced keypoints with descriptors; n < 1 or above those frames; results without descriptors (store,
+ * match_bank); a NULL or misaligned desc_dev, a NULL xy_dev / n_dev (store_rows); ratio outside [0, 1], max_dist < 0,
+ * min_score < 0, score_dev and best_dev both NULL (match_bank); a NULL slot_dev / match_dev / H_dev / ninliers_dev or
+ * parameters fpc_homography_frames refuses (homography_bank). */
+#define FPC_BANK_MAX_SLOTS 1024
+typedef struct fpc_bank_view {
+  const float*   desc;    /* [slots][rows][desc_dim]                                   */
+  const int32_t* xy;      /* [slots][rows][2]                                          */
+  const int32_t* count;   /* [slots], 0 = empty                                        */
+  int slots, rows, desc_dim;
+  int chunk;              /* slots scored per pass of fpc_match_bank                   */
+  size_t bytes;           /* everything the bank allocated, workspace included         */
+} fpc_bank_view;
+int fpc_bank_create(fpc_ctx* ctx, int slots, int rows);
+int fpc_bank_destroy(fpc_ctx* ctx);
+int fpc_bank_get(fpc_ctx* ctx, fpc_bank_view* out);
+int fpc_bank_store(fpc_ctx* ctx, int frame, int slot);
+int fpc_bank_store_rows(fpc_ctx* ctx, int slot, const float* desc_dev, const int32_t* xy_dev, const int32_t* n_dev);
+int fpc_bank_clear(fpc_ctx* ctx, int slot);
+int fpc_match_bank(fpc_ctx* ctx, int n, int cross_check, float max_dist, float ratio, int min_score, int32_t* score_dev,
+                   int32_t* best_dev, int32_t* match_dev, float* dist_dev);
+int fpc_homography_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev,
+                        const fpc_ransac_params* params, float* H_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
