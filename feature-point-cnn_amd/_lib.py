@@ -32,6 +32,7 @@ SYMBOLS = [
     "fpc_default_ransac_params", "fpc_ransac_homography", "fpc_homography_frames",
     "fpc_bank_create", "fpc_bank_destroy", "fpc_bank_get", "fpc_bank_store", "fpc_bank_store_rows", "fpc_bank_clear",
     "fpc_match_bank", "fpc_homography_bank",
+    "fpc_match_frames_guided", "fpc_match_bank_guided",
 ]
 
 ABI_VERSION = 4
@@ -172,6 +173,9 @@ def load():
     l.fpc_bank_clear.argtypes = [vp, ci]
     l.fpc_match_bank.argtypes = [vp, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp]
     l.fpc_homography_bank.argtypes = [vp, ci, vp, vp, rp, vp, vp, vp]
+    l.fpc_match_frames_guided.argtypes = [vp, ci, ci, vp, vp, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float,
+                                          vp, vp]
+    l.fpc_match_bank_guided.argtypes = [vp, ci, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float, vp, vp]
     l.fpc_sample_descriptors.argtypes = [vp, vp, vp, ci, vp]
     l.fpc_read_activation.argtypes = [vp, ctypes.c_char_p, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     l.fpc_plan_hash.argtypes = [vp]

@@ -10,6 +10,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,6 +36,7 @@
 #include "match.h"
 #include "match_frames.h"
 #include "match_bank.h"
+#include "match_guided.h"
 #include "ransac_homography.h"
 #include "homography.h"
 #include "weights.h"
@@ -4091,6 +4093,55 @@ int fpc_homography_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* m
   ransac_launch(c, a, H, ninliers, inlier, c->cap);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
+}
+
+// ---- guided matching (include/fpc.h; kernels in match_guided.h) -----------------------------------------------------------
+// Both entry points run on fpc_match_frames' workspace (norms, top-2, column minima: [max_batch][cap], and the bank's
+// rows <= cap), carved at fpc_create: nothing of their own.
+static int match_guided_launch(fpc_ctx* c, MatchFramesArgs a, const MatchGuidedArgs& g, int norm_blocks, float max_dist,
+                               float ratio, int32_t* match, float* dist) {
+  if (a.cross_check)
+    HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * a.n * c->cap, c->stream));
+  hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, norm_blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(match_guided_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, a.n), dim3(256), 0, c->stream, a, g);
+  hipLaunchKernelGGL(match_guided_finalize_kernel, dim3((c->cap + 255) / 256, a.n), dim3(256), 0, c->stream, a, max_dist,
+                     ratio, match, dist);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+static bool guided_options_ok(const float* H, float radius, float max_dist, float ratio, const int32_t* match) {
+  return H && match && std::isfinite(radius) && radius > 0.f && max_dist >= 0.f && ratio >= 0.f && ratio <= 1.f;
+}
+
+int fpc_match_frames_guided(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey, const int32_t* key_xy,
+                            const float* H, float radius, int cross_check, float max_dist, float ratio, int32_t* match,
+                            float* dist) {
+  if (!c || !guided_options_ok(H, radius, max_dist, ratio, match) ||
+      (pairing != FPC_PAIR_KEY && pairing != FPC_PAIR_PREVIOUS) || (pairing == FPC_PAIR_KEY && (!key || !key_xy)) ||
+      (key && !key_xy))
+    return FPC_E_INVALID;
+  if (int rc = match_frames_check(c, n, key, nkey)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  MatchFramesArgs a = match_frames_args(c, n, key, nkey);
+  a.pairing = pairing;
+  a.cross_check = cross_check != 0;
+  const MatchGuidedArgs g{H, c->xy, key ? key_xy : nullptr, (double)radius * (double)radius};
+  return match_guided_launch(c, a, g, n + 1, max_dist, ratio, match, dist);
+}
+
+int fpc_match_bank_guided(fpc_ctx* c, int n, const int32_t* slot, const float* H, float radius, int cross_check,
+                          float max_dist, float ratio, int32_t* match, float* dist) {
+  if (!c || !c->bank_slab || !slot || !guided_options_ok(H, radius, max_dist, ratio, match)) return FPC_E_INVALID;
+  if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const BankArgs& b = c->bank;
+  MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
+  a.cross_check = cross_check != 0;
+  a.key = b.desc; a.key_slot = slot; a.bank_norms = b.norms; a.bank_count = b.count;
+  a.bank_rows = b.rows; a.bank_slots = b.slots;
+  const MatchGuidedArgs g{H, c->xy, b.xy, (double)radius * (double)radius};
+  return match_guided_launch(c, a, g, n, max_dist, ratio, match, dist);   // (grid y = n: the bank's norms are its own)
 }
 
 int fpc_results(fpc_ctx* c, fpc_device_results* out) {

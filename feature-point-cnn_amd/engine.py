@@ -698,6 +698,73 @@ class Engine:
         self.sync()
         return hm.cpu().numpy(), ni.cpu().numpy(), mask.cpu().numpy()
 
+    # -- guided matching: the match once more under the estimated homographies (fpc_match_*_guided) -------------------
+    def _guided_h(self, n, hm):
+        """H -> a contiguous device tensor float32 [n,9] (homography_*_async's [n,3,3] output as it is, or a host array)."""
+        hm = torch.as_tensor(hm).to(self.torch_device, torch.float32).contiguous()
+        if hm.numel() != n * 9 or hm.shape[0] != n:
+            raise ValueError("H must be [n,3,3] or [n,9]")
+        return hm
+
+    def _per_frame(self, n, m, d):
+        self.sync()
+        cnt = self._frame_counts(n)
+        m, d = m.cpu().numpy(), d.cpu().numpy()
+        return [(m[f, :cnt[f]].copy(), d[f, :cnt[f]].copy()) for f in range(n)]
+
+    def match_frames_guided_async(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True, max_dist=0.0,
+                                  ratio=0.0):
+        """fpc_match_frames_guided: match_frames_async over the train rows within `radius` pixels of where H[f] (float32
+        [n,3,3], query pixel -> train pixel: homography_frames_async's output, device or host) sends the query row;
+        `key` / `key_xy` as in match_frames_async / homography_frames_async (the key's count is `key`'s) -> (match int32
+        [n,cap], dist float32 [n,cap]) on the device; a frame with H = 0 is all -1.  Does not synchronise."""
+        if pairing not in self.PAIRINGS:
+            raise ValueError("pairing must be one of %s, got %r" % (sorted(self.PAIRINGS), pairing))
+        kd, kc = self._key(key)
+        kx, _ = self._key_xy(key_xy)
+        if kd is not None and (kx is None or kx.shape[0] < kd.shape[0]):
+            raise ValueError("a key needs key_xy with a row for each of its rows")
+        hm = self._guided_h(n, H)
+        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
+        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device)
+        self._enqueue(lambda: _lib.check(self._l.fpc_match_frames_guided(
+            self._ctx, n, self.PAIRINGS[pairing], kd.data_ptr() if kd is not None else None,
+            kc.data_ptr() if kc is not None else None, kx.data_ptr() if kx is not None else None, hm.data_ptr(),
+            float(radius), int(bool(cross_check)), float(max_dist), float(ratio), m.data_ptr(), d.data_ptr()),
+            "fpc_match_frames_guided"))
+        for t in (kd, kc, kx, hm):
+            if t is not None:
+                t.record_stream(self.torch_stream())
+        return m, d
+
+    def match_frames_guided(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True, max_dist=0.0,
+                            ratio=0.0):
+        """match_frames_guided_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        return self._per_frame(n, *self.match_frames_guided_async(n, H, radius, key, key_xy, pairing, cross_check,
+                                                                  max_dist, ratio))
+
+    def match_bank_guided_async(self, n, slot, H, radius, cross_check=True, max_dist=0.0, ratio=0.0):
+        """fpc_match_bank_guided: match_frames_guided_async with frame f's train set taken from bank slot slot[f] (int32
+        [n], device; normally match_bank_async's `best`; -1: an all -1 row) and H homography_bank_async's output.  Does
+        not synchronise."""
+        self._bank_info()
+        if slot.device != self.torch_device or slot.dtype != torch.int32 or tuple(slot.shape) != (n,):
+            raise ValueError("slot must be a device tensor int32 [n]")
+        slot = slot.contiguous()
+        hm = self._guided_h(n, H)
+        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
+        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device)
+        self._enqueue(lambda: _lib.check(self._l.fpc_match_bank_guided(
+            self._ctx, n, slot.data_ptr(), hm.data_ptr(), float(radius), int(bool(cross_check)), float(max_dist),
+            float(ratio), m.data_ptr(), d.data_ptr()), "fpc_match_bank_guided"))
+        slot.record_stream(self.torch_stream())
+        hm.record_stream(self.torch_stream())
+        return m, d
+
+    def match_bank_guided(self, n, slot, H, radius, cross_check=True, max_dist=0.0, ratio=0.0):
+        """match_bank_guided_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        return self._per_frame(n, *self.match_bank_guided_async(n, slot, H, radius, cross_check, max_dist, ratio))
+
     # -- timing ----------------------------------------------------------------------
     def check_guards(self):
         """Contexts created with plan_flags=["guard_zones"] (a test facility): waits for the device and returns the number

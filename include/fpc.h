@@ -520,6 +520,44 @@ int fpc_match_bank(fpc_ctx* ctx, int n, int cross_check, float max_dist, float r
 int fpc_homography_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev,
                         const fpc_ransac_params* params, float* H_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
 
+/* --- guided matching: the match once more, under the estimated homographies as a spatial gate ---------------------------
+ * The first pass above is appearance-only: on repetitive texture a row takes a look-alike elsewhere in the image, and
+ * RANSAC then discards the pair.  With one H per frame -- what fpc_homography_frames / fpc_homography_bank wrote, passed on
+ * unchanged, or under FPC_PAIR_PREVIOUS a motion prior -- the second pass looks only where H sends the row (what
+ * python/src/homographies.py's warp_points does on the synthesis side).
+ *
+ * fpc_match_frames_guided: query sets, train sets, counts, cap and the output shapes are exactly fpc_match_frames' for the
+ * same n, pairing, key_dev, nkey_dev.  The train coordinates are fpc_homography_frames': key_xy_dev int32 [nkey][2] for
+ * the key (the same nkey_dev), xy[f-1] of the results under FPC_PAIR_PREVIOUS.
+ * fpc_match_bank_guided: frame f's train set is the bank's desc[slot[f]], xy[slot[f]], count[slot[f]]; slot_dev int32 [n]
+ * (normally fpc_match_bank's best_dev) is read on the device, and a slot outside [0, slots) gives the frame no train rows.
+ * H_dev float32 [n][9], row-major, maps a query pixel to its train pixel: the direction and layout the two homography
+ * calls write.
+ *  - Gate: query row i at the integer pixel (x, y), train row j at (u, v); in fp64 from the fp32 H
+ *        w  = H6 x + H7 y + H8
+ *        ex = H0 x + H1 y + H2 - w u
+ *        ey = H3 x + H4 y + H5 - w v
+ *    and row j is a CANDIDATE of row i iff w > 0 and ex^2 + ey^2 < radius^2 w^2 (no division).  A failed frame's nine
+ *    zeros give w = 0: no candidates, every row -1 / +inf.  The same holds for an H with any non-finite entry.
+ *  - Result: fpc_match_frames' rule over the candidates only: the nearest candidate in (d^2, index) order, dist = its
+ *    distance, max_dist and ratio as there with the second-nearest CANDIDATE as d2 (fewer than two candidates: the ratio
+ *    test fails).  Cross check: row i survives iff i is the (d^2, index)-nearest among the query rows that have j as a
+ *    candidate.  A row without a candidate: -1 / +inf; rows count[f] <= i < cap: -1 / +inf.
+ *  - Bits: for a candidate pair d^2 is the value fpc_match_frames computes for that pair (the same norms, K order,
+ *    expression and clamp), so where the guided winner equals the unguided winner dist is bit-equal, and with a radius
+ *    beyond the frame diagonal (and w > 0 over the frame) the whole output is fpc_match_frames' / the fpc_match_bank table's.
+ *  - Execution: asynchronous on the ctx stream, no host synchronisation, no device-to-host copy, no allocation (the
+ *    workspace is fpc_match_frames', carved at fpc_create); every count and slot is read on the device; deterministic
+ *    (bit-identical outputs on repeated calls).  fpc_detect, fpc_match_frames, fpc_homography_frames,
+ *    fpc_match_frames_guided, fpc_homography_frames needs no host call in between.
+ * FPC_E_INVALID (nothing is written): everything fpc_match_frames refuses; a NULL H_dev; radius not finite or not > 0;
+ * FPC_PAIR_KEY without key_xy_dev; key_dev without key_xy_dev; no bank or a NULL slot_dev (bank variant). */
+int fpc_match_frames_guided(fpc_ctx* ctx, int n, int pairing, const float* key_dev, const int32_t* nkey_dev,
+                            const int32_t* key_xy_dev, const float* H_dev, float radius, int cross_check, float max_dist,
+                            float ratio, int32_t* match_dev, float* dist_dev);
+int fpc_match_bank_guided(fpc_ctx* ctx, int n, const int32_t* slot_dev, const float* H_dev, float radius, int cross_check,
+                          float max_dist, float ratio, int32_t* match_dev, float* dist_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
