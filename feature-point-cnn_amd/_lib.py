@@ -31,7 +31,7 @@ SYMBOLS = [
     "fpc_match_frames", "fpc_first_within_frames",
     "fpc_default_ransac_params", "fpc_ransac_homography", "fpc_homography_frames",
     "fpc_bank_create", "fpc_bank_destroy", "fpc_bank_get", "fpc_bank_store", "fpc_bank_store_rows", "fpc_bank_clear",
-    "fpc_match_bank", "fpc_homography_bank",
+    "fpc_match_bank", "fpc_homography_bank", "fpc_bank_create_ex", "fpc_bank_format",
     "fpc_match_frames_guided", "fpc_match_bank_guided",
 ]
 
@@ -166,6 +166,8 @@ def load():
     l.fpc_ransac_homography.argtypes = [vp, ci, vp, vp, vp, ci, rp, vp, vp, vp]
     l.fpc_homography_frames.argtypes = [vp, ci, ci, vp, vp, vp, rp, vp, vp, vp]
     l.fpc_bank_create.argtypes = [vp, ci, ci]
+    l.fpc_bank_create_ex.argtypes = [vp, ci, ci, ci]
+    l.fpc_bank_format.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(vp)]
     l.fpc_bank_destroy.argtypes = [vp]
     l.fpc_bank_get.argtypes = [vp, ctypes.POINTER(FpcBankView)]
     l.fpc_bank_store.argtypes = [vp, ci, ci]

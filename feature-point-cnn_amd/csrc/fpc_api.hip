@@ -36,6 +36,7 @@
 #include "match.h"
 #include "match_frames.h"
 #include "match_bank.h"
+#include "match_bank_bf16.h"
 #include "match_guided.h"
 #include "ransac_homography.h"
 #include "homography.h"
@@ -575,6 +576,8 @@ struct fpc_ctx {
   char* bank_slab = nullptr;
   size_t bank_bytes = 0;
   BankArgs bank{};
+  int bank_format = FPC_BANK_F32;                              // FPC_BANK_BF16: bank.desc is null, the rows are bank16.desc
+  BankBf16Args bank16{};                                       // (match_bank_bf16.h)
   std::vector<std::pair<size_t, size_t>> bank_guards;          // (offset, bytes) of the canary zones in bank_slab
   int pts_n = 0;                     // frames of the last call that produced keypoints (fpc_detect*, fpc_get_points)
   bool pts_desc = false;             // ... and whether it sampled their descriptors
@@ -3948,9 +3951,13 @@ int fpc_homography_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy,
 // (frame, slot) pair in flight; the slots run in chunks so that this stays within BANK_WS_BUDGET (one slot at the least).
 constexpr size_t BANK_WS_BUDGET = (size_t)256 << 20;
 
-int fpc_bank_create(fpc_ctx* c, int slots, int rows) {
-  if (!c || c->bank_slab || !c->cfg.descriptor_enabled || slots < 1 || slots > FPC_BANK_MAX_SLOTS || rows < 1 || rows > c->cap)
+// A FPC_BANK_BF16 bank stores its rows at 2 B per component and adds the call's rounded query sets ([max_batch][cap][D]
+// bf16) to the workspace; the chunk formula is the same.
+int fpc_bank_create_ex(fpc_ctx* c, int slots, int rows, int format) {
+  if (!c || c->bank_slab || !c->cfg.descriptor_enabled || slots < 1 || slots > FPC_BANK_MAX_SLOTS || rows < 1 ||
+      rows > c->cap || (format != FPC_BANK_F32 && format != FPC_BANK_BF16))
     return FPC_E_INVALID;
+  const bool half = format == FPC_BANK_BF16;
   HIPCHECK(hipSetDevice(c->cfg.device));
   const size_t B = c->B, cap = c->cap, D = c->D;
   const size_t per_slot = B * (cap * 16 + (size_t)rows * 8);
@@ -3959,10 +3966,12 @@ int fpc_bank_create(fpc_ctx* c, int slots, int rows) {
   std::vector<std::pair<size_t, size_t>> zones;
   cv.zones = &zones;
   cv.guard = c->guard_zones ? GUARD_BYTES : 0;
-  const size_t o_desc = cv.take<float>((size_t)slots * rows * D), o_xy = cv.take<int32_t>((size_t)slots * rows * 2);
+  const size_t o_desc = half ? cv.take<bf16_t>((size_t)slots * rows * D) : cv.take<float>((size_t)slots * rows * D);
+  const size_t o_xy = cv.take<int32_t>((size_t)slots * rows * 2);
   const size_t o_cnt = cv.take<int32_t>(slots), o_nrm = cv.take<float>((size_t)slots * rows);
   const size_t o_top = cv.take<unsigned long long>(B * chunk * cap * 2), o_col = cv.take<unsigned long long>(B * chunk * rows);
   const size_t o_sc = cv.take<int32_t>(B * slots), o_best = cv.take<int32_t>(B);
+  const size_t o_q = half ? cv.take<bf16_t>(B * cap * D) : 0;
   char* p = nullptr;
   HIPCHECK(hipMalloc((void**)&p, cv.off));
   {
@@ -3980,7 +3989,13 @@ int fpc_bank_create(fpc_ctx* c, int slots, int rows) {
   c->bank_bytes = cv.off;
   c->bank_guards = zones;
   BankArgs& b = c->bank;
-  b.desc = reinterpret_cast<float*>(p + o_desc);
+  b.desc = half ? nullptr : reinterpret_cast<float*>(p + o_desc);
+  c->bank_format = format;
+  c->bank16 = BankBf16Args{};
+  if (half) {
+    c->bank16.desc = reinterpret_cast<bf16_t*>(p + o_desc);
+    c->bank16.q = reinterpret_cast<bf16_t*>(p + o_q);
+  }
   b.xy = reinterpret_cast<int32_t*>(p + o_xy);
   b.count = reinterpret_cast<int32_t*>(p + o_cnt);
   b.norms = reinterpret_cast<float*>(p + o_nrm);
@@ -3989,6 +4004,15 @@ int fpc_bank_create(fpc_ctx* c, int slots, int rows) {
   b.score = reinterpret_cast<int32_t*>(p + o_sc);
   b.best = reinterpret_cast<int32_t*>(p + o_best);
   b.slots = slots; b.rows = rows; b.D = c->D; b.chunk = chunk;
+  return FPC_OK;
+}
+
+int fpc_bank_create(fpc_ctx* c, int slots, int rows) { return fpc_bank_create_ex(c, slots, rows, FPC_BANK_F32); }
+
+int fpc_bank_format(fpc_ctx* c, int* format, const void** desc) {
+  if (!c || !c->bank_slab || (!format && !desc)) return FPC_E_INVALID;
+  if (format) *format = c->bank_format;
+  if (desc) *desc = c->bank_format == FPC_BANK_BF16 ? (const void*)c->bank16.desc : (const void*)c->bank.desc;
   return FPC_OK;
 }
 
@@ -4001,6 +4025,8 @@ int fpc_bank_destroy(fpc_ctx* c) {
   c->bank_bytes = 0;
   c->bank_guards.clear();
   c->bank = BankArgs{};
+  c->bank_format = FPC_BANK_F32;
+  c->bank16 = BankBf16Args{};
   return FPC_OK;
 }
 
@@ -4017,13 +4043,22 @@ int fpc_bank_get(fpc_ctx* c, fpc_bank_view* out) {
   return FPC_OK;
 }
 
+// the store kernel of the bank's format
+static void bank_store_launch(fpc_ctx* c, int slot, const float* desc, const int32_t* xy, const int32_t* n, int src_cap) {
+  const dim3 grid((c->bank.rows + 127) / 128);
+  if (c->bank_format == FPC_BANK_BF16)
+    hipLaunchKernelGGL(bank_store_bf16_kernel, grid, dim3(256), 0, c->stream, c->bank, c->bank16, slot, desc, xy, n, src_cap);
+  else
+    hipLaunchKernelGGL(bank_store_kernel, grid, dim3(256), 0, c->stream, c->bank, slot, desc, xy, n, src_cap);
+}
+
 int fpc_bank_store(fpc_ctx* c, int frame, int slot) {
   if (!c || !c->bank_slab || !c->pts_desc || frame < 0 || frame >= c->pts_n || frame >= c->B || slot < 0 ||
       slot >= c->bank.slots)
     return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
-  hipLaunchKernelGGL(bank_store_kernel, dim3((c->bank.rows + 127) / 128), dim3(256), 0, c->stream, c->bank, slot,
-                     c->desc_out + (size_t)frame * c->cap * c->D, c->xy + (size_t)frame * c->cap * 2, c->count + frame, c->cap);
+  bank_store_launch(c, slot, c->desc_out + (size_t)frame * c->cap * c->D, c->xy + (size_t)frame * c->cap * 2, c->count + frame,
+                    c->cap);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }
@@ -4033,8 +4068,7 @@ int fpc_bank_store_rows(fpc_ctx* c, int slot, const float* desc, const int32_t* 
       (reinterpret_cast<uintptr_t>(desc) & 15))
     return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
-  hipLaunchKernelGGL(bank_store_kernel, dim3((c->bank.rows + 127) / 128), dim3(256), 0, c->stream, c->bank, slot, desc, xy, n,
-                     c->bank.rows);
+  bank_store_launch(c, slot, desc, xy, n, c->bank.rows);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }
@@ -4043,6 +4077,44 @@ int fpc_bank_clear(fpc_ctx* c, int slot) {
   if (!c || !c->bank_slab || slot < -1 || slot >= c->bank.slots) return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
   hipLaunchKernelGGL(bank_clear_kernel, dim3((c->bank.slots + 255) / 256), dim3(256), 0, c->stream, c->bank, slot);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+// fpc_match_bank on a FPC_BANK_BF16 bank (match_bank_bf16.h): fpc_match_bank's sequence below with the rounding pass for
+// mf_norms_kernel and the bf16 strip for mf_strip; count, select and finalize are the fp32 path's kernels.  D is 128 or 256.
+static int match_bank_bf16(fpc_ctx* c, MatchFramesArgs a, float max_dist, float ratio, int min_score, int32_t* score,
+                           int32_t* best, int32_t* match, float* dist) {
+  const BankArgs& b = c->bank;
+  const BankBf16Args& h = c->bank16;
+  const int n = a.n;
+  const dim3 strips((c->cap + MF_ROWS - 1) / MF_ROWS, n);
+  hipLaunchKernelGGL(bank_round_queries_kernel, dim3((c->cap + 127) / 128, n), dim3(256), 0, c->stream, a, h);
+  HIPCHECK(hipMemsetAsync(b.score, 0, sizeof(int32_t) * n * b.slots, c->stream));
+  for (int s0 = 0; s0 < b.slots; s0 += b.chunk) {
+    const int ns = std::min(b.chunk, b.slots - s0);
+    if (a.cross_check)
+      HIPCHECK(hipMemsetAsync(b.colbest, 0xff, sizeof(unsigned long long) * ((size_t)(n - 1) * b.chunk + ns) * b.rows, c->stream));
+    if (c->D == 128)
+      hipLaunchKernelGGL(bank_score_bf16_kernel<8>, dim3(strips.x, n, ns), dim3(256), 0, c->stream, a, b, h, s0);
+    else
+      hipLaunchKernelGGL(bank_score_bf16_kernel<16>, dim3(strips.x, n, ns), dim3(256), 0, c->stream, a, b, h, s0);
+    hipLaunchKernelGGL(bank_count_kernel, dim3((c->cap + 255) / 256, n, ns), dim3(256), 0, c->stream, a, b, s0, max_dist, ratio);
+  }
+  hipLaunchKernelGGL(bank_select_kernel, dim3(n), dim3(256), 0, c->stream, b, min_score, score, best);
+  if (match || dist) {
+    // the table of frame f against slot best[f]: the same strip, hence the same d^2 bits as the score pass
+    a.key_slot = b.best; a.bank_norms = b.norms; a.bank_count = b.count;
+    a.bank_rows = b.rows; a.bank_slots = b.slots;
+    if (a.cross_check)
+      HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * n * c->cap, c->stream));
+    if (c->D == 128)
+      hipLaunchKernelGGL((match_bank_bf16_kernel<8, false>), strips, dim3(256), 0, c->stream, a, b, h, MatchGuidedArgs{});
+    else
+      hipLaunchKernelGGL((match_bank_bf16_kernel<16, false>), strips, dim3(256), 0, c->stream, a, b, h, MatchGuidedArgs{});
+    hipLaunchKernelGGL(match_frames_finalize_kernel, dim3((c->cap + 255) / 256, n), dim3(256), 0, c->stream, a, max_dist,
+                       ratio, match, dist);
+  }
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }
@@ -4056,6 +4128,7 @@ int fpc_match_bank(fpc_ctx* c, int n, int cross_check, float max_dist, float rat
   const BankArgs& b = c->bank;
   MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
   a.cross_check = cross_check != 0;
+  if (c->bank_format == FPC_BANK_BF16) return match_bank_bf16(c, a, max_dist, ratio, min_score, score, best, match, dist);
   // the frames' norms, once for the score pass and the table pass (grid y = n: no key block)
   hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, n), dim3(256), 0, c->stream, a);
   HIPCHECK(hipMemsetAsync(b.score, 0, sizeof(int32_t) * n * b.slots, c->stream));
@@ -4141,6 +4214,22 @@ int fpc_match_bank_guided(fpc_ctx* c, int n, const int32_t* slot, const float* H
   a.key = b.desc; a.key_slot = slot; a.bank_norms = b.norms; a.bank_count = b.count;
   a.bank_rows = b.rows; a.bank_slots = b.slots;
   const MatchGuidedArgs g{H, c->xy, b.xy, (double)radius * (double)radius};
+  if (c->bank_format == FPC_BANK_BF16) {
+    // (match_bank_bf16.h) the rounding pass for the norms, the gated bf16 strip for match_guided_kernel
+    const BankBf16Args& h = c->bank16;
+    const dim3 strips((c->cap + MF_ROWS - 1) / MF_ROWS, n);
+    if (a.cross_check)
+      HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * n * c->cap, c->stream));
+    hipLaunchKernelGGL(bank_round_queries_kernel, dim3((c->cap + 127) / 128, n), dim3(256), 0, c->stream, a, h);
+    if (c->D == 128)
+      hipLaunchKernelGGL((match_bank_bf16_kernel<8, true>), strips, dim3(256), 0, c->stream, a, b, h, g);
+    else
+      hipLaunchKernelGGL((match_bank_bf16_kernel<16, true>), strips, dim3(256), 0, c->stream, a, b, h, g);
+    hipLaunchKernelGGL(match_guided_finalize_kernel, dim3((c->cap + 255) / 256, n), dim3(256), 0, c->stream, a, max_dist,
+                       ratio, match, dist);
+    HIPCHECK(hipGetLastError());
+    return FPC_OK;
+  }
   return match_guided_launch(c, a, g, n, max_dist, ratio, match, dist);   // (grid y = n: the bank's norms are its own)
 }
 

@@ -589,14 +589,23 @@ class Engine:
         return hm.cpu().numpy(), ni.cpu().numpy(), mask.cpu().numpy()
 
     # -- key-frame bank: a batch against many stored key frames (fpc_bank_* / fpc_match_bank / fpc_homography_bank) -----
-    def bank_create(self, slots, rows=None):
-        """fpc_bank_create: a device-resident bank of `slots` key frames of up to `rows` keypoints each (default: the
-        capacity).  The only bank call that allocates; one bank per engine."""
-        _lib.check(self._l.fpc_bank_create(self._ctx, int(slots), int(self.capacity if rows is None else rows)),
-                   "fpc_bank_create")
+    BANK_FORMATS = {"f32": 0, "bf16": 1}          # include/fpc.h FPC_BANK_F32 / FPC_BANK_BF16
+
+    def bank_create(self, slots, rows=None, format="f32"):
+        """fpc_bank_create_ex: a device-resident bank of `slots` key frames of up to `rows` keypoints each (default: the
+        capacity).  format "bf16" stores the rows in bf16 and matches on the bf16 matrix path: half the memory per frame,
+        distances within the rounding of the rows instead of fpc_match_frames' bits (include/fpc.h).  The only bank call
+        that allocates; one bank per engine."""
+        if format not in self.BANK_FORMATS:
+            raise ValueError("format must be one of %s, got %r" % (sorted(self.BANK_FORMATS), format))
+        _lib.check(self._l.fpc_bank_create_ex(self._ctx, int(slots), int(self.capacity if rows is None else rows),
+                                              self.BANK_FORMATS[format]), "fpc_bank_create_ex")
         v = _lib.FpcBankView()
         _lib.check(self._l.fpc_bank_get(self._ctx, ctypes.byref(v)), "fpc_bank_get")
+        fmt, ptr = ctypes.c_int(-1), ctypes.c_void_p()
+        _lib.check(self._l.fpc_bank_format(self._ctx, ctypes.byref(fmt), ctypes.byref(ptr)), "fpc_bank_format")
         self._bank = v
+        self._bank_format = (format, ptr.value)
         return v.bytes
 
     def bank_destroy(self):
@@ -610,19 +619,23 @@ class Engine:
         return v
 
     def bank_view(self):
-        """(desc float32 [slots,rows,D], xy int32 [slots,rows,2], count int32 [slots]) aliasing the bank's device memory
-        (fpc_bank_get); `bank_info()` has the sizes."""
+        """(desc float32 [slots,rows,D] -- bfloat16 for a "bf16" bank --, xy int32 [slots,rows,2], count int32 [slots])
+        aliasing the bank's device memory (fpc_bank_get / fpc_bank_format); `bank_info()` has the sizes."""
         v = self._bank_info()
         s, r, dd = v.slots, v.rows, v.desc_dim
-        desc = torch.as_tensor(_DevArray(v.desc, s * r * dd * 4), device=self.torch_device)
+        fmt, ptr = self._bank_format
+        elem, dtype = (2, torch.bfloat16) if fmt == "bf16" else (4, torch.float32)
+        desc = torch.as_tensor(_DevArray(ptr, s * r * dd * elem), device=self.torch_device)
         xy = torch.as_tensor(_DevArray(v.xy, s * r * 2 * 4), device=self.torch_device)
         count = torch.as_tensor(_DevArray(v.count, s * 4), device=self.torch_device)
-        return desc.view(torch.float32).view(s, r, dd), xy.view(torch.int32).view(s, r, 2), count.view(torch.int32)
+        return desc.view(dtype).view(s, r, dd), xy.view(torch.int32).view(s, r, 2), count.view(torch.int32)
 
     def bank_info(self):
-        """{"slots", "rows", "desc_dim", "chunk" (slots scored per pass), "bytes" (allocated, workspace included)}."""
+        """{"slots", "rows", "desc_dim", "chunk" (slots scored per pass), "bytes" (allocated, workspace included),
+        "format" ("f32" / "bf16")}."""
         v = self._bank_info()
-        return {"slots": v.slots, "rows": v.rows, "desc_dim": v.desc_dim, "chunk": v.chunk, "bytes": v.bytes}
+        return {"slots": v.slots, "rows": v.rows, "desc_dim": v.desc_dim, "chunk": v.chunk, "bytes": v.bytes,
+                "format": self._bank_format[0]}
 
     def bank_store(self, frame, slot):
         """fpc_bank_store: frame `frame` of the last detect into slot `slot` (its most confident `rows` keypoints), on the

@@ -520,6 +520,43 @@ int fpc_match_bank(fpc_ctx* ctx, int n, int cross_check, float max_dist, float r
 int fpc_homography_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev,
                         const fpc_ransac_params* params, float* H_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
 
+/* --- the bank in bf16: half the memory per stored frame, the score pass on the bf16 matrix path --------------------------
+ * fpc_bank_create_ex(format): FPC_BANK_F32 is fpc_bank_create, and everything stated above -- every bit-identity with
+ * fpc_match_frames included -- holds for it unchanged.  FPC_BANK_BF16 is an opt-in storage AND arithmetic format for
+ * ranking slots; an unknown format is FPC_E_INVALID, everything else is as in fpc_bank_create.  One bank per ctx, of one
+ * format.  fpc_bank_format: the format, and the descriptors as float* (FPC_BANK_F32) or bf16 bit patterns, uint16_t*
+ * (FPC_BANK_BF16), [slots][rows][D]; either output may be NULL, not both.  On a bf16 bank fpc_bank_get gives desc = NULL
+ * (no fp32 rows exist); its other fields are as above, and bytes includes the query workspace below.
+ *
+ * The contract of a FPC_BANK_BF16 bank:
+ *  - Store: fpc_bank_store / fpc_bank_store_rows round each fp32 component to bf16, round to nearest even (an overflow
+ *    becomes +-inf, a NaN the quiet NaN 0x7FC0, sign and payload dropped); 2 B per component.  norms[slot][row] is
+ *    computed in fp32 FROM THE ROUNDED values.  xy and count are as above.
+ *  - fpc_match_bank: one pass at the start of the call rounds the n query sets the same way into workspace that
+ *    fpc_bank_create_ex allocated (max_batch x capacity x D x 2 B, followed by a canary zone under FPC_PLAN_GUARD_ZONES);
+ *    their fp32 norms come from the rounded values.  With q~, t~ the rounded rows
+ *        d^2 = max(|q~|^2 + |t~|^2 - 2 q~.t~, 0)
+ *    the dot product accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (products of bf16 values are exact in fp32).
+ *    Everything behind d^2 is the rule above, by the same code: nearest / second nearest in (d^2 bits, index) order, the
+ *    cross check on exact column minima, max_dist, ratio, integer scores, best with ties to the lower slot, min_score.
+ *  - The table (match_dev, dist_dev) is computed in the SAME arithmetic against slot best[f]: the number of
+ *    match[f][i] >= 0 equals score[f][best[f]] exactly.  It is NOT bit-identical to fpc_match_frames on the fp32 rows:
+ *    d^2 differs from the fp32 value by the rounding of the rows (about 1e-3 on unit-norm rows at D = 128), and where two
+ *    train rows are closer to each other than that a row may take the other one.
+ *  - fpc_match_bank_guided works on it: the gate is the one stated below, a candidate pair's d^2 is the bf16 value above
+ *    with the same bits, so with a radius beyond the frame diagonal its output is bit-identical to the fpc_match_bank
+ *    table for that slot.  fpc_homography_bank reads xy and count only.  fpc_match_bank, fpc_homography_bank,
+ *    fpc_match_bank_guided, fpc_homography_bank needs no host call in between.
+ *  - Execution as above: asynchronous on the ctx stream, no allocation after create, no host synchronisation, counts and
+ *    slots read on the device.  Deterministic: selection is integer and order-free, the matrix instruction's internal
+ *    accumulation order is fixed by the hardware; repeated calls give bit-identical outputs.
+ *  - When to use it: to rank slots under max_dist or a ratio (tests/test_match_bank_bf16.py: on planted data the scores and
+ *    best equal the fp32 rule's).  The WARNING above about a bare cross check applies, and there the two formats differ. */
+#define FPC_BANK_F32  0
+#define FPC_BANK_BF16 1
+int fpc_bank_create_ex(fpc_ctx* ctx, int slots, int rows, int format);
+int fpc_bank_format(fpc_ctx* ctx, int* format, const void** desc);
+
 /* --- guided matching: the match once more, under the estimated homographies as a spatial gate ---------------------------
  * The first pass above is appearance-only: on repetitive texture a row takes a look-alike elsewhere in the image, and
  * RANSAC then discards the pair.  With one H per frame -- what fpc_homography_frames / fpc_homography_bank wrote, passed on
