@@ -4,11 +4,13 @@ integer pixels with random unit descriptors, frame f the key's pixels under a pl
 shift and a little perspective that grow with f), rounded, rows that leave the frame replaced by unrelated ones, in random
 order (device results are sorted by confidence, which is no spatial order either).  The rows are written into the
 library's device results behind a fpc_get_points call.  Radii 4, 16 and 1e4 px under the planted H.
-    python experiments/harness/match_guided_bench.py [reps]
+    python experiments/harness/match_guided_bench.py [reps] [--cells]
 prints one JSON line per (K, radius): the median of 5 runs of `reps` (default 50) calls each by HIP events on the ctx stream
 with the runs' min and max, for the guided call and for fpc_match_frames; the share of (64-row strip, 64-row train tile)
 pairs without a candidate (counted on the host from the gate, frames 0, 11, 21, 31), which is the share of tiles the
-kernel skips, and its complement, the fraction of fpc_match_frames' MFMAs the guided kernel executes."""
+kernel skips, and its complement, the fraction of fpc_match_frames' MFMAs the guided kernel executes.
+--cells adds fpc_match_frames_guided_cells beside them (same inputs, same run, interleaved): its time, its ratio to the
+guided call, and the share of (strip, tile) pairs it visited, from the call's own counters over all 32 frames."""
 import json
 import os
 import statistics
@@ -22,7 +24,9 @@ from fpc_amd.engine import Engine
 
 H, W, N = 480, 640, 32
 RUNS = 5
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+CELLS = "--cells" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--cells"]
+reps = int(argv[0]) if argv else 50
 
 
 def spread(v):
@@ -106,13 +110,18 @@ for K in (500, 1000, 2000, 4500):
             assert lib.fpc_match_frames_guided(ctx, N, 0, kd.data_ptr(), kc.data_ptr(), kx.data_ptr(), hdev.data_ptr(), radius,
                                                1, 0.0, 0.0, m.data_ptr(), d.data_ptr()) == 0
 
-        for fn in (guided, plain):
+        def cells():
+            assert lib.fpc_match_frames_guided_cells(ctx, N, 0, kd.data_ptr(), kc.data_ptr(), kx.data_ptr(), hdev.data_ptr(),
+                                                     radius, 1, 0.0, 0.0, m.data_ptr(), d.data_ptr(), None) == 0
+
+        calls = (("guided", guided), ("plain", plain)) + ((("cells", cells),) if CELLS else ())
+        for _, fn in calls:
             for _ in range(3):
                 fn()
         e.sync()
-        times = {"guided": [], "plain": []}
+        times = {name: [] for name, _ in calls}
         for _ in range(RUNS):
-            for name, fn in (("guided", guided), ("plain", plain)):
+            for name, fn in calls:
                 t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 t0.record(st)
                 for _ in range(reps):
@@ -121,8 +130,16 @@ for K in (500, 1000, 2000, 4500):
                 e.sync()
                 times[name].append(t0.elapsed_time(t1) / reps)
         share = skipped_share(xy, key_xy, hs, radius)
-        print(json.dumps({"frames": N, "K": K, "radius": radius, "guided_ms": spread(times["guided"]),
-                          "match_frames_ms": spread(times["plain"]),
-                          "ratio": round(statistics.median(times["guided"]) / statistics.median(times["plain"]), 3),
-                          "tiles_skipped": round(share, 4), "executed_mfma_fraction": round(1.0 - share, 4)}), flush=True)
+        row = {"frames": N, "K": K, "radius": radius, "guided_ms": spread(times["guided"]),
+               "match_frames_ms": spread(times["plain"]),
+               "ratio": round(statistics.median(times["guided"]) / statistics.median(times["plain"]), 3),
+               "tiles_skipped": round(share, 4), "executed_mfma_fraction": round(1.0 - share, 4)}
+        if CELLS:
+            _, _, stats = e.match_frames_guided_cells_async(N, hdev, radius, key=(kd, kc), key_xy=(kx, kc), stats=True)
+            e.sync()
+            stats = stats.cpu().numpy().astype(np.int64)
+            row.update({"cells_ms": spread(times["cells"]),
+                        "cells_over_guided": round(statistics.median(times["cells"]) / statistics.median(times["guided"]), 3),
+                        "cells_visited_share": round(float(stats[:, 0].sum()) / float(stats[:, 1].sum()), 4)})
+        print(json.dumps(row), flush=True)
     e.close()

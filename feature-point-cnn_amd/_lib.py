@@ -33,6 +33,7 @@ SYMBOLS = [
     "fpc_bank_create", "fpc_bank_destroy", "fpc_bank_get", "fpc_bank_store", "fpc_bank_store_rows", "fpc_bank_clear",
     "fpc_match_bank", "fpc_homography_bank", "fpc_bank_create_ex", "fpc_bank_format",
     "fpc_match_frames_guided", "fpc_match_bank_guided",
+    "fpc_cell_order", "fpc_match_frames_guided_cells", "fpc_match_bank_guided_cells",
 ]
 
 ABI_VERSION = 4
@@ -178,6 +179,11 @@ def load():
     l.fpc_match_frames_guided.argtypes = [vp, ci, ci, vp, vp, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float,
                                           vp, vp]
     l.fpc_match_bank_guided.argtypes = [vp, ci, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float, vp, vp]
+    l.fpc_cell_order.argtypes = [vp, vp, vp, ci, ci, vp]
+    l.fpc_match_frames_guided_cells.argtypes = [vp, ci, ci, vp, vp, vp, vp, ctypes.c_float, ci, ctypes.c_float,
+                                                ctypes.c_float, vp, vp, vp]
+    l.fpc_match_bank_guided_cells.argtypes = [vp, ci, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float, vp, vp,
+                                              vp]
     l.fpc_sample_descriptors.argtypes = [vp, vp, vp, ci, vp]
     l.fpc_read_activation.argtypes = [vp, ctypes.c_char_p, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     l.fpc_plan_hash.argtypes = [vp]

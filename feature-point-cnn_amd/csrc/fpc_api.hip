@@ -38,6 +38,7 @@
 #include "match_bank.h"
 #include "match_bank_bf16.h"
 #include "match_guided.h"
+#include "match_guided_cells.h"
 #include "ransac_homography.h"
 #include "homography.h"
 #include "weights.h"
@@ -571,6 +572,10 @@ struct fpc_ctx {
   float4* hf_pairs = nullptr;
   int32_t *hf_row = nullptr, *hf_np = nullptr;
   unsigned long long* hf_best = nullptr;
+  // cell-ordered guided matching (fpc_match_*_guided_cells, match_guided_cells.h): the orders of the query sets and of the
+  // train sets [B][cap] each, the boxes of their runs of 64 ordered rows [2][B][ceil(cap / 64)] -- behind the RANSAC buffers
+  int32_t *mgc_perm_q = nullptr, *mgc_perm_t = nullptr;
+  int4* mgc_box = nullptr;
   // key-frame bank (fpc_bank_*, fpc_match_bank, fpc_homography_bank): one allocation of its own, made by fpc_bank_create --
   // storage, per-slot norms and fpc_match_bank's workspace, carved with canary zones in a FPC_PLAN_GUARD_ZONES context
   char* bank_slab = nullptr;
@@ -1377,6 +1382,8 @@ static int build_vgg_plan(fpc_ctx* c) {
   const size_t o_mfc = cv.take<unsigned long long>((size_t)B * c->cap);
   const size_t o_hfp = cv.take<float4>((size_t)B * c->cap), o_hfr = cv.take<int32_t>((size_t)B * c->cap);
   const size_t o_hfn = cv.take<int32_t>(B), o_hfb = cv.take<unsigned long long>(B);
+  const size_t o_gpq = cv.take<int32_t>((size_t)B * c->cap), o_gpt = cv.take<int32_t>((size_t)B * c->cap);
+  const size_t o_gbx = cv.take<int4>((size_t)2 * B * ((c->cap + 63) / 64));
   cv.finish();
   c->slab_bytes = cv.off;
   if (hipMalloc((void**)&c->slab, c->slab_bytes) != hipSuccess) {
@@ -1409,6 +1416,9 @@ static int build_vgg_plan(fpc_ctx* c) {
   c->hf_row = reinterpret_cast<int32_t*>(c->slab + o_hfr);
   c->hf_np = reinterpret_cast<int32_t*>(c->slab + o_hfn);
   c->hf_best = reinterpret_cast<unsigned long long*>(c->slab + o_hfb);
+  c->mgc_perm_q = reinterpret_cast<int32_t*>(c->slab + o_gpq);
+  c->mgc_perm_t = reinterpret_cast<int32_t*>(c->slab + o_gpt);
+  c->mgc_box = reinterpret_cast<int4*>(c->slab + o_gbx);
 
   size_t bo = BLOB_HEADER_FLOATS;
   c->ops.clear();
@@ -1601,6 +1611,8 @@ static int build_plan(fpc_ctx* c) {
   const size_t o_mfc = cv.take<unsigned long long>(de ? (size_t)B * c->cap : 64);
   const size_t o_hfp = cv.take<float4>((size_t)B * c->cap), o_hfr = cv.take<int32_t>((size_t)B * c->cap);
   const size_t o_hfn = cv.take<int32_t>(B), o_hfb = cv.take<unsigned long long>(B);
+  const size_t o_gpq = cv.take<int32_t>(de ? (size_t)B * c->cap : 64), o_gpt = cv.take<int32_t>(de ? (size_t)B * c->cap : 64);
+  const size_t o_gbx = cv.take<int4>(de ? (size_t)2 * B * ((c->cap + 63) / 64) : 64);
   cv.finish();
   c->slab_bytes = cv.off;
   if (hipMalloc((void**)&c->slab, c->slab_bytes) != hipSuccess) {
@@ -1637,6 +1649,9 @@ static int build_plan(fpc_ctx* c) {
   c->hf_row = reinterpret_cast<int32_t*>(c->slab + o_hfr);
   c->hf_np = reinterpret_cast<int32_t*>(c->slab + o_hfn);
   c->hf_best = reinterpret_cast<unsigned long long*>(c->slab + o_hfb);
+  c->mgc_perm_q = reinterpret_cast<int32_t*>(c->slab + o_gpq);
+  c->mgc_perm_t = reinterpret_cast<int32_t*>(c->slab + o_gpt);
+  c->mgc_box = reinterpret_cast<int4*>(c->slab + o_gbx);
 
   // ---- ops
   size_t bo = BLOB_HEADER_FLOATS;  // blob offset in floats (the tag of the packed format comes first)
@@ -4231,6 +4246,93 @@ int fpc_match_bank_guided(fpc_ctx* c, int n, const int32_t* slot, const float* H
     return FPC_OK;
   }
   return match_guided_launch(c, a, g, n, max_dist, ratio, match, dist);   // (grid y = n: the bank's norms are its own)
+}
+
+// ---- cell-ordered guided matching (include/fpc.h; kernels in match_guided_cells.h) ------------------------------------------
+// 32-px cells wherever the order is public; a frame of more cells than the order kernel's histogram holds (beyond
+// 16.7 MPx) is ordered in coarser cells by the guided calls, whose output does not depend on the order.
+static CellOrderArgs cell_order_args(fpc_ctx* c, int shift) {
+  CellOrderArgs o{};
+  o.shift = shift;
+  o.CX = (c->W + (1 << shift) - 1) >> shift;
+  o.CY = (c->H + (1 << shift) - 1) >> shift;
+  return o;
+}
+
+int fpc_cell_order(fpc_ctx* c, const int32_t* xy, const int32_t* n, int sets, int stride, int32_t* perm) {
+  if (!c || !xy || !n || !perm || sets < 1 || stride < 1) return FPC_E_INVALID;
+  CellOrderArgs o = cell_order_args(c, 5);
+  if ((long long)o.CX * o.CY > MGC_MAX_CELLS) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  o.xy = xy; o.n = n; o.stride = o.out_stride = stride; o.perm = perm;
+  hipLaunchKernelGGL(cell_order_kernel, dim3(sets), dim3(256), 0, c->stream, o);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+// fpc_match_*_guided's sequence with the order pass in front of the strip kernel.  The train sets: the key once (tsets = 1),
+// the bank's slot of every frame (a.key_slot), none under FPC_PAIR_PREVIOUS without a key (frame f - 1's query order).
+static int match_guided_cells_launch(fpc_ctx* c, MatchFramesArgs a, const MatchGuidedArgs& g, int norm_blocks, float max_dist,
+                                     float ratio, int32_t* match, float* dist, int32_t* stats) {
+  const int nbox = (c->cap + 63) / 64;
+  int shift = 5;
+  while ((long long)((c->W + (1 << shift) - 1) >> shift) * ((c->H + (1 << shift) - 1) >> shift) > MGC_MAX_CELLS) ++shift;
+  if (a.cross_check)
+    HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * a.n * c->cap, c->stream));
+  if (stats) HIPCHECK(hipMemsetAsync(stats, 0, sizeof(int32_t) * 2 * a.n, c->stream));
+  hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, norm_blocks), dim3(256), 0, c->stream, a);
+  CellOrderArgs o = cell_order_args(c, shift);
+  o.xy = c->xy; o.n = c->count; o.stride = o.out_stride = c->cap;
+  o.perm = c->mgc_perm_q; o.box = c->mgc_box; o.box_stride = nbox;
+  hipLaunchKernelGGL(cell_order_kernel, dim3(a.n), dim3(256), 0, c->stream, o);
+  int4* box_t = c->mgc_box + (size_t)c->B * nbox;
+  if (a.key_slot || a.key) {
+    CellOrderArgs t = cell_order_args(c, shift);
+    t.xy = g.key_xy; t.out_stride = c->cap; t.perm = c->mgc_perm_t; t.box = box_t; t.box_stride = nbox;
+    if (a.key_slot) {
+      t.n = a.bank_count; t.slot = a.key_slot; t.nslots = a.bank_slots; t.stride = a.bank_rows;
+    } else {
+      t.n = a.nkey; t.stride = c->cap;
+    }
+    hipLaunchKernelGGL(cell_order_kernel, dim3(a.key_slot ? a.n : 1), dim3(256), 0, c->stream, t);
+  }
+  const MatchCellsArgs m{c->mgc_perm_q, c->mgc_box, c->mgc_perm_t, box_t, nbox, stats};
+  hipLaunchKernelGGL(match_guided_cells_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, a.n), dim3(256), 0, c->stream, a, g, m);
+  hipLaunchKernelGGL(match_guided_finalize_kernel, dim3((c->cap + 255) / 256, a.n), dim3(256), 0, c->stream, a, max_dist,
+                     ratio, match, dist);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_match_frames_guided_cells(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey,
+                                  const int32_t* key_xy, const float* H, float radius, int cross_check, float max_dist,
+                                  float ratio, int32_t* match, float* dist, int32_t* stats) {
+  if (!c || !guided_options_ok(H, radius, max_dist, ratio, match) ||
+      (pairing != FPC_PAIR_KEY && pairing != FPC_PAIR_PREVIOUS) || (pairing == FPC_PAIR_KEY && (!key || !key_xy)) ||
+      (key && !key_xy))
+    return FPC_E_INVALID;
+  if (int rc = match_frames_check(c, n, key, nkey)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  MatchFramesArgs a = match_frames_args(c, n, key, nkey);
+  a.pairing = pairing;
+  a.cross_check = cross_check != 0;
+  const MatchGuidedArgs g{H, c->xy, key ? key_xy : nullptr, (double)radius * (double)radius};
+  return match_guided_cells_launch(c, a, g, n + 1, max_dist, ratio, match, dist, stats);
+}
+
+int fpc_match_bank_guided_cells(fpc_ctx* c, int n, const int32_t* slot, const float* H, float radius, int cross_check,
+                                float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
+  if (!c || !c->bank_slab || !slot || !guided_options_ok(H, radius, max_dist, ratio, match)) return FPC_E_INVALID;
+  if (c->bank_format != FPC_BANK_F32) return FPC_E_INVALID;    // (the bf16 bank's ordered strip: not built yet)
+  if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const BankArgs& b = c->bank;
+  MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
+  a.cross_check = cross_check != 0;
+  a.key = b.desc; a.key_slot = slot; a.bank_norms = b.norms; a.bank_count = b.count;
+  a.bank_rows = b.rows; a.bank_slots = b.slots;
+  const MatchGuidedArgs g{H, c->xy, b.xy, (double)radius * (double)radius};
+  return match_guided_cells_launch(c, a, g, n, max_dist, ratio, match, dist, stats);   // (grid y = n: the bank's norms are its own)
 }
 
 int fpc_results(fpc_ctx* c, fpc_device_results* out) {

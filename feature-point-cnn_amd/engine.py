@@ -778,6 +778,76 @@ class Engine:
         """match_bank_guided_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
         return self._per_frame(n, *self.match_bank_guided_async(n, slot, H, radius, cross_check, max_dist, ratio))
 
+    # -- cell-ordered guided matching (fpc_cell_order / fpc_match_*_guided_cells): the same tables, fewer tiles -------
+    def cell_order_async(self, xy, counts):
+        """fpc_cell_order: xy int32 [sets,stride,2], counts int32 [sets] (device tensors or host arrays) -> perm int32
+        [sets,stride] on the device: every set's rows in the stable order by 32-px cell (include/fpc.h); entries past a
+        set's count are unspecified.  Does not synchronise."""
+        xy = torch.as_tensor(xy).to(self.torch_device, torch.int32).contiguous()
+        counts = torch.as_tensor(counts).to(self.torch_device, torch.int32).contiguous()
+        if xy.dim() != 3 or xy.shape[2] != 2 or tuple(counts.shape) != (xy.shape[0],) or xy.shape[0] < 1 or xy.shape[1] < 1:
+            raise ValueError("xy must be [sets,stride,2] and counts [sets]")
+        perm = torch.empty(tuple(xy.shape[:2]), dtype=torch.int32, device=self.torch_device)
+        self._enqueue(lambda: _lib.check(self._l.fpc_cell_order(
+            self._ctx, xy.data_ptr(), counts.data_ptr(), int(xy.shape[0]), int(xy.shape[1]), perm.data_ptr()),
+            "fpc_cell_order"))
+        xy.record_stream(self.torch_stream())
+        counts.record_stream(self.torch_stream())
+        return perm
+
+    def match_frames_guided_cells_async(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True,
+                                        max_dist=0.0, ratio=0.0, stats=False):
+        """fpc_match_frames_guided_cells: match_frames_guided_async's arguments and, bit for bit, its (match, dist), from
+        the cell-ordered kernel that visits only the tiles the gate can reach.  stats=True: (match, dist, stats int32
+        [n,2]: per frame (strip, tile) pairs visited, and the pairs there are).  Does not synchronise."""
+        if pairing not in self.PAIRINGS:
+            raise ValueError("pairing must be one of %s, got %r" % (sorted(self.PAIRINGS), pairing))
+        kd, kc = self._key(key)
+        kx, _ = self._key_xy(key_xy)
+        if kd is not None and (kx is None or kx.shape[0] < kd.shape[0]):
+            raise ValueError("a key needs key_xy with a row for each of its rows")
+        hm = self._guided_h(n, H)
+        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
+        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device)
+        st = torch.empty((n, 2), dtype=torch.int32, device=self.torch_device) if stats else None
+        self._enqueue(lambda: _lib.check(self._l.fpc_match_frames_guided_cells(
+            self._ctx, n, self.PAIRINGS[pairing], kd.data_ptr() if kd is not None else None,
+            kc.data_ptr() if kc is not None else None, kx.data_ptr() if kx is not None else None, hm.data_ptr(),
+            float(radius), int(bool(cross_check)), float(max_dist), float(ratio), m.data_ptr(), d.data_ptr(),
+            st.data_ptr() if stats else None), "fpc_match_frames_guided_cells"))
+        for t in (kd, kc, kx, hm):
+            if t is not None:
+                t.record_stream(self.torch_stream())
+        return (m, d, st) if stats else (m, d)
+
+    def match_frames_guided_cells(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True,
+                                  max_dist=0.0, ratio=0.0):
+        """match_frames_guided_cells_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        return self._per_frame(n, *self.match_frames_guided_cells_async(n, H, radius, key, key_xy, pairing, cross_check,
+                                                                        max_dist, ratio))
+
+    def match_bank_guided_cells_async(self, n, slot, H, radius, cross_check=True, max_dist=0.0, ratio=0.0, stats=False):
+        """fpc_match_bank_guided_cells: match_bank_guided_async's arguments and, bit for bit, its (match, dist) on an
+        "f32" bank (a "bf16" bank is refused); stats as in match_frames_guided_cells_async.  Does not synchronise."""
+        self._bank_info()
+        if slot.device != self.torch_device or slot.dtype != torch.int32 or tuple(slot.shape) != (n,):
+            raise ValueError("slot must be a device tensor int32 [n]")
+        slot = slot.contiguous()
+        hm = self._guided_h(n, H)
+        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
+        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device)
+        st = torch.empty((n, 2), dtype=torch.int32, device=self.torch_device) if stats else None
+        self._enqueue(lambda: _lib.check(self._l.fpc_match_bank_guided_cells(
+            self._ctx, n, slot.data_ptr(), hm.data_ptr(), float(radius), int(bool(cross_check)), float(max_dist),
+            float(ratio), m.data_ptr(), d.data_ptr(), st.data_ptr() if stats else None), "fpc_match_bank_guided_cells"))
+        slot.record_stream(self.torch_stream())
+        hm.record_stream(self.torch_stream())
+        return (m, d, st) if stats else (m, d)
+
+    def match_bank_guided_cells(self, n, slot, H, radius, cross_check=True, max_dist=0.0, ratio=0.0):
+        """match_bank_guided_cells_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        return self._per_frame(n, *self.match_bank_guided_cells_async(n, slot, H, radius, cross_check, max_dist, ratio))
+
     # -- timing ----------------------------------------------------------------------
     def check_guards(self):
         """Contexts created with plan_flags=["guard_zones"] (a test facility): waits for the device and returns the number

@@ -595,6 +595,46 @@ int fpc_match_frames_guided(fpc_ctx* ctx, int n, int pairing, const float* key_d
 int fpc_match_bank_guided(fpc_ctx* ctx, int n, const int32_t* slot_dev, const float* H_dev, float radius, int cross_check,
                           float max_dist, float ratio, int32_t* match_dev, float* dist_dev);
 
+/* --- cell-ordered guided matching: the guided match, visiting only the tiles the gate can reach ---------------------------
+ * fpc_match_frames_guided / fpc_match_bank_guided test the gate against every 64 x 64 tile of (query rows, train rows);
+ * rows come in confidence order, so hardly a tile is without a candidate.  The calls below read both sides in a spatial
+ * order and skip the tiles whose bounding box no row of the strip can reach within the radius.
+ *
+ * The order (fpc_cell_order): for a point set of cnt rows with integer pixels (x, y) in a context of frame size H x W,
+ *     CX = ceil(W / 32), CY = ceil(H / 32),
+ *     cx = clamp(x >> 5, 0, CX - 1), cy = clamp(y >> 5, 0, CY - 1)   (arithmetic shift: rows may lie outside the frame),
+ *     cell = cy CX + cx,
+ * perm is the stable order by cell: ascending (cell, original index).  fpc_cell_order orders `sets` point sets: set s is
+ * xy_dev + s stride 2 (int32 [stride][2]), its count n_dev[s] is read on the device and clamped to [0, stride];
+ * perm_dev int32 [sets][stride], entries cnt <= i < stride of a row are unspecified.  It is the kernel the guided calls
+ * below run: deterministic (no atomic decides a position), asynchronous on the ctx stream, no allocation.
+ * FPC_E_INVALID: a NULL argument, sets < 1, stride < 1, a frame of more than 16384 cells (16.7 MPx).
+ *
+ * fpc_match_frames_guided_cells / fpc_match_bank_guided_cells: the arguments of fpc_match_frames_guided /
+ * fpc_match_bank_guided plus stats_dev.
+ *  - For every argument set those calls accept, match_dev and dist_dev are BIT-IDENTICAL to what they write: indices are
+ *    original row indices; rows past the count, frames without a train set, slots outside the bank and empty slots, a
+ *    zero or non-finite H and w <= 0 included.  (The result is a function of the candidate set and of each candidate
+ *    pair's d^2 bits: nearest and second nearest are the two smallest (d^2 bits, index) keys, the column minimum the
+ *    smallest, whatever order rows are visited in.  In a frame of more than 16384 cells the calls order by coarser
+ *    cells; the output is the same.)
+ *  - stats_dev int32 [n][2], or NULL: per frame {(strip, tile) pairs visited, strips x tiles where both sets are
+ *    non-empty}, a strip being 64 ordered query rows and a tile 64 ordered train rows.  Deterministic.
+ *  - Execution: as for the existing calls -- asynchronous on the ctx stream, no host synchronisation, no copy, no
+ *    allocation (orders and boxes live in the workspace carved at fpc_create; nothing is added to the bank's allocation),
+ *    every count and slot read on the device.  fpc_match_frames, fpc_homography_frames, fpc_match_frames_guided_cells,
+ *    fpc_homography_frames needs no host call in between.  Per call: the order of the query sets (frames 0 .. n-1) and of
+ *    the train sets (the key once; under FPC_PAIR_PREVIOUS frame f-1's query order is reused; the slot of every frame).
+ * FPC_E_INVALID (nothing is written, stats_dev included): everything fpc_match_frames_guided / fpc_match_bank_guided
+ * refuse; the bank variant on a FPC_BANK_BF16 bank (that format's ordered strip is the follow-up). */
+int fpc_cell_order(fpc_ctx* ctx, const int32_t* xy_dev, const int32_t* n_dev, int sets, int stride, int32_t* perm_dev);
+int fpc_match_frames_guided_cells(fpc_ctx* ctx, int n, int pairing, const float* key_dev, const int32_t* nkey_dev,
+                                  const int32_t* key_xy_dev, const float* H_dev, float radius, int cross_check,
+                                  float max_dist, float ratio, int32_t* match_dev, float* dist_dev, int32_t* stats_dev);
+int fpc_match_bank_guided_cells(fpc_ctx* ctx, int n, const int32_t* slot_dev, const float* H_dev, float radius,
+                                int cross_check, float max_dist, float ratio, int32_t* match_dev, float* dist_dev,
+                                int32_t* stats_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
