@@ -10,6 +10,12 @@ from HIP events on the ctx stream and wall-clock, the loop wall-clock; the bank'
 2 * n * S * K * K * D, the FLOPs the score pass's MFMAs execute.  With --format bf16 (fpc_bank_create_ex, FPC_BANK_BF16) every
 point times the fp32 bank first and the bf16 bank of the same frames right after it, in the same process on the same inputs,
 and prints both with their ratio and whether the two banks name the same slots; the loop (which needs fp32 rows) is left out.
+With --topk K [K ...] every point times verified relocalisation instead: fpc_match_bank_topk + fpc_homography_bank_topk (k = K)
+against the host loop of existing calls they replace -- fpc_match_bank for the scores, then for each j < K one
+fpc_match_bank_guided (identity H, a radius beyond the frame) and one fpc_homography_bank with column j of the candidates
+(taken from the new call and laid out per round before the clock starts, which favours the loop) -- on the same inputs in the
+same process, HIP events on the ctx stream, the median of 5 runs with min and max; n = 1 and 32, max_keypoints 1000 and 2000,
+S = 16.  not_slower: the new calls' fastest run against the loop's slowest, i.e. beyond the runs' spread.
 The executed-MFMA fraction needs the kernel's own duration:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python experiments/harness/match_bank_bench.py 3
 then bank_score_kernel's mean duration per case against 157.3 TF (bank_score_bf16_kernel: against 2 516 TF)."""
@@ -31,6 +37,7 @@ RUNS = 5
 ap = argparse.ArgumentParser()
 ap.add_argument("reps", nargs="?", type=int, default=5)
 ap.add_argument("--format", choices=("f32", "bf16"), default="f32")
+ap.add_argument("--topk", type=int, nargs="+", default=None, metavar="K")
 args = ap.parse_args()
 reps = args.reps
 sd = synth.make_state_dict(0, dustbin_bias=7.0)
@@ -40,9 +47,88 @@ def spread(v):
     return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
 
 
+
+
+def events_ms(e, st, fn):
+    """The median, min and max over RUNS runs of `reps` calls of fn, from HIP events on the ctx stream."""
+    fn()
+    e.sync()
+    ev = []
+    for _ in range(RUNS):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record(st)
+        for _ in range(reps):
+            fn()
+        t1.record(st)
+        e.sync()
+        ev.append(t0.elapsed_time(t1) / reps)
+    return spread(ev)
+
+
+def topk_point(e, n, K, S):
+    """One (n, K, S) point of --topk: the bank of `format`, one JSON line per k."""
+    import ctypes
+    lib, ctx, cap = e._l, e._ctx, e.capacity
+    st = e.torch_stream()
+    e.bank_create(S, K, format=args.format)
+    for s in range(S):
+        e.bank_store(s % n, s)
+    ws_bytes = e.bank_topk_reserve(max(args.topk))
+    params = e._ransac_params({})
+    ident = torch.eye(3, device="cuda").reshape(1, 9).repeat(n, 1).contiguous()
+    score = torch.empty((n, S), dtype=torch.int32, device="cuda")
+    best = torch.empty((n,), dtype=torch.int32, device="cuda")
+    for k in args.topk:
+        cs = torch.empty((n, k), dtype=torch.int32, device="cuda")
+        csc = torch.empty((n, k), dtype=torch.int32, device="cuda")
+        m = torch.empty((n, k, cap), dtype=torch.int32, device="cuda")
+        d = torch.empty((n, k, cap), dtype=torch.float32, device="cuda")
+        hm = torch.empty((n, k, 9), dtype=torch.float32, device="cuda")
+        ni = torch.empty((n, k), dtype=torch.int32, device="cuda")
+        mask = torch.empty((n, k, cap), dtype=torch.uint8, device="cuda")
+        pick = torch.empty((n,), dtype=torch.int32, device="cuda")
+        m1 = torch.empty((k, n, cap), dtype=torch.int32, device="cuda")
+        d1 = torch.empty((k, n, cap), dtype=torch.float32, device="cuda")
+        h1 = torch.empty((k, n, 9), dtype=torch.float32, device="cuda")
+        n1 = torch.empty((k, n), dtype=torch.int32, device="cuda")
+        k1 = torch.empty((k, n, cap), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+
+        def new():
+            assert lib.fpc_match_bank_topk(ctx, n, k, 1, 0.7, 0.0, 0, score.data_ptr(), cs.data_ptr(), csc.data_ptr(),
+                                           m.data_ptr(), d.data_ptr()) == 0
+            assert lib.fpc_homography_bank_topk(ctx, n, k, cs.data_ptr(), m.data_ptr(), ctypes.byref(params), hm.data_ptr(),
+                                                ni.data_ptr(), mask.data_ptr(), pick.data_ptr(), best.data_ptr()) == 0
+
+        new()
+        e.sync()
+        cols = cs.t().contiguous()                      # the candidates of round j, as the loop's slot_dev
+        torch.cuda.synchronize()
+
+        def rounds():
+            for j in range(k):
+                assert lib.fpc_match_bank_guided(ctx, n, cols[j].data_ptr(), ident.data_ptr(), 1e4, 1, 0.7, 0.0,
+                                                 m1[j].data_ptr(), d1[j].data_ptr()) == 0
+                assert lib.fpc_homography_bank(ctx, n, cols[j].data_ptr(), m1[j].data_ptr(), ctypes.byref(params),
+                                               h1[j].data_ptr(), n1[j].data_ptr(), k1[j].data_ptr()) == 0
+
+        def loop():
+            assert lib.fpc_match_bank(ctx, n, 1, 0.7, 0.0, 0, score.data_ptr(), best.data_ptr(), None, None) == 0
+            rounds()
+
+        t_new, t_loop, t_rounds = events_ms(e, st, new), events_ms(e, st, loop), events_ms(e, st, rounds)
+        same = bool((h1.permute(1, 0, 2).view(torch.int32) == hm.view(torch.int32)).all()) and \
+            bool((m1.permute(1, 0, 2) == m).all()) and bool((n1.t() == ni).all())
+        print(json.dumps({"frames": n, "K": K, "slots": S, "format": args.format, "topk": k, "workspace_bytes": ws_bytes,
+                          "new_ms": t_new, "loop_ms": t_loop, "loop_rounds_only_ms": t_rounds,
+                          "loop_over_new": round(t_loop["median"] / t_new["median"], 2),
+                          "not_slower": t_new["min"] <= t_loop["max"], "same_bits": same}), flush=True)
+    e.bank_destroy()
+
+
 for n in (1, 32):
     frames = torch.from_numpy(synth.make_batch(0, n, H, W)).cuda().contiguous()
-    for K in (500, 1000, 2000, 4500):
+    for K in ((1000, 2000) if args.topk else (500, 1000, 2000, 4500)):
         e = Engine(H, W, max_batch=n, conf_thresh=1e-6, max_keypoints=K)
         e.load_state_dict(sd)
         torch.cuda.synchronize()
@@ -52,6 +138,10 @@ for n in (1, 32):
         lib, ctx, cap, dim = e._l, e._ctx, e.capacity, e.desc_dim
         st = e.torch_stream()
         for S in (16, 64):
+            if args.topk:
+                if S == 16:
+                    topk_point(e, n, K, S)
+                continue
             if args.format == "bf16":
                 out = {"frames": n, "K": K, "slots": S}
                 answers = []

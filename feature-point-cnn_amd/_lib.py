@@ -34,6 +34,7 @@ SYMBOLS = [
     "fpc_match_bank", "fpc_homography_bank", "fpc_bank_create_ex", "fpc_bank_format",
     "fpc_match_frames_guided", "fpc_match_bank_guided",
     "fpc_cell_order", "fpc_match_frames_guided_cells", "fpc_match_bank_guided_cells",
+    "fpc_bank_topk_reserve", "fpc_match_bank_topk", "fpc_homography_bank_topk",
 ]
 
 ABI_VERSION = 4
@@ -84,6 +85,7 @@ class FpcRansacParams(ctypes.Structure):
 
 
 BANK_MAX_SLOTS = 1024         # include/fpc.h FPC_BANK_MAX_SLOTS
+BANK_TOPK_MAX = 16            # include/fpc.h FPC_BANK_TOPK_MAX
 
 
 class FpcBankView(ctypes.Structure):
@@ -184,6 +186,9 @@ def load():
                                                 ctypes.c_float, vp, vp, vp]
     l.fpc_match_bank_guided_cells.argtypes = [vp, ci, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float, vp, vp,
                                               vp]
+    l.fpc_bank_topk_reserve.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_size_t)]
+    l.fpc_match_bank_topk.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp, vp]
+    l.fpc_homography_bank_topk.argtypes = [vp, ci, ci, vp, vp, rp, vp, vp, vp, vp, vp]
     l.fpc_sample_descriptors.argtypes = [vp, vp, vp, ci, vp]
     l.fpc_read_activation.argtypes = [vp, ctypes.c_char_p, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     l.fpc_plan_hash.argtypes = [vp]

@@ -40,6 +40,7 @@
 #include "match_guided.h"
 #include "match_guided_cells.h"
 #include "ransac_homography.h"
+#include "match_bank_topk.h"
 #include "homography.h"
 #include "weights.h"
 
@@ -584,6 +585,15 @@ struct fpc_ctx {
   int bank_format = FPC_BANK_F32;                              // FPC_BANK_BF16: bank.desc is null, the rows are bank16.desc
   BankBf16Args bank16{};                                       // (match_bank_bf16.h)
   std::vector<std::pair<size_t, size_t>> bank_guards;          // (offset, bytes) of the canary zones in bank_slab
+  // top-K candidates of the bank (fpc_bank_topk_reserve, match_bank_topk.h): a third allocation, made by that call and
+  // freed with the bank -- the pair tables of max_batch x kmax (frame, candidate) pairs and the RANSAC workspace (pair
+  // lists, rows, counts, best keys) of as many problems
+  char* topk_slab = nullptr;
+  BankTopkArgs topk{};
+  float4* topk_pairs = nullptr;
+  int32_t *topk_row = nullptr, *topk_np = nullptr;
+  unsigned long long* topk_best = nullptr;
+  std::vector<std::pair<size_t, size_t>> topk_guards;          // (offset, bytes) of the canary zones in topk_slab
   int pts_n = 0;                     // frames of the last call that produced keypoints (fpc_detect*, fpc_get_points)
   bool pts_desc = false;             // ... and whether it sampled their descriptors
 
@@ -3214,6 +3224,7 @@ void fpc_destroy(fpc_ctx* c) {
   }
   if (c->slab) hipFree(c->slab);
   if (c->bank_slab) hipFree(c->bank_slab);
+  if (c->topk_slab) hipFree(c->topk_slab);
   if (c->blob) hipFree(c->blob);
   if (c->u8stage) hipFree(c->u8stage);
   if (c->ha_ws) hipFree(c->ha_ws);
@@ -3323,6 +3334,10 @@ int fpc_check_guards(fpc_ctx* c, long long* bad_words) {
   for (const auto& z : c->bank_guards) {      // the key-frame bank's zones (fpc_bank_create)
     const size_t n = z.second / 4;
     guard_count_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<const uint32_t*>(c->bank_slab + z.first), n, GUARD_PATTERN, d);
+  }
+  for (const auto& z : c->topk_guards) {      // the top-K workspace's zones (fpc_bank_topk_reserve)
+    const size_t n = z.second / 4;
+    guard_count_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<const uint32_t*>(c->topk_slab + z.first), n, GUARD_PATTERN, d);
   }
   unsigned long long h = 0;
   const hipError_t e1 = hipStreamSynchronize(c->stream);
@@ -4039,6 +4054,12 @@ int fpc_bank_destroy(fpc_ctx* c) {
   c->bank_slab = nullptr;
   c->bank_bytes = 0;
   c->bank_guards.clear();
+  if (c->topk_slab) {                                           // the top-K workspace is sized by the bank: it goes with it
+    HIPCHECK(hipFree(c->topk_slab));
+    c->topk_slab = nullptr;
+    c->topk_guards.clear();
+    c->topk = BankTopkArgs{};
+  }
   c->bank = BankArgs{};
   c->bank_format = FPC_BANK_F32;
   c->bank16 = BankBf16Args{};
@@ -4096,41 +4117,33 @@ int fpc_bank_clear(fpc_ctx* c, int slot) {
   return FPC_OK;
 }
 
-// fpc_match_bank on a FPC_BANK_BF16 bank (match_bank_bf16.h): fpc_match_bank's sequence below with the rounding pass for
-// mf_norms_kernel and the bf16 strip for mf_strip; count, select and finalize are the fp32 path's kernels.  D is 128 or 256.
-static int match_bank_bf16(fpc_ctx* c, MatchFramesArgs a, float max_dist, float ratio, int min_score, int32_t* score,
-                           int32_t* best, int32_t* match, float* dist) {
+// The score pass of fpc_match_bank and fpc_match_bank_topk, either format: the frames' norms (fp32: mf_norms_kernel, grid
+// y = n, no key block; bf16: the rounding pass of match_bank_bf16.h, which writes the rounded rows too), then every (frame,
+// slot) pair's strip and its count, the slots in chunks.  Leaves score [n][slots] in the bank's workspace; the norms (and
+// rounded rows) stay valid for a table pass behind it.  D is 128 or 256.
+static int bank_score_pass(fpc_ctx* c, const MatchFramesArgs& a, float max_dist, float ratio) {
   const BankArgs& b = c->bank;
   const BankBf16Args& h = c->bank16;
+  const bool half = c->bank_format == FPC_BANK_BF16;
   const int n = a.n;
-  const dim3 strips((c->cap + MF_ROWS - 1) / MF_ROWS, n);
-  hipLaunchKernelGGL(bank_round_queries_kernel, dim3((c->cap + 127) / 128, n), dim3(256), 0, c->stream, a, h);
+  const unsigned strips = (c->cap + MF_ROWS - 1) / MF_ROWS;
+  if (half)
+    hipLaunchKernelGGL(bank_round_queries_kernel, dim3((c->cap + 127) / 128, n), dim3(256), 0, c->stream, a, h);
+  else
+    hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, n), dim3(256), 0, c->stream, a);
   HIPCHECK(hipMemsetAsync(b.score, 0, sizeof(int32_t) * n * b.slots, c->stream));
   for (int s0 = 0; s0 < b.slots; s0 += b.chunk) {
     const int ns = std::min(b.chunk, b.slots - s0);
     if (a.cross_check)
       HIPCHECK(hipMemsetAsync(b.colbest, 0xff, sizeof(unsigned long long) * ((size_t)(n - 1) * b.chunk + ns) * b.rows, c->stream));
-    if (c->D == 128)
-      hipLaunchKernelGGL(bank_score_bf16_kernel<8>, dim3(strips.x, n, ns), dim3(256), 0, c->stream, a, b, h, s0);
+    if (!half)
+      hipLaunchKernelGGL(bank_score_kernel, dim3(strips, n, ns), dim3(256), 0, c->stream, a, b, s0);
+    else if (c->D == 128)
+      hipLaunchKernelGGL(bank_score_bf16_kernel<8>, dim3(strips, n, ns), dim3(256), 0, c->stream, a, b, h, s0);
     else
-      hipLaunchKernelGGL(bank_score_bf16_kernel<16>, dim3(strips.x, n, ns), dim3(256), 0, c->stream, a, b, h, s0);
+      hipLaunchKernelGGL(bank_score_bf16_kernel<16>, dim3(strips, n, ns), dim3(256), 0, c->stream, a, b, h, s0);
     hipLaunchKernelGGL(bank_count_kernel, dim3((c->cap + 255) / 256, n, ns), dim3(256), 0, c->stream, a, b, s0, max_dist, ratio);
   }
-  hipLaunchKernelGGL(bank_select_kernel, dim3(n), dim3(256), 0, c->stream, b, min_score, score, best);
-  if (match || dist) {
-    // the table of frame f against slot best[f]: the same strip, hence the same d^2 bits as the score pass
-    a.key_slot = b.best; a.bank_norms = b.norms; a.bank_count = b.count;
-    a.bank_rows = b.rows; a.bank_slots = b.slots;
-    if (a.cross_check)
-      HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * n * c->cap, c->stream));
-    if (c->D == 128)
-      hipLaunchKernelGGL((match_bank_bf16_kernel<8, false>), strips, dim3(256), 0, c->stream, a, b, h, MatchGuidedArgs{});
-    else
-      hipLaunchKernelGGL((match_bank_bf16_kernel<16, false>), strips, dim3(256), 0, c->stream, a, b, h, MatchGuidedArgs{});
-    hipLaunchKernelGGL(match_frames_finalize_kernel, dim3((c->cap + 255) / 256, n), dim3(256), 0, c->stream, a, max_dist,
-                       ratio, match, dist);
-  }
-  HIPCHECK(hipGetLastError());
   return FPC_OK;
 }
 
@@ -4143,25 +4156,22 @@ int fpc_match_bank(fpc_ctx* c, int n, int cross_check, float max_dist, float rat
   const BankArgs& b = c->bank;
   MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
   a.cross_check = cross_check != 0;
-  if (c->bank_format == FPC_BANK_BF16) return match_bank_bf16(c, a, max_dist, ratio, min_score, score, best, match, dist);
-  // the frames' norms, once for the score pass and the table pass (grid y = n: no key block)
-  hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, n), dim3(256), 0, c->stream, a);
-  HIPCHECK(hipMemsetAsync(b.score, 0, sizeof(int32_t) * n * b.slots, c->stream));
-  for (int s0 = 0; s0 < b.slots; s0 += b.chunk) {
-    const int ns = std::min(b.chunk, b.slots - s0);
-    if (a.cross_check)
-      HIPCHECK(hipMemsetAsync(b.colbest, 0xff, sizeof(unsigned long long) * ((size_t)(n - 1) * b.chunk + ns) * b.rows, c->stream));
-    hipLaunchKernelGGL(bank_score_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, n, ns), dim3(256), 0, c->stream, a, b, s0);
-    hipLaunchKernelGGL(bank_count_kernel, dim3((c->cap + 255) / 256, n, ns), dim3(256), 0, c->stream, a, b, s0, max_dist, ratio);
-  }
+  if (int rc = bank_score_pass(c, a, max_dist, ratio)) return rc;
   hipLaunchKernelGGL(bank_select_kernel, dim3(n), dim3(256), 0, c->stream, b, min_score, score, best);
   if (match || dist) {
-    // the table of frame f against slot best[f]: fpc_match_frames' own kernels with a per-frame key
+    // the table of frame f against slot best[f]: fpc_match_frames' own kernels with a per-frame key; on a bf16 bank the
+    // score pass's strip (match_bank_bf16.h), hence the same d^2 bits as the scores
+    const dim3 strips((c->cap + MF_ROWS - 1) / MF_ROWS, n);
     a.key = b.desc; a.key_slot = b.best; a.bank_norms = b.norms; a.bank_count = b.count;
     a.bank_rows = b.rows; a.bank_slots = b.slots;
     if (a.cross_check)
       HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * n * c->cap, c->stream));
-    hipLaunchKernelGGL(match_frames_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, n), dim3(256), 0, c->stream, a);
+    if (c->bank_format != FPC_BANK_BF16)
+      hipLaunchKernelGGL(match_frames_kernel, strips, dim3(256), 0, c->stream, a);
+    else if (c->D == 128)
+      hipLaunchKernelGGL((match_bank_bf16_kernel<8, false>), strips, dim3(256), 0, c->stream, a, b, c->bank16, MatchGuidedArgs{});
+    else
+      hipLaunchKernelGGL((match_bank_bf16_kernel<16, false>), strips, dim3(256), 0, c->stream, a, b, c->bank16, MatchGuidedArgs{});
     hipLaunchKernelGGL(match_frames_finalize_kernel, dim3((c->cap + 255) / 256, n), dim3(256), 0, c->stream, a, max_dist,
                        ratio, match, dist);
   }
@@ -4179,6 +4189,104 @@ int fpc_homography_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* m
   hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
                      (const int32_t*)nullptr, match, inlier, hb);
   ransac_launch(c, a, H, ninliers, inlier, c->cap);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+// ---- top-K candidates of the bank, each verified by RANSAC (include/fpc.h; kernels in match_bank_topk.h) -------------------
+// The only call of the three that allocates or synchronises: pair tables and RANSAC workspace for max_batch x kmax (frame,
+// candidate) pairs, an allocation of its own (the bank's bytes / chunk and the context slab are what they were).
+int fpc_bank_topk_reserve(fpc_ctx* c, int kmax, size_t* bytes) {
+  if (!c || !c->bank_slab || c->topk_slab || kmax < 1 || kmax > std::min((int)FPC_BANK_TOPK_MAX, c->bank.slots))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const size_t pairs = (size_t)c->B * kmax, cap = c->cap, rows = c->bank.rows;
+  Carver cv;
+  std::vector<std::pair<size_t, size_t>> zones;
+  cv.zones = &zones;
+  cv.guard = c->guard_zones ? GUARD_BYTES : 0;
+  const size_t o_top = cv.take<unsigned long long>(pairs * cap * 2), o_col = cv.take<unsigned long long>(pairs * rows);
+  const size_t o_slot = cv.take<int32_t>(pairs), o_sc = cv.take<int32_t>(pairs);
+  const size_t o_pairs = cv.take<float4>(pairs * cap), o_row = cv.take<int32_t>(pairs * cap);
+  const size_t o_np = cv.take<int32_t>(pairs), o_best = cv.take<unsigned long long>(pairs);
+  char* p = nullptr;
+  HIPCHECK(hipMalloc((void**)&p, cv.off));
+  {
+    hipError_t e = hipMemset(p, 0, cv.off);
+    if (e == hipSuccess) e = hipDeviceSynchronize();            // (as in fpc_bank_create: the null stream does not order c->stream)
+    for (const auto& z : zones) {
+      const size_t n = z.second / 4;
+      guard_fill_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<uint32_t*>(p + z.first), n, GUARD_PATTERN);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) hipFree(p);
+    HIPCHECK(e);
+  }
+  c->topk_slab = p;
+  c->topk_guards = zones;
+  c->topk.top2 = reinterpret_cast<unsigned long long*>(p + o_top);
+  c->topk.colbest = reinterpret_cast<unsigned long long*>(p + o_col);
+  c->topk.cand_slot = reinterpret_cast<int32_t*>(p + o_slot);
+  c->topk.cand_score = reinterpret_cast<int32_t*>(p + o_sc);
+  c->topk.kmax = kmax;
+  c->topk_pairs = reinterpret_cast<float4*>(p + o_pairs);
+  c->topk_row = reinterpret_cast<int32_t*>(p + o_row);
+  c->topk_np = reinterpret_cast<int32_t*>(p + o_np);
+  c->topk_best = reinterpret_cast<unsigned long long*>(p + o_best);
+  if (bytes) *bytes = cv.off;
+  return FPC_OK;
+}
+
+int fpc_match_bank_topk(fpc_ctx* c, int n, int k, int cross_check, float max_dist, float ratio, int min_score, int32_t* score,
+                        int32_t* cand_slot, int32_t* cand_score, int32_t* match, float* dist) {
+  if (!c || !c->bank_slab || !c->topk_slab || !cand_slot || k < 1 || k > c->topk.kmax || !(max_dist >= 0.f) ||
+      !(ratio >= 0.f && ratio <= 1.f) || min_score < 0)
+    return FPC_E_INVALID;
+  if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const BankArgs& b = c->bank;
+  const BankTopkArgs& t = c->topk;
+  MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
+  a.cross_check = cross_check != 0;
+  if (int rc = bank_score_pass(c, a, max_dist, ratio)) return rc;
+  hipLaunchKernelGGL(bank_topk_kernel, dim3(n), dim3(256), 0, c->stream, b, t, k, min_score, score, cand_slot, cand_score);
+  if (match || dist) {
+    // the k tables of every frame in one launch: the score pass's strip against slot cand_slot[f][z] (the norms, and on a
+    // bf16 bank the rounded query rows, are the score pass's)
+    const dim3 strips((c->cap + MF_ROWS - 1) / MF_ROWS, n, k);
+    if (a.cross_check)
+      HIPCHECK(hipMemsetAsync(t.colbest, 0xff, sizeof(unsigned long long) * ((size_t)(n - 1) * t.kmax + k) * b.rows, c->stream));
+    if (c->bank_format != FPC_BANK_BF16)
+      hipLaunchKernelGGL(bank_topk_table_kernel, strips, dim3(256), 0, c->stream, a, b, t);
+    else if (c->D == 128)
+      hipLaunchKernelGGL(bank_topk_table_bf16_kernel<8>, strips, dim3(256), 0, c->stream, a, b, c->bank16, t);
+    else
+      hipLaunchKernelGGL(bank_topk_table_bf16_kernel<16>, strips, dim3(256), 0, c->stream, a, b, c->bank16, t);
+    hipLaunchKernelGGL(bank_topk_finalize_kernel, dim3((c->cap + 255) / 256, n, k), dim3(256), 0, c->stream, a, b, t, k,
+                       max_dist, ratio, match, dist);
+  }
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_homography_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot, const int32_t* match,
+                             const fpc_ransac_params* p, float* H, int32_t* ninliers, uint8_t* inlier, int32_t* pick,
+                             int32_t* best) {
+  if (!c || !c->bank_slab || !c->topk_slab || !cand_slot || !match || !H || !ninliers || !ransac_params_ok(p) || k < 1 ||
+      k > c->topk.kmax)
+    return FPC_E_INVALID;
+  if (n < 1 || n > c->pts_n || n > c->B) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  // n k problems on the reserved workspace: problem f k + j is frame f against slot cand_slot[f][j] with match[f][j]
+  HfArgs a = ransac_args(c, n * k, p);
+  a.pairs = c->topk_pairs; a.row = c->topk_row; a.np = c->topk_np; a.best = c->topk_best;
+  a.per_frame = k;
+  const HfBank hb{cand_slot, c->bank.count, c->bank.rows, c->bank.slots};
+  hipLaunchKernelGGL(hf_gather_kernel, dim3(n * k), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
+                     (const int32_t*)nullptr, match, inlier, hb);
+  ransac_launch(c, a, H, ninliers, inlier, c->cap);
+  if (pick || best)
+    hipLaunchKernelGGL(bank_pick_kernel, dim3(n), dim3(64), 0, c->stream, ninliers, cand_slot, k, pick, best);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }

@@ -35,7 +35,13 @@ struct HfArgs {
   int T, refits, min_inliers;
   float thr;
   uint32_t seed;
+  // fpc_homography_bank_topk (match_bank_topk.h): the grid's index is a PROBLEM p = f per_frame + j, several per frame; it
+  // selects the pair list, the mask row and the slot, while the frame f = p / per_frame selects the query pixels and feeds
+  // the sampler.  0 (every other entry point): one problem per frame, p = f.
+  int per_frame;
 };
+
+__device__ __forceinline__ int hf_frame(const HfArgs& a, int p) { return a.per_frame > 1 ? p / a.per_frame : p; }
 
 __device__ __forceinline__ int hf_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
@@ -128,14 +134,16 @@ struct HfBank {
   int rows, slots;
 };
 
-// one workgroup per frame; rows i < count[f] with 0 <= match < the train set's row count, in ascending i
+// one workgroup per frame (per problem: HfArgs::per_frame); rows i < count[f] with 0 <= match < the train set's row count,
+// in ascending i
 __global__ __launch_bounds__(256) void hf_gather_kernel(HfArgs a, const int32_t* __restrict__ xy, const int32_t* __restrict__ count,
                                                         int pairing, const int32_t* __restrict__ key_xy,
                                                         const int32_t* __restrict__ nkey, const int32_t* __restrict__ match,
                                                         uint8_t* mask, const HfBank bank) {
   __shared__ int wsum[4];
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cap = a.cap;
-  const int cnt = hf_clamp(count[f], cap);
+  const int fq = hf_frame(a, f);               // the frame whose keypoints are the query side
+  const int cnt = hf_clamp(count[fq], cap);
   const int32_t* txy = nullptr;
   int nt = 0;
   if (bank.slot) {                            // a per-frame train table: slot bank.slot[f] of key_xy [slots][rows][2]
@@ -151,7 +159,7 @@ __global__ __launch_bounds__(256) void hf_gather_kernel(HfArgs a, const int32_t*
     txy = key_xy;
     nt = hf_clamp(nkey[0], cap);
   }
-  const int32_t* qxy = xy + (size_t)f * cap * 2;
+  const int32_t* qxy = xy + (size_t)fq * cap * 2;
   const int end = mask ? cap : cnt;
   int base = 0;
   for (int i0 = 0; i0 < end; i0 += 256) {
@@ -193,7 +201,7 @@ __global__ __launch_bounds__(256) void ransac_score_kernel(HfArgs a) {
   bool ok = t < (uint32_t)a.T;
   if (ok) {
     uint32_t i0, i1, i2, i3;
-    ok = hf_sample(a.seed, (uint32_t)f, t, (uint32_t)M, i0, i1, i2, i3);
+    ok = hf_sample(a.seed, (uint32_t)hf_frame(a, f), t, (uint32_t)M, i0, i1, i2, i3);
     if (ok) {
       double H[9];
       ok = hf_solve4(pairs[i0], pairs[i1], pairs[i2], pairs[i3], H);
@@ -277,7 +285,7 @@ __global__ __launch_bounds__(256) void ransac_refit_kernel(HfArgs a, float* __re
   bool ok = M >= 4 && key != 0ull;
   if (ok) {                                   // (uniform) every thread re-derives the best sample's H: same code, same bits
     uint32_t i0, i1, i2, i3;
-    ok = hf_sample(a.seed, (uint32_t)f, ~(uint32_t)key, (uint32_t)M, i0, i1, i2, i3) &&
+    ok = hf_sample(a.seed, (uint32_t)hf_frame(a, f), ~(uint32_t)key, (uint32_t)M, i0, i1, i2, i3) &&
          hf_solve4(pairs[i0], pairs[i1], pairs[i2], pairs[i3], H);
   }
   int total = 0;

@@ -711,6 +711,85 @@ class Engine:
         self.sync()
         return hm.cpu().numpy(), ni.cpu().numpy(), mask.cpu().numpy()
 
+    # -- verified relocalisation: the k best slots per frame, each checked by RANSAC (fpc_*_bank_topk) ------------------
+    def bank_topk_reserve(self, kmax):
+        """fpc_bank_topk_reserve: workspace for up to `kmax` candidates per frame (1 <= kmax <= min(16, slots)); the only
+        top-K call that allocates.  Freed with the bank.  Returns the bytes it allocated (bank_info()["bytes"] is
+        unchanged)."""
+        self._bank_info()
+        nbytes = ctypes.c_size_t(0)
+        _lib.check(self._l.fpc_bank_topk_reserve(self._ctx, int(kmax), ctypes.byref(nbytes)), "fpc_bank_topk_reserve")
+        self._topk_kmax = int(kmax)
+        return int(nbytes.value)
+
+    def match_bank_topk_async(self, n, k, cross_check=True, max_dist=0.0, ratio=0.0, min_score=0, table=True):
+        """fpc_match_bank_topk: match_bank_async's scores and, per frame, the k best slots in descending (score, lower slot
+        first) order -> device tensors (score int32 [n,slots], cand_slot int32 [n,k] (-1: fewer than k slots reached
+        max(min_score, 1)), cand_score int32 [n,k], match int32 [n,k,cap], dist float32 [n,k,cap]) -- the last two are the
+        table of frame f against slot cand_slot[f,j] (None with table=False).  Does not synchronise."""
+        v = self._bank_info()
+        k = int(k)
+        score = torch.empty((n, v.slots), dtype=torch.int32, device=self.torch_device)
+        cs = torch.empty((n, k), dtype=torch.int32, device=self.torch_device)
+        csc = torch.empty((n, k), dtype=torch.int32, device=self.torch_device)
+        m = torch.empty((n, k, self.capacity), dtype=torch.int32, device=self.torch_device) if table else None
+        d = torch.empty((n, k, self.capacity), dtype=torch.float32, device=self.torch_device) if table else None
+        self._enqueue(lambda: _lib.check(self._l.fpc_match_bank_topk(
+            self._ctx, n, k, int(bool(cross_check)), float(max_dist), float(ratio), int(min_score), score.data_ptr(),
+            cs.data_ptr(), csc.data_ptr(), m.data_ptr() if table else None, d.data_ptr() if table else None),
+            "fpc_match_bank_topk"))
+        return score, cs, csc, m, d
+
+    def match_bank_topk(self, n, k, cross_check=True, max_dist=0.0, ratio=0.0, min_score=0):
+        """match_bank_topk_async, then host arrays (score [n,slots], cand_slot [n,k], cand_score [n,k], match [n,k,cap],
+        dist [n,k,cap])."""
+        out = self.match_bank_topk_async(n, k, cross_check, max_dist, ratio, min_score)
+        self.sync()
+        return tuple(t.cpu().numpy() for t in out)
+
+    def homography_bank_topk_async(self, n, cand_slot, match, **params):
+        """fpc_homography_bank_topk: homography_bank_async for every candidate -- cand_slot int32 [n,k] and match int32
+        [n,k,cap] are match_bank_topk_async's -> device tensors (H [n,k,3,3], ninliers [n,k], inlier bool [n,k,cap], pick
+        int32 [n]: the candidate with the most inliers, ties to the lower j, -1: none; best int32 [n]: its slot, or -1).
+        Does not synchronise."""
+        self._bank_info()
+        p = self._ransac_params(params)
+        if cand_slot.device != self.torch_device or cand_slot.dtype != torch.int32 or cand_slot.dim() != 2 \
+                or cand_slot.shape[0] != n:
+            raise ValueError("cand_slot must be a device tensor int32 [n,k]")
+        k = int(cand_slot.shape[1])
+        if match.device != self.torch_device or match.dtype != torch.int32 or tuple(match.shape) != (n, k, self.capacity):
+            raise ValueError("match must be a device tensor int32 [n,k,%d]" % self.capacity)
+        cand_slot, match = cand_slot.contiguous(), match.contiguous()
+        hm = torch.empty((n, k, 3, 3), dtype=torch.float32, device=self.torch_device)
+        ni = torch.empty((n, k), dtype=torch.int32, device=self.torch_device)
+        mask = torch.empty((n, k, self.capacity), dtype=torch.uint8, device=self.torch_device)
+        pick = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
+        best = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
+        self._enqueue(lambda: _lib.check(self._l.fpc_homography_bank_topk(
+            self._ctx, n, k, cand_slot.data_ptr(), match.data_ptr(), ctypes.byref(p), hm.data_ptr(), ni.data_ptr(),
+            mask.data_ptr(), pick.data_ptr(), best.data_ptr()), "fpc_homography_bank_topk"))
+        cand_slot.record_stream(self.torch_stream())
+        match.record_stream(self.torch_stream())
+        return hm, ni, mask.view(torch.bool), pick, best
+
+    def homography_bank_topk(self, n, cand_slot, match, **params):
+        """homography_bank_topk_async, then host arrays (H [n,k,3,3], ninliers [n,k], inlier bool [n,k,cap], pick [n],
+        best [n])."""
+        out = self.homography_bank_topk_async(n, cand_slot, match, **params)
+        self.sync()
+        return tuple(t.cpu().numpy() for t in out)
+
+    def relocalise(self, n, k, cross_check=True, max_dist=0.7, ratio=0.0, min_score=0, **params):
+        """match_bank_topk_async then homography_bank_topk_async, one synchronisation: which stored frame does each frame
+        see, verified geometrically -> host arrays (best [n]: the candidate slot with the most inliers, -1: none verified;
+        H [n,k,3,3] and ninliers [n,k] of every candidate; cand_slot [n,k]; cand_score [n,k]).  Needs bank_topk_reserve(kmax
+        >= k); RANSAC parameters as in homography_bank_async."""
+        _, cs, csc, m, _ = self.match_bank_topk_async(n, k, cross_check, max_dist, ratio, min_score)
+        hm, ni, _, _, best = self.homography_bank_topk_async(n, cs, m, **params)
+        self.sync()
+        return tuple(t.cpu().numpy() for t in (best, hm, ni, cs, csc))
+
     # -- guided matching: the match once more under the estimated homographies (fpc_match_*_guided) -------------------
     def _guided_h(self, n, hm):
         """H -> a contiguous device tensor float32 [n,9] (homography_*_async's [n,3,3] output as it is, or a host array)."""

@@ -635,6 +635,56 @@ int fpc_match_bank_guided_cells(fpc_ctx* ctx, int n, const int32_t* slot_dev, co
                                 int cross_check, float max_dist, float ratio, int32_t* match_dev, float* dist_dev,
                                 int32_t* stats_dev);
 
+/* --- verified relocalisation: the K best slots of the bank per frame, each checked by RANSAC -----------------------------
+ * fpc_match_bank ranks the slots by appearance and returns ONE per frame; everything behind it verifies that slot.  Where a
+ * look-alike slot outscores the right one (the WARNING above; repetitive texture, revisited places) the homography fails and
+ * the frame is lost although the right slot came second.  The calls below shortlist the k best slots, estimate a homography
+ * against each of them, and keep the slot with the most inliers -- without a host loop over the candidates.
+ *
+ * fpc_bank_topk_reserve: 1 <= kmax <= min(FPC_BANK_TOPK_MAX, slots); needs a bank.  The ONLY call of the three that
+ * allocates or synchronises: workspace for max_batch x kmax (frame, candidate) pairs -- top-2 keys [max_batch][kmax][cap][2],
+ * column minima [max_batch][kmax][rows], the candidate tables, and the RANSAC pair lists, rows, counts and best keys of
+ * max_batch x kmax problems -- in an allocation of its own.  *bytes (may be NULL) receives its size; fpc_bank_get().bytes
+ * and chunk, fpc_create's workspace and the bank are what they were.  FPC_E_INVALID without a bank or when a reservation
+ * already exists; fpc_bank_destroy and fpc_destroy free it.  In a FPC_PLAN_GUARD_ZONES context every buffer of it is
+ * followed by a canary zone of its own, and fpc_check_guards counts those too.
+ *
+ * fpc_match_bank_topk: 1 <= k <= kmax; the query sets are frames 0 .. n-1 of the last results, on either bank format.
+ *  - score_dev int32 [n][slots] (may be NULL): fpc_match_bank's score, computed by the same passes: the same integers.
+ *  - cand_slot_dev int32 [n][k]: cand_slot[f][j] is the j-th slot in descending (score, then LOWER slot first) order among
+ *    the slots with score >= max(min_score, 1); entries behind the last such slot are -1.  cand_slot[f][0] is
+ *    fpc_match_bank's best[f].  An integer selection: no atomic decides a position.
+ *  - cand_score_dev int32 [n][k] (may be NULL): the scores of those slots; 0 where the slot is -1.
+ *  - match_dev int32 [n][k][cap], dist_dev float [n][k][cap] (both may be NULL): match[f][j] / dist[f][j] is the table of
+ *    frame f against slot cand_slot[f][j] in the bank's arithmetic -- bit-identical to what fpc_match_bank_guided writes
+ *    for that frame with that slot, an identity H and a radius beyond the frame diagonal, which is the fpc_match_bank table
+ *    for that slot on either format and, on a FPC_BANK_F32 bank, fpc_match_frames with the slot as its key.  The number of
+ *    match[f][j][i] >= 0 equals cand_score[f][j].  A candidate of -1: -1 / +inf rows.
+ * fpc_homography_bank_topk: one RANSAC problem per (frame, candidate).  cand_slot_dev [n][k] and match_dev [n][k][cap] are
+ * fpc_match_bank_topk's; H_dev float32 [n][k][9], ninliers_dev int32 [n][k], inlier_dev uint8 [n][k][cap] (may be NULL).
+ *  - Problem (f, j) is bit-identical to fpc_homography_bank(n, slot = cand_slot[.][j], match = match[.][j], params) at
+ *    frame index f -- H, ninliers and the mask, failed frames and candidates of -1 (nine zeros, 0, an all-zero mask)
+ *    included: the sampler hashes f, not f k + j.
+ *  - pick_dev int32 [n] (may be NULL): the j with the largest ninliers[f][j], ties to the LOWER j; -1 when every
+ *    ninliers[f][.] is 0.  best_dev int32 [n] (may be NULL): cand_slot[f][pick[f]], or -1.  The integer key
+ *    (ninliers << 32) | ~j: independent of the execution order.
+ *  - Needs keypoints only, as fpc_homography_bank.
+ * Execution: both calls are asynchronous on the ctx stream, with no host synchronisation, no device-to-host copy and no
+ * allocation; counts and slots are read on the device; repeated calls give bit-identical outputs.  The number of launches of
+ * a call does not depend on n or k (the score pass loops over the bank's slot chunks, as in fpc_match_bank).  fpc_detect,
+ * fpc_match_bank_topk, fpc_homography_bank_topk, fpc_match_bank_guided(best), fpc_homography_bank(best) needs no host call
+ * in between.
+ * FPC_E_INVALID (nothing is written): everything fpc_match_bank (but a NULL score_dev) / fpc_homography_bank refuses; no
+ * reservation; k outside [1, kmax]; a NULL cand_slot_dev; a NULL match_dev / H_dev / ninliers_dev (homography call). */
+#define FPC_BANK_TOPK_MAX 16
+int fpc_bank_topk_reserve(fpc_ctx* ctx, int kmax, size_t* bytes);
+int fpc_match_bank_topk(fpc_ctx* ctx, int n, int k, int cross_check, float max_dist, float ratio, int min_score,
+                        int32_t* score_dev, int32_t* cand_slot_dev, int32_t* cand_score_dev, int32_t* match_dev,
+                        float* dist_dev);
+int fpc_homography_bank_topk(fpc_ctx* ctx, int n, int k, const int32_t* cand_slot_dev, const int32_t* match_dev,
+                             const fpc_ransac_params* params, float* H_dev, int32_t* ninliers_dev, uint8_t* inlier_dev,
+                             int32_t* pick_dev, int32_t* best_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
