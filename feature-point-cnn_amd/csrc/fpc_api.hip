@@ -664,17 +664,46 @@ __global__ void guard_count_kernel(const uint32_t* p, size_t n, uint32_t v, unsi
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) mine += p[i] != v;
   if (mine) atomicAdd(bad, mine);
 }
+using GuardZones = std::vector<std::pair<size_t, size_t>>;
+static unsigned guard_blocks(size_t words) { return (unsigned)std::min<size_t>(4096, (words + 255) / 256); }
+
+// One slab's zones (the context's, the bank's, the top-K workspace's) on c->stream: written, or their damaged words counted.
+static void fill_zones(fpc_ctx* c, char* base, const GuardZones& zones) {
+  for (const auto& z : zones) {
+    const size_t n = z.second / 4;
+    guard_fill_kernel<<<guard_blocks(n), 256, 0, c->stream>>>(reinterpret_cast<uint32_t*>(base + z.first), n, GUARD_PATTERN);
+  }
+}
+static void count_zones(fpc_ctx* c, const char* base, const GuardZones& zones, unsigned long long* bad) {
+  for (const auto& z : zones) {
+    const size_t n = z.second / 4;
+    guard_count_kernel<<<guard_blocks(n), 256, 0, c->stream>>>(reinterpret_cast<const uint32_t*>(base + z.first), n, GUARD_PATTERN, bad);
+  }
+}
+
 static int fill_guards(fpc_ctx* c) {
   // (the hipMemset of the workspace in front of this call runs on the null stream and need not have finished when it
   // returns; c->stream is non-blocking, so nothing orders the two -- the first version lost 2 MB of pattern to it.
   // Waited for in every context: the first call's kernels must not race the zeroing either.)
   HIPCHECK(hipDeviceSynchronize());
-  if (c->guards.empty()) return FPC_OK;
-  for (const auto& z : c->guards) {
-    const size_t n = z.second / 4;
-    guard_fill_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<uint32_t*>(c->slab + z.first), n, GUARD_PATTERN);
-  }
+  fill_zones(c, c->slab, c->guards);
   if (!c->guards.empty()) HIPCHECK(hipStreamSynchronize(c->stream));
+  return FPC_OK;
+}
+
+// A side slab (the key-frame bank, the top-K workspace) of cv.off bytes: zeroed, then the zones its carver listed filled
+// -- behind a device synchronise, as in fill_guards: the null stream's memset does not order c->stream.  On failure
+// nothing stays allocated.
+static int alloc_side_slab(fpc_ctx* c, const Carver& cv, char** slab) {
+  char* p = nullptr;
+  HIPCHECK(hipMalloc((void**)&p, cv.off));
+  hipError_t e = hipMemset(p, 0, cv.off);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  fill_zones(c, p, *cv.zones);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) hipFree(p);
+  HIPCHECK(e);
+  *slab = p;
   return FPC_OK;
 }
 
@@ -3327,18 +3356,9 @@ int fpc_check_guards(fpc_ctx* c, long long* bad_words) {
     if (e0 != hipSuccess) hipFree(d);
     HIPCHECK(e0);
   }
-  for (const auto& z : c->guards) {
-    const size_t n = z.second / 4;
-    guard_count_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<const uint32_t*>(c->slab + z.first), n, GUARD_PATTERN, d);
-  }
-  for (const auto& z : c->bank_guards) {      // the key-frame bank's zones (fpc_bank_create)
-    const size_t n = z.second / 4;
-    guard_count_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<const uint32_t*>(c->bank_slab + z.first), n, GUARD_PATTERN, d);
-  }
-  for (const auto& z : c->topk_guards) {      // the top-K workspace's zones (fpc_bank_topk_reserve)
-    const size_t n = z.second / 4;
-    guard_count_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<const uint32_t*>(c->topk_slab + z.first), n, GUARD_PATTERN, d);
-  }
+  count_zones(c, c->slab, c->guards, d);
+  count_zones(c, c->bank_slab, c->bank_guards, d);      // (fpc_bank_create; none without a bank)
+  count_zones(c, c->topk_slab, c->topk_guards, d);      // (fpc_bank_topk_reserve)
   unsigned long long h = 0;
   const hipError_t e1 = hipStreamSynchronize(c->stream);
   const hipError_t e2 = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
@@ -3869,9 +3889,14 @@ int fpc_first_within(fpc_ctx* c, const float* key, int nk, const float* cur, int
   return FPC_OK;
 }
 
-// fpc_match_frames / fpc_first_within_frames: checks shared by both (include/fpc.h)
+// Argument checks of the entry points below (include/fpc.h).  A NaN max_dist or ratio fails its comparison: refused.
+static bool pairing_ok(int pairing) { return pairing == FPC_PAIR_KEY || pairing == FPC_PAIR_PREVIOUS; }
+static bool frames_ok(const fpc_ctx* c, int n) { return n >= 1 && n <= c->pts_n && n <= c->B; }
+static bool gate_ok(float max_dist, float ratio) { return max_dist >= 0.f && ratio >= 0.f && ratio <= 1.f; }
+
+// ... and of those that read the frames' descriptors, with or without a key set
 static int match_frames_check(fpc_ctx* c, int n, const float* key, const int32_t* nkey) {
-  if (!c->cfg.descriptor_enabled || !c->pts_desc || n < 1 || n > c->pts_n || n > c->B) return FPC_E_INVALID;
+  if (!c->cfg.descriptor_enabled || !c->pts_desc || !frames_ok(c, n)) return FPC_E_INVALID;
   if (key && (!nkey || (reinterpret_cast<uintptr_t>(key) & 15))) return FPC_E_INVALID;   // rows are read as float4
   return FPC_OK;
 }
@@ -3886,8 +3911,7 @@ static MatchFramesArgs match_frames_args(fpc_ctx* c, int n, const float* key, co
 
 int fpc_match_frames(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey, int cross_check,
                      float max_dist, float ratio, int32_t* match, float* dist) {
-  if (!c || !match || (pairing != FPC_PAIR_KEY && pairing != FPC_PAIR_PREVIOUS) || !(max_dist >= 0.f) ||
-      !(ratio >= 0.f && ratio <= 1.f) || (pairing == FPC_PAIR_KEY && !key))
+  if (!c || !match || !pairing_ok(pairing) || !gate_ok(max_dist, ratio) || (pairing == FPC_PAIR_KEY && !key))
     return FPC_E_INVALID;
   if (int rc = match_frames_check(c, n, key, nkey)) return rc;
   HIPCHECK(hipSetDevice(c->cfg.device));
@@ -3963,10 +3987,9 @@ int fpc_ransac_homography(fpc_ctx* c, int n, const float* src_xy, const float* d
 
 int fpc_homography_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy, const int32_t* nkey, const int32_t* match,
                           const fpc_ransac_params* p, float* H, int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !match || !H || !ninliers || !ransac_params_ok(p) || (pairing != FPC_PAIR_KEY && pairing != FPC_PAIR_PREVIOUS) ||
+  if (!c || !match || !H || !ninliers || !ransac_params_ok(p) || !pairing_ok(pairing) || !frames_ok(c, n) ||
       (pairing == FPC_PAIR_KEY && !key_xy) || (key_xy && !nkey))
     return FPC_E_INVALID;
-  if (n < 1 || n > c->pts_n || n > c->B) return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
   const HfArgs a = ransac_args(c, n, p);
   hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, pairing, key_xy, nkey, match,
@@ -4003,18 +4026,7 @@ int fpc_bank_create_ex(fpc_ctx* c, int slots, int rows, int format) {
   const size_t o_sc = cv.take<int32_t>(B * slots), o_best = cv.take<int32_t>(B);
   const size_t o_q = half ? cv.take<bf16_t>(B * cap * D) : 0;
   char* p = nullptr;
-  HIPCHECK(hipMalloc((void**)&p, cv.off));
-  {
-    hipError_t e = hipMemset(p, 0, cv.off);                     // every slot starts empty
-    if (e == hipSuccess) e = hipDeviceSynchronize();            // (as in fill_guards: the null stream does not order c->stream)
-    for (const auto& z : zones) {
-      const size_t n = z.second / 4;
-      guard_fill_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<uint32_t*>(p + z.first), n, GUARD_PATTERN);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) hipFree(p);
-    HIPCHECK(e);
-  }
+  if (int rc = alloc_side_slab(c, cv, &p)) return rc;           // (zeroed: every slot starts empty)
   c->bank_slab = p;
   c->bank_bytes = cv.off;
   c->bank_guards = zones;
@@ -4117,6 +4129,16 @@ int fpc_bank_clear(fpc_ctx* c, int slot) {
   return FPC_OK;
 }
 
+// The bf16 kernels' instance for the context's descriptors: <8> k-steps of 16 at D = 128, <16> at D = 256.
+extern "C++" template <typename K>      // (this block is extern "C")
+static K by_depth(const fpc_ctx* c, K k8, K k16) { return c->D == 128 ? k8 : k16; }
+
+// The bank as the train set of a (fp32 rows; a bf16 bank's kernels take theirs from c->bank16): frame f against slot[f].
+static void bank_as_train(MatchFramesArgs& a, const BankArgs& b, const int32_t* slot) {
+  a.key = b.desc; a.key_slot = slot; a.bank_norms = b.norms; a.bank_count = b.count;
+  a.bank_rows = b.rows; a.bank_slots = b.slots;
+}
+
 // The score pass of fpc_match_bank and fpc_match_bank_topk, either format: the frames' norms (fp32: mf_norms_kernel, grid
 // y = n, no key block; bf16: the rounding pass of match_bank_bf16.h, which writes the rounded rows too), then every (frame,
 // slot) pair's strip and its count, the slots in chunks.  Leaves score [n][slots] in the bank's workspace; the norms (and
@@ -4136,12 +4158,11 @@ static int bank_score_pass(fpc_ctx* c, const MatchFramesArgs& a, float max_dist,
     const int ns = std::min(b.chunk, b.slots - s0);
     if (a.cross_check)
       HIPCHECK(hipMemsetAsync(b.colbest, 0xff, sizeof(unsigned long long) * ((size_t)(n - 1) * b.chunk + ns) * b.rows, c->stream));
-    if (!half)
-      hipLaunchKernelGGL(bank_score_kernel, dim3(strips, n, ns), dim3(256), 0, c->stream, a, b, s0);
-    else if (c->D == 128)
-      hipLaunchKernelGGL(bank_score_bf16_kernel<8>, dim3(strips, n, ns), dim3(256), 0, c->stream, a, b, h, s0);
+    if (half)
+      hipLaunchKernelGGL(by_depth(c, bank_score_bf16_kernel<8>, bank_score_bf16_kernel<16>), dim3(strips, n, ns), dim3(256), 0,
+                         c->stream, a, b, h, s0);
     else
-      hipLaunchKernelGGL(bank_score_bf16_kernel<16>, dim3(strips, n, ns), dim3(256), 0, c->stream, a, b, h, s0);
+      hipLaunchKernelGGL(bank_score_kernel, dim3(strips, n, ns), dim3(256), 0, c->stream, a, b, s0);
     hipLaunchKernelGGL(bank_count_kernel, dim3((c->cap + 255) / 256, n, ns), dim3(256), 0, c->stream, a, b, s0, max_dist, ratio);
   }
   return FPC_OK;
@@ -4149,8 +4170,7 @@ static int bank_score_pass(fpc_ctx* c, const MatchFramesArgs& a, float max_dist,
 
 int fpc_match_bank(fpc_ctx* c, int n, int cross_check, float max_dist, float ratio, int min_score, int32_t* score,
                    int32_t* best, int32_t* match, float* dist) {
-  if (!c || !c->bank_slab || (!score && !best) || !(max_dist >= 0.f) || !(ratio >= 0.f && ratio <= 1.f) || min_score < 0)
-    return FPC_E_INVALID;
+  if (!c || !c->bank_slab || (!score && !best) || !gate_ok(max_dist, ratio) || min_score < 0) return FPC_E_INVALID;
   if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
   HIPCHECK(hipSetDevice(c->cfg.device));
   const BankArgs& b = c->bank;
@@ -4162,16 +4182,14 @@ int fpc_match_bank(fpc_ctx* c, int n, int cross_check, float max_dist, float rat
     // the table of frame f against slot best[f]: fpc_match_frames' own kernels with a per-frame key; on a bf16 bank the
     // score pass's strip (match_bank_bf16.h), hence the same d^2 bits as the scores
     const dim3 strips((c->cap + MF_ROWS - 1) / MF_ROWS, n);
-    a.key = b.desc; a.key_slot = b.best; a.bank_norms = b.norms; a.bank_count = b.count;
-    a.bank_rows = b.rows; a.bank_slots = b.slots;
+    bank_as_train(a, b, b.best);
     if (a.cross_check)
       HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * n * c->cap, c->stream));
-    if (c->bank_format != FPC_BANK_BF16)
-      hipLaunchKernelGGL(match_frames_kernel, strips, dim3(256), 0, c->stream, a);
-    else if (c->D == 128)
-      hipLaunchKernelGGL((match_bank_bf16_kernel<8, false>), strips, dim3(256), 0, c->stream, a, b, c->bank16, MatchGuidedArgs{});
+    if (c->bank_format == FPC_BANK_BF16)
+      hipLaunchKernelGGL(by_depth(c, match_bank_bf16_kernel<8, false>, match_bank_bf16_kernel<16, false>), strips, dim3(256), 0,
+                         c->stream, a, b, c->bank16, MatchGuidedArgs{});
     else
-      hipLaunchKernelGGL((match_bank_bf16_kernel<16, false>), strips, dim3(256), 0, c->stream, a, b, c->bank16, MatchGuidedArgs{});
+      hipLaunchKernelGGL(match_frames_kernel, strips, dim3(256), 0, c->stream, a);
     hipLaunchKernelGGL(match_frames_finalize_kernel, dim3((c->cap + 255) / 256, n), dim3(256), 0, c->stream, a, max_dist,
                        ratio, match, dist);
   }
@@ -4181,8 +4199,8 @@ int fpc_match_bank(fpc_ctx* c, int n, int cross_check, float max_dist, float rat
 
 int fpc_homography_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const fpc_ransac_params* p, float* H,
                         int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !c->bank_slab || !slot || !match || !H || !ninliers || !ransac_params_ok(p)) return FPC_E_INVALID;
-  if (n < 1 || n > c->pts_n || n > c->B) return FPC_E_INVALID;
+  if (!c || !c->bank_slab || !slot || !match || !H || !ninliers || !ransac_params_ok(p) || !frames_ok(c, n))
+    return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
   const HfArgs a = ransac_args(c, n, p);
   const HfBank hb{slot, c->bank.count, c->bank.rows, c->bank.slots};
@@ -4210,18 +4228,7 @@ int fpc_bank_topk_reserve(fpc_ctx* c, int kmax, size_t* bytes) {
   const size_t o_pairs = cv.take<float4>(pairs * cap), o_row = cv.take<int32_t>(pairs * cap);
   const size_t o_np = cv.take<int32_t>(pairs), o_best = cv.take<unsigned long long>(pairs);
   char* p = nullptr;
-  HIPCHECK(hipMalloc((void**)&p, cv.off));
-  {
-    hipError_t e = hipMemset(p, 0, cv.off);
-    if (e == hipSuccess) e = hipDeviceSynchronize();            // (as in fpc_bank_create: the null stream does not order c->stream)
-    for (const auto& z : zones) {
-      const size_t n = z.second / 4;
-      guard_fill_kernel<<<(unsigned)std::min<size_t>(4096, (n + 255) / 256), 256, 0, c->stream>>>(reinterpret_cast<uint32_t*>(p + z.first), n, GUARD_PATTERN);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) hipFree(p);
-    HIPCHECK(e);
-  }
+  if (int rc = alloc_side_slab(c, cv, &p)) return rc;
   c->topk_slab = p;
   c->topk_guards = zones;
   c->topk.top2 = reinterpret_cast<unsigned long long*>(p + o_top);
@@ -4239,8 +4246,8 @@ int fpc_bank_topk_reserve(fpc_ctx* c, int kmax, size_t* bytes) {
 
 int fpc_match_bank_topk(fpc_ctx* c, int n, int k, int cross_check, float max_dist, float ratio, int min_score, int32_t* score,
                         int32_t* cand_slot, int32_t* cand_score, int32_t* match, float* dist) {
-  if (!c || !c->bank_slab || !c->topk_slab || !cand_slot || k < 1 || k > c->topk.kmax || !(max_dist >= 0.f) ||
-      !(ratio >= 0.f && ratio <= 1.f) || min_score < 0)
+  if (!c || !c->bank_slab || !c->topk_slab || !cand_slot || k < 1 || k > c->topk.kmax || !gate_ok(max_dist, ratio) ||
+      min_score < 0)
     return FPC_E_INVALID;
   if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
   HIPCHECK(hipSetDevice(c->cfg.device));
@@ -4256,12 +4263,11 @@ int fpc_match_bank_topk(fpc_ctx* c, int n, int k, int cross_check, float max_dis
     const dim3 strips((c->cap + MF_ROWS - 1) / MF_ROWS, n, k);
     if (a.cross_check)
       HIPCHECK(hipMemsetAsync(t.colbest, 0xff, sizeof(unsigned long long) * ((size_t)(n - 1) * t.kmax + k) * b.rows, c->stream));
-    if (c->bank_format != FPC_BANK_BF16)
-      hipLaunchKernelGGL(bank_topk_table_kernel, strips, dim3(256), 0, c->stream, a, b, t);
-    else if (c->D == 128)
-      hipLaunchKernelGGL(bank_topk_table_bf16_kernel<8>, strips, dim3(256), 0, c->stream, a, b, c->bank16, t);
+    if (c->bank_format == FPC_BANK_BF16)
+      hipLaunchKernelGGL(by_depth(c, bank_topk_table_bf16_kernel<8>, bank_topk_table_bf16_kernel<16>), strips, dim3(256), 0,
+                         c->stream, a, b, c->bank16, t);
     else
-      hipLaunchKernelGGL(bank_topk_table_bf16_kernel<16>, strips, dim3(256), 0, c->stream, a, b, c->bank16, t);
+      hipLaunchKernelGGL(bank_topk_table_kernel, strips, dim3(256), 0, c->stream, a, b, t);
     hipLaunchKernelGGL(bank_topk_finalize_kernel, dim3((c->cap + 255) / 256, n, k), dim3(256), 0, c->stream, a, b, t, k,
                        max_dist, ratio, match, dist);
   }
@@ -4273,9 +4279,8 @@ int fpc_homography_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot,
                              const fpc_ransac_params* p, float* H, int32_t* ninliers, uint8_t* inlier, int32_t* pick,
                              int32_t* best) {
   if (!c || !c->bank_slab || !c->topk_slab || !cand_slot || !match || !H || !ninliers || !ransac_params_ok(p) || k < 1 ||
-      k > c->topk.kmax)
+      k > c->topk.kmax || !frames_ok(c, n))
     return FPC_E_INVALID;
-  if (n < 1 || n > c->pts_n || n > c->B) return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
   // n k problems on the reserved workspace: problem f k + j is frame f against slot cand_slot[f][j] with match[f][j]
   HfArgs a = ransac_args(c, n * k, p);
@@ -4291,72 +4296,7 @@ int fpc_homography_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot,
   return FPC_OK;
 }
 
-// ---- guided matching (include/fpc.h; kernels in match_guided.h) -----------------------------------------------------------
-// Both entry points run on fpc_match_frames' workspace (norms, top-2, column minima: [max_batch][cap], and the bank's
-// rows <= cap), carved at fpc_create: nothing of their own.
-static int match_guided_launch(fpc_ctx* c, MatchFramesArgs a, const MatchGuidedArgs& g, int norm_blocks, float max_dist,
-                               float ratio, int32_t* match, float* dist) {
-  if (a.cross_check)
-    HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * a.n * c->cap, c->stream));
-  hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, norm_blocks), dim3(256), 0, c->stream, a);
-  hipLaunchKernelGGL(match_guided_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, a.n), dim3(256), 0, c->stream, a, g);
-  hipLaunchKernelGGL(match_guided_finalize_kernel, dim3((c->cap + 255) / 256, a.n), dim3(256), 0, c->stream, a, max_dist,
-                     ratio, match, dist);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
-}
-
-static bool guided_options_ok(const float* H, float radius, float max_dist, float ratio, const int32_t* match) {
-  return H && match && std::isfinite(radius) && radius > 0.f && max_dist >= 0.f && ratio >= 0.f && ratio <= 1.f;
-}
-
-int fpc_match_frames_guided(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey, const int32_t* key_xy,
-                            const float* H, float radius, int cross_check, float max_dist, float ratio, int32_t* match,
-                            float* dist) {
-  if (!c || !guided_options_ok(H, radius, max_dist, ratio, match) ||
-      (pairing != FPC_PAIR_KEY && pairing != FPC_PAIR_PREVIOUS) || (pairing == FPC_PAIR_KEY && (!key || !key_xy)) ||
-      (key && !key_xy))
-    return FPC_E_INVALID;
-  if (int rc = match_frames_check(c, n, key, nkey)) return rc;
-  HIPCHECK(hipSetDevice(c->cfg.device));
-  MatchFramesArgs a = match_frames_args(c, n, key, nkey);
-  a.pairing = pairing;
-  a.cross_check = cross_check != 0;
-  const MatchGuidedArgs g{H, c->xy, key ? key_xy : nullptr, (double)radius * (double)radius};
-  return match_guided_launch(c, a, g, n + 1, max_dist, ratio, match, dist);
-}
-
-int fpc_match_bank_guided(fpc_ctx* c, int n, const int32_t* slot, const float* H, float radius, int cross_check,
-                          float max_dist, float ratio, int32_t* match, float* dist) {
-  if (!c || !c->bank_slab || !slot || !guided_options_ok(H, radius, max_dist, ratio, match)) return FPC_E_INVALID;
-  if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
-  HIPCHECK(hipSetDevice(c->cfg.device));
-  const BankArgs& b = c->bank;
-  MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
-  a.cross_check = cross_check != 0;
-  a.key = b.desc; a.key_slot = slot; a.bank_norms = b.norms; a.bank_count = b.count;
-  a.bank_rows = b.rows; a.bank_slots = b.slots;
-  const MatchGuidedArgs g{H, c->xy, b.xy, (double)radius * (double)radius};
-  if (c->bank_format == FPC_BANK_BF16) {
-    // (match_bank_bf16.h) the rounding pass for the norms, the gated bf16 strip for match_guided_kernel
-    const BankBf16Args& h = c->bank16;
-    const dim3 strips((c->cap + MF_ROWS - 1) / MF_ROWS, n);
-    if (a.cross_check)
-      HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * n * c->cap, c->stream));
-    hipLaunchKernelGGL(bank_round_queries_kernel, dim3((c->cap + 127) / 128, n), dim3(256), 0, c->stream, a, h);
-    if (c->D == 128)
-      hipLaunchKernelGGL((match_bank_bf16_kernel<8, true>), strips, dim3(256), 0, c->stream, a, b, h, g);
-    else
-      hipLaunchKernelGGL((match_bank_bf16_kernel<16, true>), strips, dim3(256), 0, c->stream, a, b, h, g);
-    hipLaunchKernelGGL(match_guided_finalize_kernel, dim3((c->cap + 255) / 256, n), dim3(256), 0, c->stream, a, max_dist,
-                       ratio, match, dist);
-    HIPCHECK(hipGetLastError());
-    return FPC_OK;
-  }
-  return match_guided_launch(c, a, g, n, max_dist, ratio, match, dist);   // (grid y = n: the bank's norms are its own)
-}
-
-// ---- cell-ordered guided matching (include/fpc.h; kernels in match_guided_cells.h) ------------------------------------------
+// ---- guided matching, plain and cell-ordered (include/fpc.h; kernels in match_guided.h, match_guided_cells.h) -------------
 // 32-px cells wherever the order is public; a frame of more cells than the order kernel's histogram holds (beyond
 // 16.7 MPx) is ordered in coarser cells by the guided calls, whose output does not depend on the order.
 static CellOrderArgs cell_order_args(fpc_ctx* c, int shift) {
@@ -4378,17 +4318,12 @@ int fpc_cell_order(fpc_ctx* c, const int32_t* xy, const int32_t* n, int sets, in
   return FPC_OK;
 }
 
-// fpc_match_*_guided's sequence with the order pass in front of the strip kernel.  The train sets: the key once (tsets = 1),
-// the bank's slot of every frame (a.key_slot), none under FPC_PAIR_PREVIOUS without a key (frame f - 1's query order).
-static int match_guided_cells_launch(fpc_ctx* c, MatchFramesArgs a, const MatchGuidedArgs& g, int norm_blocks, float max_dist,
-                                     float ratio, int32_t* match, float* dist, int32_t* stats) {
+// The order passes in front of match_guided_cells_kernel: the frames' rows, then the train sets -- the key once, the bank's
+// slot of every frame (a.key_slot), none under FPC_PAIR_PREVIOUS without a key (frame f - 1's query order).
+static MatchCellsArgs cell_order_passes(fpc_ctx* c, const MatchFramesArgs& a, const MatchGuidedArgs& g, int32_t* stats) {
   const int nbox = (c->cap + 63) / 64;
   int shift = 5;
   while ((long long)((c->W + (1 << shift) - 1) >> shift) * ((c->H + (1 << shift) - 1) >> shift) > MGC_MAX_CELLS) ++shift;
-  if (a.cross_check)
-    HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * a.n * c->cap, c->stream));
-  if (stats) HIPCHECK(hipMemsetAsync(stats, 0, sizeof(int32_t) * 2 * a.n, c->stream));
-  hipLaunchKernelGGL(mf_norms_kernel, dim3((c->cap + 127) / 128, norm_blocks), dim3(256), 0, c->stream, a);
   CellOrderArgs o = cell_order_args(c, shift);
   o.xy = c->xy; o.n = c->count; o.stride = o.out_stride = c->cap;
   o.perm = c->mgc_perm_q; o.box = c->mgc_box; o.box_stride = nbox;
@@ -4404,20 +4339,51 @@ static int match_guided_cells_launch(fpc_ctx* c, MatchFramesArgs a, const MatchG
     }
     hipLaunchKernelGGL(cell_order_kernel, dim3(a.key_slot ? a.n : 1), dim3(256), 0, c->stream, t);
   }
-  const MatchCellsArgs m{c->mgc_perm_q, c->mgc_box, c->mgc_perm_t, box_t, nbox, stats};
-  hipLaunchKernelGGL(match_guided_cells_kernel, dim3((c->cap + MF_ROWS - 1) / MF_ROWS, a.n), dim3(256), 0, c->stream, a, g, m);
+  return MatchCellsArgs{c->mgc_perm_q, c->mgc_box, c->mgc_perm_t, box_t, nbox, stats};
+}
+
+// The four guided entry points run on fpc_match_frames' workspace (norms, top-2, column minima: [max_batch][cap], and the
+// bank's rows <= cap), carved at fpc_create: nothing of their own.  One sequence for all: the column minima and the stats
+// reset, the norms (a bf16 bank: its rounding pass, match_bank_bf16.h), the variant's strip kernel (the cell-ordered one
+// behind its order passes), the finalize kernel.  norm_blocks: n + 1 with the key's block, n against the bank, whose
+// norms are its own.
+enum GuidedStrip { GUIDED_PLAIN, GUIDED_CELLS, GUIDED_BANK_BF16 };
+
+static int match_guided_launch(fpc_ctx* c, GuidedStrip strip, MatchFramesArgs a, const MatchGuidedArgs& g, int norm_blocks,
+                               float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
+  const dim3 norms((c->cap + 127) / 128, norm_blocks), strips((c->cap + MF_ROWS - 1) / MF_ROWS, a.n);
+  if (a.cross_check)
+    HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * a.n * c->cap, c->stream));
+  if (stats) HIPCHECK(hipMemsetAsync(stats, 0, sizeof(int32_t) * 2 * a.n, c->stream));
+  if (strip == GUIDED_BANK_BF16)
+    hipLaunchKernelGGL(bank_round_queries_kernel, norms, dim3(256), 0, c->stream, a, c->bank16);
+  else
+    hipLaunchKernelGGL(mf_norms_kernel, norms, dim3(256), 0, c->stream, a);
+  if (strip == GUIDED_CELLS) {
+    const MatchCellsArgs m = cell_order_passes(c, a, g, stats);
+    hipLaunchKernelGGL(match_guided_cells_kernel, strips, dim3(256), 0, c->stream, a, g, m);
+  } else if (strip == GUIDED_BANK_BF16) {
+    hipLaunchKernelGGL(by_depth(c, match_bank_bf16_kernel<8, true>, match_bank_bf16_kernel<16, true>), strips, dim3(256), 0,
+                       c->stream, a, c->bank, c->bank16, g);
+  } else {
+    hipLaunchKernelGGL(match_guided_kernel, strips, dim3(256), 0, c->stream, a, g);
+  }
   hipLaunchKernelGGL(match_guided_finalize_kernel, dim3((c->cap + 255) / 256, a.n), dim3(256), 0, c->stream, a, max_dist,
                      ratio, match, dist);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }
 
-int fpc_match_frames_guided_cells(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey,
-                                  const int32_t* key_xy, const float* H, float radius, int cross_check, float max_dist,
-                                  float ratio, int32_t* match, float* dist, int32_t* stats) {
-  if (!c || !guided_options_ok(H, radius, max_dist, ratio, match) ||
-      (pairing != FPC_PAIR_KEY && pairing != FPC_PAIR_PREVIOUS) || (pairing == FPC_PAIR_KEY && (!key || !key_xy)) ||
-      (key && !key_xy))
+static bool guided_options_ok(const float* H, float radius, float max_dist, float ratio, const int32_t* match) {
+  return H && match && std::isfinite(radius) && radius > 0.f && gate_ok(max_dist, ratio);
+}
+
+// fpc_match_frames_guided[_cells]: the key set (or frame f - 1) as the train set
+static int match_frames_guided(fpc_ctx* c, GuidedStrip strip, int n, int pairing, const float* key, const int32_t* nkey,
+                               const int32_t* key_xy, const float* H, float radius, int cross_check, float max_dist,
+                               float ratio, int32_t* match, float* dist, int32_t* stats) {
+  if (!c || !guided_options_ok(H, radius, max_dist, ratio, match) || !pairing_ok(pairing) ||
+      (pairing == FPC_PAIR_KEY && (!key || !key_xy)) || (key && !key_xy))
     return FPC_E_INVALID;
   if (int rc = match_frames_check(c, n, key, nkey)) return rc;
   HIPCHECK(hipSetDevice(c->cfg.device));
@@ -4425,22 +4391,47 @@ int fpc_match_frames_guided_cells(fpc_ctx* c, int n, int pairing, const float* k
   a.pairing = pairing;
   a.cross_check = cross_check != 0;
   const MatchGuidedArgs g{H, c->xy, key ? key_xy : nullptr, (double)radius * (double)radius};
-  return match_guided_cells_launch(c, a, g, n + 1, max_dist, ratio, match, dist, stats);
+  return match_guided_launch(c, strip, a, g, n + 1, max_dist, ratio, match, dist, stats);
+}
+
+// fpc_match_bank_guided[_cells]: bank slot slot[f] as frame f's train set
+static int match_bank_guided(fpc_ctx* c, bool cells, int n, const int32_t* slot, const float* H, float radius, int cross_check,
+                             float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
+  if (!c || !c->bank_slab || !slot || !guided_options_ok(H, radius, max_dist, ratio, match)) return FPC_E_INVALID;
+  const bool half = c->bank_format != FPC_BANK_F32;
+  if (cells && half) return FPC_E_INVALID;                     // (the bf16 bank's ordered strip: not built yet)
+  if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
+  a.cross_check = cross_check != 0;
+  bank_as_train(a, c->bank, slot);
+  const MatchGuidedArgs g{H, c->xy, c->bank.xy, (double)radius * (double)radius};
+  return match_guided_launch(c, cells ? GUIDED_CELLS : half ? GUIDED_BANK_BF16 : GUIDED_PLAIN, a, g, n, max_dist, ratio, match,
+                             dist, stats);
+}
+
+int fpc_match_frames_guided(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey, const int32_t* key_xy,
+                            const float* H, float radius, int cross_check, float max_dist, float ratio, int32_t* match,
+                            float* dist) {
+  return match_frames_guided(c, GUIDED_PLAIN, n, pairing, key, nkey, key_xy, H, radius, cross_check, max_dist, ratio, match, dist,
+                             nullptr);
+}
+
+int fpc_match_frames_guided_cells(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey,
+                                  const int32_t* key_xy, const float* H, float radius, int cross_check, float max_dist,
+                                  float ratio, int32_t* match, float* dist, int32_t* stats) {
+  return match_frames_guided(c, GUIDED_CELLS, n, pairing, key, nkey, key_xy, H, radius, cross_check, max_dist, ratio, match, dist,
+                             stats);
+}
+
+int fpc_match_bank_guided(fpc_ctx* c, int n, const int32_t* slot, const float* H, float radius, int cross_check,
+                          float max_dist, float ratio, int32_t* match, float* dist) {
+  return match_bank_guided(c, false, n, slot, H, radius, cross_check, max_dist, ratio, match, dist, nullptr);
 }
 
 int fpc_match_bank_guided_cells(fpc_ctx* c, int n, const int32_t* slot, const float* H, float radius, int cross_check,
                                 float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
-  if (!c || !c->bank_slab || !slot || !guided_options_ok(H, radius, max_dist, ratio, match)) return FPC_E_INVALID;
-  if (c->bank_format != FPC_BANK_F32) return FPC_E_INVALID;    // (the bf16 bank's ordered strip: not built yet)
-  if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
-  HIPCHECK(hipSetDevice(c->cfg.device));
-  const BankArgs& b = c->bank;
-  MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
-  a.cross_check = cross_check != 0;
-  a.key = b.desc; a.key_slot = slot; a.bank_norms = b.norms; a.bank_count = b.count;
-  a.bank_rows = b.rows; a.bank_slots = b.slots;
-  const MatchGuidedArgs g{H, c->xy, b.xy, (double)radius * (double)radius};
-  return match_guided_cells_launch(c, a, g, n, max_dist, ratio, match, dist, stats);   // (grid y = n: the bank's norms are its own)
+  return match_bank_guided(c, true, n, slot, H, radius, cross_check, max_dist, ratio, match, dist, stats);
 }
 
 int fpc_results(fpc_ctx* c, fpc_device_results* out) {

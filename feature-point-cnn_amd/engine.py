@@ -432,38 +432,69 @@ class Engine:
         call()
         cur.wait_stream(st)
 
-    def match_frames_async(self, n, key=None, pairing="key", cross_check=True, max_dist=0.0, ratio=0.0):
-        """fpc_match_frames: every frame of the last detect against the key set ("key") or its predecessor in the batch
-        ("previous"; frame 0 against the key, or nothing without one) -> (match int32 [n,cap], dist float32 [n,cap]) on
-        the device; rows past a frame's count are -1.  Does not synchronise."""
+    # -- what the wrappers below are made of ----------------------------------------------------------------------------
+    def _call(self, name, *args, inputs=()):
+        """fpc_<name>(ctx, *args) through _enqueue, tensors passed as their device pointers.  `inputs`: the caller's tensors
+        the call reads (entries that are no tensor are skipped) -- the caching allocator must not hand their memory out
+        before the ctx stream read it."""
+        fn = getattr(self._l, name)
+        self._enqueue(lambda: _lib.check(fn(self._ctx, *(_ptr(a) for a in args)), name))
+        for t in inputs:
+            if isinstance(t, torch.Tensor):
+                t.record_stream(self.torch_stream())
+
+    def _int32(self, *shape):
+        return torch.empty(shape, dtype=torch.int32, device=self.torch_device)
+
+    def _table(self, *lead):
+        """An empty (match int32, dist float32) table pair [*lead, cap]."""
+        return self._int32(*lead, self.capacity), torch.empty((*lead, self.capacity), dtype=torch.float32,
+                                                              device=self.torch_device)
+
+    def _ransac_out(self, *lead, stride=None):
+        """Empty RANSAC outputs (H float32 [*lead,3,3], ninliers int32 [*lead], mask uint8 [*lead,stride or cap])."""
+        return (torch.empty((*lead, 3, 3), dtype=torch.float32, device=self.torch_device), self._int32(*lead),
+                torch.empty((*lead, self.capacity if stride is None else stride), dtype=torch.uint8, device=self.torch_device))
+
+    def _dev_int32(self, name, t, text, *shape):
+        """`t`, contiguous, if it is an int32 tensor of `shape` (None: any extent) on this device; `text` is the shape as
+        the error names it."""
+        if t.device != self.torch_device or t.dtype != torch.int32 or t.dim() != len(shape) \
+                or any(w is not None and s != w for s, w in zip(t.shape, shape)):
+            raise ValueError("%s must be a device tensor int32 %s" % (name, text))
+        return t.contiguous()
+
+    def _pairing(self, pairing):
         if pairing not in self.PAIRINGS:
             raise ValueError("pairing must be one of %s, got %r" % (sorted(self.PAIRINGS), pairing))
-        kd, kc = self._key(key)
-        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
-        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device)
-
-        def call():
-            _lib.check(self._l.fpc_match_frames(self._ctx, n, self.PAIRINGS[pairing],
-                                                kd.data_ptr() if kd is not None else None,
-                                                kc.data_ptr() if kc is not None else None, int(bool(cross_check)),
-                                                float(max_dist), float(ratio), m.data_ptr(), d.data_ptr()),
-                       "fpc_match_frames")
-        self._enqueue(call)
-        if kd is not None:      # (the caching allocator must not hand the key's memory out before the ctx stream read it)
-            kd.record_stream(self.torch_stream())
-            kc.record_stream(self.torch_stream())
-        return m, d
+        return self.PAIRINGS[pairing]
 
     def _frame_counts(self, n):
         return self._results_view()[1][:n].cpu().numpy()
 
+    def _host(self, tensors):
+        self.sync()
+        return tuple(t.cpu().numpy() for t in tensors)
+
+    def _per_frame(self, n, m, d):
+        m, d = self._host((m, d))
+        cnt = self._frame_counts(n)
+        return [(m[f, :cnt[f]].copy(), d[f, :cnt[f]].copy()) for f in range(n)]
+
+    def match_frames_async(self, n, key=None, pairing="key", cross_check=True, max_dist=0.0, ratio=0.0):
+        """fpc_match_frames: every frame of the last detect against the key set ("key") or its predecessor in the batch
+        ("previous"; frame 0 against the key, or nothing without one) -> (match int32 [n,cap], dist float32 [n,cap]) on
+        the device; rows past a frame's count are -1.  Does not synchronise."""
+        pair = self._pairing(pairing)
+        kd, kc = self._key(key)
+        m, d = self._table(n)
+        self._call("fpc_match_frames", n, pair, kd, kc, int(bool(cross_check)), float(max_dist), float(ratio), m, d,
+                   inputs=(kd, kc))
+        return m, d
+
     def match_frames(self, n, key=None, pairing="key", cross_check=True, max_dist=0.0, ratio=0.0):
         """match_frames_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
-        m, d = self.match_frames_async(n, key, pairing, cross_check, max_dist, ratio)
-        self.sync()
-        cnt = self._frame_counts(n)
-        m, d = m.cpu().numpy(), d.cpu().numpy()
-        return [(m[f, :cnt[f]].copy(), d[f, :cnt[f]].copy()) for f in range(n)]
+        return self._per_frame(n, *self.match_frames_async(n, key, pairing, cross_check, max_dist, ratio))
 
     def first_within_frames_async(self, n, key, tolerance=0.8):
         """fpc_first_within_frames -> int32 [n,cap] on the device: per key row, the first row of frame f closer than
@@ -471,20 +502,15 @@ class Engine:
         kd, kc = self._key(key)
         if kd is None:
             raise ValueError("first_within_frames needs a key set")
-        out = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
-        self._enqueue(lambda: _lib.check(self._l.fpc_first_within_frames(self._ctx, n, kd.data_ptr(), kc.data_ptr(),
-                                                                         float(tolerance), out.data_ptr()),
-                                         "fpc_first_within_frames"))
-        kd.record_stream(self.torch_stream())
-        kc.record_stream(self.torch_stream())
+        out = self._int32(n, self.capacity)
+        self._call("fpc_first_within_frames", n, kd, kc, float(tolerance), out, inputs=(kd, kc))
         return out, kc
 
     def first_within_frames(self, n, key, tolerance=0.8):
         """SearchKeyFrameCorrespondence for every frame of the last detect: per frame int32 [nkey]."""
         out, kc = self.first_within_frames_async(n, key, tolerance)
-        self.sync()
-        nk = min(max(int(kc.cpu()[0]), 0), self.capacity)
-        out = out.cpu().numpy()
+        out, kc = self._host((out, kc))
+        nk = min(max(int(kc[0]), 0), self.capacity)
         return [out[f, :nk].copy() for f in range(n)]
 
     # -- geometric verification: RANSAC homographies on the device (fpc_ransac_homography / fpc_homography_frames) -----
@@ -541,52 +567,31 @@ class Engine:
         if src.dim() != 3 or src.shape[2] != 2 or dst.shape != src.shape or npairs.shape != (src.shape[0],):
             raise ValueError("src and dst must be [n,stride,2] and npairs [n]")
         n, stride = int(src.shape[0]), int(src.shape[1])
-        hm = torch.empty((n, 3, 3), dtype=torch.float32, device=self.torch_device)
-        ni = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
-        mask = torch.empty((n, stride), dtype=torch.uint8, device=self.torch_device)
-        self._enqueue(lambda: _lib.check(self._l.fpc_ransac_homography(
-            self._ctx, n, src.data_ptr(), dst.data_ptr(), npairs.data_ptr(), stride, ctypes.byref(p), hm.data_ptr(),
-            ni.data_ptr(), mask.data_ptr()), "fpc_ransac_homography"))
-        for t in (src, dst, npairs):
-            t.record_stream(self.torch_stream())
+        hm, ni, mask = self._ransac_out(n, stride=stride)
+        self._call("fpc_ransac_homography", n, src, dst, npairs, stride, ctypes.byref(p), hm, ni, mask,
+                   inputs=(src, dst, npairs))
         return hm, ni, mask.view(torch.bool)
 
     def ransac_homography(self, src, dst, npairs, **params):
         """ransac_homography_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,stride])."""
-        hm, ni, mask = self.ransac_homography_async(src, dst, npairs, **params)
-        self.sync()
-        return hm.cpu().numpy(), ni.cpu().numpy(), mask.cpu().numpy()
+        return self._host(self.ransac_homography_async(src, dst, npairs, **params))
 
     def homography_frames_async(self, n, match, key_xy=None, pairing="key", **params):
         """fpc_homography_frames: the pairs (xy[f][i], train_xy[match[f][i]]) of every frame of the last detect, `match`
         being match_frames_async's table (int32 [n,cap], device) for the same pairing and key, `key_xy` the key frame's
         coordinates (keep_frame_points) -> device tensors (H [n,3,3], ninliers [n], inlier bool [n,cap] by query row).
         Does not synchronise."""
-        if pairing not in self.PAIRINGS:
-            raise ValueError("pairing must be one of %s, got %r" % (sorted(self.PAIRINGS), pairing))
+        pair = self._pairing(pairing)
         p = self._ransac_params(params)
         kx, kc = self._key_xy(key_xy)
-        if match.device != self.torch_device or match.dtype != torch.int32 or tuple(match.shape) != (n, self.capacity):
-            raise ValueError("match must be a device tensor int32 [n,%d]" % self.capacity)
-        match = match.contiguous()
-        hm = torch.empty((n, 3, 3), dtype=torch.float32, device=self.torch_device)
-        ni = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
-        mask = torch.empty((n, self.capacity), dtype=torch.uint8, device=self.torch_device)
-        self._enqueue(lambda: _lib.check(self._l.fpc_homography_frames(
-            self._ctx, n, self.PAIRINGS[pairing], kx.data_ptr() if kx is not None else None,
-            kc.data_ptr() if kc is not None else None, match.data_ptr(), ctypes.byref(p), hm.data_ptr(), ni.data_ptr(),
-            mask.data_ptr()), "fpc_homography_frames"))
-        match.record_stream(self.torch_stream())
-        if kx is not None:
-            kx.record_stream(self.torch_stream())
-            kc.record_stream(self.torch_stream())
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        hm, ni, mask = self._ransac_out(n)
+        self._call("fpc_homography_frames", n, pair, kx, kc, match, ctypes.byref(p), hm, ni, mask, inputs=(match, kx, kc))
         return hm, ni, mask.view(torch.bool)
 
     def homography_frames(self, n, match, key_xy=None, pairing="key", **params):
         """homography_frames_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,cap])."""
-        hm, ni, mask = self.homography_frames_async(n, match, key_xy, pairing, **params)
-        self.sync()
-        return hm.cpu().numpy(), ni.cpu().numpy(), mask.cpu().numpy()
+        return self._host(self.homography_frames_async(n, match, key_xy, pairing, **params))
 
     # -- key-frame bank: a batch against many stored key frames (fpc_bank_* / fpc_match_bank / fpc_homography_bank) -----
     BANK_FORMATS = {"f32": 0, "bf16": 1}          # include/fpc.h FPC_BANK_F32 / FPC_BANK_BF16
@@ -640,7 +645,7 @@ class Engine:
     def bank_store(self, frame, slot):
         """fpc_bank_store: frame `frame` of the last detect into slot `slot` (its most confident `rows` keypoints), on the
         ctx stream behind that detect.  Does not synchronise."""
-        self._enqueue(lambda: _lib.check(self._l.fpc_bank_store(self._ctx, int(frame), int(slot)), "fpc_bank_store"))
+        self._call("fpc_bank_store", int(frame), int(slot))
 
     def bank_store_rows(self, slot, desc, xy):
         """fpc_bank_store_rows: a saved key frame into slot `slot`: desc [k,D], xy [k,2] (host arrays or device tensors),
@@ -649,40 +654,31 @@ class Engine:
         x, _ = self._key_xy(xy)
         if d is None or x is None or x.shape[0] < d.shape[0]:
             raise ValueError("bank_store_rows needs descriptors [k,D] and coordinates [k,2]")
-        self._enqueue(lambda: _lib.check(self._l.fpc_bank_store_rows(self._ctx, int(slot), d.data_ptr(), x.data_ptr(),
-                                                                     n.data_ptr()), "fpc_bank_store_rows"))
-        for t in (d, x, n):
-            t.record_stream(self.torch_stream())
+        self._call("fpc_bank_store_rows", int(slot), d, x, n, inputs=(d, x, n))
 
     def bank_clear(self, slot=None):
         """fpc_bank_clear: empties slot `slot`, or every slot."""
         s = -1 if slot is None else int(slot)
         if s < 0 and slot is not None:
             raise ValueError("slot must be >= 0 (None clears every slot)")
-        self._enqueue(lambda: _lib.check(self._l.fpc_bank_clear(self._ctx, s), "fpc_bank_clear"))
+        self._call("fpc_bank_clear", s)
 
     def match_bank_async(self, n, cross_check=True, max_dist=0.0, ratio=0.0, min_score=0, table=True):
         """fpc_match_bank: every frame of the last detect against every slot of the bank -> device tensors (score int32
         [n,slots], best int32 [n] (-1: no slot reached max(min_score, 1)), match int32 [n,cap], dist float32 [n,cap]) --
         the last two are match_frames_async's table against slot best[f] (None with table=False).  Give max_dist or
         ratio: a bare cross check does not tell slots apart (include/fpc.h).  Does not synchronise."""
-        v = self._bank_info()
-        score = torch.empty((n, v.slots), dtype=torch.int32, device=self.torch_device)
-        best = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
-        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device) if table else None
-        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device) if table else None
-        self._enqueue(lambda: _lib.check(self._l.fpc_match_bank(
-            self._ctx, n, int(bool(cross_check)), float(max_dist), float(ratio), int(min_score), score.data_ptr(),
-            best.data_ptr(), m.data_ptr() if table else None, d.data_ptr() if table else None), "fpc_match_bank"))
+        score, best = self._int32(n, self._bank_info().slots), self._int32(n)
+        m, d = self._table(n) if table else (None, None)
+        self._call("fpc_match_bank", n, int(bool(cross_check)), float(max_dist), float(ratio), int(min_score), score, best,
+                   m, d)
         return score, best, m, d
 
     def match_bank(self, n, cross_check=True, max_dist=0.0, ratio=0.0, min_score=0):
         """match_bank_async, then host arrays: (score [n,slots], best [n], [(match int32 [K_f], dist float32 [K_f])])."""
         score, best, m, d = self.match_bank_async(n, cross_check, max_dist, ratio, min_score)
-        self.sync()
-        cnt = self._frame_counts(n)
-        m, d = m.cpu().numpy(), d.cpu().numpy()
-        return score.cpu().numpy(), best.cpu().numpy(), [(m[f, :cnt[f]].copy(), d[f, :cnt[f]].copy()) for f in range(n)]
+        tables = self._per_frame(n, m, d)
+        return score.cpu().numpy(), best.cpu().numpy(), tables
 
     def homography_bank_async(self, n, slot, match, **params):
         """fpc_homography_bank: homography_frames_async with frame f's key coordinates taken from bank slot slot[f] (int32
@@ -690,26 +686,15 @@ class Engine:
         ninliers [n], inlier bool [n,cap]); a frame with slot -1 fails (H = 0).  Does not synchronise."""
         self._bank_info()
         p = self._ransac_params(params)
-        if slot.device != self.torch_device or slot.dtype != torch.int32 or tuple(slot.shape) != (n,):
-            raise ValueError("slot must be a device tensor int32 [n]")
-        if match.device != self.torch_device or match.dtype != torch.int32 or tuple(match.shape) != (n, self.capacity):
-            raise ValueError("match must be a device tensor int32 [n,%d]" % self.capacity)
-        slot, match = slot.contiguous(), match.contiguous()
-        hm = torch.empty((n, 3, 3), dtype=torch.float32, device=self.torch_device)
-        ni = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
-        mask = torch.empty((n, self.capacity), dtype=torch.uint8, device=self.torch_device)
-        self._enqueue(lambda: _lib.check(self._l.fpc_homography_bank(
-            self._ctx, n, slot.data_ptr(), match.data_ptr(), ctypes.byref(p), hm.data_ptr(), ni.data_ptr(),
-            mask.data_ptr()), "fpc_homography_bank"))
-        slot.record_stream(self.torch_stream())
-        match.record_stream(self.torch_stream())
+        slot = self._dev_int32("slot", slot, "[n]", n)
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        hm, ni, mask = self._ransac_out(n)
+        self._call("fpc_homography_bank", n, slot, match, ctypes.byref(p), hm, ni, mask, inputs=(slot, match))
         return hm, ni, mask.view(torch.bool)
 
     def homography_bank(self, n, slot, match, **params):
         """homography_bank_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,cap])."""
-        hm, ni, mask = self.homography_bank_async(n, slot, match, **params)
-        self.sync()
-        return hm.cpu().numpy(), ni.cpu().numpy(), mask.cpu().numpy()
+        return self._host(self.homography_bank_async(n, slot, match, **params))
 
     # -- verified relocalisation: the k best slots per frame, each checked by RANSAC (fpc_*_bank_topk) ------------------
     def bank_topk_reserve(self, kmax):
@@ -729,23 +714,16 @@ class Engine:
         table of frame f against slot cand_slot[f,j] (None with table=False).  Does not synchronise."""
         v = self._bank_info()
         k = int(k)
-        score = torch.empty((n, v.slots), dtype=torch.int32, device=self.torch_device)
-        cs = torch.empty((n, k), dtype=torch.int32, device=self.torch_device)
-        csc = torch.empty((n, k), dtype=torch.int32, device=self.torch_device)
-        m = torch.empty((n, k, self.capacity), dtype=torch.int32, device=self.torch_device) if table else None
-        d = torch.empty((n, k, self.capacity), dtype=torch.float32, device=self.torch_device) if table else None
-        self._enqueue(lambda: _lib.check(self._l.fpc_match_bank_topk(
-            self._ctx, n, k, int(bool(cross_check)), float(max_dist), float(ratio), int(min_score), score.data_ptr(),
-            cs.data_ptr(), csc.data_ptr(), m.data_ptr() if table else None, d.data_ptr() if table else None),
-            "fpc_match_bank_topk"))
+        score, cs, csc = self._int32(n, v.slots), self._int32(n, k), self._int32(n, k)
+        m, d = self._table(n, k) if table else (None, None)
+        self._call("fpc_match_bank_topk", n, k, int(bool(cross_check)), float(max_dist), float(ratio), int(min_score), score,
+                   cs, csc, m, d)
         return score, cs, csc, m, d
 
     def match_bank_topk(self, n, k, cross_check=True, max_dist=0.0, ratio=0.0, min_score=0):
         """match_bank_topk_async, then host arrays (score [n,slots], cand_slot [n,k], cand_score [n,k], match [n,k,cap],
         dist [n,k,cap])."""
-        out = self.match_bank_topk_async(n, k, cross_check, max_dist, ratio, min_score)
-        self.sync()
-        return tuple(t.cpu().numpy() for t in out)
+        return self._host(self.match_bank_topk_async(n, k, cross_check, max_dist, ratio, min_score))
 
     def homography_bank_topk_async(self, n, cand_slot, match, **params):
         """fpc_homography_bank_topk: homography_bank_async for every candidate -- cand_slot int32 [n,k] and match int32
@@ -754,31 +732,19 @@ class Engine:
         Does not synchronise."""
         self._bank_info()
         p = self._ransac_params(params)
-        if cand_slot.device != self.torch_device or cand_slot.dtype != torch.int32 or cand_slot.dim() != 2 \
-                or cand_slot.shape[0] != n:
-            raise ValueError("cand_slot must be a device tensor int32 [n,k]")
+        cand_slot = self._dev_int32("cand_slot", cand_slot, "[n,k]", n, None)
         k = int(cand_slot.shape[1])
-        if match.device != self.torch_device or match.dtype != torch.int32 or tuple(match.shape) != (n, k, self.capacity):
-            raise ValueError("match must be a device tensor int32 [n,k,%d]" % self.capacity)
-        cand_slot, match = cand_slot.contiguous(), match.contiguous()
-        hm = torch.empty((n, k, 3, 3), dtype=torch.float32, device=self.torch_device)
-        ni = torch.empty((n, k), dtype=torch.int32, device=self.torch_device)
-        mask = torch.empty((n, k, self.capacity), dtype=torch.uint8, device=self.torch_device)
-        pick = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
-        best = torch.empty((n,), dtype=torch.int32, device=self.torch_device)
-        self._enqueue(lambda: _lib.check(self._l.fpc_homography_bank_topk(
-            self._ctx, n, k, cand_slot.data_ptr(), match.data_ptr(), ctypes.byref(p), hm.data_ptr(), ni.data_ptr(),
-            mask.data_ptr(), pick.data_ptr(), best.data_ptr()), "fpc_homography_bank_topk"))
-        cand_slot.record_stream(self.torch_stream())
-        match.record_stream(self.torch_stream())
+        match = self._dev_int32("match", match, "[n,k,%d]" % self.capacity, n, k, self.capacity)
+        hm, ni, mask = self._ransac_out(n, k)
+        pick, best = self._int32(n), self._int32(n)
+        self._call("fpc_homography_bank_topk", n, k, cand_slot, match, ctypes.byref(p), hm, ni, mask, pick, best,
+                   inputs=(cand_slot, match))
         return hm, ni, mask.view(torch.bool), pick, best
 
     def homography_bank_topk(self, n, cand_slot, match, **params):
         """homography_bank_topk_async, then host arrays (H [n,k,3,3], ninliers [n,k], inlier bool [n,k,cap], pick [n],
         best [n])."""
-        out = self.homography_bank_topk_async(n, cand_slot, match, **params)
-        self.sync()
-        return tuple(t.cpu().numpy() for t in out)
+        return self._host(self.homography_bank_topk_async(n, cand_slot, match, **params))
 
     def relocalise(self, n, k, cross_check=True, max_dist=0.7, ratio=0.0, min_score=0, **params):
         """match_bank_topk_async then homography_bank_topk_async, one synchronisation: which stored frame does each frame
@@ -787,10 +753,10 @@ class Engine:
         >= k); RANSAC parameters as in homography_bank_async."""
         _, cs, csc, m, _ = self.match_bank_topk_async(n, k, cross_check, max_dist, ratio, min_score)
         hm, ni, _, _, best = self.homography_bank_topk_async(n, cs, m, **params)
-        self.sync()
-        return tuple(t.cpu().numpy() for t in (best, hm, ni, cs, csc))
+        return self._host((best, hm, ni, cs, csc))
 
-    # -- guided matching: the match once more under the estimated homographies (fpc_match_*_guided) -------------------
+    # -- guided matching: the match once more under the estimated homographies (fpc_match_*_guided), and its cell-ordered
+    # -- form (fpc_cell_order / fpc_match_*_guided_cells): the same tables, fewer tiles ------------------------------------
     def _guided_h(self, n, hm):
         """H -> a contiguous device tensor float32 [n,9] (homography_*_async's [n,3,3] output as it is, or a host array)."""
         hm = torch.as_tensor(hm).to(self.torch_device, torch.float32).contiguous()
@@ -798,11 +764,27 @@ class Engine:
             raise ValueError("H must be [n,3,3] or [n,9]")
         return hm
 
-    def _per_frame(self, n, m, d):
-        self.sync()
-        cnt = self._frame_counts(n)
-        m, d = m.cpu().numpy(), d.cpu().numpy()
-        return [(m[f, :cnt[f]].copy(), d[f, :cnt[f]].copy()) for f in range(n)]
+    def _guided(self, name, cells, stats, n, train, H, radius, cross_check, max_dist, ratio):
+        """fpc_<name>[_cells](ctx, n, *train, H, radius, ...): what every guided call does behind its train set's checks."""
+        hm = self._guided_h(n, H)
+        m, d = self._table(n)
+        st = self._int32(n, 2) if stats else None
+        self._call(name + "_cells" if cells else name, n, *train, hm, float(radius), int(bool(cross_check)), float(max_dist),
+                   float(ratio), m, d, *((st,) if cells else ()), inputs=(*train, hm))
+        return (m, d, st) if stats else (m, d)
+
+    def _guided_frames(self, cells, stats, n, H, radius, key, key_xy, pairing, *options):
+        pair = self._pairing(pairing)
+        kd, kc = self._key(key)
+        kx, _ = self._key_xy(key_xy)
+        if kd is not None and (kx is None or kx.shape[0] < kd.shape[0]):
+            raise ValueError("a key needs key_xy with a row for each of its rows")
+        return self._guided("fpc_match_frames_guided", cells, stats, n, (pair, kd, kc, kx), H, radius, *options)
+
+    def _guided_bank(self, cells, stats, n, slot, H, radius, *options):
+        self._bank_info()
+        slot = self._dev_int32("slot", slot, "[n]", n)
+        return self._guided("fpc_match_bank_guided", cells, stats, n, (slot,), H, radius, *options)
 
     def match_frames_guided_async(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True, max_dist=0.0,
                                   ratio=0.0):
@@ -810,24 +792,7 @@ class Engine:
         [n,3,3], query pixel -> train pixel: homography_frames_async's output, device or host) sends the query row;
         `key` / `key_xy` as in match_frames_async / homography_frames_async (the key's count is `key`'s) -> (match int32
         [n,cap], dist float32 [n,cap]) on the device; a frame with H = 0 is all -1.  Does not synchronise."""
-        if pairing not in self.PAIRINGS:
-            raise ValueError("pairing must be one of %s, got %r" % (sorted(self.PAIRINGS), pairing))
-        kd, kc = self._key(key)
-        kx, _ = self._key_xy(key_xy)
-        if kd is not None and (kx is None or kx.shape[0] < kd.shape[0]):
-            raise ValueError("a key needs key_xy with a row for each of its rows")
-        hm = self._guided_h(n, H)
-        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
-        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device)
-        self._enqueue(lambda: _lib.check(self._l.fpc_match_frames_guided(
-            self._ctx, n, self.PAIRINGS[pairing], kd.data_ptr() if kd is not None else None,
-            kc.data_ptr() if kc is not None else None, kx.data_ptr() if kx is not None else None, hm.data_ptr(),
-            float(radius), int(bool(cross_check)), float(max_dist), float(ratio), m.data_ptr(), d.data_ptr()),
-            "fpc_match_frames_guided"))
-        for t in (kd, kc, kx, hm):
-            if t is not None:
-                t.record_stream(self.torch_stream())
-        return m, d
+        return self._guided_frames(False, False, n, H, radius, key, key_xy, pairing, cross_check, max_dist, ratio)
 
     def match_frames_guided(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True, max_dist=0.0,
                             ratio=0.0):
@@ -839,25 +804,12 @@ class Engine:
         """fpc_match_bank_guided: match_frames_guided_async with frame f's train set taken from bank slot slot[f] (int32
         [n], device; normally match_bank_async's `best`; -1: an all -1 row) and H homography_bank_async's output.  Does
         not synchronise."""
-        self._bank_info()
-        if slot.device != self.torch_device or slot.dtype != torch.int32 or tuple(slot.shape) != (n,):
-            raise ValueError("slot must be a device tensor int32 [n]")
-        slot = slot.contiguous()
-        hm = self._guided_h(n, H)
-        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
-        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device)
-        self._enqueue(lambda: _lib.check(self._l.fpc_match_bank_guided(
-            self._ctx, n, slot.data_ptr(), hm.data_ptr(), float(radius), int(bool(cross_check)), float(max_dist),
-            float(ratio), m.data_ptr(), d.data_ptr()), "fpc_match_bank_guided"))
-        slot.record_stream(self.torch_stream())
-        hm.record_stream(self.torch_stream())
-        return m, d
+        return self._guided_bank(False, False, n, slot, H, radius, cross_check, max_dist, ratio)
 
     def match_bank_guided(self, n, slot, H, radius, cross_check=True, max_dist=0.0, ratio=0.0):
         """match_bank_guided_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
         return self._per_frame(n, *self.match_bank_guided_async(n, slot, H, radius, cross_check, max_dist, ratio))
 
-    # -- cell-ordered guided matching (fpc_cell_order / fpc_match_*_guided_cells): the same tables, fewer tiles -------
     def cell_order_async(self, xy, counts):
         """fpc_cell_order: xy int32 [sets,stride,2], counts int32 [sets] (device tensors or host arrays) -> perm int32
         [sets,stride] on the device: every set's rows in the stable order by 32-px cell (include/fpc.h); entries past a
@@ -866,12 +818,8 @@ class Engine:
         counts = torch.as_tensor(counts).to(self.torch_device, torch.int32).contiguous()
         if xy.dim() != 3 or xy.shape[2] != 2 or tuple(counts.shape) != (xy.shape[0],) or xy.shape[0] < 1 or xy.shape[1] < 1:
             raise ValueError("xy must be [sets,stride,2] and counts [sets]")
-        perm = torch.empty(tuple(xy.shape[:2]), dtype=torch.int32, device=self.torch_device)
-        self._enqueue(lambda: _lib.check(self._l.fpc_cell_order(
-            self._ctx, xy.data_ptr(), counts.data_ptr(), int(xy.shape[0]), int(xy.shape[1]), perm.data_ptr()),
-            "fpc_cell_order"))
-        xy.record_stream(self.torch_stream())
-        counts.record_stream(self.torch_stream())
+        perm = self._int32(*xy.shape[:2])
+        self._call("fpc_cell_order", xy, counts, int(xy.shape[0]), int(xy.shape[1]), perm, inputs=(xy, counts))
         return perm
 
     def match_frames_guided_cells_async(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True,
@@ -879,25 +827,7 @@ class Engine:
         """fpc_match_frames_guided_cells: match_frames_guided_async's arguments and, bit for bit, its (match, dist), from
         the cell-ordered kernel that visits only the tiles the gate can reach.  stats=True: (match, dist, stats int32
         [n,2]: per frame (strip, tile) pairs visited, and the pairs there are).  Does not synchronise."""
-        if pairing not in self.PAIRINGS:
-            raise ValueError("pairing must be one of %s, got %r" % (sorted(self.PAIRINGS), pairing))
-        kd, kc = self._key(key)
-        kx, _ = self._key_xy(key_xy)
-        if kd is not None and (kx is None or kx.shape[0] < kd.shape[0]):
-            raise ValueError("a key needs key_xy with a row for each of its rows")
-        hm = self._guided_h(n, H)
-        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
-        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device)
-        st = torch.empty((n, 2), dtype=torch.int32, device=self.torch_device) if stats else None
-        self._enqueue(lambda: _lib.check(self._l.fpc_match_frames_guided_cells(
-            self._ctx, n, self.PAIRINGS[pairing], kd.data_ptr() if kd is not None else None,
-            kc.data_ptr() if kc is not None else None, kx.data_ptr() if kx is not None else None, hm.data_ptr(),
-            float(radius), int(bool(cross_check)), float(max_dist), float(ratio), m.data_ptr(), d.data_ptr(),
-            st.data_ptr() if stats else None), "fpc_match_frames_guided_cells"))
-        for t in (kd, kc, kx, hm):
-            if t is not None:
-                t.record_stream(self.torch_stream())
-        return (m, d, st) if stats else (m, d)
+        return self._guided_frames(True, stats, n, H, radius, key, key_xy, pairing, cross_check, max_dist, ratio)
 
     def match_frames_guided_cells(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True,
                                   max_dist=0.0, ratio=0.0):
@@ -908,20 +838,7 @@ class Engine:
     def match_bank_guided_cells_async(self, n, slot, H, radius, cross_check=True, max_dist=0.0, ratio=0.0, stats=False):
         """fpc_match_bank_guided_cells: match_bank_guided_async's arguments and, bit for bit, its (match, dist) on an
         "f32" bank (a "bf16" bank is refused); stats as in match_frames_guided_cells_async.  Does not synchronise."""
-        self._bank_info()
-        if slot.device != self.torch_device or slot.dtype != torch.int32 or tuple(slot.shape) != (n,):
-            raise ValueError("slot must be a device tensor int32 [n]")
-        slot = slot.contiguous()
-        hm = self._guided_h(n, H)
-        m = torch.empty((n, self.capacity), dtype=torch.int32, device=self.torch_device)
-        d = torch.empty((n, self.capacity), dtype=torch.float32, device=self.torch_device)
-        st = torch.empty((n, 2), dtype=torch.int32, device=self.torch_device) if stats else None
-        self._enqueue(lambda: _lib.check(self._l.fpc_match_bank_guided_cells(
-            self._ctx, n, slot.data_ptr(), hm.data_ptr(), float(radius), int(bool(cross_check)), float(max_dist),
-            float(ratio), m.data_ptr(), d.data_ptr(), st.data_ptr() if stats else None), "fpc_match_bank_guided_cells"))
-        slot.record_stream(self.torch_stream())
-        hm.record_stream(self.torch_stream())
-        return (m, d, st) if stats else (m, d)
+        return self._guided_bank(True, stats, n, slot, H, radius, cross_check, max_dist, ratio)
 
     def match_bank_guided_cells(self, n, slot, H, radius, cross_check=True, max_dist=0.0, ratio=0.0):
         """match_bank_guided_cells_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
@@ -963,6 +880,11 @@ class Engine:
         out = [k for _, k, _, _, _, _ in self.timings()]
         self.set_timing(False)
         return out
+
+
+def _ptr(a):
+    """A tensor's device pointer; anything else (None, a host scalar, a ctypes reference) as it is."""
+    return a.data_ptr() if isinstance(a, torch.Tensor) else a
 
 
 class _DevArray:

@@ -81,6 +81,26 @@ def test_guard_zones_see_a_planted_store():
         e.close()
 
 
+def test_guard_zones_see_a_planted_store_in_the_bank():
+    """The same checker over the key-frame bank's allocation (the fill and count code is shared by every slab): four words
+    right behind the bank's `count` buffer (int32[2] = 8 bytes: its zone starts at the next 256-byte boundary, inside
+    the bank's own allocation) are counted."""
+    import torch
+    from fpc_amd.engine import _DevArray
+    e = engine(32, 48, 1, descriptor_enabled=True, plan_flags=["guard_zones"])
+    e.bank_create(2)
+    assert e.check_guards() == 0
+    view = torch.as_tensor(_DevArray(int(e._bank.count) + 256, 64), device=e.torch_device)
+    view[:16] = 0
+    torch.cuda.synchronize()
+    assert e.check_guards() == 4
+    if os.environ.get("FPC_GUARD_ZONES") == "1":      # (as above: damaged on purpose)
+        with pytest.raises(RuntimeError):
+            e.close()
+    else:
+        e.close()
+
+
 def test_headline_plan_one_sub_batch_on_one_stream_matches_oracle_and_default_plan():
     """bench.py's headline runs every 32-frame VGA batch as ONE sub-batch on one stream (num_streams = 1): wblock36 grids
     of 216 workgroups walking 640 tiles in three rounds, the 2 x 8 instance at layer1.  Held to (a) the oracle's own
