@@ -35,6 +35,7 @@ SYMBOLS = [
     "fpc_match_frames_guided", "fpc_match_bank_guided",
     "fpc_cell_order", "fpc_match_frames_guided_cells", "fpc_match_bank_guided_cells",
     "fpc_bank_topk_reserve", "fpc_match_bank_topk", "fpc_homography_bank_topk",
+    "fpc_ransac_fundamental", "fpc_fundamental_frames", "fpc_fundamental_bank",
 ]
 
 ABI_VERSION = 4
@@ -178,6 +179,9 @@ def load():
     l.fpc_bank_clear.argtypes = [vp, ci]
     l.fpc_match_bank.argtypes = [vp, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp]
     l.fpc_homography_bank.argtypes = [vp, ci, vp, vp, rp, vp, vp, vp]
+    l.fpc_ransac_fundamental.argtypes = [vp, ci, vp, vp, vp, ci, rp, vp, vp, vp]
+    l.fpc_fundamental_frames.argtypes = [vp, ci, ci, vp, vp, vp, rp, vp, vp, vp]
+    l.fpc_fundamental_bank.argtypes = [vp, ci, vp, vp, rp, vp, vp, vp]
     l.fpc_match_frames_guided.argtypes = [vp, ci, ci, vp, vp, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float,
                                           vp, vp]
     l.fpc_match_bank_guided.argtypes = [vp, ci, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float, vp, vp]

@@ -40,6 +40,7 @@
 #include "match_guided.h"
 #include "match_guided_cells.h"
 #include "ransac_homography.h"
+#include "ransac_fundamental.h"
 #include "match_bank_topk.h"
 #include "homography.h"
 #include "weights.h"
@@ -3999,6 +4000,42 @@ int fpc_homography_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy,
   return FPC_OK;
 }
 
+// ---- RANSAC fundamental matrices (include/fpc.h; kernels in ransac_fundamental.h) -----------------------------------------
+// The homography calls' pack / gather kernels, pair records and workspace; the 8-point sample needs 8 inliers at the least.
+static bool fundamental_params_ok(const fpc_ransac_params* p) { return ransac_params_ok(p) && p->min_inliers >= FM_SAMPLE; }
+
+static void fundamental_launch(fpc_ctx* c, const HfArgs& a, float* F, int32_t* ninliers, uint8_t* inlier, int mstride) {
+  hipLaunchKernelGGL(fm_score_kernel, dim3((a.T + FM_THREADS - 1) / FM_THREADS, a.n), dim3(FM_THREADS), 0, c->stream, a);
+  hipLaunchKernelGGL(fm_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, F, ninliers, inlier, mstride);
+}
+
+int fpc_ransac_fundamental(fpc_ctx* c, int n, const float* src_xy, const float* dst_xy, const int32_t* npairs, int stride,
+                           const fpc_ransac_params* p, float* F, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !src_xy || !dst_xy || !npairs || !F || !ninliers || !fundamental_params_ok(p)) return FPC_E_INVALID;
+  if (n < 1 || n > c->B || stride < 1 || stride > c->cap) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const HfArgs a = ransac_args(c, n, p);
+  hipLaunchKernelGGL(hf_pack_kernel, dim3((stride + 255) / 256, n), dim3(256), 0, c->stream, a, src_xy, dst_xy, npairs,
+                     stride, inlier);
+  fundamental_launch(c, a, F, ninliers, inlier, stride);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_fundamental_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy, const int32_t* nkey, const int32_t* match,
+                           const fpc_ransac_params* p, float* F, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !match || !F || !ninliers || !fundamental_params_ok(p) || !pairing_ok(pairing) || !frames_ok(c, n) ||
+      (pairing == FPC_PAIR_KEY && !key_xy) || (key_xy && !nkey))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const HfArgs a = ransac_args(c, n, p);
+  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, pairing, key_xy, nkey, match,
+                     inlier, HfBank{});
+  fundamental_launch(c, a, F, ninliers, inlier, c->cap);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
 // ---- key-frame bank (include/fpc.h; kernels in match_bank.h) -------------------------------------------------------------
 // fpc_match_bank's score pass keeps top-2 keys (16 B) per query row and a column minimum (8 B) per bank row for every
 // (frame, slot) pair in flight; the slots run in chunks so that this stays within BANK_WS_BUDGET (one slot at the least).
@@ -4207,6 +4244,20 @@ int fpc_homography_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* m
   hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
                      (const int32_t*)nullptr, match, inlier, hb);
   ransac_launch(c, a, H, ninliers, inlier, c->cap);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_fundamental_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const fpc_ransac_params* p, float* F,
+                         int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->bank_slab || !slot || !match || !F || !ninliers || !fundamental_params_ok(p) || !frames_ok(c, n))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const HfArgs a = ransac_args(c, n, p);
+  const HfBank hb{slot, c->bank.count, c->bank.rows, c->bank.slots};
+  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
+                     (const int32_t*)nullptr, match, inlier, hb);
+  fundamental_launch(c, a, F, ninliers, inlier, c->cap);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }

@@ -696,6 +696,59 @@ class Engine:
         """homography_bank_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,cap])."""
         return self._host(self.homography_bank_async(n, slot, match, **params))
 
+    # -- epipolar verification: RANSAC fundamental matrices (fpc_ransac_fundamental / fpc_fundamental_frames / _bank) --------
+    def ransac_fundamental_async(self, src, dst, npairs, **params):
+        """fpc_ransac_fundamental: ransac_homography_async's arguments -> device tensors (F float32 [n,3,3] with
+        (u, v, 1) F (x, y, 1)^T = 0 for a src pixel (x, y) and its dst pixel (u, v), norm 1, rank 2; ninliers int32 [n];
+        inlier bool [n,stride], the pairs within reproj_threshold in Sampson distance); a failed frame has F = 0 and no
+        inliers.  min_inliers must be >= 8.  Does not synchronise."""
+        p = self._ransac_params(params)
+        src = torch.as_tensor(src).to(self.torch_device, torch.float32).contiguous()
+        dst = torch.as_tensor(dst).to(self.torch_device, torch.float32).contiguous()
+        npairs = torch.as_tensor(npairs).to(self.torch_device, torch.int32).contiguous()
+        if src.dim() != 3 or src.shape[2] != 2 or dst.shape != src.shape or npairs.shape != (src.shape[0],):
+            raise ValueError("src and dst must be [n,stride,2] and npairs [n]")
+        n, stride = int(src.shape[0]), int(src.shape[1])
+        fm, ni, mask = self._ransac_out(n, stride=stride)
+        self._call("fpc_ransac_fundamental", n, src, dst, npairs, stride, ctypes.byref(p), fm, ni, mask,
+                   inputs=(src, dst, npairs))
+        return fm, ni, mask.view(torch.bool)
+
+    def ransac_fundamental(self, src, dst, npairs, **params):
+        """ransac_fundamental_async, then host arrays (F [n,3,3], ninliers [n], inlier bool [n,stride])."""
+        return self._host(self.ransac_fundamental_async(src, dst, npairs, **params))
+
+    def fundamental_frames_async(self, n, match, key_xy=None, pairing="key", **params):
+        """fpc_fundamental_frames: homography_frames_async's arguments and pairs -> device tensors (F [n,3,3], ninliers
+        [n], inlier bool [n,cap] by query row).  Does not synchronise."""
+        pair = self._pairing(pairing)
+        p = self._ransac_params(params)
+        kx, kc = self._key_xy(key_xy)
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        fm, ni, mask = self._ransac_out(n)
+        self._call("fpc_fundamental_frames", n, pair, kx, kc, match, ctypes.byref(p), fm, ni, mask, inputs=(match, kx, kc))
+        return fm, ni, mask.view(torch.bool)
+
+    def fundamental_frames(self, n, match, key_xy=None, pairing="key", **params):
+        """fundamental_frames_async, then host arrays (F [n,3,3], ninliers [n], inlier bool [n,cap])."""
+        return self._host(self.fundamental_frames_async(n, match, key_xy, pairing, **params))
+
+    def fundamental_bank_async(self, n, slot, match, **params):
+        """fpc_fundamental_bank: fundamental_frames_async with frame f's key coordinates taken from bank slot slot[f], as
+        homography_bank_async -> device tensors (F [n,3,3], ninliers [n], inlier bool [n,cap]); a frame with slot -1
+        fails (F = 0).  Does not synchronise."""
+        self._bank_info()
+        p = self._ransac_params(params)
+        slot = self._dev_int32("slot", slot, "[n]", n)
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        fm, ni, mask = self._ransac_out(n)
+        self._call("fpc_fundamental_bank", n, slot, match, ctypes.byref(p), fm, ni, mask, inputs=(slot, match))
+        return fm, ni, mask.view(torch.bool)
+
+    def fundamental_bank(self, n, slot, match, **params):
+        """fundamental_bank_async, then host arrays (F [n,3,3], ninliers [n], inlier bool [n,cap])."""
+        return self._host(self.fundamental_bank_async(n, slot, match, **params))
+
     # -- verified relocalisation: the k best slots per frame, each checked by RANSAC (fpc_*_bank_topk) ------------------
     def bank_topk_reserve(self, kmax):
         """fpc_bank_topk_reserve: workspace for up to `kmax` candidates per frame (1 <= kmax <= min(16, slots)); the only

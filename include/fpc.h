@@ -520,6 +520,64 @@ int fpc_match_bank(fpc_ctx* ctx, int n, int cross_check, float max_dist, float r
 int fpc_homography_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev,
                         const fpc_ransac_params* params, float* H_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
 
+/* --- epipolar verification: a RANSAC fundamental matrix per frame from the same device-side pair lists ------------------
+ * A homography explains two views only of a planar scene or under a pure rotation; a key frame of a room or a street seen
+ * from a moved camera supports none.  The other model is the fundamental matrix F with q^T F p = 0 for a query pixel p and
+ * its train pixel q.  fpc_ransac_fundamental, fpc_fundamental_frames and fpc_fundamental_bank mirror
+ * fpc_ransac_homography, fpc_homography_frames and fpc_homography_bank argument for argument -- the same pair definition,
+ * mask indexing, stride rules, fpc_ransac_params, workspace and execution rules (asynchronous on the ctx stream, no host
+ * synchronisation, no device-to-host copy, no allocation, every count read on the device) -- with F_dev float32 [n][9] in
+ * place of H_dev.  As for the homographies, OpenCV is not available to this build: the rule below is pinned by planted
+ * scenes and by a float64 restatement (tests/test_fundamental_ransac.py), not against cv2.findFundamentalMat.
+ *  - Direction and form: F is row-major with (u, v, 1) F (x, y, 1)^T = 0, (x, y) the query / src pixel and (u, v) the
+ *    train / dst pixel.  F has Frobenius norm 1; its element of largest magnitude (of the fp32 values; ties: the lowest
+ *    index) is positive; it has rank 2 up to its fp32 rounding.
+ *  - Inliers: with l = F p, l' = F^T q and e = q . l, a pair is an inlier when e^2 < reproj_threshold^2 (l0^2 + l1^2 +
+ *    l'0^2 + l'1^2): the Sampson distance below the threshold, without a division, evaluated in fp64 from the fp32 F that
+ *    is returned.  ninliers and inlier are those of the returned F.
+ *  - Failure: a frame with fewer than 8 pairs, with no non-degenerate sample, or with fewer than min_inliers inliers after
+ *    the last refit gets nine zeros, ninliers = 0 and an all-zero mask.
+ *  - Sampling: mix() as above with a budget of 32 draws: draw k = 0 .. 31 of hypothesis t of frame f over M pairs is
+ *        r = mix(seed ^ mix((f * 4096 + t) * 32 + k)) % M;
+ *    a draw equal to an index already taken is skipped; the first 8 distinct indices are the sample (in that order), and a
+ *    hypothesis that has not found 8 within its 32 draws is degenerate.
+ *  - Minimal solve (8-point), in fp64: the sample's 8 src points are translated to their centroid and scaled to an RMS
+ *    distance of sqrt(2), the dst points likewise (a side whose mean squared distance is not > 1e-12 is degenerate).  The
+ *    8 x 9 system of the rows [ux uy u vx vy v x y 1] is reduced by Gaussian elimination with FULL pivoting -- the pivot of
+ *    step c is the entry of largest magnitude in rows and columns >= c, ties to the lowest row, then the lowest column --
+ *    and the null vector is read by back-substitution with the unknown of the last column set to 1: no coordinate of F is
+ *    assumed non-zero (a sideways translation has F[8] = 0 exactly).  A last pivot below 1e-10 of the first makes the
+ *    sample degenerate (repeated points, rank below 8), so does a non-finite result.  F is denormalised, scaled to
+ *    max |f| = 1 and rounded to fp32.  Degenerate samples score 0 and are never chosen.
+ *  - Scoring: hypothesis t counts the pairs that pass the Sampson test above in fp32 (fmaf).  Selection: the largest
+ *    count; ties go to the lower t (an integer maximum: independent of execution order).
+ *  - The best sample's F becomes a returnable F: rank 2 is enforced in the sample's normalised coordinates as
+ *    F <- F - (F v3) v3^T, v3 the eigenvector of F^T F's smallest eigenvalue; then it is denormalised, brought to norm 1,
+ *    rounded to fp32 and given the sign above.  (In pixel coordinates the projection would be dominated by F[8].)
+ *  - Refit, `refits` times: the inliers of the current F are translated and scaled as in the homography refit (the same
+ *    moments); M = sum a a^T with a = q (x) p (36 distinct sums) is accumulated in fp64 in a fixed order (no floating-point
+ *    atomics); F takes the eigenvector of M's smallest eigenvalue, by cyclic Jacobi with 10 sweeps over (p, q), p < q in
+ *    row-major order (rotation: theta = (a_qq - a_pp) / (2 a_pq), t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)); a zero
+ *    a_pq is skipped; the smallest diagonal entry, ties to the lowest index); rank 2 is enforced as above with the same
+ *    routine at N = 3; then denormalised, norm 1, fp32, sign.  Fewer than 8 inliers, a point set of zero spread or a
+ *    non-finite result keeps the previous F and ends the refits.
+ *  - Determinism: as for the homography calls; the three entry points give bit-identical outputs on equal pair lists, and
+ *    fpc_fundamental_bank is bit-identical to fpc_fundamental_frames with that slot as key at the SAME frame index.
+ *  - Caveat: on a planar scene or under a pure rotation F is not unique.  With measured (rounded, noisy) points, or with
+ *    a few outliers among the pairs, the call returns ONE F the pairs agree with.  Pairs that follow a homography EXACTLY
+ *    and have no outlier among them (an integer image shift, a frame against itself) leave every 8-point system at rank 6:
+ *    every sample is degenerate and the frame FAILS with nine zeros, as under "Failure".  Such scenes are what the
+ *    homography calls are for; choosing between the two models is the caller's job.
+ * FPC_E_INVALID (nothing is written): everything the homography twin refuses, and min_inliers < 8. */
+int fpc_ransac_fundamental(fpc_ctx* ctx, int n, const float* src_xy_dev, const float* dst_xy_dev, const int32_t* npairs_dev,
+                           int stride, const fpc_ransac_params* params, float* F_dev, int32_t* ninliers_dev,
+                           uint8_t* inlier_dev);
+int fpc_fundamental_frames(fpc_ctx* ctx, int n, int pairing, const int32_t* key_xy_dev, const int32_t* nkey_dev,
+                           const int32_t* match_dev, const fpc_ransac_params* params, float* F_dev, int32_t* ninliers_dev,
+                           uint8_t* inlier_dev);
+int fpc_fundamental_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev,
+                         const fpc_ransac_params* params, float* F_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
+
 /* --- the bank in bf16: half the memory per stored frame, the score pass on the bf16 matrix path --------------------------
  * fpc_bank_create_ex(format): FPC_BANK_F32 is fpc_bank_create, and everything stated above -- every bit-identity with
  * fpc_match_frames included -- holds for it unchanged.  FPC_BANK_BF16 is an opt-in storage AND arithmetic format for
