@@ -39,6 +39,7 @@
 #include "match_bank_bf16.h"
 #include "match_guided.h"
 #include "match_guided_cells.h"
+#include "match_guided_epipolar.h"
 #include "ransac_homography.h"
 #include "ransac_fundamental.h"
 #include "match_bank_topk.h"
@@ -4347,7 +4348,8 @@ int fpc_homography_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot,
   return FPC_OK;
 }
 
-// ---- guided matching, plain and cell-ordered (include/fpc.h; kernels in match_guided.h, match_guided_cells.h) -------------
+// ---- guided matching: plain, cell-ordered and epipolar (include/fpc.h; kernels in match_guided.h, match_guided_cells.h,
+// ---- match_guided_epipolar.h) ------------------------------------------------------------------------------------------------
 // 32-px cells wherever the order is public; a frame of more cells than the order kernel's histogram holds (beyond
 // 16.7 MPx) is ordered in coarser cells by the guided calls, whose output does not depend on the order.
 static CellOrderArgs cell_order_args(fpc_ctx* c, int shift) {
@@ -4393,12 +4395,12 @@ static MatchCellsArgs cell_order_passes(fpc_ctx* c, const MatchFramesArgs& a, co
   return MatchCellsArgs{c->mgc_perm_q, c->mgc_box, c->mgc_perm_t, box_t, nbox, stats};
 }
 
-// The four guided entry points run on fpc_match_frames' workspace (norms, top-2, column minima: [max_batch][cap], and the
+// The six guided entry points run on fpc_match_frames' workspace (norms, top-2, column minima: [max_batch][cap], and the
 // bank's rows <= cap), carved at fpc_create: nothing of their own.  One sequence for all: the column minima and the stats
 // reset, the norms (a bf16 bank: its rounding pass, match_bank_bf16.h), the variant's strip kernel (the cell-ordered one
 // behind its order passes), the finalize kernel.  norm_blocks: n + 1 with the key's block, n against the bank, whose
 // norms are its own.
-enum GuidedStrip { GUIDED_PLAIN, GUIDED_CELLS, GUIDED_BANK_BF16 };
+enum GuidedStrip { GUIDED_PLAIN, GUIDED_CELLS, GUIDED_BANK_BF16, GUIDED_EPIPOLAR };
 
 static int match_guided_launch(fpc_ctx* c, GuidedStrip strip, MatchFramesArgs a, const MatchGuidedArgs& g, int norm_blocks,
                                float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
@@ -4416,6 +4418,8 @@ static int match_guided_launch(fpc_ctx* c, GuidedStrip strip, MatchFramesArgs a,
   } else if (strip == GUIDED_BANK_BF16) {
     hipLaunchKernelGGL(by_depth(c, match_bank_bf16_kernel<8, true>, match_bank_bf16_kernel<16, true>), strips, dim3(256), 0,
                        c->stream, a, c->bank, c->bank16, g);
+  } else if (strip == GUIDED_EPIPOLAR) {
+    hipLaunchKernelGGL(match_guided_epipolar_kernel, strips, dim3(256), 0, c->stream, a, g);     // (g.H holds F)
   } else {
     hipLaunchKernelGGL(match_guided_kernel, strips, dim3(256), 0, c->stream, a, g);
   }
@@ -4429,7 +4433,7 @@ static bool guided_options_ok(const float* H, float radius, float max_dist, floa
   return H && match && std::isfinite(radius) && radius > 0.f && gate_ok(max_dist, ratio);
 }
 
-// fpc_match_frames_guided[_cells]: the key set (or frame f - 1) as the train set
+// fpc_match_frames_guided[_cells | _epipolar]: the key set (or frame f - 1) as the train set
 static int match_frames_guided(fpc_ctx* c, GuidedStrip strip, int n, int pairing, const float* key, const int32_t* nkey,
                                const int32_t* key_xy, const float* H, float radius, int cross_check, float max_dist,
                                float ratio, int32_t* match, float* dist, int32_t* stats) {
@@ -4445,20 +4449,20 @@ static int match_frames_guided(fpc_ctx* c, GuidedStrip strip, int n, int pairing
   return match_guided_launch(c, strip, a, g, n + 1, max_dist, ratio, match, dist, stats);
 }
 
-// fpc_match_bank_guided[_cells]: bank slot slot[f] as frame f's train set
-static int match_bank_guided(fpc_ctx* c, bool cells, int n, const int32_t* slot, const float* H, float radius, int cross_check,
+// fpc_match_bank_guided[_cells | _epipolar]: bank slot slot[f] as frame f's train set (strip: GUIDED_PLAIN stands for the
+// bank's own format, fp32 or bf16)
+static int match_bank_guided(fpc_ctx* c, GuidedStrip strip, int n, const int32_t* slot, const float* H, float radius, int cross_check,
                              float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
   if (!c || !c->bank_slab || !slot || !guided_options_ok(H, radius, max_dist, ratio, match)) return FPC_E_INVALID;
   const bool half = c->bank_format != FPC_BANK_F32;
-  if (cells && half) return FPC_E_INVALID;                     // (the bf16 bank's ordered strip: not built yet)
+  if (strip != GUIDED_PLAIN && half) return FPC_E_INVALID;     // (the bf16 bank's ordered and epipolar strips: not built yet)
   if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
   HIPCHECK(hipSetDevice(c->cfg.device));
   MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
   a.cross_check = cross_check != 0;
   bank_as_train(a, c->bank, slot);
   const MatchGuidedArgs g{H, c->xy, c->bank.xy, (double)radius * (double)radius};
-  return match_guided_launch(c, cells ? GUIDED_CELLS : half ? GUIDED_BANK_BF16 : GUIDED_PLAIN, a, g, n, max_dist, ratio, match,
-                             dist, stats);
+  return match_guided_launch(c, half ? GUIDED_BANK_BF16 : strip, a, g, n, max_dist, ratio, match, dist, stats);
 }
 
 int fpc_match_frames_guided(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey, const int32_t* key_xy,
@@ -4477,12 +4481,24 @@ int fpc_match_frames_guided_cells(fpc_ctx* c, int n, int pairing, const float* k
 
 int fpc_match_bank_guided(fpc_ctx* c, int n, const int32_t* slot, const float* H, float radius, int cross_check,
                           float max_dist, float ratio, int32_t* match, float* dist) {
-  return match_bank_guided(c, false, n, slot, H, radius, cross_check, max_dist, ratio, match, dist, nullptr);
+  return match_bank_guided(c, GUIDED_PLAIN, n, slot, H, radius, cross_check, max_dist, ratio, match, dist, nullptr);
 }
 
 int fpc_match_bank_guided_cells(fpc_ctx* c, int n, const int32_t* slot, const float* H, float radius, int cross_check,
                                 float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
-  return match_bank_guided(c, true, n, slot, H, radius, cross_check, max_dist, ratio, match, dist, stats);
+  return match_bank_guided(c, GUIDED_CELLS, n, slot, H, radius, cross_check, max_dist, ratio, match, dist, stats);
+}
+
+int fpc_match_frames_guided_epipolar(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey,
+                                     const int32_t* key_xy, const float* F, float radius, int cross_check, float max_dist,
+                                     float ratio, int32_t* match, float* dist) {
+  return match_frames_guided(c, GUIDED_EPIPOLAR, n, pairing, key, nkey, key_xy, F, radius, cross_check, max_dist, ratio, match,
+                             dist, nullptr);
+}
+
+int fpc_match_bank_guided_epipolar(fpc_ctx* c, int n, const int32_t* slot, const float* F, float radius, int cross_check,
+                                   float max_dist, float ratio, int32_t* match, float* dist) {
+  return match_bank_guided(c, GUIDED_EPIPOLAR, n, slot, F, radius, cross_check, max_dist, ratio, match, dist, nullptr);
 }
 
 int fpc_results(fpc_ctx* c, fpc_device_results* out) {

@@ -810,34 +810,37 @@ class Engine:
 
     # -- guided matching: the match once more under the estimated homographies (fpc_match_*_guided), and its cell-ordered
     # -- form (fpc_cell_order / fpc_match_*_guided_cells): the same tables, fewer tiles ------------------------------------
-    def _guided_h(self, n, hm):
-        """H -> a contiguous device tensor float32 [n,9] (homography_*_async's [n,3,3] output as it is, or a host array)."""
+    def _guided_h(self, n, hm, what="H"):
+        """H (or F) -> a contiguous device tensor float32 [n,9] (homography_*_async's / fundamental_*_async's [n,3,3] output
+        as it is, or a host array)."""
         hm = torch.as_tensor(hm).to(self.torch_device, torch.float32).contiguous()
         if hm.numel() != n * 9 or hm.shape[0] != n:
-            raise ValueError("H must be [n,3,3] or [n,9]")
+            raise ValueError("%s must be [n,3,3] or [n,9]" % what)
         return hm
 
-    def _guided(self, name, cells, stats, n, train, H, radius, cross_check, max_dist, ratio):
-        """fpc_<name>[_cells](ctx, n, *train, H, radius, ...): what every guided call does behind its train set's checks."""
-        hm = self._guided_h(n, H)
+    def _guided(self, name, variant, stats, n, train, H, radius, cross_check, max_dist, ratio):
+        """fpc_<name><variant>(ctx, n, *train, H, radius, ...): what every guided call does behind its train set's checks.
+        variant: "" (the plain call), "_cells" (takes stats_dev as well) or "_epipolar" (H is then F)."""
+        cells = variant == "_cells"
+        hm = self._guided_h(n, H, "F" if variant == "_epipolar" else "H")
         m, d = self._table(n)
         st = self._int32(n, 2) if stats else None
-        self._call(name + "_cells" if cells else name, n, *train, hm, float(radius), int(bool(cross_check)), float(max_dist),
+        self._call(name + variant, n, *train, hm, float(radius), int(bool(cross_check)), float(max_dist),
                    float(ratio), m, d, *((st,) if cells else ()), inputs=(*train, hm))
         return (m, d, st) if stats else (m, d)
 
-    def _guided_frames(self, cells, stats, n, H, radius, key, key_xy, pairing, *options):
+    def _guided_frames(self, variant, stats, n, H, radius, key, key_xy, pairing, *options):
         pair = self._pairing(pairing)
         kd, kc = self._key(key)
         kx, _ = self._key_xy(key_xy)
         if kd is not None and (kx is None or kx.shape[0] < kd.shape[0]):
             raise ValueError("a key needs key_xy with a row for each of its rows")
-        return self._guided("fpc_match_frames_guided", cells, stats, n, (pair, kd, kc, kx), H, radius, *options)
+        return self._guided("fpc_match_frames_guided", variant, stats, n, (pair, kd, kc, kx), H, radius, *options)
 
-    def _guided_bank(self, cells, stats, n, slot, H, radius, *options):
+    def _guided_bank(self, variant, stats, n, slot, H, radius, *options):
         self._bank_info()
         slot = self._dev_int32("slot", slot, "[n]", n)
-        return self._guided("fpc_match_bank_guided", cells, stats, n, (slot,), H, radius, *options)
+        return self._guided("fpc_match_bank_guided", variant, stats, n, (slot,), H, radius, *options)
 
     def match_frames_guided_async(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True, max_dist=0.0,
                                   ratio=0.0):
@@ -845,7 +848,7 @@ class Engine:
         [n,3,3], query pixel -> train pixel: homography_frames_async's output, device or host) sends the query row;
         `key` / `key_xy` as in match_frames_async / homography_frames_async (the key's count is `key`'s) -> (match int32
         [n,cap], dist float32 [n,cap]) on the device; a frame with H = 0 is all -1.  Does not synchronise."""
-        return self._guided_frames(False, False, n, H, radius, key, key_xy, pairing, cross_check, max_dist, ratio)
+        return self._guided_frames("", False, n, H, radius, key, key_xy, pairing, cross_check, max_dist, ratio)
 
     def match_frames_guided(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True, max_dist=0.0,
                             ratio=0.0):
@@ -857,7 +860,7 @@ class Engine:
         """fpc_match_bank_guided: match_frames_guided_async with frame f's train set taken from bank slot slot[f] (int32
         [n], device; normally match_bank_async's `best`; -1: an all -1 row) and H homography_bank_async's output.  Does
         not synchronise."""
-        return self._guided_bank(False, False, n, slot, H, radius, cross_check, max_dist, ratio)
+        return self._guided_bank("", False, n, slot, H, radius, cross_check, max_dist, ratio)
 
     def match_bank_guided(self, n, slot, H, radius, cross_check=True, max_dist=0.0, ratio=0.0):
         """match_bank_guided_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
@@ -880,7 +883,7 @@ class Engine:
         """fpc_match_frames_guided_cells: match_frames_guided_async's arguments and, bit for bit, its (match, dist), from
         the cell-ordered kernel that visits only the tiles the gate can reach.  stats=True: (match, dist, stats int32
         [n,2]: per frame (strip, tile) pairs visited, and the pairs there are).  Does not synchronise."""
-        return self._guided_frames(True, stats, n, H, radius, key, key_xy, pairing, cross_check, max_dist, ratio)
+        return self._guided_frames("_cells", stats, n, H, radius, key, key_xy, pairing, cross_check, max_dist, ratio)
 
     def match_frames_guided_cells(self, n, H, radius, key=None, key_xy=None, pairing="key", cross_check=True,
                                   max_dist=0.0, ratio=0.0):
@@ -891,11 +894,37 @@ class Engine:
     def match_bank_guided_cells_async(self, n, slot, H, radius, cross_check=True, max_dist=0.0, ratio=0.0, stats=False):
         """fpc_match_bank_guided_cells: match_bank_guided_async's arguments and, bit for bit, its (match, dist) on an
         "f32" bank (a "bf16" bank is refused); stats as in match_frames_guided_cells_async.  Does not synchronise."""
-        return self._guided_bank(True, stats, n, slot, H, radius, cross_check, max_dist, ratio)
+        return self._guided_bank("_cells", stats, n, slot, H, radius, cross_check, max_dist, ratio)
 
     def match_bank_guided_cells(self, n, slot, H, radius, cross_check=True, max_dist=0.0, ratio=0.0):
         """match_bank_guided_cells_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
         return self._per_frame(n, *self.match_bank_guided_cells_async(n, slot, H, radius, cross_check, max_dist, ratio))
+
+    # -- epipolar guided matching: the match once more under the estimated fundamental matrices (fpc_match_*_guided_epipolar)
+    def match_frames_guided_epipolar_async(self, n, F, radius, key=None, key_xy=None, pairing="key", cross_check=True,
+                                           max_dist=0.0, ratio=0.0):
+        """fpc_match_frames_guided_epipolar: match_frames_guided_async's arguments with F (float32 [n,3,3] or [n,9], (u, v, 1)
+        F (x, y, 1)^T = 0 for a query pixel (x, y) and its train pixel (u, v): fundamental_frames_async's output, device or
+        host) in the place of H; the candidates of a row are the train rows within `radius` pixels (Sampson) of its epipolar
+        line -> (match int32 [n,cap], dist float32 [n,cap]) on the device; a frame with F = 0 is all -1.  Does not
+        synchronise."""
+        return self._guided_frames("_epipolar", False, n, F, radius, key, key_xy, pairing, cross_check, max_dist, ratio)
+
+    def match_frames_guided_epipolar(self, n, F, radius, key=None, key_xy=None, pairing="key", cross_check=True, max_dist=0.0,
+                                     ratio=0.0):
+        """match_frames_guided_epipolar_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        return self._per_frame(n, *self.match_frames_guided_epipolar_async(n, F, radius, key, key_xy, pairing, cross_check,
+                                                                           max_dist, ratio))
+
+    def match_bank_guided_epipolar_async(self, n, slot, F, radius, cross_check=True, max_dist=0.0, ratio=0.0):
+        """fpc_match_bank_guided_epipolar: match_frames_guided_epipolar_async with frame f's train set taken from bank slot
+        slot[f] (as match_bank_guided_async) and F fundamental_bank_async's output; an "f32" bank only (a "bf16" bank is
+        refused).  Does not synchronise."""
+        return self._guided_bank("_epipolar", False, n, slot, F, radius, cross_check, max_dist, ratio)
+
+    def match_bank_guided_epipolar(self, n, slot, F, radius, cross_check=True, max_dist=0.0, ratio=0.0):
+        """match_bank_guided_epipolar_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        return self._per_frame(n, *self.match_bank_guided_epipolar_async(n, slot, F, radius, cross_check, max_dist, ratio))
 
     # -- timing ----------------------------------------------------------------------
     def check_guards(self):

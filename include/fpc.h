@@ -693,6 +693,48 @@ int fpc_match_bank_guided_cells(fpc_ctx* ctx, int n, const int32_t* slot_dev, co
                                 int cross_check, float max_dist, float ratio, int32_t* match_dev, float* dist_dev,
                                 int32_t* stats_dev);
 
+/* --- epipolar guided matching: the match once more, under the estimated fundamental matrices as the gate ------------------
+ * The guided calls above close the loop for scenes a homography explains.  For the other model -- a room or a street seen
+ * from a moved camera, fpc_fundamental_frames / fpc_fundamental_bank -- the gate is a band around the epipolar line: with
+ * one F per frame, what those calls wrote, passed on unchanged, the second pass looks only along the line F gives the row.
+ *
+ * fpc_match_frames_guided_epipolar / fpc_match_bank_guided_epipolar: the arguments of fpc_match_frames_guided /
+ * fpc_match_bank_guided, argument for argument, with F_dev float32 [n][9] where H_dev stands.  Query sets, train sets, train
+ * coordinates, counts, cap, the output shapes, the pairing, the key rules and the slot rules are those calls', unchanged.
+ *  - F is row-major with (u, v, 1) F (x, y, 1)^T = 0, (x, y) the query pixel and (u, v) the train pixel: the direction and
+ *    layout the three fundamental calls write.
+ *  - Gate: query row i at the integer pixel p = (x, y, 1), train row j at q = (u, v, 1); in fp64 from the fp32 F
+ *        l  = F p
+ *        l' = F^T q
+ *        e  = q . l = l0 u + l1 v + l2
+ *    and row j is a CANDIDATE of row i iff e^2 < radius^2 (l0^2 + l1^2 + l'0^2 + l'1^2): the Sampson distance below the
+ *    radius.  This is the inlier test of fpc_ransac_fundamental with radius in the place of reproj_threshold: a pair that a
+ *    fundamental call marks as an inlier at threshold t is a candidate at radius t.  No division and no sign condition (a
+ *    line has no "behind the camera"): F and -F give the same output.  A failed frame's nine zeros give 0 < 0: no
+ *    candidates, every row -1 / +inf.  The same holds for an F with any non-finite entry.
+ *  - Result: fpc_match_frames' rule over the candidates only: the nearest candidate in (d^2, index) order, dist = its
+ *    distance, max_dist and ratio as there with the second-nearest CANDIDATE as d2 (fewer than two candidates: the ratio
+ *    test fails).  Cross check: row i survives iff i is the (d^2, index)-nearest among the query rows that have j as a
+ *    candidate.  A row without a candidate: -1 / +inf; rows count[f] <= i < cap: -1 / +inf.
+ *  - Bits: for a candidate pair d^2 is the value fpc_match_frames computes for that pair (the same norms, K order,
+ *    expression and clamp), so where the guided winner equals the unguided winner dist is bit-equal, and under a radius at
+ *    which EVERY pair of a frame is a candidate the frame's output is fpc_match_frames' / the fpc_match_bank table's, bit
+ *    for bit.  Unlike the homography gate, no fixed radius guarantees that for every F: the epipolar line of a pixel need
+ *    not cross the frame, so the radius that admits every pair depends on F.
+ *  - Execution: asynchronous on the ctx stream, no host synchronisation, no device-to-host copy, no allocation (the
+ *    workspace is fpc_match_frames', carved at fpc_create; nothing new is carved, the plan hash and the guard zones are what
+ *    they were); every count and slot is read on the device; deterministic (bit-identical outputs on repeated calls).
+ *    fpc_detect, fpc_match_frames, fpc_fundamental_frames, fpc_match_frames_guided_epipolar, fpc_fundamental_frames needs no
+ *    host call in between; the same holds through the bank with fpc_match_bank, fpc_fundamental_bank,
+ *    fpc_match_bank_guided_epipolar, fpc_fundamental_bank.
+ * FPC_E_INVALID (nothing is written): everything fpc_match_frames_guided / fpc_match_bank_guided refuse, with F_dev for
+ * H_dev; the bank variant on a FPC_BANK_BF16 bank (that format's epipolar gate is the follow-up). */
+int fpc_match_frames_guided_epipolar(fpc_ctx* ctx, int n, int pairing, const float* key_dev, const int32_t* nkey_dev,
+                                     const int32_t* key_xy_dev, const float* F_dev, float radius, int cross_check,
+                                     float max_dist, float ratio, int32_t* match_dev, float* dist_dev);
+int fpc_match_bank_guided_epipolar(fpc_ctx* ctx, int n, const int32_t* slot_dev, const float* F_dev, float radius,
+                                   int cross_check, float max_dist, float ratio, int32_t* match_dev, float* dist_dev);
+
 /* --- verified relocalisation: the K best slots of the bank per frame, each checked by RANSAC -----------------------------
  * fpc_match_bank ranks the slots by appearance and returns ONE per frame; everything behind it verifies that slot.  Where a
  * look-alike slot outscores the right one (the WARNING above; repetitive texture, revisited places) the homography fails and
