@@ -37,6 +37,7 @@ SYMBOLS = [
     "fpc_bank_topk_reserve", "fpc_match_bank_topk", "fpc_homography_bank_topk",
     "fpc_ransac_fundamental", "fpc_fundamental_frames", "fpc_fundamental_bank",
     "fpc_match_frames_guided_epipolar", "fpc_match_bank_guided_epipolar",
+    "fpc_match_frames_guided_epipolar_cells", "fpc_match_bank_guided_epipolar_cells",
 ]
 
 ABI_VERSION = 4
@@ -193,6 +194,8 @@ def load():
                                               vp]
     l.fpc_match_frames_guided_epipolar.argtypes = list(l.fpc_match_frames_guided.argtypes)      # F_dev where H_dev stands
     l.fpc_match_bank_guided_epipolar.argtypes = list(l.fpc_match_bank_guided.argtypes)
+    l.fpc_match_frames_guided_epipolar_cells.argtypes = list(l.fpc_match_frames_guided_cells.argtypes)   # likewise
+    l.fpc_match_bank_guided_epipolar_cells.argtypes = list(l.fpc_match_bank_guided_cells.argtypes)
     l.fpc_bank_topk_reserve.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_size_t)]
     l.fpc_match_bank_topk.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp, vp]
     l.fpc_homography_bank_topk.argtypes = [vp, ci, ci, vp, vp, rp, vp, vp, vp, vp, vp]

@@ -40,6 +40,7 @@
 #include "match_guided.h"
 #include "match_guided_cells.h"
 #include "match_guided_epipolar.h"
+#include "match_guided_epipolar_cells.h"
 #include "ransac_homography.h"
 #include "ransac_fundamental.h"
 #include "match_bank_topk.h"
@@ -4349,7 +4350,7 @@ int fpc_homography_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot,
 }
 
 // ---- guided matching: plain, cell-ordered and epipolar (include/fpc.h; kernels in match_guided.h, match_guided_cells.h,
-// ---- match_guided_epipolar.h) ------------------------------------------------------------------------------------------------
+// ---- match_guided_epipolar.h, match_guided_epipolar_cells.h) -----------------------------------------------------------------
 // 32-px cells wherever the order is public; a frame of more cells than the order kernel's histogram holds (beyond
 // 16.7 MPx) is ordered in coarser cells by the guided calls, whose output does not depend on the order.
 static CellOrderArgs cell_order_args(fpc_ctx* c, int shift) {
@@ -4371,8 +4372,9 @@ int fpc_cell_order(fpc_ctx* c, const int32_t* xy, const int32_t* n, int sets, in
   return FPC_OK;
 }
 
-// The order passes in front of match_guided_cells_kernel: the frames' rows, then the train sets -- the key once, the bank's
-// slot of every frame (a.key_slot), none under FPC_PAIR_PREVIOUS without a key (frame f - 1's query order).
+// The order passes in front of match_guided_cells_kernel / match_guided_epipolar_cells_kernel: the frames' rows, then the
+// train sets -- the key once, the bank's slot of every frame (a.key_slot), none under FPC_PAIR_PREVIOUS without a key
+// (frame f - 1's query order).
 static MatchCellsArgs cell_order_passes(fpc_ctx* c, const MatchFramesArgs& a, const MatchGuidedArgs& g, int32_t* stats) {
   const int nbox = (c->cap + 63) / 64;
   int shift = 5;
@@ -4395,12 +4397,12 @@ static MatchCellsArgs cell_order_passes(fpc_ctx* c, const MatchFramesArgs& a, co
   return MatchCellsArgs{c->mgc_perm_q, c->mgc_box, c->mgc_perm_t, box_t, nbox, stats};
 }
 
-// The six guided entry points run on fpc_match_frames' workspace (norms, top-2, column minima: [max_batch][cap], and the
+// The eight guided entry points run on fpc_match_frames' workspace (norms, top-2, column minima: [max_batch][cap], and the
 // bank's rows <= cap), carved at fpc_create: nothing of their own.  One sequence for all: the column minima and the stats
-// reset, the norms (a bf16 bank: its rounding pass, match_bank_bf16.h), the variant's strip kernel (the cell-ordered one
-// behind its order passes), the finalize kernel.  norm_blocks: n + 1 with the key's block, n against the bank, whose
+// reset, the norms (a bf16 bank: its rounding pass, match_bank_bf16.h), the variant's strip kernel (the cell-ordered ones
+// behind their order passes), the finalize kernel.  norm_blocks: n + 1 with the key's block, n against the bank, whose
 // norms are its own.
-enum GuidedStrip { GUIDED_PLAIN, GUIDED_CELLS, GUIDED_BANK_BF16, GUIDED_EPIPOLAR };
+enum GuidedStrip { GUIDED_PLAIN, GUIDED_CELLS, GUIDED_BANK_BF16, GUIDED_EPIPOLAR, GUIDED_EPIPOLAR_CELLS };
 
 static int match_guided_launch(fpc_ctx* c, GuidedStrip strip, MatchFramesArgs a, const MatchGuidedArgs& g, int norm_blocks,
                                float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
@@ -4418,6 +4420,9 @@ static int match_guided_launch(fpc_ctx* c, GuidedStrip strip, MatchFramesArgs a,
   } else if (strip == GUIDED_BANK_BF16) {
     hipLaunchKernelGGL(by_depth(c, match_bank_bf16_kernel<8, true>, match_bank_bf16_kernel<16, true>), strips, dim3(256), 0,
                        c->stream, a, c->bank, c->bank16, g);
+  } else if (strip == GUIDED_EPIPOLAR_CELLS) {
+    const MatchCellsArgs m = cell_order_passes(c, a, g, stats);
+    hipLaunchKernelGGL(match_guided_epipolar_cells_kernel, strips, dim3(256), 0, c->stream, a, g, m);     // (g.H holds F)
   } else if (strip == GUIDED_EPIPOLAR) {
     hipLaunchKernelGGL(match_guided_epipolar_kernel, strips, dim3(256), 0, c->stream, a, g);     // (g.H holds F)
   } else {
@@ -4433,7 +4438,7 @@ static bool guided_options_ok(const float* H, float radius, float max_dist, floa
   return H && match && std::isfinite(radius) && radius > 0.f && gate_ok(max_dist, ratio);
 }
 
-// fpc_match_frames_guided[_cells | _epipolar]: the key set (or frame f - 1) as the train set
+// fpc_match_frames_guided[_cells | _epipolar | _epipolar_cells]: the key set (or frame f - 1) as the train set
 static int match_frames_guided(fpc_ctx* c, GuidedStrip strip, int n, int pairing, const float* key, const int32_t* nkey,
                                const int32_t* key_xy, const float* H, float radius, int cross_check, float max_dist,
                                float ratio, int32_t* match, float* dist, int32_t* stats) {
@@ -4449,8 +4454,8 @@ static int match_frames_guided(fpc_ctx* c, GuidedStrip strip, int n, int pairing
   return match_guided_launch(c, strip, a, g, n + 1, max_dist, ratio, match, dist, stats);
 }
 
-// fpc_match_bank_guided[_cells | _epipolar]: bank slot slot[f] as frame f's train set (strip: GUIDED_PLAIN stands for the
-// bank's own format, fp32 or bf16)
+// fpc_match_bank_guided[_cells | _epipolar | _epipolar_cells]: bank slot slot[f] as frame f's train set (strip: GUIDED_PLAIN
+// stands for the bank's own format, fp32 or bf16)
 static int match_bank_guided(fpc_ctx* c, GuidedStrip strip, int n, const int32_t* slot, const float* H, float radius, int cross_check,
                              float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
   if (!c || !c->bank_slab || !slot || !guided_options_ok(H, radius, max_dist, ratio, match)) return FPC_E_INVALID;
@@ -4499,6 +4504,18 @@ int fpc_match_frames_guided_epipolar(fpc_ctx* c, int n, int pairing, const float
 int fpc_match_bank_guided_epipolar(fpc_ctx* c, int n, const int32_t* slot, const float* F, float radius, int cross_check,
                                    float max_dist, float ratio, int32_t* match, float* dist) {
   return match_bank_guided(c, GUIDED_EPIPOLAR, n, slot, F, radius, cross_check, max_dist, ratio, match, dist, nullptr);
+}
+
+int fpc_match_frames_guided_epipolar_cells(fpc_ctx* c, int n, int pairing, const float* key, const int32_t* nkey,
+                                           const int32_t* key_xy, const float* F, float radius, int cross_check,
+                                           float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
+  return match_frames_guided(c, GUIDED_EPIPOLAR_CELLS, n, pairing, key, nkey, key_xy, F, radius, cross_check, max_dist, ratio,
+                             match, dist, stats);
+}
+
+int fpc_match_bank_guided_epipolar_cells(fpc_ctx* c, int n, const int32_t* slot, const float* F, float radius, int cross_check,
+                                         float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
+  return match_bank_guided(c, GUIDED_EPIPOLAR_CELLS, n, slot, F, radius, cross_check, max_dist, ratio, match, dist, stats);
 }
 
 int fpc_results(fpc_ctx* c, fpc_device_results* out) {

@@ -820,9 +820,10 @@ class Engine:
 
     def _guided(self, name, variant, stats, n, train, H, radius, cross_check, max_dist, ratio):
         """fpc_<name><variant>(ctx, n, *train, H, radius, ...): what every guided call does behind its train set's checks.
-        variant: "" (the plain call), "_cells" (takes stats_dev as well) or "_epipolar" (H is then F)."""
-        cells = variant == "_cells"
-        hm = self._guided_h(n, H, "F" if variant == "_epipolar" else "H")
+        variant: "" (the plain call), "_cells" (takes stats_dev as well), "_epipolar" (H is then F) or "_epipolar_cells"
+        (both)."""
+        cells = variant.endswith("_cells")
+        hm = self._guided_h(n, H, "F" if variant.startswith("_epipolar") else "H")
         m, d = self._table(n)
         st = self._int32(n, 2) if stats else None
         self._call(name + variant, n, *train, hm, float(radius), int(bool(cross_check)), float(max_dist),
@@ -925,6 +926,34 @@ class Engine:
     def match_bank_guided_epipolar(self, n, slot, F, radius, cross_check=True, max_dist=0.0, ratio=0.0):
         """match_bank_guided_epipolar_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
         return self._per_frame(n, *self.match_bank_guided_epipolar_async(n, slot, F, radius, cross_check, max_dist, ratio))
+
+    # -- cell-ordered epipolar guided matching: the same tables, only the tiles the bands can reach
+    # -- (fpc_match_*_guided_epipolar_cells)
+    def match_frames_guided_epipolar_cells_async(self, n, F, radius, key=None, key_xy=None, pairing="key", cross_check=True,
+                                                 max_dist=0.0, ratio=0.0, stats=False):
+        """fpc_match_frames_guided_epipolar_cells: match_frames_guided_epipolar_async's arguments and, bit for bit, its
+        (match, dist), from the cell-ordered kernel that visits only the tiles whose pixel box a row's epipolar band can
+        reach.  stats=True: (match, dist, stats int32 [n,2]: per frame (strip, tile) pairs visited, and the pairs there
+        are).  Does not synchronise."""
+        return self._guided_frames("_epipolar_cells", stats, n, F, radius, key, key_xy, pairing, cross_check, max_dist, ratio)
+
+    def match_frames_guided_epipolar_cells(self, n, F, radius, key=None, key_xy=None, pairing="key", cross_check=True,
+                                           max_dist=0.0, ratio=0.0):
+        """match_frames_guided_epipolar_cells_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        return self._per_frame(n, *self.match_frames_guided_epipolar_cells_async(n, F, radius, key, key_xy, pairing,
+                                                                                 cross_check, max_dist, ratio))
+
+    def match_bank_guided_epipolar_cells_async(self, n, slot, F, radius, cross_check=True, max_dist=0.0, ratio=0.0,
+                                               stats=False):
+        """fpc_match_bank_guided_epipolar_cells: match_bank_guided_epipolar_async's arguments and, bit for bit, its (match,
+        dist) on an "f32" bank (a "bf16" bank is refused); stats as in match_frames_guided_epipolar_cells_async.  Does not
+        synchronise."""
+        return self._guided_bank("_epipolar_cells", stats, n, slot, F, radius, cross_check, max_dist, ratio)
+
+    def match_bank_guided_epipolar_cells(self, n, slot, F, radius, cross_check=True, max_dist=0.0, ratio=0.0):
+        """match_bank_guided_epipolar_cells_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        return self._per_frame(n, *self.match_bank_guided_epipolar_cells_async(n, slot, F, radius, cross_check, max_dist,
+                                                                               ratio))
 
     # -- timing ----------------------------------------------------------------------
     def check_guards(self):

@@ -735,6 +735,51 @@ int fpc_match_frames_guided_epipolar(fpc_ctx* ctx, int n, int pairing, const flo
 int fpc_match_bank_guided_epipolar(fpc_ctx* ctx, int n, const int32_t* slot_dev, const float* F_dev, float radius,
                                    int cross_check, float max_dist, float ratio, int32_t* match_dev, float* dist_dev);
 
+/* --- cell-ordered epipolar guided matching: the epipolar match, visiting only the tiles the bands can reach ---------------
+ * fpc_match_frames_guided_epipolar / fpc_match_bank_guided_epipolar test the gate against every 64 x 64 tile of (query rows,
+ * train rows); rows come in confidence order, so every tile has a pair inside some row's band and none is skipped.  The calls
+ * below read both sides in fpc_cell_order's spatial order and skip the tiles whose bounding box no band of the strip can
+ * reach: what the cell-ordered calls above do for the homography gate, for the epipolar one.
+ *
+ * fpc_match_frames_guided_epipolar_cells / fpc_match_bank_guided_epipolar_cells: the arguments of
+ * fpc_match_frames_guided_cells / fpc_match_bank_guided_cells, argument for argument, with F_dev where H_dev stands.
+ *  - Output: for every argument set fpc_match_frames_guided_epipolar / fpc_match_bank_guided_epipolar accept, match_dev and
+ *    dist_dev are BIT-IDENTICAL to what they write: indices are original row indices; rows past the count, frames without a
+ *    train set, slots outside the bank and empty slots, nine zeros, a non-finite F, and F versus -F included.  (The result
+ *    is a function of the candidate set and of each candidate pair's d^2 bits, whatever order rows are visited in.)
+ *  - stats_dev int32 [n][2], or NULL, with the meaning of the cell-ordered calls above: per frame {(strip, tile) pairs
+ *    visited, strips x tiles where both sets are non-empty}, a strip being 64 ordered query rows and a tile 64 ordered train
+ *    rows.  Deterministic.
+ *  - Order: the order and the boxes are fpc_cell_order's -- the same kernel, the same coarser cells in a frame of more than
+ *    16384 cells, the same workspace.  Per call: the order of the query sets (frames 0 .. n-1) and of the train sets (the
+ *    key once; under FPC_PAIR_PREVIOUS frame f-1's query order serves as the train order; the slot of every frame).
+ *  - Cull: with l = F p and g = l0^2 + l1^2 of the gate above for a query row (g = -inf for a row that passes nowhere: a row
+ *    past the count, a non-finite F), and a train tile whose 64 ordered rows have the pixel box [u0, u1] x [v0, v1]:
+ *        e_lo, e_hi = the minimum and the maximum of l0 u + l1 v + l2 over the four corners of the box
+ *                     (e is linear: this is its exact range over the box),
+ *        m  = 0 if e_lo <= 0 <= e_hi, else min(|e_lo|, |e_hi|),
+ *        G  = max over the four corners of l'0^2 + max over the four corners of l'1^2,  l' = F^T (u, v, 1)
+ *             (once per tile, the same for every row),
+ *    the row can reach the tile iff m^2 < radius^2 (g + G), and a strip visits a tile iff one of its rows can reach it.
+ *    Every candidate pair has |e| >= m and l'0^2 + l'1^2 <= G, so no tile that holds a candidate is dropped; the device
+ *    evaluates the rule in fp64 with e_lo, e_hi and the range of l' widened by a few units in the last place, which makes
+ *    this hold for the gate as the device computes it, whichever way its sums are fused.
+ *  - Execution: as for the twins -- asynchronous on the ctx stream, no host synchronisation, no copy, no allocation, every
+ *    count and slot read on the device.  Nothing new is carved: orders and boxes live in the workspace of the cell-ordered
+ *    calls above, the plan hash and the guard zones are what they were, nothing is added to the bank's allocation.
+ *    fpc_match_frames, fpc_fundamental_frames, fpc_match_frames_guided_epipolar_cells, fpc_fundamental_frames needs no host
+ *    call in between; the same holds through the bank with fpc_match_bank, fpc_fundamental_bank,
+ *    fpc_match_bank_guided_epipolar_cells, fpc_fundamental_bank.
+ * FPC_E_INVALID (nothing is written, stats_dev included): everything fpc_match_frames_guided_epipolar /
+ * fpc_match_bank_guided_epipolar refuse; the bank variant on a FPC_BANK_BF16 bank (that format's strip is the follow-up). */
+int fpc_match_frames_guided_epipolar_cells(fpc_ctx* ctx, int n, int pairing, const float* key_dev, const int32_t* nkey_dev,
+                                           const int32_t* key_xy_dev, const float* F_dev, float radius, int cross_check,
+                                           float max_dist, float ratio, int32_t* match_dev, float* dist_dev,
+                                           int32_t* stats_dev);
+int fpc_match_bank_guided_epipolar_cells(fpc_ctx* ctx, int n, const int32_t* slot_dev, const float* F_dev, float radius,
+                                         int cross_check, float max_dist, float ratio, int32_t* match_dev, float* dist_dev,
+                                         int32_t* stats_dev);
+
 /* --- verified relocalisation: the K best slots of the bank per frame, each checked by RANSAC -----------------------------
  * fpc_match_bank ranks the slots by appearance and returns ONE per frame; everything behind it verifies that slot.  Where a
  * look-alike slot outscores the right one (the WARNING above; repetitive texture, revisited places) the homography fails and
