@@ -38,6 +38,7 @@ SYMBOLS = [
     "fpc_ransac_fundamental", "fpc_fundamental_frames", "fpc_fundamental_bank",
     "fpc_match_frames_guided_epipolar", "fpc_match_bank_guided_epipolar",
     "fpc_match_frames_guided_epipolar_cells", "fpc_match_bank_guided_epipolar_cells",
+    "fpc_default_pose_params", "fpc_pose_fundamental", "fpc_pose_frames", "fpc_pose_bank",
 ]
 
 ABI_VERSION = 4
@@ -85,6 +86,13 @@ class FpcRansacParams(ctypes.Structure):
     """fpc_ransac_params (include/fpc.h)."""
     _fields_ = [("iterations", ctypes.c_int), ("reproj_threshold", ctypes.c_float), ("seed", ctypes.c_uint32),
                 ("refits", ctypes.c_int), ("min_inliers", ctypes.c_int)]
+
+
+class FpcPoseParams(ctypes.Structure):
+    """fpc_pose_params (include/fpc.h)."""
+    _fields_ = [("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
+                ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
+                ("reproj_threshold", ctypes.c_float), ("min_front", ctypes.c_int)]
 
 
 BANK_MAX_SLOTS = 1024         # include/fpc.h FPC_BANK_MAX_SLOTS
@@ -184,6 +192,12 @@ def load():
     l.fpc_ransac_fundamental.argtypes = [vp, ci, vp, vp, vp, ci, rp, vp, vp, vp]
     l.fpc_fundamental_frames.argtypes = [vp, ci, ci, vp, vp, vp, rp, vp, vp, vp]
     l.fpc_fundamental_bank.argtypes = [vp, ci, vp, vp, rp, vp, vp, vp]
+    pp = ctypes.POINTER(FpcPoseParams)
+    l.fpc_default_pose_params.argtypes = [pp]
+    # the fundamental twins' arguments with (F_dev, params) where their params stand and five outputs for their three
+    l.fpc_pose_fundamental.argtypes = [vp, ci, vp, vp, vp, ci, vp, pp, vp, vp, vp, vp, vp]
+    l.fpc_pose_frames.argtypes = [vp, ci, ci, vp, vp, vp, vp, pp, vp, vp, vp, vp, vp]
+    l.fpc_pose_bank.argtypes = [vp, ci, vp, vp, vp, pp, vp, vp, vp, vp, vp]
     l.fpc_match_frames_guided.argtypes = [vp, ci, ci, vp, vp, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float,
                                           vp, vp]
     l.fpc_match_bank_guided.argtypes = [vp, ci, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float, vp, vp]

@@ -43,6 +43,7 @@
 #include "match_guided_epipolar_cells.h"
 #include "ransac_homography.h"
 #include "ransac_fundamental.h"
+#include "pose_epipolar.h"
 #include "match_bank_topk.h"
 #include "homography.h"
 #include "weights.h"
@@ -4260,6 +4261,86 @@ int fpc_fundamental_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* 
   hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
                      (const int32_t*)nullptr, match, inlier, hb);
   fundamental_launch(c, a, F, ninliers, inlier, c->cap);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+// ---- relative pose from a fundamental matrix (include/fpc.h; kernel in pose_epipolar.h) ------------------------------------
+// The fundamental calls' pack / gather kernels with a NULL mask (nothing of the caller's is zeroed), their pair records and
+// workspace: a pose call leaves the pair list its fundamental twin built, built again.
+int fpc_default_pose_params(fpc_pose_params* p) {
+  if (!p) return FPC_E_INVALID;
+  p->q_fx = p->q_fy = p->t_fx = p->t_fy = 500.0f;
+  p->q_cx = p->t_cx = 320.0f;
+  p->q_cy = p->t_cy = 240.0f;
+  p->reproj_threshold = 3.0f;
+  p->min_front = 8;
+  return FPC_OK;
+}
+
+static bool pose_params_ok(const fpc_pose_params* p) {
+  if (!p) return false;
+  const float k[8] = {p->q_fx, p->q_fy, p->q_cx, p->q_cy, p->t_fx, p->t_fy, p->t_cx, p->t_cy};
+  for (float v : k)
+    if (!std::isfinite(v)) return false;
+  return p->q_fx > 0.f && p->q_fy > 0.f && p->t_fx > 0.f && p->t_fy > 0.f && p->reproj_threshold > 0.f &&
+         p->reproj_threshold < 1e18f && p->min_front >= 1;
+}
+
+static HfArgs pose_args(fpc_ctx* c, int n, const fpc_pose_params* p) {
+  HfArgs a{};
+  a.pairs = c->hf_pairs; a.row = c->hf_row; a.np = c->hf_np; a.best = c->hf_best;
+  a.cap = c->cap; a.n = n;
+  a.thr = p->reproj_threshold;
+  return a;
+}
+
+// the kernel the three entry points share, behind their pack / gather kernel
+static void pose_launch(fpc_ctx* c, const HfArgs& a, const fpc_pose_params* p, const float* F, float* R, float* t,
+                        int32_t* nfront, float* xyz, uint8_t* front, int ostride) {
+  const PoseArgs pa{p->q_fx, p->q_fy, p->q_cx, p->q_cy, p->t_fx, p->t_fy, p->t_cx, p->t_cy, p->min_front};
+  hipLaunchKernelGGL(pose_kernel, dim3(a.n), dim3(256), 0, c->stream, a, pa, F, R, t, nfront, xyz, front, ostride);
+}
+
+int fpc_pose_fundamental(fpc_ctx* c, int n, const float* src_xy, const float* dst_xy, const int32_t* npairs, int stride,
+                         const float* F, const fpc_pose_params* p, float* R, float* t, int32_t* nfront, float* xyz,
+                         uint8_t* front) {
+  if (!c || !src_xy || !dst_xy || !npairs || !F || !R || !t || !nfront || !pose_params_ok(p)) return FPC_E_INVALID;
+  if (n < 1 || n > c->B || stride < 1 || stride > c->cap) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const HfArgs a = pose_args(c, n, p);
+  hipLaunchKernelGGL(hf_pack_kernel, dim3((stride + 255) / 256, n), dim3(256), 0, c->stream, a, src_xy, dst_xy, npairs,
+                     stride, (uint8_t*)nullptr);
+  pose_launch(c, a, p, F, R, t, nfront, xyz, front, stride);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_pose_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy, const int32_t* nkey, const int32_t* match,
+                    const float* F, const fpc_pose_params* p, float* R, float* t, int32_t* nfront, float* xyz,
+                    uint8_t* front) {
+  if (!c || !match || !F || !R || !t || !nfront || !pose_params_ok(p) || !pairing_ok(pairing) || !frames_ok(c, n) ||
+      (pairing == FPC_PAIR_KEY && !key_xy) || (key_xy && !nkey))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const HfArgs a = pose_args(c, n, p);
+  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, pairing, key_xy, nkey, match,
+                     (uint8_t*)nullptr, HfBank{});
+  pose_launch(c, a, p, F, R, t, nfront, xyz, front, c->cap);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_pose_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const float* F, const fpc_pose_params* p,
+                  float* R, float* t, int32_t* nfront, float* xyz, uint8_t* front) {
+  if (!c || !c->bank_slab || !slot || !match || !F || !R || !t || !nfront || !pose_params_ok(p) || !frames_ok(c, n))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const HfArgs a = pose_args(c, n, p);
+  const HfBank hb{slot, c->bank.count, c->bank.rows, c->bank.slots};
+  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
+                     (const int32_t*)nullptr, match, (uint8_t*)nullptr, hb);
+  pose_launch(c, a, p, F, R, t, nfront, xyz, front, c->cap);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }

@@ -749,6 +749,108 @@ class Engine:
         """fundamental_bank_async, then host arrays (F [n,3,3], ninliers [n], inlier bool [n,cap])."""
         return self._host(self.fundamental_bank_async(n, slot, match, **params))
 
+    # -- relative pose from the fundamental matrices: R, t and triangulated points (fpc_pose_fundamental / _frames / _bank) ---
+    @staticmethod
+    def _intrinsics(k, name):
+        """A 3 x 3 camera matrix or (fx, fy, cx, cy) -> (fx, fy, cx, cy); None: the defaults of fpc_default_pose_params."""
+        if k is None:
+            return None
+        k = np.asarray(k, dtype=np.float64)
+        if k.shape == (3, 3):
+            if k[0, 1] != 0 or k[1, 0] != 0 or k[2, 0] != 0 or k[2, 1] != 0 or k[2, 2] != 1:
+                raise ValueError("%s must be [fx 0 cx; 0 fy cy; 0 0 1]" % name)
+            return float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+        if k.shape == (4,):
+            return tuple(float(v) for v in k)
+        raise ValueError("%s must be a 3 x 3 matrix or (fx, fy, cx, cy)" % name)
+
+    def _pose_params(self, K_query, K_train, params):
+        p = _lib.FpcPoseParams()
+        _lib.check(self._l.fpc_default_pose_params(ctypes.byref(p)), "fpc_default_pose_params")
+        for side, k in (("q", self._intrinsics(K_query, "K_query")), ("t", self._intrinsics(K_train, "K_train"))):
+            if k is not None:
+                for field, v in zip(("fx", "fy", "cx", "cy"), k):
+                    setattr(p, "%s_%s" % (side, field), v)
+        for k, v in params.items():
+            if k not in ("reproj_threshold", "min_front"):
+                raise TypeError("unknown pose parameter %r" % (k,))
+            setattr(p, k, v)
+        return p
+
+    def _pose_out(self, n, stride, points):
+        """Empty pose outputs (R float32 [n,3,3], t float32 [n,3], nfront int32 [n], xyz float32 [n,stride,3], front uint8
+        [n,stride]); the last two None without `points`."""
+        dev = self.torch_device
+        rm, tv = torch.empty((n, 3, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev)
+        xyz = torch.empty((n, stride, 3), dtype=torch.float32, device=dev) if points else None
+        front = torch.empty((n, stride), dtype=torch.uint8, device=dev) if points else None
+        return rm, tv, self._int32(n), xyz, front
+
+    @staticmethod
+    def _pose_result(rm, tv, nf, xyz, front):
+        return rm, tv, nf, xyz, None if front is None else front.view(torch.bool)
+
+    def _host_pose(self, out):
+        self.sync()
+        return tuple(None if t is None else t.cpu().numpy() for t in out)
+
+    def pose_fundamental_async(self, src, dst, npairs, F, K_query=None, K_train=None, points=True, **params):
+        """fpc_pose_fundamental: ransac_fundamental_async's pairs and the F it returned (device [n,3,3] as it is, or a host
+        array) -> device tensors (R float32 [n,3,3] and t float32 [n,3] with X_train = R X_query + t, |t| = 1; nfront int32
+        [n]; xyz float32 [n,stride,3], the triangulated points in the query camera's frame; front bool [n,stride], the
+        pairs in front of both cameras); xyz and front are None with points=False.  K_query / K_train: 3 x 3 camera
+        matrices or (fx, fy, cx, cy).  Parameters: reproj_threshold, min_front.  A failed frame is all zeros.  Does not
+        synchronise."""
+        p = self._pose_params(K_query, K_train, params)
+        src = torch.as_tensor(src).to(self.torch_device, torch.float32).contiguous()
+        dst = torch.as_tensor(dst).to(self.torch_device, torch.float32).contiguous()
+        npairs = torch.as_tensor(npairs).to(self.torch_device, torch.int32).contiguous()
+        if src.dim() != 3 or src.shape[2] != 2 or dst.shape != src.shape or npairs.shape != (src.shape[0],):
+            raise ValueError("src and dst must be [n,stride,2] and npairs [n]")
+        n, stride = int(src.shape[0]), int(src.shape[1])
+        fm = self._guided_h(n, F, "F")
+        out = self._pose_out(n, stride, points)
+        self._call("fpc_pose_fundamental", n, src, dst, npairs, stride, fm, ctypes.byref(p), *out,
+                   inputs=(src, dst, npairs, fm))
+        return self._pose_result(*out)
+
+    def pose_fundamental(self, src, dst, npairs, F, K_query=None, K_train=None, points=True, **params):
+        """pose_fundamental_async, then host arrays (R [n,3,3], t [n,3], nfront [n], xyz [n,stride,3], front bool
+        [n,stride])."""
+        return self._host_pose(self.pose_fundamental_async(src, dst, npairs, F, K_query, K_train, points, **params))
+
+    def pose_frames_async(self, n, match, F, key_xy=None, pairing="key", K_query=None, K_train=None, points=True, **params):
+        """fpc_pose_frames: fundamental_frames_async's arguments, pairs and output F -> device tensors (R [n,3,3], t [n,3],
+        nfront [n], xyz [n,cap,3] and front bool [n,cap] by query row).  Does not synchronise."""
+        pair = self._pairing(pairing)
+        p = self._pose_params(K_query, K_train, params)
+        kx, kc = self._key_xy(key_xy)
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        fm = self._guided_h(n, F, "F")
+        out = self._pose_out(n, self.capacity, points)
+        self._call("fpc_pose_frames", n, pair, kx, kc, match, fm, ctypes.byref(p), *out, inputs=(match, kx, kc, fm))
+        return self._pose_result(*out)
+
+    def pose_frames(self, n, match, F, key_xy=None, pairing="key", K_query=None, K_train=None, points=True, **params):
+        """pose_frames_async, then host arrays (R [n,3,3], t [n,3], nfront [n], xyz [n,cap,3], front bool [n,cap])."""
+        return self._host_pose(self.pose_frames_async(n, match, F, key_xy, pairing, K_query, K_train, points, **params))
+
+    def pose_bank_async(self, n, slot, match, F, K_query=None, K_train=None, points=True, **params):
+        """fpc_pose_bank: pose_frames_async with frame f's key coordinates taken from bank slot slot[f], as
+        fundamental_bank_async, and F that call's output; a frame with slot -1 fails (zeros).  Does not synchronise."""
+        self._bank_info()
+        p = self._pose_params(K_query, K_train, params)
+        slot = self._dev_int32("slot", slot, "[n]", n)
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        fm = self._guided_h(n, F, "F")
+        out = self._pose_out(n, self.capacity, points)
+        self._call("fpc_pose_bank", n, slot, match, fm, ctypes.byref(p), *out, inputs=(slot, match, fm))
+        return self._pose_result(*out)
+
+    def pose_bank(self, n, slot, match, F, K_query=None, K_train=None, points=True, **params):
+        """pose_bank_async, then host arrays (R [n,3,3], t [n,3], nfront [n], xyz [n,cap,3], front bool [n,cap])."""
+        return self._host_pose(self.pose_bank_async(n, slot, match, F, K_query, K_train, points, **params))
+
     # -- verified relocalisation: the k best slots per frame, each checked by RANSAC (fpc_*_bank_topk) ------------------
     def bank_topk_reserve(self, kmax):
         """fpc_bank_topk_reserve: workspace for up to `kmax` candidates per frame (1 <= kmax <= min(16, slots)); the only

@@ -830,6 +830,81 @@ int fpc_homography_bank_topk(fpc_ctx* ctx, int n, int k, const int32_t* cand_slo
                              const fpc_ransac_params* params, float* H_dev, int32_t* ninliers_dev, uint8_t* inlier_dev,
                              int32_t* pick_dev, int32_t* best_dev);
 
+/* --- relative pose: R, t and triangulated points from a fundamental matrix and the pairs behind it ------------------------
+ * The fundamental calls end in an F and an inlier mask; a tracker, a relocaliser or a mapper wants where the camera moved
+ * and where the points are.  With the intrinsics of the two cameras, fpc_pose_fundamental, fpc_pose_frames and fpc_pose_bank
+ * turn one F per frame -- what fpc_ransac_fundamental / fpc_fundamental_frames / fpc_fundamental_bank wrote, passed on
+ * unchanged -- into a rotation, a translation direction and one 3-D point per pair, on the device.  They mirror those three
+ * calls argument for argument: the same pair definition, strides, clamping of counts, pairing, key and slot rules, workspace
+ * and execution rules, with F_dev float32 [n][9] as an INPUT and fpc_pose_params in the place of fpc_ransac_params.
+ * Outputs: R_dev float32 [n][9] row-major, t_dev float32 [n][3], nfront_dev int32 [n], xyz_dev float32 [n][S][3] (may be
+ * NULL), front_dev uint8 [n][S] (may be NULL); S is `stride` for fpc_pose_fundamental and the capacity for the other two,
+ * and a row of xyz / front is a pair (fpc_pose_fundamental) or a query row (frames, bank), as for the inlier masks.
+ *  - Convention: X_train = R X_query + t with det R = +1 and |t| = 1: the scale of a translation is unobservable from two
+ *    views.  The points are in the query camera's frame, at that scale.
+ *  - Pairs used: the pairs of the list that pass the Sampson test of the fundamental section above with this struct's
+ *    reproj_threshold, evaluated in fp64 from the fp32 F.  With the threshold F was estimated with, these are exactly the
+ *    pairs of that call's mask.
+ *  - Essential matrix: with K = [fx 0 cx; 0 fy cy; 0 0 1] of either side, E = K_t^T F K_q in fp64, scaled to max |e| = 1.
+ *  - Decomposition: A = E^T E is diagonalised by the cyclic Jacobi of the fundamental section at N = 3 (10 sweeps, the same
+ *    rotation rule).  i1, i2 are the indices of the two largest diagonal entries, in descending order, ties to the lowest
+ *    index, lambda1 >= lambda2 those entries; the frame fails unless lambda2 > 1e-12 lambda1.  v1, v2 are the eigenvectors
+ *    (columns i1, i2), v3 = v1 x v2; u1 = E v1 / |E v1|; u2 = E v2 with its u1 component removed, then normalised;
+ *    u3 = u1 x u2;
+ *        R_a =  u2 v1^T - u1 v2^T + u3 v3^T,      R_b = -u2 v1^T + u1 v2^T + u3 v3^T,
+ *    and the four candidates are c = 0 .. 3 = (R_a, +u3), (R_a, -u3), (R_b, +u3), (R_b, -u3).
+ *  - Triangulation (midpoint), per used pair and candidate (R, t), in fp64: p^ = ((x - q_cx) / q_fx, (y - q_cy) / q_fy, 1)
+ *    for the query pixel, q^ likewise from the train pixel and the train intrinsics; a = R p^, b = q^,
+ *        det = (a.a)(b.b) - (a.b)^2,
+ *        lam = ((a.b)(b.t) - (a.t)(b.b)) / det,      mu = ((a.a)(b.t) - (a.b)(a.t)) / det
+ *    (the parameters at which the rays lam a + t and mu b are closest).  The pair is IN FRONT under the candidate when
+ *    det > 1e-12 (a.a)(b.b) and lam > 0 and mu > 0.
+ *  - Selection: the candidate with the most pairs in front; ties go to the lower c.  The counts are integers, so the result
+ *    does not depend on the execution order.
+ *  - Outputs: nfront is that count; front[row] = 1 for the chosen candidate's pairs in front and 0 elsewhere -- pairs that
+ *    are not used, rows past the count and rows that are no pair included; xyz[row] = (lam p^ + R^T (mu q^ - t)) / 2, the
+ *    midpoint of the two closest points, for those pairs and three zeros elsewhere.  R and t are rounded to fp32.  The
+ *    call writes every row of its frames' front / xyz: nothing needs to be cleared beforehand.
+ *  - Failure: an all-zero F (a failed frame of the fundamental calls) or one with a non-finite entry, no pair used, a failed
+ *    rank test, a non-finite R or t, or nfront < min_front: nine zeros, three zeros, nfront = 0, an all-zero front and an
+ *    all-zero xyz.  A bank slot outside [0, slots) leaves the frame without pairs and fails the same way.
+ *  - Which candidate gets which index c: for a true essential matrix lambda1 = lambda2, and for an estimated one nearly so;
+ *    the eigenvector basis (v1, v2) of that plane is then arbitrary (it is whatever the Jacobi sweeps arrive at).  A
+ *    rotation of the basis within its plane changes nothing; an odd permutation (v1 <-> v2) swaps the labels R_a <-> R_b
+ *    and the sign of u3.  The SET of four candidates, and with it the selected pose, nfront, front and xyz, is invariant;
+ *    the index c of a candidate, and so the outcome of an exact tie between two candidates, is not.  A tie between
+ *    candidates that both reach min_front does not arise from a scene with depth: a point in front of both cameras under
+ *    one candidate is behind one of them under the other three.
+ *  - Workspace: the calls run the fundamental calls' pack / gather kernels (without a mask: nothing of the caller's is
+ *    zeroed) into the same pair-list workspace, so a pose call replaces the previous RANSAC call's pair list by an equal
+ *    one.  Nothing new is carved; the plan hash and the guard zones are what they were.
+ *  - Execution: asynchronous on the ctx stream, no host synchronisation, no device-to-host copy, no allocation; every count
+ *    and slot is read on the device.  fpc_match_frames, fpc_fundamental_frames, fpc_pose_frames needs no host call in
+ *    between; the same holds through the bank with fpc_match_bank, fpc_fundamental_bank, fpc_pose_bank.
+ *  - Determinism: bit-identical outputs on repeated calls (no floating-point atomics; the counts are sums of 0 / 1); the
+ *    three entry points give bit-identical outputs on equal pair lists, and fpc_pose_bank is bit-identical to
+ *    fpc_pose_frames with that slot as key.
+ * FPC_E_INVALID (nothing is written): everything the fundamental twin refuses for the arguments they share; a NULL F_dev /
+ * params / R_dev / t_dev / nfront_dev; fx or fy not > 0 or any non-finite intrinsic; reproj_threshold not > 0 (or not
+ * below 1e18); min_front < 1. */
+typedef struct fpc_pose_params {
+  float q_fx, q_fy, q_cx, q_cy;   /* intrinsics of the query camera (pixels), fx, fy > 0                                  */
+  float t_fx, t_fy, t_cx, t_cy;   /* intrinsics of the train camera                                                       */
+  float reproj_threshold;         /* px, > 0: which pairs count (the Sampson rule of fpc_ransac_fundamental)              */
+  int   min_front;                /* >= 1; fewer pairs in front of both cameras -> the frame fails                        */
+} fpc_pose_params;
+/* fx = fy = 500, centre (320, 240) on both sides, reproj_threshold 3.0, min_front 8 */
+int fpc_default_pose_params(fpc_pose_params* params);
+int fpc_pose_fundamental(fpc_ctx* ctx, int n, const float* src_xy_dev, const float* dst_xy_dev, const int32_t* npairs_dev,
+                         int stride, const float* F_dev, const fpc_pose_params* params, float* R_dev, float* t_dev,
+                         int32_t* nfront_dev, float* xyz_dev, uint8_t* front_dev);
+int fpc_pose_frames(fpc_ctx* ctx, int n, int pairing, const int32_t* key_xy_dev, const int32_t* nkey_dev,
+                    const int32_t* match_dev, const float* F_dev, const fpc_pose_params* params, float* R_dev, float* t_dev,
+                    int32_t* nfront_dev, float* xyz_dev, uint8_t* front_dev);
+int fpc_pose_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const float* F_dev,
+                  const fpc_pose_params* params, float* R_dev, float* t_dev, int32_t* nfront_dev, float* xyz_dev,
+                  uint8_t* front_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
