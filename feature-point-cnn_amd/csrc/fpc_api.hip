@@ -40,7 +40,6 @@
 #include "match_guided.h"
 #include "match_guided_cells.h"
 #include "match_guided_epipolar.h"
-#include "match_guided_epipolar_cells.h"
 #include "ransac_homography.h"
 #include "ransac_fundamental.h"
 #include "pose_epipolar.h"
@@ -4430,8 +4429,8 @@ int fpc_homography_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot,
   return FPC_OK;
 }
 
-// ---- guided matching: plain, cell-ordered and epipolar (include/fpc.h; kernels in match_guided.h, match_guided_cells.h,
-// ---- match_guided_epipolar.h, match_guided_epipolar_cells.h) -----------------------------------------------------------------
+// ---- guided matching: plain, cell-ordered and epipolar (include/fpc.h; two strip skeletons and two gates in match_guided.h,
+// ---- match_guided_cells.h and match_guided_epipolar.h, four kernels) ------------------------------------------------------------
 // 32-px cells wherever the order is public; a frame of more cells than the order kernel's histogram holds (beyond
 // 16.7 MPx) is ordered in coarser cells by the guided calls, whose output does not depend on the order.
 static CellOrderArgs cell_order_args(fpc_ctx* c, int shift) {
@@ -4480,8 +4479,9 @@ static MatchCellsArgs cell_order_passes(fpc_ctx* c, const MatchFramesArgs& a, co
 
 // The eight guided entry points run on fpc_match_frames' workspace (norms, top-2, column minima: [max_batch][cap], and the
 // bank's rows <= cap), carved at fpc_create: nothing of their own.  One sequence for all: the column minima and the stats
-// reset, the norms (a bf16 bank: its rounding pass, match_bank_bf16.h), the variant's strip kernel (the cell-ordered ones
-// behind their order passes), the finalize kernel.  norm_blocks: n + 1 with the key's block, n against the bank, whose
+// reset, the norms (a bf16 bank: its rounding pass, match_bank_bf16.h), the variant's strip kernel (the four fp32 ones are
+// mg_strip / mgc_strip with the homography or the epipolar gate; the cell-ordered ones run behind their order passes), the
+// finalize kernel.  norm_blocks: n + 1 with the key's block, n against the bank, whose
 // norms are its own.
 enum GuidedStrip { GUIDED_PLAIN, GUIDED_CELLS, GUIDED_BANK_BF16, GUIDED_EPIPOLAR, GUIDED_EPIPOLAR_CELLS };
 

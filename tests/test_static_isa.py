@@ -84,7 +84,8 @@ def code_object(tmp_path_factory):
     for blk in notes.split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
         meta[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
-                      for k in ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")}
+                      for k in ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
+                                "group_segment_fixed_size")}
         meta[name]["agpr_count"] = int(blk.split()[0])
     return funcs, meta
 
@@ -360,3 +361,30 @@ def test_round5_conv2_kernel_is_lean_and_spill_free(code_object):
         assert 2 * valu(body) < valu(funcs[old]), (name, valu(body), valu(funcs[old]))
         pairs += 1
     assert pairs == 2, pairs
+
+
+# The four guided strip kernels' figures in the code object of commit 01c1a76 (three of them are now
+# two skeletons, mg_strip / mgc_strip, instantiated with two gates): `.vgpr_count` (VGPRs + AGPRs of the
+# unified file), `.agpr_count`, `.group_segment_fixed_size`.  Two workgroups of four waves per CU need <= 256 registers
+# and <= 80 KiB of LDS; the figures below are tighter than that on purpose -- shared parts must not cost a kernel anything.
+GUIDED_STRIPS = {
+    "_ZN3fpc19match_guided_kernelENS_15MatchFramesArgsENS_15MatchGuidedArgsE": (176, 64, 76032),
+    "_ZN3fpc25match_guided_cells_kernelENS_15MatchFramesArgsENS_15MatchGuidedArgsENS_14MatchCellsArgsE": (192, 64, 79376),
+    "_ZN3fpc28match_guided_epipolar_kernelENS_15MatchFramesArgsENS_15MatchGuidedArgsE": (188, 64, 76032),
+    "_ZN3fpc34match_guided_epipolar_cells_kernelENS_15MatchFramesArgsENS_15MatchGuidedArgsENS_14MatchCellsArgsE": (204, 64, 79376),
+}
+
+
+def test_guided_strip_kernels_keep_their_registers(code_object):
+    """match_guided.h / match_guided_cells.h / match_guided_epipolar.h: every strip kernel keeps its LDS size, holds nothing
+    in scratch, spills nothing, and needs no more registers -- in all, and below the point where the AGPRs begin -- than
+    in commit 01c1a76."""
+    _, meta = code_object
+    for name, (vgpr, agpr, lds) in GUIDED_STRIPS.items():
+        assert name in meta, name
+        m = meta[name]
+        assert m["private_segment_fixed_size"] == 0, (name, m)
+        assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (name, m)
+        assert m["group_segment_fixed_size"] == lds, (name, m)
+        assert m["agpr_count"] <= agpr and m["vgpr_count"] <= vgpr, (name, m)
+        assert m["vgpr_count"] - m["agpr_count"] <= vgpr - agpr, (name, m)
