@@ -39,6 +39,8 @@ SYMBOLS = [
     "fpc_match_frames_guided_epipolar", "fpc_match_bank_guided_epipolar",
     "fpc_match_frames_guided_epipolar_cells", "fpc_match_bank_guided_epipolar_cells",
     "fpc_default_pose_params", "fpc_pose_fundamental", "fpc_pose_frames", "fpc_pose_bank",
+    "fpc_default_pnp_params", "fpc_pnp_reserve", "fpc_bank_landmarks_reserve", "fpc_bank_store_landmarks",
+    "fpc_bank_landmarks_get", "fpc_ransac_pnp", "fpc_pnp_frames", "fpc_pnp_bank",
 ]
 
 ABI_VERSION = 4
@@ -93,6 +95,13 @@ class FpcPoseParams(ctypes.Structure):
     _fields_ = [("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
                 ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
                 ("reproj_threshold", ctypes.c_float), ("min_front", ctypes.c_int)]
+
+
+class FpcPnpParams(ctypes.Structure):
+    """fpc_pnp_params (include/fpc.h)."""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("iterations", ctypes.c_int), ("reproj_threshold", ctypes.c_float), ("seed", ctypes.c_uint32),
+                ("refits", ctypes.c_int), ("min_inliers", ctypes.c_int)]
 
 
 BANK_MAX_SLOTS = 1024         # include/fpc.h FPC_BANK_MAX_SLOTS
@@ -198,6 +207,15 @@ def load():
     l.fpc_pose_fundamental.argtypes = [vp, ci, vp, vp, vp, ci, vp, pp, vp, vp, vp, vp, vp]
     l.fpc_pose_frames.argtypes = [vp, ci, ci, vp, vp, vp, vp, pp, vp, vp, vp, vp, vp]
     l.fpc_pose_bank.argtypes = [vp, ci, vp, vp, vp, pp, vp, vp, vp, vp, vp]
+    np_ = ctypes.POINTER(FpcPnpParams)
+    l.fpc_default_pnp_params.argtypes = [np_]
+    l.fpc_pnp_reserve.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
+    l.fpc_bank_landmarks_reserve.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
+    l.fpc_bank_store_landmarks.argtypes = [vp, ci, vp, vp]
+    l.fpc_bank_landmarks_get.argtypes = [vp, ctypes.POINTER(vp)]
+    l.fpc_ransac_pnp.argtypes = [vp, ci, vp, vp, vp, ci, np_, vp, vp, vp, vp]
+    l.fpc_pnp_frames.argtypes = [vp, ci, vp, vp, vp, vp, np_, vp, vp, vp, vp]
+    l.fpc_pnp_bank.argtypes = [vp, ci, vp, vp, np_, vp, vp, vp, vp]
     l.fpc_match_frames_guided.argtypes = [vp, ci, ci, vp, vp, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float,
                                           vp, vp]
     l.fpc_match_bank_guided.argtypes = [vp, ci, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float, vp, vp]

@@ -44,6 +44,7 @@
 #include "ransac_fundamental.h"
 #include "pose_epipolar.h"
 #include "match_bank_topk.h"
+#include "pnp_ransac.h"
 #include "homography.h"
 #include "weights.h"
 
@@ -597,6 +598,17 @@ struct fpc_ctx {
   int32_t *topk_row = nullptr, *topk_np = nullptr;
   unsigned long long* topk_best = nullptr;
   std::vector<std::pair<size_t, size_t>> topk_guards;          // (offset, bytes) of the canary zones in topk_slab
+  // RANSAC PnP (fpc_pnp_reserve, pnp_ransac.h): an allocation of its own, made by that call and freed by fpc_destroy -- the
+  // pair records (with their mask rows), counts and best keys of max_batch problems
+  char* pnp_slab = nullptr;
+  float4* pnp_rec = nullptr;
+  int32_t* pnp_np = nullptr;
+  unsigned long long* pnp_best = nullptr;
+  std::vector<std::pair<size_t, size_t>> pnp_guards;           // (offset, bytes) of the canary zones in pnp_slab
+  // landmarks of the bank's rows (fpc_bank_landmarks_reserve): float4 [slots][rows], w = 1 valid / 0; freed with the bank
+  char* lm_slab = nullptr;
+  float4* lm_xyzw = nullptr;
+  std::vector<std::pair<size_t, size_t>> lm_guards;            // (offset, bytes) of the canary zones in lm_slab
   int pts_n = 0;                     // frames of the last call that produced keypoints (fpc_detect*, fpc_get_points)
   bool pts_desc = false;             // ... and whether it sampled their descriptors
 
@@ -3257,6 +3269,8 @@ void fpc_destroy(fpc_ctx* c) {
   if (c->slab) hipFree(c->slab);
   if (c->bank_slab) hipFree(c->bank_slab);
   if (c->topk_slab) hipFree(c->topk_slab);
+  if (c->pnp_slab) hipFree(c->pnp_slab);
+  if (c->lm_slab) hipFree(c->lm_slab);
   if (c->blob) hipFree(c->blob);
   if (c->u8stage) hipFree(c->u8stage);
   if (c->ha_ws) hipFree(c->ha_ws);
@@ -3362,6 +3376,8 @@ int fpc_check_guards(fpc_ctx* c, long long* bad_words) {
   count_zones(c, c->slab, c->guards, d);
   count_zones(c, c->bank_slab, c->bank_guards, d);      // (fpc_bank_create; none without a bank)
   count_zones(c, c->topk_slab, c->topk_guards, d);      // (fpc_bank_topk_reserve)
+  count_zones(c, c->pnp_slab, c->pnp_guards, d);        // (fpc_pnp_reserve)
+  count_zones(c, c->lm_slab, c->lm_guards, d);          // (fpc_bank_landmarks_reserve)
   unsigned long long h = 0;
   const hipError_t e1 = hipStreamSynchronize(c->stream);
   const hipError_t e2 = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
@@ -4111,6 +4127,12 @@ int fpc_bank_destroy(fpc_ctx* c) {
     c->topk_guards.clear();
     c->topk = BankTopkArgs{};
   }
+  if (c->lm_slab) {                                             // ... and so do the landmarks of its rows
+    HIPCHECK(hipFree(c->lm_slab));
+    c->lm_slab = nullptr;
+    c->lm_xyzw = nullptr;
+    c->lm_guards.clear();
+  }
   c->bank = BankArgs{};
   c->bank_format = FPC_BANK_F32;
   c->bank16 = BankBf16Args{};
@@ -4130,6 +4152,14 @@ int fpc_bank_get(fpc_ctx* c, fpc_bank_view* out) {
   return FPC_OK;
 }
 
+// With a landmark reservation alive (fpc_bank_landmarks_reserve), whatever rewrites or empties a slot (-1: every slot)
+// invalidates its landmarks: old points never attach to new rows.  Nothing is launched without a reservation.
+static void landmarks_invalidate(fpc_ctx* c, int slot) {
+  if (!c->lm_slab) return;
+  hipLaunchKernelGGL(pnp_landmarks_invalidate_kernel, dim3((c->bank.rows + 255) / 256, slot < 0 ? c->bank.slots : 1), dim3(256),
+                     0, c->stream, c->lm_xyzw, c->bank.rows, slot);
+}
+
 // the store kernel of the bank's format
 static void bank_store_launch(fpc_ctx* c, int slot, const float* desc, const int32_t* xy, const int32_t* n, int src_cap) {
   const dim3 grid((c->bank.rows + 127) / 128);
@@ -4137,6 +4167,7 @@ static void bank_store_launch(fpc_ctx* c, int slot, const float* desc, const int
     hipLaunchKernelGGL(bank_store_bf16_kernel, grid, dim3(256), 0, c->stream, c->bank, c->bank16, slot, desc, xy, n, src_cap);
   else
     hipLaunchKernelGGL(bank_store_kernel, grid, dim3(256), 0, c->stream, c->bank, slot, desc, xy, n, src_cap);
+  landmarks_invalidate(c, slot);
 }
 
 int fpc_bank_store(fpc_ctx* c, int frame, int slot) {
@@ -4164,6 +4195,7 @@ int fpc_bank_clear(fpc_ctx* c, int slot) {
   if (!c || !c->bank_slab || slot < -1 || slot >= c->bank.slots) return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
   hipLaunchKernelGGL(bank_clear_kernel, dim3((c->bank.slots + 255) / 256), dim3(256), 0, c->stream, c->bank, slot);
+  landmarks_invalidate(c, slot);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }
@@ -4340,6 +4372,138 @@ int fpc_pose_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, 
   hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
                      (const int32_t*)nullptr, match, (uint8_t*)nullptr, hb);
   pose_launch(c, a, p, F, R, t, nfront, xyz, front, c->cap);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+// ---- absolute pose from bank landmarks: RANSAC PnP (include/fpc.h; kernels in pnp_ransac.h) ------------------------------------
+int fpc_default_pnp_params(fpc_pnp_params* p) {
+  if (!p) return FPC_E_INVALID;
+  p->fx = p->fy = 500.0f;
+  p->cx = 320.0f;
+  p->cy = 240.0f;
+  p->iterations = 1024;
+  p->reproj_threshold = 3.0f;
+  p->seed = 0;
+  p->refits = 4;
+  p->min_inliers = 12;
+  return FPC_OK;
+}
+
+static bool pnp_params_ok(const fpc_pnp_params* p) {
+  if (!p) return false;
+  const float k[4] = {p->fx, p->fy, p->cx, p->cy};
+  for (float v : k)
+    if (!std::isfinite(v)) return false;
+  return p->fx > 0.f && p->fy > 0.f && p->iterations >= 1 && p->iterations <= HF_MAX_ITERATIONS && p->reproj_threshold > 0.f &&
+         p->reproj_threshold < 1e18f && p->refits >= 0 && p->refits <= 4 && p->min_inliers >= PNP_SAMPLE;
+}
+
+// The only PnP call that allocates or synchronises: pair records, counts and best keys of max_batch problems, an allocation
+// of its own (the context slab, the plan hash, the bank's bytes and the RANSAC pair-list workspace are what they were).
+int fpc_pnp_reserve(fpc_ctx* c, size_t* bytes) {
+  if (!c || c->pnp_slab) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  Carver cv;
+  std::vector<std::pair<size_t, size_t>> zones;
+  cv.zones = &zones;
+  cv.guard = c->guard_zones ? GUARD_BYTES : 0;
+  const size_t B = c->B, cap = c->cap;
+  const size_t o_rec = cv.take<float4>(B * cap * 2), o_np = cv.take<int32_t>(B), o_best = cv.take<unsigned long long>(B);
+  char* p = nullptr;
+  if (int rc = alloc_side_slab(c, cv, &p)) return rc;
+  c->pnp_slab = p;
+  c->pnp_guards = zones;
+  c->pnp_rec = reinterpret_cast<float4*>(p + o_rec);
+  c->pnp_np = reinterpret_cast<int32_t*>(p + o_np);
+  c->pnp_best = reinterpret_cast<unsigned long long*>(p + o_best);
+  if (bytes) *bytes = cv.off;
+  return FPC_OK;
+}
+
+int fpc_bank_landmarks_reserve(fpc_ctx* c, size_t* bytes) {
+  if (!c || !c->bank_slab || c->lm_slab) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  Carver cv;
+  std::vector<std::pair<size_t, size_t>> zones;
+  cv.zones = &zones;
+  cv.guard = c->guard_zones ? GUARD_BYTES : 0;
+  const size_t o_lm = cv.take<float4>((size_t)c->bank.slots * c->bank.rows);
+  char* p = nullptr;
+  if (int rc = alloc_side_slab(c, cv, &p)) return rc;           // (zeroed: no row is valid)
+  c->lm_slab = p;
+  c->lm_guards = zones;
+  c->lm_xyzw = reinterpret_cast<float4*>(p + o_lm);
+  if (bytes) *bytes = cv.off;
+  return FPC_OK;
+}
+
+int fpc_bank_store_landmarks(fpc_ctx* c, int slot, const float* xyz, const uint8_t* valid) {
+  if (!c || !c->bank_slab || !c->lm_slab || slot < 0 || slot >= c->bank.slots || !xyz) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(pnp_landmarks_store_kernel, dim3((c->bank.rows + 255) / 256), dim3(256), 0, c->stream, c->lm_xyzw,
+                     c->bank.count, c->bank.rows, slot, xyz, valid);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_bank_landmarks_get(fpc_ctx* c, const float** xyzw) {
+  if (!c || !xyzw || !c->bank_slab || !c->lm_slab) return FPC_E_INVALID;
+  *xyzw = reinterpret_cast<const float*>(c->lm_xyzw);
+  return FPC_OK;
+}
+
+static PnpArgs pnp_args(fpc_ctx* c, int n, const fpc_pnp_params* p) {
+  PnpArgs a{};
+  a.rec = c->pnp_rec; a.np = c->pnp_np; a.best = c->pnp_best;
+  a.cap = c->cap; a.n = n;
+  a.T = p->iterations; a.refits = p->refits; a.min_inliers = p->min_inliers;
+  a.thr = p->reproj_threshold; a.seed = p->seed;
+  a.fx = p->fx; a.fy = p->fy; a.cx = p->cx; a.cy = p->cy;
+  return a;
+}
+
+// the kernels the three entry points share, behind their pack / gather kernel
+static void pnp_launch(fpc_ctx* c, const PnpArgs& a, float* R, float* t, int32_t* ninliers, uint8_t* inlier, int mstride) {
+  hipLaunchKernelGGL(pnp_score_kernel, dim3((a.T + PNP_THREADS - 1) / PNP_THREADS, a.n), dim3(PNP_THREADS), 0, c->stream, a);
+  hipLaunchKernelGGL(pnp_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, R, t, ninliers, inlier, mstride);
+}
+
+int fpc_ransac_pnp(fpc_ctx* c, int n, const float* xy, const float* xyz, const int32_t* npairs, int stride,
+                   const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->pnp_slab || !xy || !xyz || !npairs || !R || !t || !ninliers || !pnp_params_ok(p)) return FPC_E_INVALID;
+  if (n < 1 || n > c->B || stride < 1 || stride > c->cap) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const PnpArgs a = pnp_args(c, n, p);
+  hipLaunchKernelGGL(pnp_pack_kernel, dim3((stride + 255) / 256, n), dim3(256), 0, c->stream, a, xy, xyz, npairs, stride, inlier);
+  pnp_launch(c, a, R, t, ninliers, inlier, stride);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_pnp_frames(fpc_ctx* c, int n, const float* key_xyz, const uint8_t* key_valid, const int32_t* nkey, const int32_t* match,
+                   const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->pnp_slab || !key_xyz || !nkey || !match || !R || !t || !ninliers || !pnp_params_ok(p) || !frames_ok(c, n))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const PnpArgs a = pnp_args(c, n, p);
+  const PnpTrain tr{key_xyz, key_valid, nkey, nullptr, nullptr, nullptr, 0, 0};
+  hipLaunchKernelGGL(pnp_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, match, inlier, tr);
+  pnp_launch(c, a, R, t, ninliers, inlier, c->cap);
+  HIPCHECK(hipGetLastError());
+  return FPC_OK;
+}
+
+int fpc_pnp_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const fpc_pnp_params* p, float* R, float* t,
+                 int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->pnp_slab || !c->bank_slab || !slot || !match || !R || !t || !ninliers || !pnp_params_ok(p) || !frames_ok(c, n))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const PnpArgs a = pnp_args(c, n, p);
+  // (without landmark storage lm is null: no frame has pairs)
+  const PnpTrain tr{nullptr, nullptr, nullptr, slot, c->lm_xyzw, c->bank.count, c->bank.rows, c->bank.slots};
+  hipLaunchKernelGGL(pnp_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, match, inlier, tr);
+  pnp_launch(c, a, R, t, ninliers, inlier, c->cap);
   HIPCHECK(hipGetLastError());
   return FPC_OK;
 }

@@ -1,0 +1,584 @@
+// Batched RANSAC perspective-n-point (fpc_ransac_pnp / fpc_pnp_frames / fpc_pnp_bank; the rule is stated in include/fpc.h and
+// restated in float64 by tests/test_pnp_ransac.py).  The hash, the (count << 32) | ~t selection and hf_block_sum are
+// ransac_homography.h's, the Jacobi routine is ransac_fundamental.h's.
+//
+//   pnp_pack_kernel / pnp_gather_kernel   twins of hf_pack_kernel / hf_gather_kernel: every problem's pair list as 32-byte
+//                     records [x, y, X, Y | Z, row, -, -] (two float4; `row` is the mask row of the pair, as int bits), the
+//                     pair count, and the zeroed best key and mask.  The gather is the same order-preserving compaction
+//                     (ballot + popcount prefix, no atomics); a landmark's validity (its w, or valid[] and the finiteness
+//                     of its coordinates) is part of the pair test.
+//   pnp_score_kernel  grid ceil(T / 64) x n, one thread per hypothesis: draws its 6 pairs and solves the normalised 6-point
+//                     DLT in fp64 by Gaussian elimination with full pivoting.  The 11 x 12 system needs dynamic row and
+//                     column indices, so it lives in LDS, struct-of-arrays (sys[132][64]); the column permutation is twelve
+//                     nibbles of one 64-bit register.  132 doubles x 64 lanes = 66 KiB: ONE wave per workgroup, so that
+//                     two workgroups share a CU's 160 KiB (128 lanes would need 132 KiB and run alone).  P then sits in 12
+//                     fp32 VGPRs and the pair list is walked through the same LDS in 1 024-record chunks (32 KiB), every
+//                     lane reading the same record: the broadcast case.
+//   pnp_refit_kernel  one workgroup of 256 per problem: one lane re-derives the best sample's P with the same device
+//                     function and takes its polar step (fm_jacobi at N = 3); then `refits` times one pass over the pairs
+//                     (the 21 + 6 sums of J^T J and J^T r, and the count, in fp64 through hf_block_sum) and one lane's
+//                     6 x 6 elimination in LDS; writes R, t, the inlier count and the mask of the pose it returns.
+//   pnp_landmarks_store_kernel / pnp_landmarks_invalidate_kernel   element-wise, over one slot's rows (or every slot's).
+#pragma once
+#include "ransac_fundamental.h"
+
+constexpr int PNP_DRAWS = 32;          // draw budget of one sample
+constexpr int PNP_SAMPLE = 6;
+constexpr int PNP_THREADS = 64;        // hypotheses per workgroup of pnp_score_kernel: 66 KiB of LDS, two workgroups per CU
+constexpr int PNP_ROWS = 11, PNP_COLS = 12;
+constexpr int PNP_CHUNK = 1024;        // records staged per LDS chunk (32 KiB)
+constexpr double PNP_PIVOT = 1e-10;    // last pivot / first pivot below which a sample is degenerate
+constexpr double PNP_RANK = 1e-12;     // lambda_min / lambda_max of A^T A at or below which P has no rotation
+constexpr double PNP_SINGULAR = 1e-14; // pivot / largest diagonal entry of J^T J at or below which a refit is singular
+constexpr int PNP_NSUM = 28;           // 21 of J^T J, 6 of J^T r, the inlier count
+
+struct PnpArgs {
+  float4* rec;                  // [B][cap][2]  (x, y, X, Y), (Z, row, -, -)
+  int32_t* np;                  // [B]          pairs of the frame
+  unsigned long long* best;     // [B]          (inlier count << 32) | ~t of the best hypothesis; 0: none
+  int cap, n;
+  int T, refits, min_inliers;
+  float thr;
+  uint32_t seed;
+  float fx, fy, cx, cy;
+};
+
+struct PnpPair { float x, y, X, Y, Z; int row; };
+
+__device__ __forceinline__ PnpPair pnp_load(const float4* __restrict__ rec, int k) {
+  const float4 a = rec[2 * k], b = rec[2 * k + 1];
+  return {a.x, a.y, a.z, a.w, b.x, __float_as_int(b.y)};
+}
+
+__device__ __forceinline__ bool pnp_finite3(float X, float Y, float Z) {
+  return fabsf(X) <= 3.402823466e38f && fabsf(Y) <= 3.402823466e38f && fabsf(Z) <= 3.402823466e38f;   // (false for NaN)
+}
+
+// the sampler of include/fpc.h: the first 6 distinct of 32 draws (selects, not an indexed store: that becomes scratch)
+__device__ __forceinline__ bool pnp_sample(uint32_t seed, uint32_t f, uint32_t t, uint32_t M, uint32_t (&idx)[PNP_SAMPLE]) {
+#pragma unroll
+  for (int j = 0; j < PNP_SAMPLE; ++j) idx[j] = M;
+  int got = 0;
+  for (uint32_t k = 0; k < (uint32_t)PNP_DRAWS && got < PNP_SAMPLE; ++k) {
+    const uint32_t r = hf_mix(seed ^ hf_mix((f * (uint32_t)HF_MAX_ITERATIONS + t) * (uint32_t)PNP_DRAWS + k)) % M;
+    bool fresh = true;
+#pragma unroll
+    for (int j = 0; j < PNP_SAMPLE; ++j) fresh = fresh && r != idx[j];
+#pragma unroll
+    for (int j = 0; j < PNP_SAMPLE; ++j) idx[j] = (fresh && got == j) ? r : idx[j];
+    got += fresh ? 1 : 0;
+  }
+  return got == PNP_SAMPLE;
+}
+
+// The 6-point DLT.  sys: this thread's 11 x 12 system, element (r, c) at sys[(r * 12 + c) * S] (LDS).  Image points in
+// normalised coordinates, landmarks translated to their centroid and scaled to an RMS distance of sqrt(3); elimination with
+// full pivoting (ties: lowest row, then lowest column), the null vector by back-substitution with the last column's unknown
+// = 1; P is denormalised to the landmarks' own coordinates (image side still normalised): P = [A | a4], row-major 3 x 4.
+// Contraction is off so that the score kernel and the refit kernel, which inline this at different strides, compute the
+// same bits.  -> the sample's first pair in `first`.  false: degenerate.
+template <int S>
+__device__ __forceinline__ bool pnp_solve6(double* sys, const float4* __restrict__ rec, const uint32_t (&idx)[PNP_SAMPLE],
+                                           const PnpArgs& a, double (&P)[12], PnpPair& first) {
+#pragma clang fp contract(off)
+  PnpPair r[PNP_SAMPLE];
+#pragma unroll
+  for (int i = 0; i < PNP_SAMPLE; ++i) r[i] = pnp_load(rec, (int)idx[i]);
+  first = r[0];
+  double mx = 0.0, my = 0.0, mz = 0.0;
+#pragma unroll
+  for (int i = 0; i < PNP_SAMPLE; ++i) { mx += (double)r[i].X; my += (double)r[i].Y; mz += (double)r[i].Z; }
+  mx = mx / 6.0; my = my / 6.0; mz = mz / 6.0;
+  double var = 0.0;
+#pragma unroll
+  for (int i = 0; i < PNP_SAMPLE; ++i) {
+    const double dx = (double)r[i].X - mx, dy = (double)r[i].Y - my, dz = (double)r[i].Z - mz;
+    var += dx * dx; var += dy * dy; var += dz * dz;
+  }
+  var = var / 6.0;
+  if (!(var > 0.0) || !(var < 1e300)) return false;             // (NaN fails the first test, Inf the second)
+  const double s = sqrt(3.0 / var);
+  const double fx = a.fx, fy = a.fy, cx = a.cx, cy = a.cy;
+#pragma unroll
+  for (int i = 0; i < PNP_SAMPLE; ++i) {
+    const double X = ((double)r[i].X - mx) * s, Y = ((double)r[i].Y - my) * s, Z = ((double)r[i].Z - mz) * s;
+    const double xh = ((double)r[i].x - cx) / fx, yh = ((double)r[i].y - cy) / fy;
+    double* row = sys + (size_t)(2 * i) * PNP_COLS * S;
+    row[0] = X; row[S] = Y; row[2 * S] = Z; row[3 * S] = 1.0; row[4 * S] = 0.0; row[5 * S] = 0.0; row[6 * S] = 0.0; row[7 * S] = 0.0;
+    row[8 * S] = -xh * X; row[9 * S] = -xh * Y; row[10 * S] = -xh * Z; row[11 * S] = -xh;
+    if (i < PNP_SAMPLE - 1) {                                   // (the sixth point gives its first row only)
+      row += (size_t)PNP_COLS * S;
+      row[0] = 0.0; row[S] = 0.0; row[2 * S] = 0.0; row[3 * S] = 0.0; row[4 * S] = X; row[5 * S] = Y; row[6 * S] = Z; row[7 * S] = 1.0;
+      row[8 * S] = -yh * X; row[9 * S] = -yh * Y; row[10 * S] = -yh * Z; row[11 * S] = -yh;
+    }
+  }
+  unsigned long long perm = 0xBA9876543210ull;                  // nibble c: the unknown that column c holds
+  double firstp = 0.0, last = 0.0;
+#pragma unroll 1
+  for (int c = 0; c < PNP_ROWS; ++c) {
+    double pv = -1.0;
+    int pr = c, pc = c;
+    for (int i = c; i < PNP_ROWS; ++i)
+      for (int j = c; j < PNP_COLS; ++j) {
+        const double v = fabs(sys[(i * PNP_COLS + j) * S]);
+        if (v > pv) { pv = v; pr = i; pc = j; }
+      }
+    if (c == 0) firstp = pv;
+    last = pv;
+    if (!(pv > 0.0)) return false;
+    if (pr != c)
+      for (int j = c; j < PNP_COLS; ++j) {
+        const double tmp = sys[(c * PNP_COLS + j) * S];
+        sys[(c * PNP_COLS + j) * S] = sys[(pr * PNP_COLS + j) * S];
+        sys[(pr * PNP_COLS + j) * S] = tmp;
+      }
+    if (pc != c) {
+      for (int i = 0; i < PNP_ROWS; ++i) {
+        const double tmp = sys[(i * PNP_COLS + c) * S];
+        sys[(i * PNP_COLS + c) * S] = sys[(i * PNP_COLS + pc) * S];
+        sys[(i * PNP_COLS + pc) * S] = tmp;
+      }
+      const unsigned long long nc = (perm >> (4 * c)) & 15ull, np = (perm >> (4 * pc)) & 15ull;
+      perm = (perm & ~((15ull << (4 * c)) | (15ull << (4 * pc)))) | (np << (4 * c)) | (nc << (4 * pc));
+    }
+    const double piv = sys[(c * PNP_COLS + c) * S];
+    for (int i = c + 1; i < PNP_ROWS; ++i) {
+      const double fct = sys[(i * PNP_COLS + c) * S] / piv;
+      for (int j = c + 1; j < PNP_COLS; ++j)
+        sys[(i * PNP_COLS + j) * S] = sys[(i * PNP_COLS + j) * S] - fct * sys[(c * PNP_COLS + j) * S];
+    }
+  }
+  if (!(last >= PNP_PIVOT * firstp)) return false;
+  // back-substitution; y_i replaces the pivot it was divided by
+#pragma unroll 1
+  for (int i = PNP_ROWS - 1; i >= 0; --i) {
+    double acc = 0.0;
+    for (int j = i + 1; j < PNP_ROWS; ++j) acc = acc + sys[(i * PNP_COLS + j) * S] * sys[(j * PNP_COLS + j) * S];
+    acc = acc + sys[(i * PNP_COLS + PNP_ROWS) * S];
+    sys[(i * PNP_COLS + i) * S] = -acc / sys[(i * PNP_COLS + i) * S];
+  }
+  double Pn[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) Pn[k] = 0.0;
+#pragma unroll 1
+  for (int i = 0; i < PNP_COLS; ++i) {
+    const double yi = i < PNP_ROWS ? sys[(i * PNP_COLS + i) * S] : 1.0;
+    const int pi = (int)((perm >> (4 * i)) & 15ull);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Pn[k] = pi == k ? yi : Pn[k];
+  }
+  // P = Pn [s I, -s m; 0 1]
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    P[i * 4 + 0] = Pn[i * 4 + 0] * s;
+    P[i * 4 + 1] = Pn[i * 4 + 1] * s;
+    P[i * 4 + 2] = Pn[i * 4 + 2] * s;
+    P[i * 4 + 3] = Pn[i * 4 + 3] - s * (mx * Pn[i * 4 + 0] + my * Pn[i * 4 + 1] + mz * Pn[i * 4 + 2]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) finite = finite && fabs(P[i * 4 + j]) < 1e300;        // (false for NaN and Inf)
+  }
+  return finite;
+}
+
+// the hypothesis as it is scored: P_px = K P scaled to max |p| = 1, w > 0 at the sample's first pair, rounded to fp32
+__device__ __forceinline__ bool pnp_hypothesis(const double (&P)[12], const PnpArgs& a, const PnpPair& first, float (&P32)[12]) {
+#pragma clang fp contract(off)
+  double Q[12];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    Q[j] = (double)a.fx * P[j] + (double)a.cx * P[8 + j];
+    Q[4 + j] = (double)a.fy * P[4 + j] + (double)a.cy * P[8 + j];
+    Q[8 + j] = P[8 + j];
+  }
+  double mx = 0.0;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) mx = fmax(mx, fabs(Q[i]));
+  if (!(mx > 0.0) || !(mx < 1e300)) return false;
+  const double w0 = ((Q[8] * (double)first.X + Q[9] * (double)first.Y) + Q[10] * (double)first.Z) + Q[11];
+  const double sg = w0 < 0.0 ? -1.0 : 1.0;
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const double v = sg * (Q[i] / mx);
+    finite = finite && (fabs(v) <= 1.0);                        // (false for NaN)
+    P32[i] = (float)v;
+  }
+  return finite;
+}
+
+// ---- pair lists -------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pnp_pack_kernel(PnpArgs a, const float* __restrict__ xy, const float* __restrict__ xyz,
+                                                       const int32_t* __restrict__ npairs, int stride, uint8_t* mask) {
+  const int f = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+  const int M = hf_clamp(npairs[f], stride);
+  if (k == 0) {
+    a.np[f] = M;
+    a.best[f] = 0ull;
+  }
+  if (k >= stride) return;
+  if (mask) mask[(size_t)f * stride + k] = 0;
+  if (k < M) {
+    const size_t i = (size_t)f * stride + k;
+    float4* out = a.rec + ((size_t)f * a.cap + k) * 2;
+    out[0] = make_float4(xy[i * 2], xy[i * 2 + 1], xyz[i * 3], xyz[i * 3 + 1]);
+    out[1] = make_float4(xyz[i * 3 + 2], __int_as_float(k), 0.f, 0.f);
+  }
+}
+
+// The landmarks of frame f: fpc_pnp_frames' key (xyz [nkey][3], valid [nkey] or null, nkey[0]) with bank.slot null, or slot
+// bank.slot[f] of the bank's landmark storage (float4 [slots][rows], w = 1 valid / 0; count [slots]).  A slot outside
+// [0, slots) or a bank without landmark storage leaves the frame without pairs.
+struct PnpTrain {
+  const float* key_xyz;
+  const uint8_t* key_valid;
+  const int32_t* nkey;
+  const int32_t* slot;          // [n] device
+  const float4* lm;             // [slots][rows]
+  const int32_t* count;         // [slots]
+  int rows, slots;
+};
+
+// one workgroup per frame; rows i < count[f] with 0 <= match < the train count and a valid landmark, in ascending i
+__global__ __launch_bounds__(256) void pnp_gather_kernel(PnpArgs a, const int32_t* __restrict__ xy, const int32_t* __restrict__ count,
+                                                         const int32_t* __restrict__ match, uint8_t* mask, const PnpTrain tr) {
+  __shared__ int wsum[4];
+  const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cap = a.cap;
+  const int cnt = hf_clamp(count[f], cap);
+  const float4* lm = nullptr;
+  int nt = 0;
+  if (tr.slot) {
+    const int sl = tr.slot[f];
+    if (tr.lm && sl >= 0 && sl < tr.slots) {
+      lm = tr.lm + (size_t)sl * tr.rows;
+      nt = hf_clamp(tr.count[sl], tr.rows);
+    }
+  } else {
+    nt = hf_clamp(tr.nkey[0], cap);
+  }
+  const int32_t* qxy = xy + (size_t)f * cap * 2;
+  const int end = mask ? cap : cnt;
+  int base = 0;
+  for (int i0 = 0; i0 < end; i0 += 256) {
+    const int i = i0 + tid;
+    int m = -1;
+    if (i < cnt) m = match[(size_t)f * cap + i];
+    bool flag = m >= 0 && m < nt;
+    float X = 0.f, Y = 0.f, Z = 0.f;
+    if (flag) {
+      if (tr.slot) {
+        const float4 p = lm[m];
+        X = p.x; Y = p.y; Z = p.z;
+        flag = p.w != 0.f;
+      } else {
+        X = tr.key_xyz[3 * (size_t)m]; Y = tr.key_xyz[3 * (size_t)m + 1]; Z = tr.key_xyz[3 * (size_t)m + 2];
+        flag = (!tr.key_valid || tr.key_valid[m] != 0) && pnp_finite3(X, Y, Z);
+      }
+    }
+    if (mask && i < cap) mask[(size_t)f * cap + i] = 0;
+    const unsigned long long b = __ballot(flag);
+    const int before = __popcll(b & ((1ull << lane) - 1ull));
+    __syncthreads();
+    if (lane == 0) wsum[wave] = __popcll(b);
+    __syncthreads();
+    int off = base + before;
+    for (int w = 0; w < 4; ++w) {
+      if (w < wave) off += wsum[w];
+      base += wsum[w];
+    }
+    if (flag) {
+      float4* out = a.rec + ((size_t)f * cap + off) * 2;
+      out[0] = make_float4((float)qxy[2 * i], (float)qxy[2 * i + 1], X, Y);
+      out[1] = make_float4(Z, __int_as_float(i), 0.f, 0.f);
+    }
+  }
+  if (tid == 0) {
+    a.np[f] = base;
+    a.best[f] = 0ull;
+  }
+}
+
+// ---- scoring ----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PNP_THREADS) void pnp_score_kernel(PnpArgs a) {
+  __shared__ double sys[PNP_ROWS * PNP_COLS * PNP_THREADS];  // the systems; afterwards the staged pair chunk
+  static_assert(sizeof(double) * PNP_ROWS * PNP_COLS * PNP_THREADS >= sizeof(float4) * 2 * PNP_CHUNK,
+                "the pair chunk reuses the systems' LDS");
+  float4* stage = reinterpret_cast<float4*>(sys);
+  const int f = blockIdx.y, tid = threadIdx.x;
+  const int M = hf_clamp(a.np[f], a.cap);
+  if (M < PNP_SAMPLE) return;
+  const float4* __restrict__ rec = a.rec + (size_t)f * a.cap * 2;
+  const uint32_t t = blockIdx.x * (uint32_t)PNP_THREADS + tid;
+  float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f, p4 = 0.f, p5 = 0.f, p6 = 0.f, p7 = 0.f, p8 = 0.f, p9 = 0.f, p10 = 0.f, p11 = 0.f;
+  bool ok = t < (uint32_t)a.T;
+  if (ok) {
+    uint32_t idx[PNP_SAMPLE];
+    ok = pnp_sample(a.seed, (uint32_t)f, t, (uint32_t)M, idx);
+    if (ok) {
+      double P[12];
+      PnpPair first;
+      float P32[12];
+      ok = pnp_solve6<PNP_THREADS>(sys + tid, rec, idx, a, P, first) && pnp_hypothesis(P, a, first, P32);
+      if (ok) {
+        p0 = P32[0]; p1 = P32[1]; p2 = P32[2]; p3 = P32[3]; p4 = P32[4]; p5 = P32[5];
+        p6 = P32[6]; p7 = P32[7]; p8 = P32[8]; p9 = P32[9]; p10 = P32[10]; p11 = P32[11];
+      }
+    }
+  }
+  // (a degenerate hypothesis keeps P = 0: w = 0 is never > 0, it counts nothing; such lanes still meet the barriers)
+  const float thr = a.thr;
+  int cnt = 0;
+  for (int c0 = 0; c0 < M; c0 += PNP_CHUNK) {
+    const int m = min(PNP_CHUNK, M - c0);
+    __syncthreads();
+    for (int i = tid; i < 2 * m; i += PNP_THREADS) stage[i] = rec[2 * c0 + i];
+    __syncthreads();
+#pragma unroll 4
+    for (int k = 0; k < m; ++k) {
+      const float4 q = stage[2 * k];
+      const float Z = stage[2 * k + 1].x;
+      const float w = fmaf(p10, Z, fmaf(p9, q.w, fmaf(p8, q.z, p11)));
+      const float u = fmaf(p2, Z, fmaf(p1, q.w, fmaf(p0, q.z, p3)));
+      const float v = fmaf(p6, Z, fmaf(p5, q.w, fmaf(p4, q.z, p7)));
+      const float ex = fmaf(-w, q.x, u), ey = fmaf(-w, q.y, v);
+      const float tw = thr * w;
+      cnt += (w > 0.f && fmaf(ex, ex, ey * ey) < tw * tw) ? 1 : 0;
+    }
+  }
+  unsigned long long key = (ok && cnt > 0) ? (((unsigned long long)(uint32_t)cnt << 32) | (unsigned long long)(~t)) : 0ull;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const unsigned long long other = __shfl_xor(key, o);
+    key = other > key ? other : key;
+  }
+  if (tid == 0 && key) atomicMax(a.best + f, key);
+}
+
+// ---- refit ------------------------------------------------------------------------------------------------------------
+// P = [A | a4] (LDS, 12 doubles) -> the nearest pose: negated if det A < 0; A^T A = V diag(lambda) V^T by fm_jacobi at
+// N = 3; R = A V diag(lambda^-1/2) V^T, sigma the mean of sqrt(lambda), t = a4 / sigma; out (LDS) gets the 12 fp32 values
+// (R row-major, then t) as doubles.  false: the rank test fails or the result is not finite.  One lane.
+__device__ __forceinline__ bool pnp_polar(double* P, double* A, double* V, double* W, double* out) {
+  const double det = P[0] * (P[5] * P[10] - P[6] * P[9]) - P[1] * (P[4] * P[10] - P[6] * P[8]) + P[2] * (P[4] * P[9] - P[5] * P[8]);
+  if (det < 0.0)
+    for (int i = 0; i < 12; ++i) P[i] = -P[i];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) A[i * 3 + j] = P[i] * P[j] + P[4 + i] * P[4 + j] + P[8 + i] * P[8 + j];
+  fm_jacobi(A, V, 3);
+  const double l0 = A[0], l1 = A[4], l2 = A[8];
+  const double lmin = fmin(l0, fmin(l1, l2)), lmax = fmax(l0, fmax(l1, l2));
+  if (!(lmin > PNP_RANK * lmax)) return false;                  // (false for NaN)
+  const double r0 = sqrt(l0), r1 = sqrt(l1), r2 = sqrt(l2);
+  const double sigma = (r0 + r1 + r2) / 3.0;
+  // W = V diag(1 / sqrt(lambda)) V^T
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) W[i * 3 + j] = V[i * 3] * V[j * 3] / r0 + V[i * 3 + 1] * V[j * 3 + 1] / r1 + V[i * 3 + 2] * V[j * 3 + 2] / r2;
+  bool finite = true;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) {
+      const float v = (float)(P[i * 4] * W[j] + P[i * 4 + 1] * W[3 + j] + P[i * 4 + 2] * W[6 + j]);
+      finite = finite && fabsf(v) < 3e38f;                      // (false for NaN and Inf)
+      out[i * 3 + j] = (double)v;
+    }
+    const float v = (float)(P[i * 4 + 3] / sigma);
+    finite = finite && fabsf(v) < 3e38f;
+    out[9 + i] = (double)v;
+  }
+  return finite;
+}
+
+// the reprojection test of include/fpc.h in fp64; -> (a, b, c) = R X + t
+__device__ __forceinline__ bool pnp_inlier(const double (&R)[9], const double (&t)[3], const PnpArgs& g, const PnpPair& p,
+                                           double thr2, double& a, double& b, double& c) {
+  const double X = p.X, Y = p.Y, Z = p.Z;
+  a = R[0] * X + R[1] * Y + R[2] * Z + t[0];
+  b = R[3] * X + R[4] * Y + R[5] * Z + t[1];
+  c = R[6] * X + R[7] * Y + R[8] * Z + t[2];
+  const double ex = (double)g.fx * a - ((double)p.x - (double)g.cx) * c, ey = (double)g.fy * b - ((double)p.y - (double)g.cy) * c;
+  return c > 0.0 && ex * ex + ey * ey < thr2 * c * c;
+}
+
+__global__ __launch_bounds__(256) void pnp_refit_kernel(PnpArgs a, float* __restrict__ Rout, float* __restrict__ tout,
+                                                        int32_t* __restrict__ ninl, uint8_t* mask, int mstride) {
+  __shared__ double red[4 * PNP_NSUM];
+  __shared__ double sys[PNP_ROWS * PNP_COLS];
+  __shared__ double jm[9], jv[9], jw[9];
+  __shared__ double s28[PNP_NSUM];
+  __shared__ double sm[6][7];
+  __shared__ double pw[12], pose[12];
+  __shared__ int solved;
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const int M = hf_clamp(a.np[f], a.cap);
+  const unsigned long long key = a.best[f];
+  const float4* __restrict__ rec = a.rec + (size_t)f * a.cap * 2;
+  const double thr2 = (double)a.thr * (double)a.thr;
+  const double fx = a.fx, fy = a.fy, cx = a.cx, cy = a.cy;
+  double R[9], t[3];
+  bool ok = M >= PNP_SAMPLE && key != 0ull;
+  if (ok) {                                     // (uniform) one lane re-derives the best sample's P: same function, same bits
+    if (tid == 0) {
+      uint32_t idx[PNP_SAMPLE];
+      double P[12];
+      PnpPair first;
+      int good = pnp_sample(a.seed, (uint32_t)f, ~(uint32_t)key, (uint32_t)M, idx) && pnp_solve6<1>(sys, rec, idx, a, P, first);
+      if (good) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) pw[i] = P[i];
+        good = pnp_polar(pw, jm, jv, jw, pose);
+      }
+      solved = good;
+    }
+    __syncthreads();
+    ok = solved != 0;
+  }
+  int total = 0;
+  if (ok) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = pose[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = pose[9 + i];
+    for (int r = 0; r < a.refits; ++r) {
+      // one Gauss-Newton step: J^T J (upper triangle, row-major), J^T r and the count over the inliers of (R, t)
+      double s[PNP_NSUM];
+#pragma unroll
+      for (int i = 0; i < PNP_NSUM; ++i) s[i] = 0.0;
+      for (int k = tid; k < M; k += 256) {
+        const PnpPair p = pnp_load(rec, k);
+        double xa, xb, xc;
+        if (pnp_inlier(R, t, a, p, thr2, xa, xb, xc)) {
+          const double ic = 1.0 / xc, u = xa * ic, v = xb * ic;
+          const double ru = fx * (u - ((double)p.x - cx) / fx), rv = fy * (v - ((double)p.y - cy) / fy);
+          const double ju[6] = {fx * (-u * v), fx * (1.0 + u * u), fx * (-v), fx * ic, 0.0, fx * (-u * ic)};
+          const double jv2[6] = {fy * (-(1.0 + v * v)), fy * (u * v), fy * u, 0.0, fy * ic, fy * (-v * ic)};
+          int q = 0;
+#pragma unroll
+          for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) s[q++] += ju[i] * ju[j] + jv2[i] * jv2[j];
+#pragma unroll
+          for (int i = 0; i < 6; ++i) s[21 + i] += ju[i] * ru + jv2[i] * rv;
+          s[27] += 1.0;
+        }
+      }
+      hf_block_sum<PNP_NSUM>(s, red);
+      if (s[27] < 6.0) break;
+      if (tid == 0) {
+#pragma unroll
+        for (int i = 0; i < PNP_NSUM; ++i) s28[i] = s[i];                   // (through LDS: s[dynamic] would be scratch)
+        int q = 0;
+        double dmax = 0.0;
+        for (int i = 0; i < 6; ++i) {
+          for (int j = i; j < 6; ++j) { sm[i][j] = s28[q]; sm[j][i] = s28[q]; ++q; }
+          sm[i][6] = -s28[21 + i];
+          dmax = fmax(dmax, fabs(sm[i][i]));
+        }
+        // Gaussian elimination with partial pivoting, in LDS (dynamic indices must not become scratch)
+        int good = 1;
+        const double tiny = PNP_SINGULAR * dmax;
+        for (int c = 0; c < 6 && good; ++c) {
+          int pr = c;
+          double pv = fabs(sm[c][c]);
+          for (int i = c + 1; i < 6; ++i) {
+            const double v = fabs(sm[i][c]);
+            if (v > pv) { pv = v; pr = i; }
+          }
+          if (!(pv > tiny)) { good = 0; break; }
+          if (pr != c)
+            for (int j = c; j < 7; ++j) { const double tmp = sm[c][j]; sm[c][j] = sm[pr][j]; sm[pr][j] = tmp; }
+          const double ip = 1.0 / sm[c][c];
+          for (int i = c + 1; i < 6; ++i) {
+            const double fct = sm[i][c] * ip;
+            for (int j = c; j < 7; ++j) sm[i][j] -= fct * sm[c][j];
+          }
+        }
+        if (good) {
+          for (int i = 5; i >= 0; --i) {
+            double acc = sm[i][6];
+            for (int j = i + 1; j < 6; ++j) acc -= sm[i][j] * sm[j][6];
+            sm[i][6] = acc / sm[i][i];
+          }
+          const double w0 = sm[0][6], w1 = sm[1][6], w2 = sm[2][6], v0 = sm[3][6], v1 = sm[4][6], v2 = sm[5][6];
+          const double th2 = w0 * w0 + w1 * w1 + w2 * w2;
+          double A = 1.0, B = 0.5;
+          if (!(th2 < 1e-16)) {
+            const double th = sqrt(th2);
+            A = sin(th) / th;
+            B = (1.0 - cos(th)) / th2;
+          }
+          // E = I + A [w]x + B [w]x^2,  [w]x^2 = w w^T - |w|^2 I
+          const double E[9] = {1.0 + B * (w0 * w0 - th2), -A * w2 + B * w0 * w1, A * w1 + B * w0 * w2,
+                               A * w2 + B * w0 * w1, 1.0 + B * (w1 * w1 - th2), -A * w0 + B * w1 * w2,
+                               -A * w1 + B * w0 * w2, A * w0 + B * w1 * w2, 1.0 + B * (w2 * w2 - th2)};
+          const double vv[3] = {v0, v1, v2};
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+              const float v = (float)(E[i * 3] * R[j] + E[i * 3 + 1] * R[3 + j] + E[i * 3 + 2] * R[6 + j]);
+              if (!(fabsf(v) < 3e38f)) good = 0;
+              pose[i * 3 + j] = (double)v;
+            }
+            const float v = (float)(E[i * 3] * t[0] + E[i * 3 + 1] * t[1] + E[i * 3 + 2] * t[2] + vv[i]);
+            if (!(fabsf(v) < 3e38f)) good = 0;
+            pose[9 + i] = (double)v;
+          }
+        }
+        solved = good;
+      }
+      __syncthreads();
+      if (!solved) break;                                                   // a singular system keeps the previous pose
+#pragma unroll
+      for (int i = 0; i < 9; ++i) R[i] = pose[i];                           // (the next write of pose is behind hf_block_sum's barriers)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) t[i] = pose[9 + i];
+    }
+    double c1[1] = {0.0};
+    for (int k = tid; k < M; k += 256) {
+      double xa, xb, xc;
+      c1[0] += pnp_inlier(R, t, a, pnp_load(rec, k), thr2, xa, xb, xc) ? 1.0 : 0.0;
+    }
+    hf_block_sum<1>(c1, red);
+    total = (int)c1[0];
+    ok = total >= a.min_inliers;
+  }
+  if (ok && mask)                                                           // (the pack / gather kernel zeroed the mask)
+    for (int k = tid; k < M; k += 256) {
+      const PnpPair p = pnp_load(rec, k);
+      double xa, xb, xc;
+      if (pnp_inlier(R, t, a, p, thr2, xa, xb, xc)) mask[(size_t)f * mstride + p.row] = 1;
+    }
+  __syncthreads();
+  if (tid == 0) {                                                           // (through LDS: R[tid] would be scratch)
+#pragma unroll
+    for (int i = 0; i < 9; ++i) pose[i] = ok ? R[i] : 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) pose[9 + i] = ok ? t[i] : 0.0;
+    ninl[f] = ok ? total : 0;
+  }
+  __syncthreads();
+  if (tid < 9) Rout[f * 9 + tid] = (float)pose[tid];
+  if (tid < 3) tout[f * 3 + tid] = (float)pose[9 + tid];
+}
+
+// ---- landmarks of the key-frame bank ----------------------------------------------------------------------------------
+// rows i < count[slot] get (X, Y, Z, valid && finite ? 1 : 0), the rows behind the count (0, 0, 0, 0); grid ceil(rows / 256)
+__global__ __launch_bounds__(256) void pnp_landmarks_store_kernel(float4* __restrict__ lm, const int32_t* __restrict__ count,
+                                                                  int rows, int slot, const float* __restrict__ xyz,
+                                                                  const uint8_t* __restrict__ valid) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows) return;
+  const int cnt = hf_clamp(count[slot], rows);
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (i < cnt) {
+    v.x = xyz[3 * (size_t)i]; v.y = xyz[3 * (size_t)i + 1]; v.z = xyz[3 * (size_t)i + 2];
+    v.w = ((!valid || valid[i] != 0) && pnp_finite3(v.x, v.y, v.z)) ? 1.f : 0.f;
+  }
+  lm[(size_t)slot * rows + i] = v;
+}
+
+// grid (ceil(rows / 256), 1): slot `slot`; slot == -1, grid (ceil(rows / 256), slots): every slot
+__global__ __launch_bounds__(256) void pnp_landmarks_invalidate_kernel(float4* __restrict__ lm, int rows, int slot) {
+  const int i = blockIdx.x * 256 + threadIdx.x, s = slot >= 0 ? slot : (int)blockIdx.y;
+  if (i >= rows) return;
+  lm[(size_t)s * rows + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}

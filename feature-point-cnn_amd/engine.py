@@ -851,6 +851,130 @@ class Engine:
         """pose_bank_async, then host arrays (R [n,3,3], t [n,3], nfront [n], xyz [n,cap,3], front bool [n,cap])."""
         return self._host_pose(self.pose_bank_async(n, slot, match, F, K_query, K_train, points, **params))
 
+    # -- absolute pose from landmarks: RANSAC PnP (fpc_pnp_reserve / fpc_bank_*landmarks* / fpc_ransac_pnp / _frames / _bank) ----
+    def pnp_reserve(self):
+        """fpc_pnp_reserve: the PnP workspace (pair records, counts and best keys of max_batch problems); the only PnP call
+        that allocates.  Freed with the engine.  Returns the bytes it allocated."""
+        nbytes = ctypes.c_size_t(0)
+        _lib.check(self._l.fpc_pnp_reserve(self._ctx, ctypes.byref(nbytes)), "fpc_pnp_reserve")
+        return int(nbytes.value)
+
+    def bank_landmarks_reserve(self):
+        """fpc_bank_landmarks_reserve: one 3-D point per bank row (float4 [slots,rows], no row valid yet).  Freed with the
+        bank.  Returns the bytes it allocated (bank_info()["bytes"] is unchanged)."""
+        self._bank_info()
+        nbytes = ctypes.c_size_t(0)
+        _lib.check(self._l.fpc_bank_landmarks_reserve(self._ctx, ctypes.byref(nbytes)), "fpc_bank_landmarks_reserve")
+        return int(nbytes.value)
+
+    def bank_store_landmarks(self, slot, xyz, valid=None):
+        """fpc_bank_store_landmarks: the 3-D points of slot `slot`'s rows, in that key frame's camera frame: xyz float32
+        [k,3] and valid bool / uint8 [k] with k >= rows (device tensors -- `xyz[f]`, `front[f]` of pose_*_async go in as
+        they are -- or host arrays); valid=None: every row.  Call it AFTER the store that filled the slot, which
+        invalidates the slot's landmarks.  Does not synchronise."""
+        rows = self._bank_info().rows
+        xyz = torch.as_tensor(xyz).to(self.torch_device, torch.float32).contiguous()
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < rows:
+            raise ValueError("xyz must be [k,3] with k >= the bank's rows (%d)" % rows)
+        if valid is not None:
+            valid = torch.as_tensor(valid).to(self.torch_device)
+            valid = (valid.view(torch.uint8) if valid.dtype == torch.bool else valid.to(torch.uint8)).contiguous()
+            if valid.dim() != 1 or valid.shape[0] < rows:
+                raise ValueError("valid must be [k] with k >= the bank's rows (%d)" % rows)
+        self._call("fpc_bank_store_landmarks", int(slot), xyz, valid, inputs=(xyz, valid))
+
+    def bank_landmarks(self):
+        """float32 [slots,rows,4] aliasing the bank's landmark storage (fpc_bank_landmarks_get): (X, Y, Z, w), w = 1 valid
+        / 0."""
+        v = self._bank_info()
+        ptr = ctypes.c_void_p()
+        _lib.check(self._l.fpc_bank_landmarks_get(self._ctx, ctypes.byref(ptr)), "fpc_bank_landmarks_get")
+        lm = torch.as_tensor(_DevArray(ptr.value, v.slots * v.rows * 16), device=self.torch_device)
+        return lm.view(torch.float32).view(v.slots, v.rows, 4)
+
+    def _pnp_params(self, K, params):
+        p = _lib.FpcPnpParams()
+        _lib.check(self._l.fpc_default_pnp_params(ctypes.byref(p)), "fpc_default_pnp_params")
+        k = self._intrinsics(K, "K")
+        if k is not None:
+            p.fx, p.fy, p.cx, p.cy = k
+        for name, v in params.items():
+            if name not in ("iterations", "reproj_threshold", "seed", "refits", "min_inliers"):
+                raise TypeError("unknown PnP parameter %r" % (name,))
+            setattr(p, name, v)
+        return p
+
+    def _pnp_out(self, n, stride=None):
+        """Empty PnP outputs (R float32 [n,3,3], t float32 [n,3], ninliers int32 [n], mask uint8 [n,stride or cap])."""
+        rm, ni, mask = self._ransac_out(n, stride=stride)
+        return rm, torch.empty((n, 3), dtype=torch.float32, device=self.torch_device), ni, mask
+
+    def ransac_pnp_async(self, xy, xyz, npairs, K=None, **params):
+        """fpc_ransac_pnp: xy float32 [n,stride,2] pixels, xyz float32 [n,stride,3] points and npairs int32 [n] (device
+        tensors or host arrays) -> device tensors (R float32 [n,3,3] and t float32 [n,3] with X_cam = R X + t, ninliers
+        int32 [n], inlier bool [n,stride]); a failed frame is all zeros.  K: the camera as a 3 x 3 matrix or (fx, fy, cx,
+        cy).  Parameters: the other fields of fpc_pnp_params.  Needs pnp_reserve().  Does not synchronise."""
+        p = self._pnp_params(K, params)
+        xy = torch.as_tensor(xy).to(self.torch_device, torch.float32).contiguous()
+        xyz = torch.as_tensor(xyz).to(self.torch_device, torch.float32).contiguous()
+        npairs = torch.as_tensor(npairs).to(self.torch_device, torch.int32).contiguous()
+        if xy.dim() != 3 or xy.shape[2] != 2 or xyz.shape != (*xy.shape[:2], 3) or npairs.shape != (xy.shape[0],):
+            raise ValueError("xy must be [n,stride,2], xyz [n,stride,3] and npairs [n]")
+        n, stride = int(xy.shape[0]), int(xy.shape[1])
+        rm, tv, ni, mask = self._pnp_out(n, stride)
+        self._call("fpc_ransac_pnp", n, xy, xyz, npairs, stride, ctypes.byref(p), rm, tv, ni, mask, inputs=(xy, xyz, npairs))
+        return rm, tv, ni, mask.view(torch.bool)
+
+    def ransac_pnp(self, xy, xyz, npairs, K=None, **params):
+        """ransac_pnp_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,stride])."""
+        return self._host(self.ransac_pnp_async(xy, xyz, npairs, K, **params))
+
+    def pnp_frames_async(self, n, match, key_xyz, key_valid=None, K=None, **params):
+        """fpc_pnp_frames: the pairs (xy[f][i], key_xyz[match[f][i]]) of every frame of the last detect, `match` being
+        match_frames_async's table against the key frame whose rows' 3-D points are key_xyz (float32 [k,3], or a device
+        pair (xyz, count)) and key_valid (bool / uint8 [k], None: every row) -> device tensors (R [n,3,3], t [n,3],
+        ninliers [n], inlier bool [n,cap] by query row).  Does not synchronise."""
+        p = self._pnp_params(K, params)
+        if isinstance(key_xyz, tuple):
+            kx, kc = key_xyz
+        else:
+            kx = torch.as_tensor(key_xyz).to(self.torch_device, torch.float32).contiguous()
+            kc = torch.tensor([kx.shape[0]], dtype=torch.int32, device=self.torch_device)
+        if kx.device != self.torch_device or kx.dtype != torch.float32 or kx.dim() != 2 or kx.shape[1] != 3 \
+                or kc.device != self.torch_device or kc.dtype != torch.int32:
+            raise ValueError("key_xyz must be float32 [k,3], or device tensors (float32 [k,3], int32 [1])")
+        kx = kx.contiguous()
+        kv = None
+        if key_valid is not None:
+            kv = torch.as_tensor(key_valid).to(self.torch_device)
+            kv = (kv.view(torch.uint8) if kv.dtype == torch.bool else kv.to(torch.uint8)).contiguous()
+            if kv.dim() != 1 or kv.shape[0] < kx.shape[0]:
+                raise ValueError("key_valid must be [k]")
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        rm, tv, ni, mask = self._pnp_out(n)
+        self._call("fpc_pnp_frames", n, kx, kv, kc, match, ctypes.byref(p), rm, tv, ni, mask, inputs=(kx, kv, kc, match))
+        return rm, tv, ni, mask.view(torch.bool)
+
+    def pnp_frames(self, n, match, key_xyz, key_valid=None, K=None, **params):
+        """pnp_frames_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""
+        return self._host(self.pnp_frames_async(n, match, key_xyz, key_valid, K, **params))
+
+    def pnp_bank_async(self, n, slot, match, K=None, **params):
+        """fpc_pnp_bank: pnp_frames_async with frame f's landmarks taken from bank slot slot[f] (int32 [n], device; normally
+        match_bank_async's `best`) and `match` that call's table; a frame with slot -1, or a bank without landmarks, fails
+        (zeros).  Does not synchronise."""
+        self._bank_info()
+        p = self._pnp_params(K, params)
+        slot = self._dev_int32("slot", slot, "[n]", n)
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        rm, tv, ni, mask = self._pnp_out(n)
+        self._call("fpc_pnp_bank", n, slot, match, ctypes.byref(p), rm, tv, ni, mask, inputs=(slot, match))
+        return rm, tv, ni, mask.view(torch.bool)
+
+    def pnp_bank(self, n, slot, match, K=None, **params):
+        """pnp_bank_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""
+        return self._host(self.pnp_bank_async(n, slot, match, K, **params))
+
     # -- verified relocalisation: the k best slots per frame, each checked by RANSAC (fpc_*_bank_topk) ------------------
     def bank_topk_reserve(self, kmax):
         """fpc_bank_topk_reserve: workspace for up to `kmax` candidates per frame (1 <= kmax <= min(16, slots)); the only

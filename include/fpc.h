@@ -905,6 +905,110 @@ int fpc_pose_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* m
                   const fpc_pose_params* params, float* R_dev, float* t_dev, int32_t* nfront_dev, float* xyz_dev,
                   uint8_t* front_dev);
 
+/* --- absolute pose from bank landmarks: RANSAC perspective-n-point on the device ------------------------------------------
+ * fpc_pose_* ends in a translation DIRECTION: two views cannot give its scale, so every relocalisation comes back at a scale
+ * of its own.  The triangulated points it writes remove that limit.  They are indexed by the query row, which is the row
+ * order fpc_bank_store keeps for the same frame; once a stored key frame carries its 3-D points (landmarks), a later frame
+ * that matches that slot has 2-D <-> 3-D pairs, and perspective-n-point on those gives R and t at the map's scale from ONE
+ * view -- also where the baseline to the key frame is too short for an F.  fpc_ransac_pnp, fpc_pnp_frames and fpc_pnp_bank
+ * mirror fpc_ransac_fundamental, fpc_fundamental_frames and fpc_fundamental_bank: explicit pairs, the frames of the last
+ * detect against one key set, and those frames against bank slots.  OpenCV is not available to this build: the rule below
+ * is pinned by planted scenes and by a float64 restatement (tests/test_pnp_ransac.py), not against cv2.solvePnPRansac.
+ *  - Workspace: fpc_pnp_reserve allocates the pair records (with their mask rows), counts and best keys of max_batch
+ *    problems.  It is the only PnP call that allocates or synchronises; the allocation is its own (guard zones under
+ *    FPC_PLAN_GUARD_ZONES), freed by fpc_destroy; FPC_E_INVALID when a reservation exists.  It needs no bank and carves
+ *    nothing from the ctx slab: the plan hash, the packed size, fpc_bank_get().bytes and the RANSAC pair-list workspace stay
+ *    what they are.  `bytes` (may be NULL) gets the size.
+ *  - Landmarks: fpc_bank_landmarks_reserve (needs a bank; FPC_E_INVALID when a reservation exists) allocates float4
+ *    [slots][rows], zeroed so that no row is valid, with the same guard zones; fpc_bank_destroy and fpc_destroy free it.
+ *    fpc_bank_store_landmarks(slot, xyz_dev float32 [rows][3], valid_dev uint8 [rows] or NULL = every row valid): rows
+ *    i < count[slot] (read on the device) get (X, Y, Z, valid && all three finite ? 1 : 0), rows behind the count get four
+ *    zeros.  Only the first `rows` rows of either array are read, and rows <= capacity, so `xyz + f * cap * 3` and
+ *    `front + f * cap` of a fpc_pose_* call go in unchanged, right behind fpc_bank_store(f, slot): the strides are
+ *    compatible.  The landmarks are in THAT key frame's camera frame, at the scale the caller gave them.
+ *    fpc_bank_landmarks_get returns the storage (float4 [slots][rows], w = 1 valid / 0).  With a reservation alive,
+ *    fpc_bank_store, fpc_bank_store_rows and fpc_bank_clear invalidate (zero) the landmarks of the slots they touch with
+ *    one more small launch, so that old points never attach to new rows: store the landmarks AFTER the rows.  Without a
+ *    reservation those calls do exactly what they did.
+ *  - Pairs.  Explicit: pair k < npairs[f] (clamped to [0, stride]) is (xy[f][k], xyz[f][k]); xy_dev float32 [n][stride][2],
+ *    xyz_dev float32 [n][stride][3].  Frames and bank: for query row i < count[f] with 0 <= j = match[f][i] < the train
+ *    count and landmark j valid, the pair is (xy[f][i], landmark[j]), in ascending i.  For fpc_pnp_frames the landmarks are
+ *    key_xyz_dev float32 [nkey][3], nkey_dev[0] clamped to the capacity, and landmark j is valid when key_valid_dev[j] != 0
+ *    (NULL: every row) and its three coordinates are finite -- the rule of fpc_bank_store_landmarks.  fpc_pnp_frames knows
+ *    FPC_PAIR_KEY only (a predecessor frame has no landmarks), so it has no pairing argument.  A bank slot outside
+ *    [0, slots), or a bank without landmark storage, leaves the frame without pairs.  The mask inlier_dev (may be NULL) is
+ *    uint8 [n][stride] indexed by the pair (explicit) or [n][capacity] indexed by the query row (frames, bank).
+ *  - Convention: X_cam = R X + t with det R = +1, and the pixel of X_cam = (X_c, Y_c, Z_c) is (fx X_c / Z_c + cx,
+ *    fy Y_c / Z_c + cy): FROM the landmark frame INTO the query camera.  This is the INVERSE direction of fpc_pose_*'s
+ *    X_train = R X_query + t.  R_dev float32 [n][9] row-major, t_dev float32 [n][3].
+ *  - Inliers: with (a, b, c) = R X + t in fp64 from the returned fp32 R and t, a pair is an inlier when c > 0 and
+ *    (fx a - (x - cx) c)^2 + (fy b - (y - cy) c)^2 < reproj_threshold^2 c^2.  ninliers and the mask are those of the
+ *    returned pose.
+ *  - Sampling: mix() as above with a budget of 32 draws: r = mix(seed ^ mix((f * 4096 + t) * 32 + k)) % M; the first 6
+ *    distinct indices are the sample, in that order; a hypothesis that has not found 6 within its 32 draws is degenerate.
+ *  - Minimal solve (6-point DLT), in fp64: image points go to x^ = (x - cx) / fx, y^ = (y - cy) / fy; the six landmarks are
+ *    translated to their centroid and scaled to an RMS distance of sqrt(3) (a mean squared distance that is not > 0 or not
+ *    finite is degenerate).  The 11 x 12 system has the rows [X Y Z 1 0 0 0 0 -x^X -x^Y -x^Z -x^] and
+ *    [0 0 0 0 X Y Z 1 -y^X -y^Y -y^Z -y^] of points 0 .. 4 (rows 2i, 2i + 1) and the first row only of point 5.  It is
+ *    reduced by Gaussian elimination with FULL pivoting with the tie rules of the 8-point solve, and the null vector comes
+ *    from back-substitution with the last column's unknown set to 1.  A last pivot below 1e-10 of the first, or a
+ *    non-finite result, makes the sample degenerate.  P (3 x 4, row-major) is denormalised to the landmarks' own
+ *    coordinates: P = Pn [s I, -s m; 0 1], m the centroid and s the scale.
+ *  - Scoring: P_px = K P is scaled to max |p| = 1, oriented so that w = p3 . (X, 1) > 0 at the sample's first pair
+ *    (evaluated in fp64 before rounding), and rounded to fp32.  Hypothesis t counts the pairs with, in fp32 (fmaf, the
+ *    products added in the order X, Y, Z onto the fourth column), w = p3 . (X, 1) > 0 and
+ *    (p1 . (X, 1) - x w)^2 + (p2 . (X, 1) - y w)^2 < (thr w)^2.  The raw projective camera is scored, as the raw minimal F
+ *    and H are; only the winner is made a pose.  Selection: the largest count; ties go to the lower t.
+ *  - Best sample -> pose (fp64): re-derive P = [A | a4] in normalised image coordinates, negated if det A < 0.  A^T A is
+ *    diagonalised by the cyclic Jacobi of the fundamental section at N = 3: A^T A = V diag(lambda) V^T.  The frame fails
+ *    unless lambda_min > 1e-12 lambda_max.  R = A V diag(lambda^-1/2) V^T, sigma = (sqrt(lambda0) + sqrt(lambda1) +
+ *    sqrt(lambda2)) / 3, t = a4 / sigma; both rounded to fp32.
+ *  - Refit, `refits` times, one Gauss-Newton step each, in fp64: over the inliers of the current fp32 (R, t), with
+ *    X_c = R X + t = (a, b, c), u = a / c, v = b / c: residuals r = (fx (u - x^), fy (v - y^)); left perturbation
+ *    X_c <- X_c + omega x X_c + upsilon, unknowns xi = (omega, upsilon), so that the rows of J are
+ *        fx [-uv, 1 + u^2, -v, 1/c, 0, -u/c],      fy [-(1 + v^2), uv, u, 0, 1/c, -v/c].
+ *    The 21 distinct sums of J^T J and the 6 of J^T r are accumulated in a fixed order (no floating-point atomics).  SIGN:
+ *    the step solves (J^T J) xi = -J^T r and is applied as it is: R <- E R, t <- E t + upsilon, with
+ *    E = I + A [omega]x + B [omega]x^2, A = sin(theta) / theta, B = (1 - cos(theta)) / theta^2, theta = |omega| (A = 1,
+ *    B = 1/2 when theta^2 < 1e-16).  The system is solved by Gaussian elimination with partial pivoting; a pivot not above
+ *    1e-14 of the largest diagonal entry of J^T J makes it singular.  R and t are rounded to fp32.  Fewer than 6 inliers, a
+ *    singular system or a non-finite result keeps the previous pose and ends the refits.
+ *  - Failure: a frame with fewer than 6 pairs, with no non-degenerate sample, with a failed rank test, or with fewer than
+ *    min_inliers inliers after the last refit gets nine zeros, three zeros, ninliers = 0 and an all-zero mask.
+ *  - Caveat: coplanar landmarks leave the DLT at rank < 11.  A slot whose valid landmarks all lie on one plane fails, just
+ *    as an exact-homography scene fails the fundamental calls.
+ *  - Determinism, execution: as for the fundamental calls.  The three entry points give bit-identical outputs on equal pair
+ *    lists, and fpc_pnp_bank is bit-identical to fpc_pnp_frames with that slot's landmarks at the SAME frame index.
+ *    Everything but the two reserve calls is asynchronous on the ctx stream: no host synchronisation, no device-to-host
+ *    copy, no allocation; every count and slot is read on the device.  fpc_detect, fpc_match_bank, fpc_pnp_bank needs no
+ *    host call in between.
+ * FPC_E_INVALID (nothing is written): everything the fundamental twins refuse for the arguments they share; no PnP
+ * reservation; NULL params, R_dev, t_dev or ninliers_dev; fx or fy not > 0 or a non-finite intrinsic; iterations outside
+ * 1 .. 4096; reproj_threshold not > 0 (or not below 1e18); refits outside 0 .. 4; min_inliers < 6.  Landmark calls: no bank,
+ * no landmark reservation (store, get), a slot outside [0, slots), a NULL xyz_dev.  fpc_pnp_frames: a NULL key_xyz_dev or
+ * nkey_dev. */
+typedef struct fpc_pnp_params {
+  float fx, fy, cx, cy;      /* query camera, pixels; fx, fy > 0                                                          */
+  int iterations;            /* 1 .. 4096                                                                                 */
+  float reproj_threshold;    /* px, > 0                                                                                   */
+  uint32_t seed;
+  int refits;                /* 0 .. 4 Gauss-Newton steps on the inlier set                                               */
+  int min_inliers;           /* >= 6                                                                                      */
+} fpc_pnp_params;
+/* fx = fy = 500, centre (320, 240), 1024 iterations, 3.0 px, seed 0, 4 refits, 12 inliers */
+int fpc_default_pnp_params(fpc_pnp_params* params);
+int fpc_pnp_reserve(fpc_ctx* ctx, size_t* bytes);
+int fpc_bank_landmarks_reserve(fpc_ctx* ctx, size_t* bytes);
+int fpc_bank_store_landmarks(fpc_ctx* ctx, int slot, const float* xyz_dev, const uint8_t* valid_dev);
+int fpc_bank_landmarks_get(fpc_ctx* ctx, const float** xyzw_dev);
+int fpc_ransac_pnp(fpc_ctx* ctx, int n, const float* xy_dev, const float* xyz_dev, const int32_t* npairs_dev, int stride,
+                   const fpc_pnp_params* params, float* R_dev, float* t_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
+int fpc_pnp_frames(fpc_ctx* ctx, int n, const float* key_xyz_dev, const uint8_t* key_valid_dev, const int32_t* nkey_dev,
+                   const int32_t* match_dev, const fpc_pnp_params* params, float* R_dev, float* t_dev,
+                   int32_t* ninliers_dev, uint8_t* inlier_dev);
+int fpc_pnp_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const fpc_pnp_params* params,
+                 float* R_dev, float* t_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
