@@ -3971,87 +3971,116 @@ int fpc_default_ransac_params(fpc_ransac_params* p) {
   return FPC_OK;
 }
 
-static bool ransac_params_ok(const fpc_ransac_params* p) {
-  return p && p->iterations >= 1 && p->iterations <= HF_MAX_ITERATIONS && p->reproj_threshold > 0.f &&
-         p->reproj_threshold < 1e18f && p->refits >= 0 && p->refits <= 4 && p->min_inliers >= 4;
+// ---- the geometry chain's host path (include/fpc.h): every call below is a pair list -- explicit pairs, the frames' match
+// ---- table, or a match table against bank slots -- and its family's solver step behind it ------------------------------------
+// field checks of the parameter structs (a NaN fails its comparison: refused); sample: the floor of min_inliers
+static bool threshold_ok(float thr) { return thr > 0.f && thr < 1e18f; }
+static bool camera_ok(float fx, float fy, float cx, float cy) {
+  return std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy) && fx > 0.f && fy > 0.f;
+}
+static bool ransac_fields_ok(int iterations, float thr, int refits, int min_inliers, int sample) {
+  return iterations >= 1 && iterations <= HF_MAX_ITERATIONS && threshold_ok(thr) && refits >= 0 && refits <= 4 &&
+         min_inliers >= sample;
+}
+static bool ransac_params_ok(const fpc_ransac_params* p, int sample = 4) {
+  return p && ransac_fields_ok(p->iterations, p->reproj_threshold, p->refits, p->min_inliers, sample);
 }
 
-static HfArgs ransac_args(fpc_ctx* c, int n, const fpc_ransac_params* p) {
+// what the pair sources refuse (the PnP calls, whose records and kernels are their own, use these too), and every call's tail
+static bool explicit_ok(const fpc_ctx* c, int n, int stride) { return !(n < 1 || n > c->B || stride < 1 || stride > c->cap); }
+static bool bank_ok(const fpc_ctx* c, int n, const int32_t* slot, const int32_t* match) {
+  return c->bank_slab && slot && match && frames_ok(c, n);
+}
+static int launched() { HIPCHECK(hipGetLastError()); return FPC_OK; }
+
+// An HfArgs on the pair-list workspace: the context's, one problem per frame; with per_frame = k the top-K reservation's,
+// whose n problems are k per frame.  ransac_args adds the RANSAC parameters; the pose calls need none.
+static HfArgs hf_args(const fpc_ctx* c, int n, float thr, int per_frame = 0) {
   HfArgs a{};
-  a.pairs = c->hf_pairs; a.row = c->hf_row; a.np = c->hf_np; a.best = c->hf_best;
-  a.cap = c->cap; a.n = n;
-  a.T = p->iterations; a.refits = p->refits; a.min_inliers = p->min_inliers;
-  a.thr = p->reproj_threshold; a.seed = p->seed;
+  a.pairs = per_frame ? c->topk_pairs : c->hf_pairs; a.row = per_frame ? c->topk_row : c->hf_row;
+  a.np = per_frame ? c->topk_np : c->hf_np; a.best = per_frame ? c->topk_best : c->hf_best;
+  a.cap = c->cap; a.n = n; a.thr = thr; a.per_frame = per_frame;
+  return a;
+}
+static HfArgs ransac_args(const fpc_ctx* c, int n, const fpc_ransac_params* p, int per_frame = 0) {
+  HfArgs a = hf_args(c, n, p->reproj_threshold, per_frame);
+  a.T = p->iterations; a.refits = p->refits; a.min_inliers = p->min_inliers; a.seed = p->seed;
   return a;
 }
 
-// the kernels both entry points share, behind their pack / gather kernel
-static void ransac_launch(fpc_ctx* c, const HfArgs& a, float* H, int32_t* ninliers, uint8_t* inlier, int mstride) {
+// The pair list of a's a.n problems, one helper per source: it checks the source's arguments, selects the device and
+// launches the kernel that fills a's workspace.  mask (the caller's inlier rows, zeroed here) may be NULL: the pose calls.
+static int pairs_explicit(fpc_ctx* c, const HfArgs& a, const float* src_xy, const float* dst_xy, const int32_t* npairs,
+                          int stride, uint8_t* mask) {
+  if (!src_xy || !dst_xy || !npairs || !explicit_ok(c, a.n, stride)) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(hf_pack_kernel, dim3((stride + 255) / 256, a.n), dim3(256), 0, c->stream, a, src_xy, dst_xy, npairs,
+                     stride, mask);
+  return FPC_OK;
+}
+static int pairs_gather(fpc_ctx* c, const HfArgs& a, int pairing, const int32_t* key_xy, const int32_t* nkey,
+                        const int32_t* match, uint8_t* mask, const HfBank& bank = {}) {
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(hf_gather_kernel, dim3(a.n), dim3(256), 0, c->stream, a, c->xy, c->count, pairing, key_xy, nkey, match,
+                     mask, bank);
+  return FPC_OK;
+}
+static int pairs_frames(fpc_ctx* c, const HfArgs& a, int pairing, const int32_t* key_xy, const int32_t* nkey,
+                        const int32_t* match, uint8_t* mask) {
+  if (!match || !pairing_ok(pairing) || !frames_ok(c, a.n) || (pairing == FPC_PAIR_KEY && !key_xy) || (key_xy && !nkey))
+    return FPC_E_INVALID;
+  return pairs_gather(c, a, pairing, key_xy, nkey, match, mask);     // (no bank: its HfBank is all null)
+}
+// (n frames; slot and match hold a.n entries: one per frame, or per_frame of them -- fpc_homography_bank_topk)
+static int pairs_bank(fpc_ctx* c, const HfArgs& a, int n, const int32_t* slot, const int32_t* match, uint8_t* mask) {
+  if (!bank_ok(c, n, slot, match)) return FPC_E_INVALID;
+  return pairs_gather(c, a, (int)FPC_PAIR_KEY, c->bank.xy, nullptr, match, mask,
+                      HfBank{slot, c->bank.count, c->bank.rows, c->bank.slots});
+}
+
+// ---- RANSAC homographies and fundamental matrices (kernels in ransac_homography.h and ransac_fundamental.h): one pack /
+// ---- gather kernel, pair record and workspace for both; the 8-point sample needs 8 inliers at the least ------------------------
+static int ransac_launch(fpc_ctx* c, const HfArgs& a, float* H, int32_t* ninliers, uint8_t* inlier, int mstride) {
   hipLaunchKernelGGL(ransac_score_kernel, dim3((a.T + 255) / 256, a.n), dim3(256), 0, c->stream, a);
   hipLaunchKernelGGL(ransac_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, H, ninliers, inlier, mstride);
+  return launched();
+}
+static int fundamental_launch(fpc_ctx* c, const HfArgs& a, float* F, int32_t* ninliers, uint8_t* inlier, int mstride) {
+  hipLaunchKernelGGL(fm_score_kernel, dim3((a.T + FM_THREADS - 1) / FM_THREADS, a.n), dim3(FM_THREADS), 0, c->stream, a);
+  hipLaunchKernelGGL(fm_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, F, ninliers, inlier, mstride);
+  return launched();
 }
 
 int fpc_ransac_homography(fpc_ctx* c, int n, const float* src_xy, const float* dst_xy, const int32_t* npairs, int stride,
                           const fpc_ransac_params* p, float* H, int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !src_xy || !dst_xy || !npairs || !H || !ninliers || !ransac_params_ok(p)) return FPC_E_INVALID;
-  if (n < 1 || n > c->B || stride < 1 || stride > c->cap) return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
+  if (!c || !H || !ninliers || !ransac_params_ok(p)) return FPC_E_INVALID;
   const HfArgs a = ransac_args(c, n, p);
-  hipLaunchKernelGGL(hf_pack_kernel, dim3((stride + 255) / 256, n), dim3(256), 0, c->stream, a, src_xy, dst_xy, npairs,
-                     stride, inlier);
-  ransac_launch(c, a, H, ninliers, inlier, stride);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  if (int rc = pairs_explicit(c, a, src_xy, dst_xy, npairs, stride, inlier)) return rc;
+  return ransac_launch(c, a, H, ninliers, inlier, stride);
 }
 
 int fpc_homography_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy, const int32_t* nkey, const int32_t* match,
                           const fpc_ransac_params* p, float* H, int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !match || !H || !ninliers || !ransac_params_ok(p) || !pairing_ok(pairing) || !frames_ok(c, n) ||
-      (pairing == FPC_PAIR_KEY && !key_xy) || (key_xy && !nkey))
-    return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
+  if (!c || !H || !ninliers || !ransac_params_ok(p)) return FPC_E_INVALID;
   const HfArgs a = ransac_args(c, n, p);
-  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, pairing, key_xy, nkey, match,
-                     inlier, HfBank{});
-  ransac_launch(c, a, H, ninliers, inlier, c->cap);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
-}
-
-// ---- RANSAC fundamental matrices (include/fpc.h; kernels in ransac_fundamental.h) -----------------------------------------
-// The homography calls' pack / gather kernels, pair records and workspace; the 8-point sample needs 8 inliers at the least.
-static bool fundamental_params_ok(const fpc_ransac_params* p) { return ransac_params_ok(p) && p->min_inliers >= FM_SAMPLE; }
-
-static void fundamental_launch(fpc_ctx* c, const HfArgs& a, float* F, int32_t* ninliers, uint8_t* inlier, int mstride) {
-  hipLaunchKernelGGL(fm_score_kernel, dim3((a.T + FM_THREADS - 1) / FM_THREADS, a.n), dim3(FM_THREADS), 0, c->stream, a);
-  hipLaunchKernelGGL(fm_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, F, ninliers, inlier, mstride);
+  if (int rc = pairs_frames(c, a, pairing, key_xy, nkey, match, inlier)) return rc;
+  return ransac_launch(c, a, H, ninliers, inlier, c->cap);
 }
 
 int fpc_ransac_fundamental(fpc_ctx* c, int n, const float* src_xy, const float* dst_xy, const int32_t* npairs, int stride,
                            const fpc_ransac_params* p, float* F, int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !src_xy || !dst_xy || !npairs || !F || !ninliers || !fundamental_params_ok(p)) return FPC_E_INVALID;
-  if (n < 1 || n > c->B || stride < 1 || stride > c->cap) return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
+  if (!c || !F || !ninliers || !ransac_params_ok(p, FM_SAMPLE)) return FPC_E_INVALID;
   const HfArgs a = ransac_args(c, n, p);
-  hipLaunchKernelGGL(hf_pack_kernel, dim3((stride + 255) / 256, n), dim3(256), 0, c->stream, a, src_xy, dst_xy, npairs,
-                     stride, inlier);
-  fundamental_launch(c, a, F, ninliers, inlier, stride);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  if (int rc = pairs_explicit(c, a, src_xy, dst_xy, npairs, stride, inlier)) return rc;
+  return fundamental_launch(c, a, F, ninliers, inlier, stride);
 }
 
 int fpc_fundamental_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy, const int32_t* nkey, const int32_t* match,
                            const fpc_ransac_params* p, float* F, int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !match || !F || !ninliers || !fundamental_params_ok(p) || !pairing_ok(pairing) || !frames_ok(c, n) ||
-      (pairing == FPC_PAIR_KEY && !key_xy) || (key_xy && !nkey))
-    return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
+  if (!c || !F || !ninliers || !ransac_params_ok(p, FM_SAMPLE)) return FPC_E_INVALID;
   const HfArgs a = ransac_args(c, n, p);
-  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, pairing, key_xy, nkey, match,
-                     inlier, HfBank{});
-  fundamental_launch(c, a, F, ninliers, inlier, c->cap);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  if (int rc = pairs_frames(c, a, pairing, key_xy, nkey, match, inlier)) return rc;
+  return fundamental_launch(c, a, F, ninliers, inlier, c->cap);
 }
 
 // ---- key-frame bank (include/fpc.h; kernels in match_bank.h) -------------------------------------------------------------
@@ -4270,30 +4299,18 @@ int fpc_match_bank(fpc_ctx* c, int n, int cross_check, float max_dist, float rat
 
 int fpc_homography_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const fpc_ransac_params* p, float* H,
                         int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !c->bank_slab || !slot || !match || !H || !ninliers || !ransac_params_ok(p) || !frames_ok(c, n))
-    return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
+  if (!c || !H || !ninliers || !ransac_params_ok(p)) return FPC_E_INVALID;
   const HfArgs a = ransac_args(c, n, p);
-  const HfBank hb{slot, c->bank.count, c->bank.rows, c->bank.slots};
-  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
-                     (const int32_t*)nullptr, match, inlier, hb);
-  ransac_launch(c, a, H, ninliers, inlier, c->cap);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  if (int rc = pairs_bank(c, a, n, slot, match, inlier)) return rc;
+  return ransac_launch(c, a, H, ninliers, inlier, c->cap);
 }
 
 int fpc_fundamental_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const fpc_ransac_params* p, float* F,
                          int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !c->bank_slab || !slot || !match || !F || !ninliers || !fundamental_params_ok(p) || !frames_ok(c, n))
-    return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
+  if (!c || !F || !ninliers || !ransac_params_ok(p, FM_SAMPLE)) return FPC_E_INVALID;
   const HfArgs a = ransac_args(c, n, p);
-  const HfBank hb{slot, c->bank.count, c->bank.rows, c->bank.slots};
-  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
-                     (const int32_t*)nullptr, match, inlier, hb);
-  fundamental_launch(c, a, F, ninliers, inlier, c->cap);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  if (int rc = pairs_bank(c, a, n, slot, match, inlier)) return rc;
+  return fundamental_launch(c, a, F, ninliers, inlier, c->cap);
 }
 
 // ---- relative pose from a fundamental matrix (include/fpc.h; kernel in pose_epipolar.h) ------------------------------------
@@ -4310,70 +4327,42 @@ int fpc_default_pose_params(fpc_pose_params* p) {
 }
 
 static bool pose_params_ok(const fpc_pose_params* p) {
-  if (!p) return false;
-  const float k[8] = {p->q_fx, p->q_fy, p->q_cx, p->q_cy, p->t_fx, p->t_fy, p->t_cx, p->t_cy};
-  for (float v : k)
-    if (!std::isfinite(v)) return false;
-  return p->q_fx > 0.f && p->q_fy > 0.f && p->t_fx > 0.f && p->t_fy > 0.f && p->reproj_threshold > 0.f &&
-         p->reproj_threshold < 1e18f && p->min_front >= 1;
+  return p && camera_ok(p->q_fx, p->q_fy, p->q_cx, p->q_cy) && camera_ok(p->t_fx, p->t_fy, p->t_cx, p->t_cy) &&
+         threshold_ok(p->reproj_threshold) && p->min_front >= 1;
 }
 
-static HfArgs pose_args(fpc_ctx* c, int n, const fpc_pose_params* p) {
-  HfArgs a{};
-  a.pairs = c->hf_pairs; a.row = c->hf_row; a.np = c->hf_np; a.best = c->hf_best;
-  a.cap = c->cap; a.n = n;
-  a.thr = p->reproj_threshold;
-  return a;
-}
-
-// the kernel the three entry points share, behind their pack / gather kernel
-static void pose_launch(fpc_ctx* c, const HfArgs& a, const fpc_pose_params* p, const float* F, float* R, float* t,
-                        int32_t* nfront, float* xyz, uint8_t* front, int ostride) {
+// the solver step behind the pair list (a: hf_args with the parameters' threshold, nothing of RANSAC's)
+static int pose_launch(fpc_ctx* c, const HfArgs& a, const fpc_pose_params* p, const float* F, float* R, float* t,
+                       int32_t* nfront, float* xyz, uint8_t* front, int ostride) {
   const PoseArgs pa{p->q_fx, p->q_fy, p->q_cx, p->q_cy, p->t_fx, p->t_fy, p->t_cx, p->t_cy, p->min_front};
   hipLaunchKernelGGL(pose_kernel, dim3(a.n), dim3(256), 0, c->stream, a, pa, F, R, t, nfront, xyz, front, ostride);
+  return launched();
 }
 
 int fpc_pose_fundamental(fpc_ctx* c, int n, const float* src_xy, const float* dst_xy, const int32_t* npairs, int stride,
                          const float* F, const fpc_pose_params* p, float* R, float* t, int32_t* nfront, float* xyz,
                          uint8_t* front) {
-  if (!c || !src_xy || !dst_xy || !npairs || !F || !R || !t || !nfront || !pose_params_ok(p)) return FPC_E_INVALID;
-  if (n < 1 || n > c->B || stride < 1 || stride > c->cap) return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
-  const HfArgs a = pose_args(c, n, p);
-  hipLaunchKernelGGL(hf_pack_kernel, dim3((stride + 255) / 256, n), dim3(256), 0, c->stream, a, src_xy, dst_xy, npairs,
-                     stride, (uint8_t*)nullptr);
-  pose_launch(c, a, p, F, R, t, nfront, xyz, front, stride);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  if (!c || !F || !R || !t || !nfront || !pose_params_ok(p)) return FPC_E_INVALID;
+  const HfArgs a = hf_args(c, n, p->reproj_threshold);
+  if (int rc = pairs_explicit(c, a, src_xy, dst_xy, npairs, stride, nullptr)) return rc;
+  return pose_launch(c, a, p, F, R, t, nfront, xyz, front, stride);
 }
 
 int fpc_pose_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy, const int32_t* nkey, const int32_t* match,
                     const float* F, const fpc_pose_params* p, float* R, float* t, int32_t* nfront, float* xyz,
                     uint8_t* front) {
-  if (!c || !match || !F || !R || !t || !nfront || !pose_params_ok(p) || !pairing_ok(pairing) || !frames_ok(c, n) ||
-      (pairing == FPC_PAIR_KEY && !key_xy) || (key_xy && !nkey))
-    return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
-  const HfArgs a = pose_args(c, n, p);
-  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, pairing, key_xy, nkey, match,
-                     (uint8_t*)nullptr, HfBank{});
-  pose_launch(c, a, p, F, R, t, nfront, xyz, front, c->cap);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  if (!c || !F || !R || !t || !nfront || !pose_params_ok(p)) return FPC_E_INVALID;
+  const HfArgs a = hf_args(c, n, p->reproj_threshold);
+  if (int rc = pairs_frames(c, a, pairing, key_xy, nkey, match, nullptr)) return rc;
+  return pose_launch(c, a, p, F, R, t, nfront, xyz, front, c->cap);
 }
 
 int fpc_pose_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const float* F, const fpc_pose_params* p,
                   float* R, float* t, int32_t* nfront, float* xyz, uint8_t* front) {
-  if (!c || !c->bank_slab || !slot || !match || !F || !R || !t || !nfront || !pose_params_ok(p) || !frames_ok(c, n))
-    return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
-  const HfArgs a = pose_args(c, n, p);
-  const HfBank hb{slot, c->bank.count, c->bank.rows, c->bank.slots};
-  hipLaunchKernelGGL(hf_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
-                     (const int32_t*)nullptr, match, (uint8_t*)nullptr, hb);
-  pose_launch(c, a, p, F, R, t, nfront, xyz, front, c->cap);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  if (!c || !F || !R || !t || !nfront || !pose_params_ok(p)) return FPC_E_INVALID;
+  const HfArgs a = hf_args(c, n, p->reproj_threshold);
+  if (int rc = pairs_bank(c, a, n, slot, match, nullptr)) return rc;
+  return pose_launch(c, a, p, F, R, t, nfront, xyz, front, c->cap);
 }
 
 // ---- absolute pose from bank landmarks: RANSAC PnP (include/fpc.h; kernels in pnp_ransac.h) ------------------------------------
@@ -4391,12 +4380,8 @@ int fpc_default_pnp_params(fpc_pnp_params* p) {
 }
 
 static bool pnp_params_ok(const fpc_pnp_params* p) {
-  if (!p) return false;
-  const float k[4] = {p->fx, p->fy, p->cx, p->cy};
-  for (float v : k)
-    if (!std::isfinite(v)) return false;
-  return p->fx > 0.f && p->fy > 0.f && p->iterations >= 1 && p->iterations <= HF_MAX_ITERATIONS && p->reproj_threshold > 0.f &&
-         p->reproj_threshold < 1e18f && p->refits >= 0 && p->refits <= 4 && p->min_inliers >= PNP_SAMPLE;
+  return p && camera_ok(p->fx, p->fy, p->cx, p->cy) &&
+         ransac_fields_ok(p->iterations, p->reproj_threshold, p->refits, p->min_inliers, PNP_SAMPLE);
 }
 
 // The only PnP call that allocates or synchronises: pair records, counts and best keys of max_batch problems, an allocation
@@ -4463,49 +4448,46 @@ static PnpArgs pnp_args(fpc_ctx* c, int n, const fpc_pnp_params* p) {
   return a;
 }
 
-// the kernels the three entry points share, behind their pack / gather kernel
-static void pnp_launch(fpc_ctx* c, const PnpArgs& a, float* R, float* t, int32_t* ninliers, uint8_t* inlier, int mstride) {
+// the solver step behind the pair list
+static int pnp_launch(fpc_ctx* c, const PnpArgs& a, float* R, float* t, int32_t* ninliers, uint8_t* inlier, int mstride) {
   hipLaunchKernelGGL(pnp_score_kernel, dim3((a.T + PNP_THREADS - 1) / PNP_THREADS, a.n), dim3(PNP_THREADS), 0, c->stream, a);
   hipLaunchKernelGGL(pnp_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, R, t, ninliers, inlier, mstride);
+  return launched();
+}
+
+// fpc_pnp_frames / fpc_pnp_bank: the gather kernel over either train set, then the solver
+static int pnp_gather(fpc_ctx* c, int n, const PnpTrain& tr, const int32_t* match, const fpc_pnp_params* p, float* R, float* t,
+                      int32_t* ninliers, uint8_t* inlier) {
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const PnpArgs a = pnp_args(c, n, p);
+  hipLaunchKernelGGL(pnp_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, match, inlier, tr);
+  return pnp_launch(c, a, R, t, ninliers, inlier, c->cap);
 }
 
 int fpc_ransac_pnp(fpc_ctx* c, int n, const float* xy, const float* xyz, const int32_t* npairs, int stride,
                    const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !c->pnp_slab || !xy || !xyz || !npairs || !R || !t || !ninliers || !pnp_params_ok(p)) return FPC_E_INVALID;
-  if (n < 1 || n > c->B || stride < 1 || stride > c->cap) return FPC_E_INVALID;
+  if (!c || !c->pnp_slab || !xy || !xyz || !npairs || !R || !t || !ninliers || !pnp_params_ok(p) || !explicit_ok(c, n, stride))
+    return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
   const PnpArgs a = pnp_args(c, n, p);
   hipLaunchKernelGGL(pnp_pack_kernel, dim3((stride + 255) / 256, n), dim3(256), 0, c->stream, a, xy, xyz, npairs, stride, inlier);
-  pnp_launch(c, a, R, t, ninliers, inlier, stride);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  return pnp_launch(c, a, R, t, ninliers, inlier, stride);
 }
 
 int fpc_pnp_frames(fpc_ctx* c, int n, const float* key_xyz, const uint8_t* key_valid, const int32_t* nkey, const int32_t* match,
                    const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
   if (!c || !c->pnp_slab || !key_xyz || !nkey || !match || !R || !t || !ninliers || !pnp_params_ok(p) || !frames_ok(c, n))
     return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
-  const PnpArgs a = pnp_args(c, n, p);
-  const PnpTrain tr{key_xyz, key_valid, nkey, nullptr, nullptr, nullptr, 0, 0};
-  hipLaunchKernelGGL(pnp_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, match, inlier, tr);
-  pnp_launch(c, a, R, t, ninliers, inlier, c->cap);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  return pnp_gather(c, n, PnpTrain{key_xyz, key_valid, nkey, nullptr, nullptr, nullptr, 0, 0}, match, p, R, t, ninliers, inlier);
 }
 
 int fpc_pnp_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const fpc_pnp_params* p, float* R, float* t,
                  int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !c->pnp_slab || !c->bank_slab || !slot || !match || !R || !t || !ninliers || !pnp_params_ok(p) || !frames_ok(c, n))
+  if (!c || !c->pnp_slab || !R || !t || !ninliers || !pnp_params_ok(p) || !bank_ok(c, n, slot, match))
     return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
-  const PnpArgs a = pnp_args(c, n, p);
   // (without landmark storage lm is null: no frame has pairs)
-  const PnpTrain tr{nullptr, nullptr, nullptr, slot, c->lm_xyzw, c->bank.count, c->bank.rows, c->bank.slots};
-  hipLaunchKernelGGL(pnp_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, match, inlier, tr);
-  pnp_launch(c, a, R, t, ninliers, inlier, c->cap);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  return pnp_gather(c, n, PnpTrain{nullptr, nullptr, nullptr, slot, c->lm_xyzw, c->bank.count, c->bank.rows, c->bank.slots},
+                    match, p, R, t, ninliers, inlier);
 }
 
 // ---- top-K candidates of the bank, each verified by RANSAC (include/fpc.h; kernels in match_bank_topk.h) -------------------
@@ -4575,22 +4557,15 @@ int fpc_match_bank_topk(fpc_ctx* c, int n, int k, int cross_check, float max_dis
 int fpc_homography_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot, const int32_t* match,
                              const fpc_ransac_params* p, float* H, int32_t* ninliers, uint8_t* inlier, int32_t* pick,
                              int32_t* best) {
-  if (!c || !c->bank_slab || !c->topk_slab || !cand_slot || !match || !H || !ninliers || !ransac_params_ok(p) || k < 1 ||
-      k > c->topk.kmax || !frames_ok(c, n))
+  if (!c || !H || !ninliers || !ransac_params_ok(p) || !c->topk_slab || k < 1 || k > c->topk.kmax || !frames_ok(c, n))
     return FPC_E_INVALID;
-  HIPCHECK(hipSetDevice(c->cfg.device));
   // n k problems on the reserved workspace: problem f k + j is frame f against slot cand_slot[f][j] with match[f][j]
-  HfArgs a = ransac_args(c, n * k, p);
-  a.pairs = c->topk_pairs; a.row = c->topk_row; a.np = c->topk_np; a.best = c->topk_best;
-  a.per_frame = k;
-  const HfBank hb{cand_slot, c->bank.count, c->bank.rows, c->bank.slots};
-  hipLaunchKernelGGL(hf_gather_kernel, dim3(n * k), dim3(256), 0, c->stream, a, c->xy, c->count, (int)FPC_PAIR_KEY, c->bank.xy,
-                     (const int32_t*)nullptr, match, inlier, hb);
-  ransac_launch(c, a, H, ninliers, inlier, c->cap);
+  const HfArgs a = ransac_args(c, n * k, p, k);
+  if (int rc = pairs_bank(c, a, n, cand_slot, match, inlier)) return rc;
+  if (int rc = ransac_launch(c, a, H, ninliers, inlier, c->cap)) return rc;
   if (pick || best)
     hipLaunchKernelGGL(bank_pick_kernel, dim3(n), dim3(64), 0, c->stream, ninliers, cand_slot, k, pick, best);
-  HIPCHECK(hipGetLastError());
-  return FPC_OK;
+  return launched();
 }
 
 // ---- guided matching: plain, cell-ordered and epipolar (include/fpc.h; two strip skeletons and two gates in match_guided.h,

@@ -54,21 +54,9 @@ __device__ __forceinline__ bool pnp_finite3(float X, float Y, float Z) {
   return fabsf(X) <= 3.402823466e38f && fabsf(Y) <= 3.402823466e38f && fabsf(Z) <= 3.402823466e38f;   // (false for NaN)
 }
 
-// the sampler of include/fpc.h: the first 6 distinct of 32 draws (selects, not an indexed store: that becomes scratch)
+// the sampler of include/fpc.h: the first 6 distinct of 32 draws
 __device__ __forceinline__ bool pnp_sample(uint32_t seed, uint32_t f, uint32_t t, uint32_t M, uint32_t (&idx)[PNP_SAMPLE]) {
-#pragma unroll
-  for (int j = 0; j < PNP_SAMPLE; ++j) idx[j] = M;
-  int got = 0;
-  for (uint32_t k = 0; k < (uint32_t)PNP_DRAWS && got < PNP_SAMPLE; ++k) {
-    const uint32_t r = hf_mix(seed ^ hf_mix((f * (uint32_t)HF_MAX_ITERATIONS + t) * (uint32_t)PNP_DRAWS + k)) % M;
-    bool fresh = true;
-#pragma unroll
-    for (int j = 0; j < PNP_SAMPLE; ++j) fresh = fresh && r != idx[j];
-#pragma unroll
-    for (int j = 0; j < PNP_SAMPLE; ++j) idx[j] = (fresh && got == j) ? r : idx[j];
-    got += fresh ? 1 : 0;
-  }
-  return got == PNP_SAMPLE;
+  return hf_sample_distinct<PNP_SAMPLE, PNP_DRAWS>(seed, f, t, M, idx);
 }
 
 // The 6-point DLT.  sys: this thread's 11 x 12 system, element (r, c) at sys[(r * 12 + c) * S] (LDS).  Image points in

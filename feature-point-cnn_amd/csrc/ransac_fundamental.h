@@ -22,21 +22,9 @@ constexpr double FM_PIVOT = 1e-10;    // last pivot / first pivot below which a 
 constexpr int FM_SWEEPS = 10;         // cyclic Jacobi sweeps
 constexpr int FM_NSUM = 36;
 
-// the sampler of include/fpc.h: the first 8 distinct of 32 draws (selects, not an indexed store: that becomes scratch)
+// the sampler of include/fpc.h: the first 8 distinct of 32 draws
 __device__ __forceinline__ bool fm_sample(uint32_t seed, uint32_t f, uint32_t t, uint32_t M, uint32_t (&idx)[FM_SAMPLE]) {
-#pragma unroll
-  for (int j = 0; j < FM_SAMPLE; ++j) idx[j] = M;
-  int got = 0;
-  for (uint32_t k = 0; k < (uint32_t)FM_DRAWS && got < FM_SAMPLE; ++k) {
-    const uint32_t r = hf_mix(seed ^ hf_mix((f * (uint32_t)HF_MAX_ITERATIONS + t) * (uint32_t)FM_DRAWS + k)) % M;
-    bool fresh = true;
-#pragma unroll
-    for (int j = 0; j < FM_SAMPLE; ++j) fresh = fresh && r != idx[j];
-#pragma unroll
-    for (int j = 0; j < FM_SAMPLE; ++j) idx[j] = (fresh && got == j) ? r : idx[j];
-    got += fresh ? 1 : 0;
-  }
-  return got == FM_SAMPLE;
+  return hf_sample_distinct<FM_SAMPLE, FM_DRAWS>(seed, f, t, M, idx);
 }
 
 // Hartley normalisation of one side: centroid and the scale that brings the RMS distance to sqrt(2)

@@ -65,6 +65,24 @@ __device__ __forceinline__ bool hf_sample(uint32_t seed, uint32_t f, uint32_t t,
   }
   return got == 4;
 }
+// ... and of the 8-point (fundamental) and 6-point (PnP) solvers: the first N distinct of DRAWS draws (selects, not an indexed
+// store: that becomes scratch)
+template <int N, int DRAWS>
+__device__ __forceinline__ bool hf_sample_distinct(uint32_t seed, uint32_t f, uint32_t t, uint32_t M, uint32_t (&idx)[N]) {
+#pragma unroll
+  for (int j = 0; j < N; ++j) idx[j] = M;
+  int got = 0;
+  for (uint32_t k = 0; k < (uint32_t)DRAWS && got < N; ++k) {
+    const uint32_t r = hf_mix(seed ^ hf_mix((f * (uint32_t)HF_MAX_ITERATIONS + t) * (uint32_t)DRAWS + k)) % M;
+    bool fresh = true;
+#pragma unroll
+    for (int j = 0; j < N; ++j) fresh = fresh && r != idx[j];
+#pragma unroll
+    for (int j = 0; j < N; ++j) idx[j] = (fresh && got == j) ? r : idx[j];
+    got += fresh ? 1 : 0;
+  }
+  return got == N;
+}
 
 struct HfV3 { double x, y, z; };
 __device__ __forceinline__ HfV3 hf_cross(const HfV3& a, const HfV3& b) {

@@ -474,7 +474,12 @@ class Engine:
 
     def _host(self, tensors):
         self.sync()
-        return tuple(t.cpu().numpy() for t in tensors)
+        return tuple(None if t is None else t.cpu().numpy() for t in tensors)
+
+    def _dev_uint8(self, t):
+        """A bool / integer mask (device tensor or host array) as a contiguous uint8 device tensor."""
+        t = torch.as_tensor(t).to(self.torch_device)
+        return (t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)).contiguous()
 
     def _per_frame(self, n, m, d):
         m, d = self._host((m, d))
@@ -530,14 +535,53 @@ class Engine:
         with torch.cuda.stream(self.torch_stream()):
             return self._points_view()[0][f].clone()
 
-    def _ransac_params(self, params):
-        p = _lib.FpcRansacParams()
-        _lib.check(self._l.fpc_default_ransac_params(ctypes.byref(p)), "fpc_default_ransac_params")
+    # -- what the geometry wrappers are made of: a parameter struct, one of three pair sources, a solver call ----------------
+    _RANSAC_FIELDS = ("iterations", "reproj_threshold", "seed", "refits", "min_inliers")
+
+    def _params(self, struct, default, fields, word, params):
+        """A `struct` filled by fpc_<default> and then from `params`, whose keys must be among `fields`; `word` names the
+        family in the TypeError."""
+        p = struct()
+        _lib.check(getattr(self._l, default)(ctypes.byref(p)), default)
         for k, v in params.items():
-            if k not in ("iterations", "reproj_threshold", "seed", "refits", "min_inliers"):
-                raise TypeError("unknown RANSAC parameter %r" % (k,))
+            if k not in fields:
+                raise TypeError("unknown %s parameter %r" % (word, k))
             setattr(p, k, v)
         return p
+
+    def _ransac_params(self, params):
+        return self._params(_lib.FpcRansacParams, "fpc_default_ransac_params", self._RANSAC_FIELDS, "RANSAC", params)
+
+    def _explicit_pairs(self, a, b, npairs, width=2, text="src and dst must be [n,stride,2] and npairs [n]"):
+        """Explicit pairs on the device: a float32 [n,stride,2], b float32 [n,stride,width], npairs int32 [n] -> (n, the
+        calls' arguments (a, b, npairs, stride))."""
+        a = torch.as_tensor(a).to(self.torch_device, torch.float32).contiguous()
+        b = torch.as_tensor(b).to(self.torch_device, torch.float32).contiguous()
+        npairs = torch.as_tensor(npairs).to(self.torch_device, torch.int32).contiguous()
+        if a.dim() != 3 or a.shape[2] != 2 or b.shape != (*a.shape[:2], width) or npairs.shape != (a.shape[0],):
+            raise ValueError(text)
+        return int(a.shape[0]), (a, b, npairs, int(a.shape[1]))
+
+    def _frames_pairs(self, n, pairing, key_xy, match, fill, *args):
+        """The frames' pair source -> (fill(*args), the calls' arguments (pairing, key_xy, its device count, match)).
+        `fill` makes the call's parameter struct, between the pairing's check and the key's as it always was."""
+        pair = self._pairing(pairing)
+        p = fill(*args)
+        kx, kc = self._key_xy(key_xy)
+        return p, (pair, kx, kc, self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity))
+
+    def _bank_pairs(self, n, slot, match, fill, *args):
+        """The bank's pair source -> (fill(*args), the calls' arguments (slot, match)); `fill` as in _frames_pairs, behind
+        the check that a bank exists."""
+        self._bank_info()
+        p = fill(*args)
+        slot = self._dev_int32("slot", slot, "[n]", n)
+        return p, (slot, self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity))
+
+    def _solve(self, name, n, pairs, p, out, *more):
+        """fpc_<name>(ctx, n, *pairs, *more, params, *out) -> out, its last tensor (a uint8 mask, or None) as bool."""
+        self._call(name, n, *pairs, *more, ctypes.byref(p), *out, inputs=(*pairs, *more))
+        return (*out[:-1], None if out[-1] is None else out[-1].view(torch.bool))
 
     def _key_xy(self, key_xy):
         """key_xy -> (xy int32 [k,2], device count) or (None, None).  An (xy, count) pair of device tensors is used as it
@@ -561,16 +605,8 @@ class Engine:
         device tensors (H float32 [n,3,3] mapping src to dst with H[2,2] = 1, ninliers int32 [n], inlier bool [n,stride]);
         a failed frame has H = 0 and no inliers.  Parameters: the fields of fpc_ransac_params.  Does not synchronise."""
         p = self._ransac_params(params)
-        src = torch.as_tensor(src).to(self.torch_device, torch.float32).contiguous()
-        dst = torch.as_tensor(dst).to(self.torch_device, torch.float32).contiguous()
-        npairs = torch.as_tensor(npairs).to(self.torch_device, torch.int32).contiguous()
-        if src.dim() != 3 or src.shape[2] != 2 or dst.shape != src.shape or npairs.shape != (src.shape[0],):
-            raise ValueError("src and dst must be [n,stride,2] and npairs [n]")
-        n, stride = int(src.shape[0]), int(src.shape[1])
-        hm, ni, mask = self._ransac_out(n, stride=stride)
-        self._call("fpc_ransac_homography", n, src, dst, npairs, stride, ctypes.byref(p), hm, ni, mask,
-                   inputs=(src, dst, npairs))
-        return hm, ni, mask.view(torch.bool)
+        n, pairs = self._explicit_pairs(src, dst, npairs)
+        return self._solve("fpc_ransac_homography", n, pairs, p, self._ransac_out(n, stride=pairs[3]))
 
     def ransac_homography(self, src, dst, npairs, **params):
         """ransac_homography_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,stride])."""
@@ -581,13 +617,8 @@ class Engine:
         being match_frames_async's table (int32 [n,cap], device) for the same pairing and key, `key_xy` the key frame's
         coordinates (keep_frame_points) -> device tensors (H [n,3,3], ninliers [n], inlier bool [n,cap] by query row).
         Does not synchronise."""
-        pair = self._pairing(pairing)
-        p = self._ransac_params(params)
-        kx, kc = self._key_xy(key_xy)
-        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
-        hm, ni, mask = self._ransac_out(n)
-        self._call("fpc_homography_frames", n, pair, kx, kc, match, ctypes.byref(p), hm, ni, mask, inputs=(match, kx, kc))
-        return hm, ni, mask.view(torch.bool)
+        p, pairs = self._frames_pairs(n, pairing, key_xy, match, self._ransac_params, params)
+        return self._solve("fpc_homography_frames", n, pairs, p, self._ransac_out(n))
 
     def homography_frames(self, n, match, key_xy=None, pairing="key", **params):
         """homography_frames_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,cap])."""
@@ -684,13 +715,8 @@ class Engine:
         """fpc_homography_bank: homography_frames_async with frame f's key coordinates taken from bank slot slot[f] (int32
         [n], device; normally match_bank_async's `best`) and `match` that call's table -> device tensors (H [n,3,3],
         ninliers [n], inlier bool [n,cap]); a frame with slot -1 fails (H = 0).  Does not synchronise."""
-        self._bank_info()
-        p = self._ransac_params(params)
-        slot = self._dev_int32("slot", slot, "[n]", n)
-        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
-        hm, ni, mask = self._ransac_out(n)
-        self._call("fpc_homography_bank", n, slot, match, ctypes.byref(p), hm, ni, mask, inputs=(slot, match))
-        return hm, ni, mask.view(torch.bool)
+        p, pairs = self._bank_pairs(n, slot, match, self._ransac_params, params)
+        return self._solve("fpc_homography_bank", n, pairs, p, self._ransac_out(n))
 
     def homography_bank(self, n, slot, match, **params):
         """homography_bank_async, then host arrays (H [n,3,3], ninliers [n], inlier bool [n,cap])."""
@@ -703,16 +729,8 @@ class Engine:
         inlier bool [n,stride], the pairs within reproj_threshold in Sampson distance); a failed frame has F = 0 and no
         inliers.  min_inliers must be >= 8.  Does not synchronise."""
         p = self._ransac_params(params)
-        src = torch.as_tensor(src).to(self.torch_device, torch.float32).contiguous()
-        dst = torch.as_tensor(dst).to(self.torch_device, torch.float32).contiguous()
-        npairs = torch.as_tensor(npairs).to(self.torch_device, torch.int32).contiguous()
-        if src.dim() != 3 or src.shape[2] != 2 or dst.shape != src.shape or npairs.shape != (src.shape[0],):
-            raise ValueError("src and dst must be [n,stride,2] and npairs [n]")
-        n, stride = int(src.shape[0]), int(src.shape[1])
-        fm, ni, mask = self._ransac_out(n, stride=stride)
-        self._call("fpc_ransac_fundamental", n, src, dst, npairs, stride, ctypes.byref(p), fm, ni, mask,
-                   inputs=(src, dst, npairs))
-        return fm, ni, mask.view(torch.bool)
+        n, pairs = self._explicit_pairs(src, dst, npairs)
+        return self._solve("fpc_ransac_fundamental", n, pairs, p, self._ransac_out(n, stride=pairs[3]))
 
     def ransac_fundamental(self, src, dst, npairs, **params):
         """ransac_fundamental_async, then host arrays (F [n,3,3], ninliers [n], inlier bool [n,stride])."""
@@ -721,13 +739,8 @@ class Engine:
     def fundamental_frames_async(self, n, match, key_xy=None, pairing="key", **params):
         """fpc_fundamental_frames: homography_frames_async's arguments and pairs -> device tensors (F [n,3,3], ninliers
         [n], inlier bool [n,cap] by query row).  Does not synchronise."""
-        pair = self._pairing(pairing)
-        p = self._ransac_params(params)
-        kx, kc = self._key_xy(key_xy)
-        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
-        fm, ni, mask = self._ransac_out(n)
-        self._call("fpc_fundamental_frames", n, pair, kx, kc, match, ctypes.byref(p), fm, ni, mask, inputs=(match, kx, kc))
-        return fm, ni, mask.view(torch.bool)
+        p, pairs = self._frames_pairs(n, pairing, key_xy, match, self._ransac_params, params)
+        return self._solve("fpc_fundamental_frames", n, pairs, p, self._ransac_out(n))
 
     def fundamental_frames(self, n, match, key_xy=None, pairing="key", **params):
         """fundamental_frames_async, then host arrays (F [n,3,3], ninliers [n], inlier bool [n,cap])."""
@@ -737,13 +750,8 @@ class Engine:
         """fpc_fundamental_bank: fundamental_frames_async with frame f's key coordinates taken from bank slot slot[f], as
         homography_bank_async -> device tensors (F [n,3,3], ninliers [n], inlier bool [n,cap]); a frame with slot -1
         fails (F = 0).  Does not synchronise."""
-        self._bank_info()
-        p = self._ransac_params(params)
-        slot = self._dev_int32("slot", slot, "[n]", n)
-        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
-        fm, ni, mask = self._ransac_out(n)
-        self._call("fpc_fundamental_bank", n, slot, match, ctypes.byref(p), fm, ni, mask, inputs=(slot, match))
-        return fm, ni, mask.view(torch.bool)
+        p, pairs = self._bank_pairs(n, slot, match, self._ransac_params, params)
+        return self._solve("fpc_fundamental_bank", n, pairs, p, self._ransac_out(n))
 
     def fundamental_bank(self, n, slot, match, **params):
         """fundamental_bank_async, then host arrays (F [n,3,3], ninliers [n], inlier bool [n,cap])."""
@@ -765,16 +773,12 @@ class Engine:
         raise ValueError("%s must be a 3 x 3 matrix or (fx, fy, cx, cy)" % name)
 
     def _pose_params(self, K_query, K_train, params):
-        p = _lib.FpcPoseParams()
-        _lib.check(self._l.fpc_default_pose_params(ctypes.byref(p)), "fpc_default_pose_params")
-        for side, k in (("q", self._intrinsics(K_query, "K_query")), ("t", self._intrinsics(K_train, "K_train"))):
+        cameras = (("q", self._intrinsics(K_query, "K_query")), ("t", self._intrinsics(K_train, "K_train")))
+        p = self._params(_lib.FpcPoseParams, "fpc_default_pose_params", ("reproj_threshold", "min_front"), "pose", params)
+        for side, k in cameras:
             if k is not None:
                 for field, v in zip(("fx", "fy", "cx", "cy"), k):
                     setattr(p, "%s_%s" % (side, field), v)
-        for k, v in params.items():
-            if k not in ("reproj_threshold", "min_front"):
-                raise TypeError("unknown pose parameter %r" % (k,))
-            setattr(p, k, v)
         return p
 
     def _pose_out(self, n, stride, points):
@@ -786,13 +790,9 @@ class Engine:
         front = torch.empty((n, stride), dtype=torch.uint8, device=dev) if points else None
         return rm, tv, self._int32(n), xyz, front
 
-    @staticmethod
-    def _pose_result(rm, tv, nf, xyz, front):
-        return rm, tv, nf, xyz, None if front is None else front.view(torch.bool)
-
-    def _host_pose(self, out):
-        self.sync()
-        return tuple(None if t is None else t.cpu().numpy() for t in out)
+    def _pose(self, name, n, pairs, F, p, stride, points):
+        """fpc_<name> behind its pair source: F [n,3,3] goes in front of the parameters."""
+        return self._solve(name, n, pairs, p, self._pose_out(n, stride, points), self._guided_h(n, F, "F"))
 
     def pose_fundamental_async(self, src, dst, npairs, F, K_query=None, K_train=None, points=True, **params):
         """fpc_pose_fundamental: ransac_fundamental_async's pairs and the F it returned (device [n,3,3] as it is, or a host
@@ -802,54 +802,33 @@ class Engine:
         matrices or (fx, fy, cx, cy).  Parameters: reproj_threshold, min_front.  A failed frame is all zeros.  Does not
         synchronise."""
         p = self._pose_params(K_query, K_train, params)
-        src = torch.as_tensor(src).to(self.torch_device, torch.float32).contiguous()
-        dst = torch.as_tensor(dst).to(self.torch_device, torch.float32).contiguous()
-        npairs = torch.as_tensor(npairs).to(self.torch_device, torch.int32).contiguous()
-        if src.dim() != 3 or src.shape[2] != 2 or dst.shape != src.shape or npairs.shape != (src.shape[0],):
-            raise ValueError("src and dst must be [n,stride,2] and npairs [n]")
-        n, stride = int(src.shape[0]), int(src.shape[1])
-        fm = self._guided_h(n, F, "F")
-        out = self._pose_out(n, stride, points)
-        self._call("fpc_pose_fundamental", n, src, dst, npairs, stride, fm, ctypes.byref(p), *out,
-                   inputs=(src, dst, npairs, fm))
-        return self._pose_result(*out)
+        n, pairs = self._explicit_pairs(src, dst, npairs)
+        return self._pose("fpc_pose_fundamental", n, pairs, F, p, pairs[3], points)
 
     def pose_fundamental(self, src, dst, npairs, F, K_query=None, K_train=None, points=True, **params):
         """pose_fundamental_async, then host arrays (R [n,3,3], t [n,3], nfront [n], xyz [n,stride,3], front bool
         [n,stride])."""
-        return self._host_pose(self.pose_fundamental_async(src, dst, npairs, F, K_query, K_train, points, **params))
+        return self._host(self.pose_fundamental_async(src, dst, npairs, F, K_query, K_train, points, **params))
 
     def pose_frames_async(self, n, match, F, key_xy=None, pairing="key", K_query=None, K_train=None, points=True, **params):
         """fpc_pose_frames: fundamental_frames_async's arguments, pairs and output F -> device tensors (R [n,3,3], t [n,3],
         nfront [n], xyz [n,cap,3] and front bool [n,cap] by query row).  Does not synchronise."""
-        pair = self._pairing(pairing)
-        p = self._pose_params(K_query, K_train, params)
-        kx, kc = self._key_xy(key_xy)
-        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
-        fm = self._guided_h(n, F, "F")
-        out = self._pose_out(n, self.capacity, points)
-        self._call("fpc_pose_frames", n, pair, kx, kc, match, fm, ctypes.byref(p), *out, inputs=(match, kx, kc, fm))
-        return self._pose_result(*out)
+        p, pairs = self._frames_pairs(n, pairing, key_xy, match, self._pose_params, K_query, K_train, params)
+        return self._pose("fpc_pose_frames", n, pairs, F, p, self.capacity, points)
 
     def pose_frames(self, n, match, F, key_xy=None, pairing="key", K_query=None, K_train=None, points=True, **params):
         """pose_frames_async, then host arrays (R [n,3,3], t [n,3], nfront [n], xyz [n,cap,3], front bool [n,cap])."""
-        return self._host_pose(self.pose_frames_async(n, match, F, key_xy, pairing, K_query, K_train, points, **params))
+        return self._host(self.pose_frames_async(n, match, F, key_xy, pairing, K_query, K_train, points, **params))
 
     def pose_bank_async(self, n, slot, match, F, K_query=None, K_train=None, points=True, **params):
         """fpc_pose_bank: pose_frames_async with frame f's key coordinates taken from bank slot slot[f], as
         fundamental_bank_async, and F that call's output; a frame with slot -1 fails (zeros).  Does not synchronise."""
-        self._bank_info()
-        p = self._pose_params(K_query, K_train, params)
-        slot = self._dev_int32("slot", slot, "[n]", n)
-        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
-        fm = self._guided_h(n, F, "F")
-        out = self._pose_out(n, self.capacity, points)
-        self._call("fpc_pose_bank", n, slot, match, fm, ctypes.byref(p), *out, inputs=(slot, match, fm))
-        return self._pose_result(*out)
+        p, pairs = self._bank_pairs(n, slot, match, self._pose_params, K_query, K_train, params)
+        return self._pose("fpc_pose_bank", n, pairs, F, p, self.capacity, points)
 
     def pose_bank(self, n, slot, match, F, K_query=None, K_train=None, points=True, **params):
         """pose_bank_async, then host arrays (R [n,3,3], t [n,3], nfront [n], xyz [n,cap,3], front bool [n,cap])."""
-        return self._host_pose(self.pose_bank_async(n, slot, match, F, K_query, K_train, points, **params))
+        return self._host(self.pose_bank_async(n, slot, match, F, K_query, K_train, points, **params))
 
     # -- absolute pose from landmarks: RANSAC PnP (fpc_pnp_reserve / fpc_bank_*landmarks* / fpc_ransac_pnp / _frames / _bank) ----
     def pnp_reserve(self):
@@ -877,8 +856,7 @@ class Engine:
         if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < rows:
             raise ValueError("xyz must be [k,3] with k >= the bank's rows (%d)" % rows)
         if valid is not None:
-            valid = torch.as_tensor(valid).to(self.torch_device)
-            valid = (valid.view(torch.uint8) if valid.dtype == torch.bool else valid.to(torch.uint8)).contiguous()
+            valid = self._dev_uint8(valid)
             if valid.dim() != 1 or valid.shape[0] < rows:
                 raise ValueError("valid must be [k] with k >= the bank's rows (%d)" % rows)
         self._call("fpc_bank_store_landmarks", int(slot), xyz, valid, inputs=(xyz, valid))
@@ -893,15 +871,10 @@ class Engine:
         return lm.view(torch.float32).view(v.slots, v.rows, 4)
 
     def _pnp_params(self, K, params):
-        p = _lib.FpcPnpParams()
-        _lib.check(self._l.fpc_default_pnp_params(ctypes.byref(p)), "fpc_default_pnp_params")
         k = self._intrinsics(K, "K")
+        p = self._params(_lib.FpcPnpParams, "fpc_default_pnp_params", self._RANSAC_FIELDS, "PnP", params)
         if k is not None:
             p.fx, p.fy, p.cx, p.cy = k
-        for name, v in params.items():
-            if name not in ("iterations", "reproj_threshold", "seed", "refits", "min_inliers"):
-                raise TypeError("unknown PnP parameter %r" % (name,))
-            setattr(p, name, v)
         return p
 
     def _pnp_out(self, n, stride=None):
@@ -915,15 +888,8 @@ class Engine:
         int32 [n], inlier bool [n,stride]); a failed frame is all zeros.  K: the camera as a 3 x 3 matrix or (fx, fy, cx,
         cy).  Parameters: the other fields of fpc_pnp_params.  Needs pnp_reserve().  Does not synchronise."""
         p = self._pnp_params(K, params)
-        xy = torch.as_tensor(xy).to(self.torch_device, torch.float32).contiguous()
-        xyz = torch.as_tensor(xyz).to(self.torch_device, torch.float32).contiguous()
-        npairs = torch.as_tensor(npairs).to(self.torch_device, torch.int32).contiguous()
-        if xy.dim() != 3 or xy.shape[2] != 2 or xyz.shape != (*xy.shape[:2], 3) or npairs.shape != (xy.shape[0],):
-            raise ValueError("xy must be [n,stride,2], xyz [n,stride,3] and npairs [n]")
-        n, stride = int(xy.shape[0]), int(xy.shape[1])
-        rm, tv, ni, mask = self._pnp_out(n, stride)
-        self._call("fpc_ransac_pnp", n, xy, xyz, npairs, stride, ctypes.byref(p), rm, tv, ni, mask, inputs=(xy, xyz, npairs))
-        return rm, tv, ni, mask.view(torch.bool)
+        n, pairs = self._explicit_pairs(xy, xyz, npairs, 3, "xy must be [n,stride,2], xyz [n,stride,3] and npairs [n]")
+        return self._solve("fpc_ransac_pnp", n, pairs, p, self._pnp_out(n, pairs[3]))
 
     def ransac_pnp(self, xy, xyz, npairs, K=None, **params):
         """ransac_pnp_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,stride])."""
@@ -946,14 +912,11 @@ class Engine:
         kx = kx.contiguous()
         kv = None
         if key_valid is not None:
-            kv = torch.as_tensor(key_valid).to(self.torch_device)
-            kv = (kv.view(torch.uint8) if kv.dtype == torch.bool else kv.to(torch.uint8)).contiguous()
+            kv = self._dev_uint8(key_valid)
             if kv.dim() != 1 or kv.shape[0] < kx.shape[0]:
                 raise ValueError("key_valid must be [k]")
         match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
-        rm, tv, ni, mask = self._pnp_out(n)
-        self._call("fpc_pnp_frames", n, kx, kv, kc, match, ctypes.byref(p), rm, tv, ni, mask, inputs=(kx, kv, kc, match))
-        return rm, tv, ni, mask.view(torch.bool)
+        return self._solve("fpc_pnp_frames", n, (kx, kv, kc, match), p, self._pnp_out(n))
 
     def pnp_frames(self, n, match, key_xyz, key_valid=None, K=None, **params):
         """pnp_frames_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""
@@ -963,13 +926,8 @@ class Engine:
         """fpc_pnp_bank: pnp_frames_async with frame f's landmarks taken from bank slot slot[f] (int32 [n], device; normally
         match_bank_async's `best`) and `match` that call's table; a frame with slot -1, or a bank without landmarks, fails
         (zeros).  Does not synchronise."""
-        self._bank_info()
-        p = self._pnp_params(K, params)
-        slot = self._dev_int32("slot", slot, "[n]", n)
-        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
-        rm, tv, ni, mask = self._pnp_out(n)
-        self._call("fpc_pnp_bank", n, slot, match, ctypes.byref(p), rm, tv, ni, mask, inputs=(slot, match))
-        return rm, tv, ni, mask.view(torch.bool)
+        p, pairs = self._bank_pairs(n, slot, match, self._pnp_params, K, params)
+        return self._solve("fpc_pnp_bank", n, pairs, p, self._pnp_out(n))
 
     def pnp_bank(self, n, slot, match, K=None, **params):
         """pnp_bank_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""

@@ -332,6 +332,7 @@ def test_bad_arguments_are_refused(qvga):
     src = torch.zeros((N, cap, 2), dtype=torch.float32, device=dev)
     npairs = torch.full((N,), 10, dtype=torch.int32, device=dev)
     match = torch.full((N, cap), -1, dtype=torch.int32, device=dev)
+    slot = torch.zeros((N,), dtype=torch.int32, device=dev)
     key_pts = e.keep_frame_points(0)
     one = torch.ones((1,), dtype=torch.int32, device=dev)
     hm = torch.full((N, 9), 7.0, dtype=torch.float32, device=dev)
@@ -339,7 +340,7 @@ def test_bad_arguments_are_refused(qvga):
     mask = torch.full((N, cap), 7, dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()
     sp, np_, mp, kp, op = src.data_ptr(), npairs.data_ptr(), match.data_ptr(), key_pts.data_ptr(), one.data_ptr()
-    hp, ip, kp_mask = hm.data_ptr(), ni.data_ptr(), mask.data_ptr()
+    hp, ip, kp_mask, lp = hm.data_ptr(), ni.data_ptr(), mask.data_ptr(), slot.data_ptr()
 
     def params(**kw):
         p = _lib.FpcRansacParams()
@@ -349,6 +350,7 @@ def test_bad_arguments_are_refused(qvga):
         return ctypes.byref(p)
     rh = lambda n, s, d, c, stride, p, h, i: lib.fpc_ransac_homography(e._ctx, n, s, d, c, stride, p, h, i, kp_mask)   # noqa: E731
     hf = lambda n, pairing, k, kc, m, p, h, i: lib.fpc_homography_frames(e._ctx, n, pairing, k, kc, m, p, h, i, kp_mask)   # noqa: E731
+    hb = lambda n, s, m, p, h, i: lib.fpc_homography_bank(e._ctx, n, s, m, p, h, i, kp_mask)   # noqa: E731
     ok = params()
     bad = [params(iterations=0), params(iterations=4097), params(reproj_threshold=0.0), params(reproj_threshold=-1.0),
            params(reproj_threshold=float("nan")), params(refits=-1), params(refits=5), params(min_inliers=3), None]
@@ -372,6 +374,19 @@ def test_bad_arguments_are_refused(qvga):
     assert hf(N, 0, kp, op, mp, ok, hp, None) == FPC_E_INVALID
     assert hf(0, 0, kp, op, mp, ok, hp, ip) == FPC_E_INVALID
     assert hf(N + 1, 0, kp, op, mp, ok, hp, ip) == FPC_E_INVALID
+    assert hb(N, lp, mp, ok, hp, ip) == FPC_E_INVALID                               # no bank
+    e.bank_create(2, cap)
+    try:
+        for p in bad:
+            assert hb(N, lp, mp, p, hp, ip) == FPC_E_INVALID
+        assert hb(N, None, mp, ok, hp, ip) == FPC_E_INVALID
+        assert hb(N, lp, None, ok, hp, ip) == FPC_E_INVALID
+        assert hb(N, lp, mp, ok, None, ip) == FPC_E_INVALID
+        assert hb(N, lp, mp, ok, hp, None) == FPC_E_INVALID
+        assert hb(0, lp, mp, ok, hp, ip) == FPC_E_INVALID
+        assert hb(N + 1, lp, mp, ok, hp, ip) == FPC_E_INVALID
+    finally:
+        e.bank_destroy()
     e.sync()
     e.detect(synth.make_batch(300, 2, H, W))                                        # a detect of fewer frames bounds n
     assert hf(3, 0, kp, op, mp, ok, hp, ip) == FPC_E_INVALID
