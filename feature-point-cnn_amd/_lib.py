@@ -27,7 +27,7 @@ SYMBOLS = [
     "fpc_get_counts", "fpc_get_keypoints", "fpc_set_timing", "fpc_get_timings", "fpc_match", "fpc_first_within",
     "fpc_detect_u8", "fpc_u8_staging", "fpc_homography_adaptation", "fpc_detect_u8_resized",
     "fpc_sample_descriptors", "fpc_plan_hash", "fpc_broadcast_weights", "fpc_read_activation",
-    "fpc_pack_layout_revision", "fpc_check_guards", "fpc_stream_report", "fpc_output_range",
+    "fpc_pack_layout_revision", "fpc_tile_choice", "fpc_check_guards", "fpc_stream_report", "fpc_output_range",
     "fpc_match_frames", "fpc_first_within_frames",
     "fpc_default_ransac_params", "fpc_ransac_homography", "fpc_homography_frames",
     "fpc_bank_create", "fpc_bank_destroy", "fpc_bank_get", "fpc_bank_store", "fpc_bank_store_rows", "fpc_bank_clear",
@@ -52,6 +52,7 @@ PLAN_FLAGS = {
     "no_xcd_order": 1 << 4, "no_fused_stem_pool": 1 << 5, "split_heads": 1 << 6, "nms_in_line": 1 << 7,
     "no_persistent_grid": 1 << 8, "layer1_tile_8x16": 1 << 9, "winograd_gen1": 1 << 10, "no_latency_tiles": 1 << 11,
     "nms_one_workgroup": 1 << 12, "no_fused_softmax": 1 << 13, "winograd_gen2": 1 << 14, "guard_zones": 1 << 15, "detector_gen1": 1 << 16, "heads_in_line": 1 << 17, "w36_one_wave": 1 << 18, "convt_phases": 1 << 19, "stem_round3": 1 << 20, "conv_round1": 1 << 21,
+    "tiles_round5": 1 << 22,
 }
 
 
@@ -237,6 +238,7 @@ def load():
     l.fpc_plan_hash.restype = ctypes.c_uint64
     l.fpc_broadcast_weights.argtypes = [vp, vp, ci]
     l.fpc_pack_layout_revision.restype = ci
+    l.fpc_tile_choice.argtypes = [ci, ci, ci, ci, ctypes.c_uint]
     l.fpc_check_guards.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     l.fpc_stream_report.argtypes = [vp, ctypes.POINTER(FpcStreamReport)]
     l.fpc_set_timing.argtypes = [vp, ci]

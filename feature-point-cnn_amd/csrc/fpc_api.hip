@@ -161,7 +161,10 @@ static const LeanKindInfo* lean_kind(Kind k) {
   X(B320_s2_K32_C256, 3, 20, 2, 32, 1, 4, 2, 2, 256)         \
   X(B310_s2_K32_C256, 3, 10, 2, 32, 1, 4, 1, 2, 256)         \
   X(B320_s2_K32_C128, 3, 20, 2, 32, 1, 4, 2, 1, 128)         \
-  X(B320_s1_K64_C256, 3, 20, 1, 64, 1, 4, 2, 2, 256)
+  X(B320_s1_K64_C256, 3, 20, 1, 64, 1, 4, 2, 2, 256)         \
+  X(B416_s2_K32_C128, 4, 16, 2, 32, 1, 4, 2, 1, 128)
+// (B416_s2_K32_C128, round 6: B320_s2_K32_C128's fragments on 64 pixels that fill the M = 64 rows -- retile_rows below.
+// New instances go at the END of this list: plan_hash mixes the enumerators of the round-5 choice.)
 
 enum BKind {
 #define X(name, ...) BK_##name,
@@ -233,6 +236,14 @@ static const BKindInfo g_bkinds[BK_COUNT] = {
   X(W36_C65_4x4, 4, 4)    \
   X(W36_C65_2x8, 2, 8)
 
+// W36SKIND(name, NB, TYT, TXT): wblock36s_kernel (round 6: wblock36_kernel<NB, TYT, TXT> walking a launch's frames as one
+// stacked image; chosen per LAUNCH -- w36_stacked below -- so no op of the plan carries it)
+#define FPC_W36S_KINDS(X) \
+  X(W36S_C128_4x4, 2, 4, 4)
+// W36PCKIND(name, TYT, TXT): wconv36p_kernel (round 6: the paired body's conv-only entry point, which also admits 8 x 2)
+#define FPC_W36PC_KINDS(X) \
+  X(W36PC_C64_8x2, 8, 2)
+
 enum WKind {
 #define X(name, ...) WK_##name,
   FPC_WBLOCK_KINDS(X)
@@ -241,6 +252,8 @@ enum WKind {
   FPC_W36D_KINDS(X)
   FPC_W36P_KINDS(X)
   FPC_W36PD_KINDS(X)
+  FPC_W36S_KINDS(X)
+  FPC_W36PC_KINDS(X)      // (round 6's lists go behind round 5's: plan_hash mixes the enumerators of the round-5 choice)
 #undef X
       WK_COUNT
 };
@@ -301,6 +314,20 @@ FPC_W36P_KINDS(X)
   }
 FPC_W36PD_KINDS(X)
 #undef X
+#define X(name, NB, TYT, TXT)                                                                             \
+  static void launchw_##name(const WBlockArgs& a, dim3 grid, hipStream_t st) {                            \
+    constexpr int lds = W36Cfg<NB, TYT, TXT>::LDS_BYTES;                                                  \
+    hipLaunchKernelGGL((wblock36s_kernel<NB, TYT, TXT>), grid, dim3(256), lds, st, a);                    \
+  }
+FPC_W36S_KINDS(X)
+#undef X
+#define X(name, TYT, TXT)                                                                                  \
+  static void launchw_##name(const WBlockArgs& a, dim3 grid, hipStream_t st) {                            \
+    constexpr int lds = W36PCfg<TYT, TXT, false, true>::LDS_BYTES;                                        \
+    hipLaunchKernelGGL((wconv36p_kernel<TYT, TXT>), grid, dim3(512), lds, st, a);                         \
+  }
+FPC_W36PC_KINDS(X)
+#undef X
 
 static const WKindInfo g_wkinds[WK_COUNT] = {
 #define X(name, KC, NBT, CMID)                                                                            \
@@ -332,6 +359,16 @@ static const WKindInfo g_wkinds[WK_COUNT] = {
   {#name, "wblock36p_dust_kernel<" #TYT ", " #TXT ", 3>", 3, 16, 2, 64,                                    \
    W36PCfg<TYT, TXT, true>::LDS_BYTES, 4, 4 * TYT, 4 * TXT, 512, (const void*)wblock36p_dust_kernel<TYT, TXT>, launchw_##name, true},
     FPC_W36PD_KINDS(X)
+#undef X
+#define X(name, NB, TYT, TXT)                                                                             \
+  {#name, "wblock36s_kernel<" #NB ", " #TYT ", " #TXT ">", 3, 16, 2 * NB, 64 * NB,                         \
+   W36Cfg<NB, TYT, TXT>::LDS_BYTES, 4 * NB, 4 * TYT, 4 * TXT, 256, (const void*)wblock36s_kernel<NB, TYT, TXT>, launchw_##name},
+    FPC_W36S_KINDS(X)
+#undef X
+#define X(name, TYT, TXT)                                                                                 \
+  {#name, "wconv36p_kernel<" #TYT ", " #TXT ", 3>", 3, 16, 2, 64,                                            \
+   W36PCfg<TYT, TXT, false, true>::LDS_BYTES, 4, 4 * TYT, 4 * TXT, 512, (const void*)wconv36p_kernel<TYT, TXT>, launchw_##name},
+    FPC_W36PC_KINDS(X)
 #undef X
 };
 
@@ -369,13 +406,31 @@ static int w36_conv_part(int cout, int tiles, int cus) {
 // Generation 3: the arrangement of the 16 Winograd tiles (4 x 4 or 2 x 8) that covers the map with fewer tiles
 // (cout == 64, `paired`: the two-waves-per-SIMD instance, wblock36p_mfma.h -- the default since round 5; a block's
 // projection must then be a multiple of 64 channels wide, which every 64-channel layer of both networks is)
-static WKind w36_kind(int cout, int H, int W, bool paired = false) {
-  const int t44 = ((H + 15) / 16) * ((W + 15) / 16), t28 = ((H + 7) / 8) * ((W + 31) / 32);
+// (`conv82`, round 6: a conv-only 64-channel paired launch may also take 8 x 2 -- 32 x 8 pixels, wconv36p_kernel -- where
+// that needs fewer tiles than both: a 30 x 40 map is 5 of them against 6 and 8.  A tie keeps the choice without it.)
+static WKind w36_kind(int cout, int H, int W, bool paired = false, bool conv82 = false) {
+  const int t44 = ((H + 15) / 16) * ((W + 15) / 16), t28 = ((H + 7) / 8) * ((W + 31) / 32), t82 = ((H + 31) / 32) * ((W + 7) / 8);
+  if (conv82 && cout == 64 && paired && t82 < std::min(t44, t28)) return WK_W36PC_C64_8x2;
   if (cout == 65 && paired) return t28 < t44 ? WK_W36PD_C65_2x8 : WK_W36PD_C65_4x4;
   if (cout == 65) return t28 < t44 ? WK_W36_C65_2x8 : WK_W36_C65_4x4;
   if (cout == 64 && paired) return t28 < t44 ? WK_W36P_C64_2x8 : WK_W36P_C64_4x4;
   if (cout == 64) return t28 < t44 ? WK_W36_C64_2x8 : WK_W36_C64_4x4;
   return t28 < t44 ? WK_W36_C128_2x8 : WK_W36_C128_4x4;
+}
+
+// Round 6: the instance that walks a launch's frames as one stacked image for an op on `wk` (WK_COUNT: none).  The 128-channel
+// arrangements share their fragments, so a 2 x 8 op may take the 4 x 4 stacked walk too.
+static WKind w36_stacked_kind(WKind wk) { return wk == WK_W36_C128_4x4 || wk == WK_W36_C128_2x8 ? WK_W36S_C128_4x4 : WK_COUNT; }
+// ... and its tile rows for `frames` frames of Hf x W on instance `sk`, where that is FEWER tiles than the `tiles_now` per
+// frame the op launches frame by frame (60 rows on 16-row tiles: 18.75 tile rows per frame instead of 20; a height that is
+// a multiple of the tile's gains nothing) -- 0 where it is not, or where the kernel does not apply: it needs every
+// Winograd tile inside one frame (Hf % 4 == 0) and at most one seam per tile (Hf >= the tile's height).
+static int w36_stacked_rows(int Hf, int W, int frames, WKind sk, int tiles_now) {
+  if (sk == WK_COUNT) return 0;
+  const int th = g_wkinds[sk].TH, tw = g_wkinds[sk].TW;
+  if (Hf % 4 != 0 || Hf < th) return 0;
+  const int rows = (frames * Hf + th - 1) / th;
+  return rows * ((W + tw - 1) / tw) < frames * tiles_now ? rows : 0;
 }
 
 // bf16 / split-operand instances.  FKIND(name, KERNEL, CFG, PLANES, TH,TW, S,EXT, KC, WM,WN, MB,NB, CMIDP)
@@ -459,6 +514,7 @@ struct Op {
   BKind bkind = BK_COUNT;
   BlockArgs bargs{};
   WKind wkind = WK_COUNT;
+  int hash_bkind = -1, hash_wkind = -1;   // round 6: the instance FPC_PLAN_TILES_ROUND5 launches where `bkind` / `wkind` is a re-tiling of it (same fragments): what plan_hash mixes, so blobs travel between the two plans
   WBlockArgs wargs{};
   FKind fkind = FK_COUNT;
   BlockBfArgs fargs{};
@@ -487,6 +543,8 @@ struct Timing {
   hipEvent_t start, stop;
   int op;
   int frames;  // frames covered by this launch (a sub-batch)
+  int wkind = -1;            // round 6: the instance that ran where it is not the op's (the stacked walk) ...
+  double mfma_flops = -1.0;  // ... and what its tiles issued
 };
 
 }  // namespace fpc
@@ -543,6 +601,7 @@ struct fpc_ctx {
   bool winograd_in1 = true;          // descriptor.layer_in.1 (256 ch): conv-only Winograd x2 + 1x1 (FPC_WINOGRAD_IN1=0: fused direct block)
   bool winograd_det = true;          // ... also the detector's 65-channel blocks (FPC_WINOGRAD_DET=0: direct)
   int w36_cus = 0;                   // FPC_W36_CUS: CUs a generation-3 launch may take (0 = all): A/B knob for contexts that share the GPU
+  bool tiles_round6 = true;          // tiles chosen by the matrix rows they issue: layer2.0 on 4 x 16 (FPC_PLAN_TILES_ROUND5 / FPC_TILES_ROUND6=0: round 5's tilings)
   bool w36_paired = true;            // the 64-channel F(4x4,3x3) layers on wblock36p_kernel, two waves per SIMD (FPC_PLAN_W36_ONE_WAVE / FPC_W36_PAIRED=0: wblock36_kernel<1, ..>)
   bool winograd_det_gen3 = true;     // ... on wblock36_dust_kernel in batch calls (FPC_PLAN_DETECTOR_GEN1 / FPC_WINOGRAD_DET_GEN=1: round 1's kernel)
   bool winograd = true;              // stride-1 blocks with <= 128 channels: Winograd F(2x2,3x3) (FPC_WINOGRAD=0: direct)
@@ -899,8 +958,7 @@ static void add_block(fpc_ctx* c, const BlockSpec& s, size_t* blob_off) {
 // latency of a single frame's layer is one tile's time (20 - 40 tiles per frame on 256 CUs), and a 32-frame batch runs
 // 3 - 10 % faster on them too (shorter tail, more workgroups per CU in flight) -- measured, so they serve every call.
 // FPC_PLAN_NO_LATENCY_TILES keeps round 1's tiles.
-static void retile_last(fpc_ctx* c, BKind small) {
-  if (!c->latency_tiles || c->ops.empty() || c->ops.back().type != OP_BLOCK) return;
+static void retile_block(fpc_ctx* c, BKind small) {
   const BKindInfo &k0 = g_bkinds[c->ops.back().bkind], &k = g_bkinds[small];
   if (k.KC != k0.KC || k.WN * k.NB != k0.WN * k0.NB || k.S != k0.S || k.CMIDP != k0.CMIDP) { c->plan_error = true; return; }
   Op& o = c->ops.back();
@@ -913,6 +971,27 @@ static void retile_last(fpc_ctx* c, BKind small) {
   a.tiles_y = (a.Ho + k.TH - 1) / k.TH;
   o.mfma_flops_per_frame = 2.0 * a.tiles_x * a.tiles_y * (k.WM * k.MB * 32.0) * (k.WN * k.NB * 32.0) *
                            ((double)a.nchunk * k.KC * 9 + (a.k8_h + a.k8_x) * 8.0);
+}
+static void retile_last(fpc_ctx* c, BKind small) {
+  if (!c->latency_tiles || c->ops.empty() || c->ops.back().type != OP_BLOCK) return;
+  retile_block(c, small);
+}
+// MFMA rows a fused block issues per frame on instance `k`: its tiles x the M of a tile (padding included)
+static long block_rows(BKind k, int Ho, int Wo) {
+  const BKindInfo& b = g_bkinds[k];
+  return (long)((Ho + b.TH - 1) / b.TH) * ((Wo + b.TW - 1) / b.TW) * (b.WM * b.MB * 32);
+}
+// Round 6: the op just added moves to `fit` (same fragments, as above) where that instance issues FEWER rows on the matrix
+// cores -- layer2.0's 60 x 80 output is 75 tiles of 4 x 16 = 64 full rows instead of 80 tiles of 3 x 20 = 60 rows in M = 64.
+// A tie keeps the instance it has.  plan_hash keeps mixing the instance it had: the blob is the same.
+// FPC_PLAN_TILES_ROUND5 keeps round 5's tiles.
+static void retile_rows(fpc_ctx* c, BKind fit) {
+  if (!c->tiles_round6 || c->ops.empty() || c->ops.back().type != OP_BLOCK) return;
+  Op& o = c->ops.back();
+  if (block_rows(fit, o.bargs.Ho, o.bargs.Wo) >= block_rows(o.bkind, o.bargs.Ho, o.bargs.Wo)) return;
+  const BKind had = o.bkind;
+  retile_block(c, fit);
+  if (!c->plan_error) c->ops.back().hash_bkind = had;
 }
 
 static void retile_last(fpc_ctx* c, Kind small) {
@@ -1048,6 +1127,7 @@ static void add_wconv(fpc_ctx* c, const std::string& prefix, bool bn, WKind wk, 
             (cout > k.CMID ? ", channels " + std::to_string(n0) + ".." + std::to_string(n0 + k.CMID - 1) : std::string()) + "]";
   op.prefix = prefix;
   op.wkind = wk;
+  if (wk == WK_W36PC_C64_8x2) op.hash_wkind = w36_kind(64, H, W, true);   // the same fragments: plan_hash as FPC_PLAN_TILES_ROUND5's
   op.wconv = true;
   op.plain_conv = !bn;
   op.n0 = n0;
@@ -1796,6 +1876,7 @@ static int build_plan(fpc_ctx* c) {
   block("encoder.layer2.0", K_T620_3x3s2_K32_N128, K_T620_1x1_K64_N128, 2, c->x2, 64, 64, 64, H4, W4, c->h8, 128,
         128, 128, c->x3, 128, true, false, BK_B620_s2_K32_C128);
   if (c->fuse_blocks) retile_last(c, BK_B320_s2_K32_C128);
+  if (c->fuse_blocks) retile_rows(c, BK_B416_s2_K32_C128);
   block("encoder.layer2.1", K_T620_3x3_K64_N128, K_T620_1x1_K64_N128, 1, c->x3, 128, 128, 128, Hc, Wc, c->h8, 128,
         128, 128, feat, 256, false, false, BK_B620_s1_K64_C128);
   if (c->fuse_blocks) {
@@ -1848,7 +1929,7 @@ static int build_plan(fpc_ctx* c) {
       const bool g3 = c->winograd_gen == 3 && w36_fits(c->B, H16, W16, 256, 256);
       const int in1_parts = g3 ? 4 : 2;
       for (int n0 = 0; n0 < 256; n0 += 256 / in1_parts)
-        add_wconv(c, p, true, g3 ? w36_kind(64, H16, W16, c->w36_paired) : c->winograd_gen >= 2 ? WK_W16_C128 : WK_W816_K32_C128, c->y16a, 256, 256, H16, W16, c->h16, 256, 256, n0, true, &bo);
+        add_wconv(c, p, true, g3 ? w36_kind(64, H16, W16, c->w36_paired, c->tiles_round6) : c->winograd_gen >= 2 ? WK_W16_C128 : WK_W816_K32_C128, c->y16a, 256, 256, H16, W16, c->h16, 256, 256, n0, true, &bo);
       const size_t in1_ops = in1_parts + 1;      // [the launch, its shadows, the 1x1 below]
       ConvSpec t{};
       t.name = p + ".conv2+bn2+identity+relu";
@@ -1986,7 +2067,8 @@ static uint64_t plan_hash(const fpc_ctx* c) {
   mix(c->vconv0_off);
   for (size_t i = 0; i < c->ops.size(); ++i) {
     const Op& op = c->ops[i];
-    mix((uint64_t)op.type); mix((uint64_t)op.kind); mix((uint64_t)op.bkind); mix((uint64_t)op.wkind); mix((uint64_t)op.fkind);
+    mix((uint64_t)op.type); mix((uint64_t)op.kind); mix((uint64_t)(op.hash_bkind >= 0 ? (BKind)op.hash_bkind : op.bkind));
+    mix((uint64_t)(op.hash_wkind >= 0 ? (WKind)op.hash_wkind : op.wkind)); mix((uint64_t)op.fkind);
     mix((uint64_t)(op.phase + 1)); mix((uint64_t)op.n0);
     for (char ch : op.prefix) mix((uint64_t)(unsigned char)ch);
     const fpc_ctx::ConvW& cw = c->convw[i];
@@ -2533,6 +2615,8 @@ struct LaunchTimer {
   hipStream_t st;
   int frames;
   hipEvent_t s{}, e{};
+  int wkind = -1;
+  double mfma_flops = -1.0;
   LaunchTimer(fpc_ctx* c_, int op_, hipStream_t st_, int frames_) : c(c_), op(op_), st(st_), frames(frames_) {
     if (c->timing) {
       s = next_event(c);
@@ -2543,7 +2627,7 @@ struct LaunchTimer {
   ~LaunchTimer() {
     if (c->timing) {
       hipEventRecord(e, st);
-      c->timings.push_back({s, e, op, frames});
+      c->timings.push_back({s, e, op, frames, wkind, mfma_flops});
     }
   }
 };
@@ -2669,13 +2753,25 @@ static void run_network(fpc_ctx* c, const float* frames, const Sub& sb0, int whi
           const int fpl = w36_frames_per_launch(a.H, a.W, a.csx, a.cso);
           const float* x0 = a.x;
           float* o0 = a.out;
+          const int Hf = a.H, tx_f = a.tiles_x, ty_f = a.tiles_y;
+          const WKind sk = c->tiles_round6 ? w36_stacked_kind(op.wkind) : WK_COUNT;
+          double mf = 0.0;
           for (int g0 = 0; g0 < n; g0 += fpl) {
             const int gn = std::min(fpl, n - g0);
             a.frame0 = 0;
-            a.x = x0 + (size_t)(f0 + g0) * a.H * a.W * a.csx;
-            a.out = o0 + (size_t)(f0 + g0) * a.H * a.W * a.cso;
-            a.total = a.tiles_x * a.tiles_y * gn;
-            a.x_bytes = (unsigned)((unsigned long long)gn * a.H * a.W * a.csx * sizeof(float));
+            a.x = x0 + (size_t)(f0 + g0) * Hf * a.W * a.csx;
+            a.out = o0 + (size_t)(f0 + g0) * Hf * a.W * a.cso;
+            a.x_bytes = (unsigned)((unsigned long long)gn * Hf * a.W * a.csx * sizeof(float));
+            // round 6: the launch's frames as ONE image of gn x Hf rows where that is fewer tiles (wblock36s_kernel)
+            const int srows = w36_stacked_rows(Hf, a.W, gn, sk, tx_f * ty_f);
+            const WKind lk = srows ? sk : op.wkind;
+            a.H = srows ? gn * Hf : Hf;
+            a.frame_h = srows ? Hf : 0;
+            a.tiles_x = srows ? (a.W + g_wkinds[sk].TW - 1) / g_wkinds[sk].TW : tx_f;
+            a.tiles_y = srows ? srows : ty_f;
+            a.total = srows ? a.tiles_x * srows : tx_f * ty_f * gn;
+            if (srows) t.wkind = sk;
+            mf += srows ? wkind_mfma_flops(g_wkinds[sk], a.total, a.nchunk, a.k8_h + a.k8_x) : op.mfma_flops_per_frame * gn;
             // One workgroup per CU (137 KB of LDS), so a launch lasts ceil(tiles / CUs) tile times whatever the grid: take
             // the SMALLEST grid that still finishes in that many rounds (a multiple of 8: the tile walk is per XCD) and
             // leave the other CUs to the launches of the other sub-batch's stream -- 640 tiles: 216 workgroups x 3 rounds
@@ -2685,8 +2781,9 @@ static void run_network(fpc_ctx* c, const float* frames, const Sub& sb0, int whi
             const int cus8 = std::max(1, cus_cap / 8 / std::max(1, op.grid_y)), per_xcd = (a.total + 7) / 8;
             const int rounds = (per_xcd + cus8 - 1) / cus8;
             const int grid3 = 8 * std::min(cus8, (per_xcd + rounds - 1) / rounds);
-            g_wkinds[op.wkind].launch(a, dim3(std::min(a.total, grid3), op.grid_y), sb.st);
+            g_wkinds[lk].launch(a, dim3(std::min(a.total, grid3), op.grid_y), sb.st);
           }
+          if (t.wkind >= 0) t.mfma_flops = mf;
           break;
         }
         g_wkinds[op.wkind].launch(a, dim3(std::min(a.total, grid), op.grid_y), sb.st);
@@ -3135,6 +3232,8 @@ int fpc_create(fpc_ctx** out, const fpc_config* cfg) {
     c->winograd_det_gen3 = !(pf & FPC_PLAN_DETECTOR_GEN1);
     c->w36_paired = !(pf & FPC_PLAN_W36_ONE_WAVE);
     if (const char* e = getenv("FPC_W36_PAIRED")) c->w36_paired = atoi(e) != 0;
+    c->tiles_round6 = !(pf & FPC_PLAN_TILES_ROUND5);
+    if (const char* e = getenv("FPC_TILES_ROUND6")) c->tiles_round6 = atoi(e) != 0;
     if (const char* e = getenv("FPC_W36_CUS")) c->w36_cus = std::max(0, atoi(e));
     if (const char* e = getenv("FPC_WINOGRAD_DET_GEN")) c->winograd_det_gen3 = atoi(e) >= 3;
     c->winograd = !(pf & FPC_PLAN_NO_WINOGRAD);
@@ -3359,6 +3458,24 @@ int fpc_mark_weights_loaded(fpc_ctx* c) {
 }
 
 uint64_t fpc_plan_hash(const fpc_ctx* c) { return c ? plan_hash(c) : 0; }
+
+int fpc_tile_choice(int what, int H, int W, int frames, unsigned plan_flags) {
+  const bool r6 = !(plan_flags & FPC_PLAN_TILES_ROUND5);
+  if (H <= 0 || W <= 0 || frames <= 0) return FPC_E_INVALID;
+  switch (what) {
+    case 0: {
+      const WKindInfo& k = g_wkinds[w36_kind(128, H, W)];
+      return r6 ? w36_stacked_rows(H, W, frames, WK_W36S_C128_4x4, ((H + k.TH - 1) / k.TH) * ((W + k.TW - 1) / k.TW)) : 0;
+    }
+    case 1: { const WKindInfo& k = g_wkinds[w36_kind(64, H, W, true, r6)]; return 100 * k.TH + k.TW; }
+    case 2: {
+      const BKind k5 = BK_B320_s2_K32_C128, k6 = BK_B416_s2_K32_C128;
+      const BKindInfo& k = g_bkinds[r6 && block_rows(k6, H, W) < block_rows(k5, H, W) ? k6 : k5];
+      return 100 * k.TH + k.TW;
+    }
+  }
+  return FPC_E_INVALID;
+}
 
 int fpc_check_guards(fpc_ctx* c, long long* bad_words) {
   if (!c || !bad_words) return FPC_E_INVALID;
@@ -4838,7 +4955,7 @@ int fpc_get_timings(fpc_ctx* c, int cap, const char** names, const char** kernel
           case OP_POOL: k = "maxpool_kernel"; break;
           case OP_CONV: k = op->lean ? lean_kind(op->kind)->symbol : g_kinds[op->kind].symbol; break;
           case OP_BLOCK: k = g_bkinds[op->bkind].symbol; break;
-          case OP_WBLOCK: k = g_wkinds[op->wkind].symbol; break;
+          case OP_WBLOCK: k = g_wkinds[t.wkind >= 0 ? t.wkind : op->wkind].symbol; break;
           case OP_BF16: k = g_fkinds[op->fkind].symbol; break;
           case OP_SOFTMAX: k = "softmax_d2s_kernel"; break;
           case OP_NMS: k = c->nms_one_workgroup ? "nms_rounds_kernel+nms_sort_kernel" : "nms_rounds_kernel+nms_finish_kernel+nms_chunk_sort_kernel+nms_merge_kernel"; break;
@@ -4851,7 +4968,7 @@ int fpc_get_timings(fpc_ctx* c, int cap, const char** names, const char** kernel
     }
     if (ms) ms[i] = v;
     if (flops) flops[i] = op ? op->flops_per_frame * t.frames : 0.0;
-    if (mfma_flops) mfma_flops[i] = op ? op->mfma_flops_per_frame * t.frames : 0.0;
+    if (mfma_flops) mfma_flops[i] = !op ? 0.0 : t.mfma_flops >= 0 ? t.mfma_flops : op->mfma_flops_per_frame * t.frames;
     if (bytes) bytes[i] = op ? op->bytes_per_frame * t.frames : 0.0;
   }
   return n;

@@ -202,9 +202,21 @@ __device__ __forceinline__ void fpc_mfma_step16(f32x4& c00, f32x4& c01, f32x4& c
 #undef FPC_MFMA16_IN
 }
 
-template <int NB, int TYT, int TXT, bool DUST>
+// STACK (round 6, wblock36s_kernel): the launch's frames -- contiguous NHWC -- walked as ONE image of a.H = n x a.frame_h rows,
+// so that a map whose height is no multiple of the tile's (60 rows: 3.75 tiles) pays the partial tile row once per launch
+// instead of once per frame.  a.frame_h is a multiple of 4, so every Winograd tile lies inside one frame; only the
+// workgroup tile can straddle a seam between two frames, and with a.frame_h >= TH at most one.  What changes is the halo
+// (halo_tile, once per tile):
+//   * a seam d rows into the tile (0 < d <= TH): the LDS halo gets one more row -- Z, all zeros, at row d + 1: the upper
+//     frame's bottom padding and the lower frame's top padding at once (HH + 1 rows: 19 x 18 pixels x 5 slots = 1 710 of
+//     the 7 x 256 slots the buffers have); the rows behind Z take their source one row up, and the Winograd rows below the
+//     seam read their patches one halo row further down (a Winograd row is a wave's: a uniform offset);
+//   * a seam on the tile's top edge (d = 0): the top halo row is the frame above's last row and carries the marker.
+// Addresses, x staging, rows_valid and the output see one frame of a.H rows and are what they were.
+template <int NB, int TYT, int TXT, bool DUST, bool STACK = false>
 __device__ __forceinline__ void wblock36_body(const WBlockArgs& a) {
   using C = W36Cfg<NB, TYT, TXT, DUST>;
+  static_assert(!STACK || (!DUST && (C::HH + 1) * C::HW * 5 <= C::HIT * C::NT), "the stacked walk's extra halo row must fit the halo buffer");
   constexpr int NT = C::NT, TH = C::TH, TW = C::TW, HW = C::HW, HH = C::HH, HROW = C::HROW, HIT = C::HIT;
   constexpr int N = C::N, RH = C::RH, RX = C::RX, RING = C::RING, STEPS = C::STEPS, HPX = C::HPX;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -256,20 +268,42 @@ __device__ __forceinline__ void wblock36_body(const WBlockArgs& a) {
   auto halo_base = [&](const TilePos& q) {               // byte offset of the tile's first pixel, channel 0
     return __builtin_amdgcn_readfirstlane(((q.b * a.H + q.ty * TH) * a.W + q.tx * TW) * a.csx * 4);
   };
-  auto halo_tile = [&](const TilePos& q) {               // okoff[] for that tile
+  // STACK: the tile's seam as the halo row that reads as zeros -- d + 1 (Z) for a seam d rows into the tile, 0 for one on
+  // its top edge, -1 for none (uniform: one division per tile, beside tile_pos's two)
+  auto seam_row = [&](const TilePos& q) {
+    if constexpr (STACK) {
+      const int r = (q.ty * TH) % a.frame_h;
+      const int d = r == 0 ? 0 : a.frame_h - r;
+      return d > TH ? -1 : d == 0 ? 0 : d + 1;
+    } else {
+      return -1;
+    }
+  };
+  // ... and what it adds to the transform's read base: a Winograd row below Z starts one halo row further down
+  const int wrow_u = STACK ? __builtin_amdgcn_readfirstlane((tid >> 4) / TXT) : 0;      // this wave's Winograd row (TXT = 4: the wave, 8: wave / 2)
+  auto seam_shift = [&](int zrow) { return (STACK && zrow > 0 && 4 * wrow_u + 1 >= zrow) ? HW * HROW : 0; };
+  auto halo_tile = [&](const TilePos& q, [[maybe_unused]] int zrow = -1) {               // okoff[] for that tile
     int tl = tid;
     asm volatile("" : "+v"(tl));
     const int iy0 = q.ty * TH - 1, ix0 = q.tx * TW - 1;
     const int hlim = q.live ? a.H : 0;
+    [[maybe_unused]] const int zs = zrow > 0 ? zrow : 0x7fff, hmax = zrow > 0 ? HH + 1 : HH;
 #pragma unroll
     for (int i = 0; i < HIT; ++i) {
       const int e = tl + i * NT;
       const int pix = (e * 13108) >> 16, c4 = e - pix * 5;                    // e / 5 (e < 1792: 13108 / 65536 = 0.2 + 1.2e-5)
       const int hy = HW == 18 ? (pix * 3641) >> 16 : (pix * 1928) >> 16;     // pix / 18 (pix < 469), pix / 34 (pix < 441)
       const int hx = pix - hy * HW;
+      if constexpr (STACK) {
+        const int hys = hy - (hy > zs ? 1 : 0);                               // the halo row's source row: one up behind Z
+        const bool ok = ((unsigned)(iy0 + hys) < (unsigned)hlim) & ((unsigned)(ix0 + hx) < (unsigned)a.W) & (hy < hmax) & (hy != zrow) & (c4 < 4);
+        const int off = (((hys - 1) * a.W + (hx - 1)) * a.csx + c4 * 4) * 4;
+        okoff[i] = ok ? off : W36_MARKER;
+      } else {
       const bool ok = ((unsigned)(iy0 + hy) < (unsigned)hlim) & ((unsigned)(ix0 + hx) < (unsigned)a.W) & (hy < HH) & (c4 < 4);
       const int off = (((hy - 1) * a.W + (hx - 1)) * a.csx + c4 * 4) * 4;
       okoff[i] = ok ? off : W36_MARKER;
+      }
     }
     if constexpr (DUST) {
 #pragma unroll
@@ -397,13 +431,16 @@ __device__ __forceinline__ void wblock36_body(const WBlockArgs& a) {
   // ---------------------------------------------------------------- pipeline fill for the first tile
   TilePos pos_cur = tile_pos(wg_first);
   int base_cur = halo_base(pos_cur);
-  halo_tile(pos_cur);
+  [[maybe_unused]] int zrow_cur = seam_row(pos_cur);
+  if constexpr (STACK) halo_tile(pos_cur, zrow_cur);
+  else halo_tile(pos_cur);
   load_halo64(base_cur);
   load_halo(base_cur, C::OFF_H0);
   load_halo(base_cur + 64, C::OFF_H1);
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HIT) : "memory");      // chunk 0 has landed (this wave's part of it)
   FPC_LDS_BARRIER();
-  transform_all(C::OFF_H0, C::OFF_V0);
+  if constexpr (STACK) transform_all(C::OFF_H0 + seam_shift(zrow_cur), C::OFF_V0);
+  else transform_all(C::OFF_H0, C::OFF_V0);
   FPC_LDS_BARRIER();
   // state at the top of iteration c of a tile: V[c & 1] = chunk c transformed; halo[(c + 1) & 1] = chunk c + 1 requested
   // (landed, as far as this wave's own requests go, by the barrier that ended iteration c - 1)
@@ -425,6 +462,7 @@ __device__ __forceinline__ void wblock36_body(const WBlockArgs& a) {
     const int b = pos_cur.b, ty = pos_cur.ty, tx = pos_cur.tx;
     const TilePos pos_next = tile_pos(wg + wg_step);
     const int base_next = halo_base(pos_next);
+    [[maybe_unused]] const int zrow_next = seam_row(pos_next);
     if (wg == wg_stamp) { FPC_STAMP(0) FPC_RSTAMP(6) }
 
     f32x4 acc[36][NB];
@@ -459,6 +497,8 @@ __device__ __forceinline__ void wblock36_body(const WBlockArgs& a) {
       const bool nxt = c3 >= nchunk;
       const int l_base = (nxt ? base_next : base_cur) + (nxt ? c3 - nchunk : c3) * 64;
       int ao = aoff4 + VB_OFF / 4, trd_c = trd + HN_OFF, twr_c = twr + VN_OFF;
+      // STACK: chunk c + 1 is this tile's -- or, in the tile's last chunk (odd: nchunk is even), the next tile's first
+      if constexpr (STACK) trd_c += seam_shift(par && c + 1 >= nchunk ? zrow_next : zrow_cur);
       asm volatile("" : "+v"(ao), "+v"(trd_c), "+v"(twr_c));
       [[maybe_unused]] int dva = d_va + VB_OFF / 4;      // DUST: this lane's float4 of position w, this chunk's buffer
       [[maybe_unused]] f32x4 dv[3];
@@ -493,6 +533,8 @@ __device__ __forceinline__ void wblock36_body(const WBlockArgs& a) {
         for (int u = 0; u < SPS; ++u) {
           const int slot = s * SPS + u;
           if (slot == 1) {
+            if constexpr (STACK) { if (c3 == nchunk) halo_tile(pos_next, zrow_next); }
+            else
             if (c3 == nchunk) halo_tile(pos_next);      // (uniform; no memory operation inside, so the join merges identical counter states)
             load_halo(l_base, HS_OFF);
           } else if (slot >= 2 && slot < 14) {
@@ -1041,12 +1083,20 @@ __device__ __forceinline__ void wblock36_body(const WBlockArgs& a) {
     }  // halves
     pos_cur = pos_next;
     base_cur = base_next;
+    if constexpr (STACK) zrow_cur = zrow_next;
   }  // persistent tile loop
 }
 
 template <int NB, int TYT, int TXT>
 __global__ __launch_bounds__(256, 1) void wblock36_kernel(const WBlockArgs a) {
   wblock36_body<NB, TYT, TXT, false>(a);
+}
+
+// The stacked walk (STACK above): a launch's frames as one image of a.H = n x a.frame_h rows.  Same packed weights, same
+// operands in the same order for every Winograd tile and every output pixel as wblock36_kernel<NB, TYT, TXT>.
+template <int NB, int TYT, int TXT>
+__global__ __launch_bounds__(256, 1) void wblock36s_kernel(const WBlockArgs a) {
+  wblock36_body<NB, TYT, TXT, false, true>(a);
 }
 
 // The detector's blocks: 64 channels as wblock36_kernel<1, ...> + the 65th ("dustbin") channel beside them (W36Dust).

@@ -28,11 +28,13 @@
 
 namespace fpc {
 
-template <int TYT_, int TXT_, bool DUST_ = false>
+// CONV (round 6): the conv-only entry point wconv36p_kernel -- the body without the 1x1 phase, which also admits the 8 x 2
+// arrangement (32 x 8 pixels: a 30 x 40 map is five of them instead of 2 x 3 tiles of 16 x 16)
+template <int TYT_, int TXT_, bool DUST_ = false, bool CONV_ = false>
 struct W36PCfg {
   static constexpr int TYT = TYT_, TXT = TXT_;
-  static constexpr bool DUST = DUST_;
-  static_assert(TYT * TXT == 16 && (TYT == 4 || TYT == 2), "16 Winograd tiles per workgroup tile: 4 x 4 or 2 x 8");
+  static constexpr bool DUST = DUST_, CONV = CONV_;
+  static_assert(TYT * TXT == 16 && (TYT == 4 || TYT == 2 || (CONV && !DUST && TYT == 8)), "16 Winograd tiles per workgroup tile: 4 x 4 or 2 x 8 (conv-only: or 8 x 2)");
   static constexpr int NT = 512, NTH = 256, NPOS = 36, KC = 16, N = 64;
   static constexpr int TH = 4 * TYT, TW = 4 * TXT, HH = TH + 2, HW = TW + 2, NHALO = HH * HW;
   static constexpr int HROW = 20;
@@ -52,16 +54,16 @@ struct W36PCfg {
   static constexpr int LDS_BYTES = LDS_FLOATS * 4;
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
   static constexpr int STEPS = 9;                                   // per wave: 18 positions, two per step
-  static constexpr int WPAD = W36Cfg<1, TYT, TXT>::WPAD, WPAD2 = W36Cfg<1, TYT, TXT>::WPAD2;
+  static constexpr int WPAD = W36Cfg<1, 4, 4>::WPAD, WPAD2 = W36Cfg<1, 4, 4>::WPAD2;      // (the same for every arrangement)
   static_assert(WPAD >= 36, "a wave prefetches up to one chunk past its stream's end");
 };
 
 // RING: depth of the fragment ring in steps (3 or 9: slot indices must line up across chunks); a wave's fragments are
 // requested RING - 1 steps ahead.  Measured: 9 (a whole chunk ahead, 72 registers, 16 of them spilled) is 5-7 % SLOWER
 // than 3 (24 registers; two steps = 1 k cycles of cover with the partner's MFMAs in between)
-template <int TYT, int TXT, int RING, bool DUST>
+template <int TYT, int TXT, int RING, bool DUST, bool CONV = false>
 __device__ __forceinline__ void wblock36p_body(const WBlockArgs& a) {
-  using C = W36PCfg<TYT, TXT, DUST>;
+  using C = W36PCfg<TYT, TXT, DUST, CONV>;
   constexpr int TH = C::TH, TW = C::TW, HW = C::HW, HH = C::HH, HROW = C::HROW, HIT = C::HIT, NTH = C::NTH;
   constexpr int N = C::N, RH = C::RH, STEPS = C::STEPS, PX = C::PX;
   static_assert(STEPS % RING == 0 && RING >= 2, "ring slots must line up across chunks");
@@ -114,7 +116,8 @@ __device__ __forceinline__ void wblock36p_body(const WBlockArgs& a) {
   auto slot_hyx = [&](int tl, int i) {
     const int e = tl + i * NTH;
     const int pix = (e * 13108) >> 16, c4 = e - pix * 5;                    // e / 5 (e < 1792)
-    const int hy = HW == 18 ? (pix * 3641) >> 16 : (pix * 1928) >> 16;     // pix / 18 (pix < 469), pix / 34 (pix < 441)
+    const int hy = HW == 18 ? (pix * 3641) >> 16 : HW == 34 ? (pix * 1928) >> 16 : (pix * 6554) >> 16;     // pix / 18 (pix < 469), pix / 34 (pix < 441), pix / 10 (pix < 16389)
+    static_assert(HW == 18 || HW == 34 || HW == 10, "a division constant per halo width");
     const int hx = pix - hy * HW;
     const bool slot_ok = (hy < HH) & (c4 < 4);
     return slot_ok ? (hy << 16) | (c4 << 8) | hx : 0x7fff0000;
@@ -133,7 +136,7 @@ __device__ __forceinline__ void wblock36p_body(const WBlockArgs& a) {
   [[maybe_unused]] int okoff64[C::HIT64];
   auto slot_hyx64 = [&](int tl, int i) {
     const int pix = tl + i * NTH;
-    const int hy = HW == 18 ? (pix * 3641) >> 16 : (pix * 1928) >> 16;
+    const int hy = HW == 18 ? (pix * 3641) >> 16 : HW == 34 ? (pix * 1928) >> 16 : (pix * 6554) >> 16;
     const int hx = pix - hy * HW;
     return (hy < HH && a.dust_in) ? (hy << 16) | hx : 0x7fff0000;
   };
@@ -618,7 +621,7 @@ __device__ __forceinline__ void wblock36p_body(const WBlockArgs& a) {
         const int prow = i * RPI + rsub;                              // (uniform per wave)
         if (prow < rows_valid) {
           f32x4 v = lds4[erd + i * PPI * (RH / 4)];
-          if (!a.conv_only) {
+          if (!CONV && !a.conv_only) {
             v.x = v.x > 0.f ? v.x : 0.f;
             v.y = v.y > 0.f ? v.y : 0.f;
             v.z = v.z > 0.f ? v.z : 0.f;
@@ -632,10 +635,10 @@ __device__ __forceinline__ void wblock36p_body(const WBlockArgs& a) {
       }
     };
 
-    if (a.conv_only) {  // h is the result: [256 px][64] in LDS -> 16-byte stores (ReLU already applied)
+    if (CONV || a.conv_only) {  // h is the result: [256 px][64] in LDS -> 16-byte stores (ReLU already applied)
       store_out();
       FPC_LDS_BARRIER();   // the region is reused by the next tile's pipeline
-    } else {
+    } else if constexpr (!CONV) {
       // ------------------------------------------------ phase 2: 1x1 over h (+ projection over x): eight pixel blocks of this wave's channel group
       f32x4 acc2[8];
       const int pb = hs;                          // pixel blocks 8 pb .. 8 pb + 7 (pixels 128 pb .. + 127)
@@ -831,6 +834,13 @@ __device__ __forceinline__ void wblock36p_body(const WBlockArgs& a) {
 template <int TYT, int TXT, int RING = 3>
 __global__ __launch_bounds__(512, 1) void wblock36p_kernel(const WBlockArgs a) {
   wblock36p_body<TYT, TXT, RING, false>(a);
+}
+
+// The conv-only entry point (round 6): 3x3 + bias + ReLU, any arrangement of the 16 Winograd tiles W36PCfg admits -- 8 x 2
+// for descriptor.layer_in.1's conv1.  Same WBlockArgs (conv_only = 1), same packed weights as wblock36p_kernel.
+template <int TYT, int TXT, int RING = 3>
+__global__ __launch_bounds__(512, 1) void wconv36p_kernel(const WBlockArgs a) {
+  wblock36p_body<TYT, TXT, RING, false, true>(a);
 }
 
 // The detector's blocks at two waves per SIMD: 64 channels as wblock36p_kernel + the 65th ("dustbin") channel beside them

@@ -39,6 +39,7 @@ struct WBlockArgs {
                          // the layers of the C++ network, conv1 of a block too wide to fuse); w2 / b2 unused
   const float* dust;     // wblock36_kernel<..., DUST>: the 65th channel's weights (W36Dust, wblock36_mfma.h); else unused
   int dust_in;           // ... 1: the INPUT has a 65th channel too (x[..][64]: detector.layer.1), not covered by nchunk
+  int frame_h;           // wblock36s_kernel: rows of one frame of the stacked image (H = frames x frame_h, one "frame"); else 0
 #ifdef FPC_DIAG
   unsigned long long* stamps;
 #endif

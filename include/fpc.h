@@ -139,6 +139,7 @@ enum {
   FPC_PLAN_STEM_ROUND3 = 1 << 20,          /* FPC_F32: round 3's stem_pool_kernel also where round 5's stem_pool2_kernel applies (conv map of whole 16x16 tiles) (FPC_STEM_LEAN=0) */
   FPC_PLAN_CONV_ROUND1 = 1 << 21,          /* FPC_F32: round 1's conv_mfma_kernel also where round 5's conv2_mfma_kernel applies (ConvTranspose, layer_in.1's 1x1) (FPC_CONV_LEAN=0) */
   FPC_PLAN_CONVT_PHASES = 1 << 19,         /* FPC_BF16: the ConvTranspose as four output-parity launches (rounds 2-4) instead of round 5's one  (FPC_CONVT_FUSED=0) */
+  FPC_PLAN_TILES_ROUND5 = 1 << 22,         /* FPC_F32: round 5's tilings where round 6 picks the tile that issues fewer padded matrix rows (layer2.0 on 3x20 instead of 4x16); same blob, same plan hash, same results bit for bit  (FPC_TILES_ROUND6=0) */
   FPC_PLAN_GUARD_ZONES = 1 << 15           /* TEST FACILITY: 64 KiB of a canary pattern behind every buffer of the workspace and
                                               2 GiB behind the last one (the workspace grows by that much); fpc_check_guards
                                               counts the words a kernel has overwritten.  Not for production contexts.          */
@@ -210,6 +211,15 @@ int fpc_mark_weights_loaded(fpc_ctx* ctx);
 uint64_t fpc_plan_hash(const fpc_ctx* ctx);
 /* FPC_PACK_LAYOUT_REVISION of the library as built (a binding compares it with the header it was written against). */
 int fpc_pack_layout_revision(void);
+
+/* Which tiling a launch plan picks for a map -- the plan's own choice functions, answered without a device or a context
+ * (round 6; FPC_PLAN_TILES_ROUND5 in plan_flags gives round 5's answer).  FPC_E_INVALID for an unknown `what`.
+ *   what = 0: the 128-channel F(4x4,3x3) blocks.  Tile rows of ONE launch of `frames` frames of H x W walked as one
+ *             stacked image on 16 x 16 tiles, or 0 where the launch walks frame by frame (as few tiles, or fewer).
+ *   what = 1: a conv-only 64-channel launch of the paired F(4x4,3x3) kernel on an H x W map: its tile as
+ *             100 x tile height + tile width in pixels (1616, 832, or 3208 = the 8 x 2 arrangement).
+ *   what = 2: the stride-2 128-channel fused block (encoder.layer2.0) with an H x W OUTPUT: its tile likewise (320 or 416). */
+int fpc_tile_choice(int what, int H, int W, int frames, unsigned plan_flags);
 
 /* TEST FACILITY (contexts created with FPC_PLAN_GUARD_ZONES only; FPC_E_INVALID otherwise): waits for the device, then
  * counts the 32-bit words of the workspace's canary zones -- behind every activation / result buffer, and 2 GiB behind
