@@ -721,6 +721,17 @@ struct Carver {
     }
     return o;
   }
+  // take<T>(n) for a buffer whose pointer `*slot` becomes once the slab exists (bind): taken and assigned in one place
+  struct Bound { void* slot; size_t off; };
+  std::vector<Bound> bound;
+  template <typename T>
+  void into(T** slot, size_t n) { bound.push_back({slot, take<T>(n)}); }
+  void bind(char* slab) const {
+    for (const Bound& b : bound) {
+      char* p = slab + b.off;
+      memcpy(b.slot, &p, sizeof p);
+    }
+  }
   void finish() {
     if (guard) {
       zones->push_back({off, GUARD_TAIL});
@@ -784,6 +795,96 @@ static int alloc_side_slab(fpc_ctx* c, const Carver& cv, char** slab) {
 // ---- architecture walk ---------------------------------------------------------------
 // Builds ctx->ops with geometry and buffer pointers, and assigns blob offsets.  The
 // weight VALUES are filled by pack_all() when a checkpoint arrives.
+
+// The rest of the slab behind a network's activations: what post-processing, matching, RANSAC and the cell orders use,
+// the same buffers in the same order for both networks.  Then the slab itself: allocated, zeroed, its canary zones
+// filled, every pointer taken with Carver::into assigned.
+static int carve_results(fpc_ctx* c, Carver& cv) {
+  const size_t B = c->B, HW = (size_t)c->H * c->W, cap = c->cap;
+  // the matching buffers shrink to a stub where the Python network runs without descriptors (the C++ network's plan
+  // has always carved them whole)
+  const bool whole = c->vgg || c->cfg.descriptor_enabled != 0;
+  cv.into(&c->prob, B * HW);
+  cv.into(&c->nmsmap, B * HW); cv.into(&c->cand, B * HW);
+  cv.into(&c->ncand, B); cv.into(&c->count, B);
+  cv.into(&c->status, 4 + BLOB_HEADER_FLOATS);   // + the 64-byte tag of fpc_broadcast_weights
+  cv.into(&c->range, B * FPC_RANGE_WORDS);       // per-frame range words (kernels_misc.h)
+  cv.into(&c->rowmax, B * (c->H / 8));           // largest logit per row of cells (softmax_d2s_kernel)
+  cv.into(&c->xy, B * cap * 2); cv.into(&c->conf, B * cap);
+  cv.into(&c->desc_out, whole ? B * cap * c->D : 64);
+  cv.into(&c->sort_scratch, B * c->sort_cap);
+  cv.into(&c->nms_aux, B * NMS_AUX_INTS);
+  cv.into(&c->rowbest, cap); cv.into(&c->colbest, cap);
+  cv.into(&c->mf_norms, whole ? (B + 1) * cap : 64);
+  cv.into(&c->mf_top2, whole ? B * cap * 2 : 64);
+  cv.into(&c->mf_colbest, whole ? B * cap : 64);
+  cv.into(&c->hf_pairs, B * cap); cv.into(&c->hf_row, B * cap);
+  cv.into(&c->hf_np, B); cv.into(&c->hf_best, B);
+  cv.into(&c->mgc_perm_q, whole ? B * cap : 64); cv.into(&c->mgc_perm_t, whole ? B * cap : 64);
+  cv.into(&c->mgc_box, whole ? 2 * B * ((cap + 63) / 64) : 64);
+  cv.finish();
+  c->slab_bytes = cv.off;
+  if (hipMalloc((void**)&c->slab, c->slab_bytes) != hipSuccess) {
+    g_hip_err = "hipMalloc(workspace " + std::to_string(c->slab_bytes >> 20) + " MiB) failed";
+    return FPC_E_HIP;
+  }
+  HIPCHECK(hipMemset(c->slab, 0, c->slab_bytes));
+  if (int grc = fill_guards(c)) return grc;
+  cv.bind(c->slab);
+  c->bcast_tag = reinterpret_cast<uint32_t*>(c->status + 4);
+  return FPC_OK;
+}
+
+// An op without weights of its own: its (unused) blob offsets keep `convw` parallel to `ops`
+static Op& push_op(fpc_ctx* c, OpType type, const std::string& name) {
+  Op op;
+  op.type = type;
+  op.name = name;
+  c->ops.push_back(op);
+  c->convw.push_back({});
+  return c->ops.back();
+}
+
+// The end of either network's plan: the post-processing ops, the blob, and every op's weight pointers into it.
+// (A conv-only Winograd or split-operand op has no second stage: its w_off[1] and b2_off are 0, so w2 / b2 point at the
+// blob's tag, in bounds, and the kernels do not read them under conv_only.)
+static int finish_plan(fpc_ctx* c, size_t blob_floats) {
+  push_op(c, OP_NMS, "nms+sort+border_crop");
+  if (c->cfg.descriptor_enabled) push_op(c, OP_DESC, "descriptor_sample+l2norm");
+  for (Op& op : c->ops)
+    if (op.type == OP_SOFTMAX) op.bytes_per_frame = 4.0 * (65.0 * c->Hc * c->Wc + 2.0 * c->H * c->W);   // logits in; prob + NMS state map out
+  c->blob_floats = blob_floats;
+  HIPCHECK(hipMalloc((void**)&c->blob, c->blob_floats * sizeof(float)));
+  HIPCHECK(hipMemset(c->blob, 0, c->blob_floats * sizeof(float)));
+  for (size_t i = 0; i < c->ops.size(); ++i) {
+    Op& op = c->ops[i];
+    const fpc_ctx::ConvW& cw = c->convw[i];
+    const float *w1 = c->blob + cw.w_off[0], *w2 = c->blob + cw.w_off[1], *b1 = c->blob + cw.b_off, *b2 = c->blob + cw.b2_off;
+    switch (op.type) {
+      case OP_WBLOCK:
+        op.wargs.w1 = reinterpret_cast<const float4*>(w1); op.wargs.b1 = b1;
+        op.wargs.w2 = reinterpret_cast<const float4*>(w2); op.wargs.b2 = b2;
+        op.wargs.dust = g_wkinds[op.wkind].dust ? c->blob + cw.w_off[2] : nullptr;
+        break;
+      case OP_BF16:
+        op.fargs.w1 = reinterpret_cast<const uint4*>(w1); op.fargs.b1 = b1;
+        op.fargs.w2 = reinterpret_cast<const uint4*>(w2); op.fargs.b2 = b2;
+        break;
+      case OP_BLOCK:
+        op.bargs.w1 = reinterpret_cast<const float4*>(w1); op.bargs.b1 = b1;
+        op.bargs.w2 = reinterpret_cast<const float4*>(w2); op.bargs.b2 = b2;
+        break;
+      case OP_CONV:
+        for (int z = 0; z < op.grid_z; ++z)
+          op.args.sub[z].wfrag = reinterpret_cast<const float4*>(c->blob + cw.w_off[z]);
+        op.args.bias = b1;
+        break;
+      default:
+        break;
+    }
+  }
+  return FPC_OK;
+}
 
 struct ConvSpec {
   std::string name;
@@ -1386,13 +1487,7 @@ static void build_bf16_ops(fpc_ctx* c, size_t* bo) {
   add_fblock(c, {"detector.layer.0", FK_F816_s1_K128_C80w, feat, 256, 0, 128, 128, Hc, Wc, c->d0, 80, 0, 65, true, false}, bo);
   add_fblock(c, {"detector.layer.1", FK_F816_s1_K80_C80, c->d0, 80, 0, 65, 80, Hc, Wc, c->lg, 80, 1, 65, false, false}, bo);
   c->ops.back().fused_softmax_capable = c->fuse_softmax;
-  {
-    Op op;
-    op.type = OP_SOFTMAX;
-    op.name = "exp-softmax+depth_to_space+threshold";
-    c->ops.push_back(op);
-    c->convw.push_back({});
-  }
+  push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
   if (de) {
     add_fblock(c, {"descriptor.layer_in.0", FK_F320_s2_K128_C256, feat, 256, 0, 128, 128, Hc, Wc, c->y16a, 256, 0, 256, true, true}, bo);
     add_fblock(c, {"descriptor.layer_in.1", FK_F416_s1_K128_C256, c->y16a, 256, 0, 256, 256, H16, W16, c->y16b, 256, 0, 256, false, true}, bo);
@@ -1418,13 +1513,7 @@ static void build_x3_ops(fpc_ctx* c, size_t* bo) {
   add_fblock(c, {"encoder.layer2.1", split_kind(c, FK_S620_s1_K64_C128), c->x3, 128, 1, 128, 128, Hc, Wc, feat, 256, 1, 128, false, false}, bo);
   add_fblock(c, {"detector.layer.0", split_kind(c, FK_S620_s1_K64_C80), feat, 256, 1, 128, 128, Hc, Wc, c->d0, 80, 1, 65, true, false}, bo);
   add_fblock(c, {"detector.layer.1", split_kind(c, FK_S620_s1_K16_C80), c->d0, 80, 1, 65, 80, Hc, Wc, c->lg, 80, 1, 65, false, false}, bo);
-  {
-    Op op;
-    op.type = OP_SOFTMAX;
-    op.name = "exp-softmax+depth_to_space+threshold";
-    c->ops.push_back(op);
-    c->convw.push_back({});
-  }
+  push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
   if (de) {
     add_fblock(c, {"descriptor.layer_in.0", split_kind(c, FK_S320_s2_K16_C256), feat, 256, 1, 128, 128, Hc, Wc, c->y16a, 256, 1, 256, true, true}, bo);
     add_fblock(c, {"descriptor.layer_in.1", split_kind(c, FK_S320_s1_K64_C256), c->y16a, 256, 1, 256, 256, H16, W16, c->y16b, 256, 1, 256, false, true}, bo);
@@ -1494,65 +1583,15 @@ static int build_vgg_plan(fpc_ctx* c) {
   cv.guard = c->guard_zones ? GUARD_BYTES : 0;
   // activations: one buffer per tensor (sub-batches of one call run different layers at the same time)
   const int ah[4] = {H, H / 2, H / 4, Hc}, aw[4] = {W, W / 2, W / 4, Wc}, ac[4] = {64, 64, 128, 128};
-  size_t o_a[4], o_b[4], o_p[3];
+  float *act_a[4], *act_b[4], *act_p[3], *det_a, *desc_a;
   for (int i = 0; i < 4; ++i) {
-    o_a[i] = cv.take<float>((size_t)B * ah[i] * aw[i] * ac[i]);
-    o_b[i] = cv.take<float>((size_t)B * ah[i] * aw[i] * ac[i]);
-    if (i < 3) o_p[i] = cv.take<float>((size_t)B * ah[i + 1] * aw[i + 1] * ac[i]);
+    cv.into(&act_a[i], (size_t)B * ah[i] * aw[i] * ac[i]);
+    cv.into(&act_b[i], (size_t)B * ah[i] * aw[i] * ac[i]);
+    if (i < 3) cv.into(&act_p[i], (size_t)B * ah[i + 1] * aw[i + 1] * ac[i]);
   }
-  const size_t o_pa = cv.take<float>(npix8 * 256), o_da = cv.take<float>(npix8 * 256);
-  const size_t o_lg = cv.take<float>(npix8 * 80), o_desc = cv.take<float>(npix8 * 256), o_descin = cv.take<float>(npix8 * 256);
-  const size_t o_prob = cv.take<float>((size_t)B * H * W);
-  const size_t o_map = cv.take<uint32_t>((size_t)B * H * W), o_cand = cv.take<uint32_t>((size_t)B * H * W);
-  const size_t o_ncand = cv.take<int32_t>(B), o_count = cv.take<int32_t>(B), o_status = cv.take<int32_t>(4 + BLOB_HEADER_FLOATS);   // + the 64-byte tag of fpc_broadcast_weights
-  const size_t o_range = cv.take<uint32_t>((size_t)B * FPC_RANGE_WORDS);   // per-frame range words (kernels_misc.h)
-  const size_t o_rowmax = cv.take<float>((size_t)B * (H / 8));             // largest logit per row of cells (softmax_d2s_kernel)
-  const size_t o_xy = cv.take<int32_t>((size_t)B * c->cap * 2), o_conf = cv.take<float>((size_t)B * c->cap);
-  const size_t o_dout = cv.take<float>((size_t)B * c->cap * 256);
-  const size_t o_sort = cv.take<unsigned long long>((size_t)B * c->sort_cap);
-  const size_t o_aux = cv.take<int32_t>((size_t)B * NMS_AUX_INTS);
-  const size_t o_rowbest = cv.take<unsigned long long>(c->cap), o_colbest = cv.take<unsigned long long>(c->cap);
-  const size_t o_mfn = cv.take<float>((size_t)(B + 1) * c->cap), o_mft = cv.take<unsigned long long>((size_t)B * c->cap * 2);
-  const size_t o_mfc = cv.take<unsigned long long>((size_t)B * c->cap);
-  const size_t o_hfp = cv.take<float4>((size_t)B * c->cap), o_hfr = cv.take<int32_t>((size_t)B * c->cap);
-  const size_t o_hfn = cv.take<int32_t>(B), o_hfb = cv.take<unsigned long long>(B);
-  const size_t o_gpq = cv.take<int32_t>((size_t)B * c->cap), o_gpt = cv.take<int32_t>((size_t)B * c->cap);
-  const size_t o_gbx = cv.take<int4>((size_t)2 * B * ((c->cap + 63) / 64));
-  cv.finish();
-  c->slab_bytes = cv.off;
-  if (hipMalloc((void**)&c->slab, c->slab_bytes) != hipSuccess) {
-    g_hip_err = "hipMalloc(workspace " + std::to_string(c->slab_bytes >> 20) + " MiB) failed";
-    return FPC_E_HIP;
-  }
-  HIPCHECK(hipMemset(c->slab, 0, c->slab_bytes));
-  if (int grc = fill_guards(c)) return grc;
-  auto F = [&](size_t o) { return reinterpret_cast<float*>(c->slab + o); };
-  c->lg = F(o_lg); c->desc_map = F(o_desc); c->desc_in_nhwc = F(o_descin); c->prob = F(o_prob);
-  c->nmsmap = reinterpret_cast<uint32_t*>(c->slab + o_map);
-  c->cand = reinterpret_cast<uint32_t*>(c->slab + o_cand);
-  c->ncand = reinterpret_cast<int32_t*>(c->slab + o_ncand);
-  c->count = reinterpret_cast<int32_t*>(c->slab + o_count);
-  c->status = reinterpret_cast<int32_t*>(c->slab + o_status);
-  c->bcast_tag = reinterpret_cast<uint32_t*>(c->status + 4);
-  c->range = reinterpret_cast<uint32_t*>(c->slab + o_range);
-  c->rowmax = reinterpret_cast<float*>(c->slab + o_rowmax);
-  c->xy = reinterpret_cast<int32_t*>(c->slab + o_xy);
-  c->conf = F(o_conf);
-  c->desc_out = F(o_dout);
-  c->sort_scratch = reinterpret_cast<unsigned long long*>(c->slab + o_sort);
-  c->nms_aux = reinterpret_cast<int32_t*>(c->slab + o_aux);
-  c->rowbest = reinterpret_cast<unsigned long long*>(c->slab + o_rowbest);
-  c->colbest = reinterpret_cast<unsigned long long*>(c->slab + o_colbest);
-  c->mf_norms = F(o_mfn);
-  c->mf_top2 = reinterpret_cast<unsigned long long*>(c->slab + o_mft);
-  c->mf_colbest = reinterpret_cast<unsigned long long*>(c->slab + o_mfc);
-  c->hf_pairs = reinterpret_cast<float4*>(c->slab + o_hfp);
-  c->hf_row = reinterpret_cast<int32_t*>(c->slab + o_hfr);
-  c->hf_np = reinterpret_cast<int32_t*>(c->slab + o_hfn);
-  c->hf_best = reinterpret_cast<unsigned long long*>(c->slab + o_hfb);
-  c->mgc_perm_q = reinterpret_cast<int32_t*>(c->slab + o_gpq);
-  c->mgc_perm_t = reinterpret_cast<int32_t*>(c->slab + o_gpt);
-  c->mgc_box = reinterpret_cast<int4*>(c->slab + o_gbx);
+  cv.into(&det_a, npix8 * 256); cv.into(&desc_a, npix8 * 256);
+  cv.into(&c->lg, npix8 * 80); cv.into(&c->desc_map, npix8 * 256); cv.into(&c->desc_in_nhwc, npix8 * 256);
+  if (int rc = carve_results(c, cv)) return rc;
 
   size_t bo = BLOB_HEADER_FLOATS;
   c->ops.clear();
@@ -1605,19 +1644,15 @@ static int build_vgg_plan(fpc_ctx* c) {
   const float* x = nullptr;
   for (int i = 0; i < 4; ++i) {
     const std::string pa = "encoder_conv" + std::to_string(i) + "_a", pb = "encoder_conv" + std::to_string(i) + "_b";
-    float* a = F(o_a[i]);
-    float* b = F(o_b[i]);
+    float* a = act_a[i];
+    float* b = act_b[i];
     if (i == 0) {  // Conv2d(1, 64): K = 9, plain FMAs
-      Op op;
-      op.type = OP_VCONV0;
-      op.name = pa + " [conv+bias+relu, 1 input channel]";
+      Op& op = push_op(c, OP_VCONV0, pa + " [conv+bias+relu, 1 input channel]");
       op.prefix = pa;
       op.pout = a;
       op.pH = H; op.pW = W;
       op.flops_per_frame = 2.0 * H * W * 64 * 9;
       op.bytes_per_frame = 4.0 * ((double)H * W + 64.0 * H * W);
-      c->ops.push_back(op);
-      c->convw.push_back({});
       c->vconv0_off = bo;
       bo += 640;
     } else {
@@ -1625,77 +1660,28 @@ static int build_vgg_plan(fpc_ctx* c) {
     }
     conv(pb, a, ac[i], ah[i], aw[i], b, ac[i], ac[i], 3, true, false);
     if (i < 3) {
-      Op op;
-      op.type = OP_POOL2;
-      op.name = "max_pool2d(2,2) after " + pb;
+      Op& op = push_op(c, OP_POOL2, "max_pool2d(2,2) after " + pb);
       op.pin = b;
-      op.pout = F(o_p[i]);
+      op.pout = act_p[i];
       op.pH = ah[i]; op.pW = aw[i]; op.pC = ac[i];
       op.bytes_per_frame = 4.0 * 1.25 * ac[i] * ah[i] * aw[i];
-      c->ops.push_back(op);
-      c->convw.push_back({});
       x = op.pout;
     } else {
       x = b;
     }
   }
-  const int lgcs = c->lgcs;
-  conv("detector_conv_a", x, 128, Hc, Wc, F(o_pa), 256, 256, 3, true, false);
-  conv("detector_conv_b", F(o_pa), 256, Hc, Wc, c->lg, lgcs, 65, 1, false, false);
-  {
-    Op op;
-    op.type = OP_SOFTMAX;
-    op.name = "exp-softmax+depth_to_space+threshold";
-    c->ops.push_back(op);
-    c->convw.push_back({});
-  }
-  const bool de = c->cfg.descriptor_enabled != 0;
-  if (de) {
-    conv("descriptor_conv_a", x, 128, Hc, Wc, F(o_da), 256, 256, 3, true, true);
-    conv("descriptor_conv_b", F(o_da), 256, Hc, Wc, c->desc_map, 256, 256, 1, false, true);
-    Op op;
-    op.type = OP_L2NORM;
-    op.name = "descriptor L2 normalisation over channels";
+  conv("detector_conv_a", x, 128, Hc, Wc, det_a, 256, 256, 3, true, false);
+  conv("detector_conv_b", det_a, 256, Hc, Wc, c->lg, c->lgcs, 65, 1, false, false);
+  push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
+  if (c->cfg.descriptor_enabled) {
+    conv("descriptor_conv_a", x, 128, Hc, Wc, desc_a, 256, 256, 3, true, true);
+    conv("descriptor_conv_b", desc_a, 256, Hc, Wc, c->desc_map, 256, 256, 1, false, true);
+    Op& op = push_op(c, OP_L2NORM, "descriptor L2 normalisation over channels");
     op.descriptor_branch = true;
     op.pout = c->desc_map;
     op.bytes_per_frame = 4.0 * 2 * 256.0 * Hc * Wc;
-    c->ops.push_back(op);
-    c->convw.push_back({});
   }
-  {
-    Op op;
-    op.type = OP_NMS;
-    op.name = "nms+sort+border_crop";
-    c->ops.push_back(op);
-    c->convw.push_back({});
-    if (de) {
-      op.type = OP_DESC;
-      op.name = "descriptor_sample+l2norm";
-      c->ops.push_back(op);
-      c->convw.push_back({});
-    }
-  }
-  for (Op& op : c->ops)
-    if (op.type == OP_SOFTMAX) op.bytes_per_frame = 4.0 * (65.0 * Hc * Wc + 2.0 * H * W);
-  c->blob_floats = bo;
-  HIPCHECK(hipMalloc((void**)&c->blob, c->blob_floats * sizeof(float)));
-  HIPCHECK(hipMemset(c->blob, 0, c->blob_floats * sizeof(float)));
-  for (size_t i = 0; i < c->ops.size(); ++i) {
-    Op& op = c->ops[i];
-    if (op.type == OP_BF16) {
-      op.fargs.w1 = reinterpret_cast<const uint4*>(c->blob + c->convw[i].w_off[0]);
-      op.fargs.b1 = c->blob + c->convw[i].b_off;
-    }
-    if (op.type == OP_CONV) {
-      op.args.sub[0].wfrag = reinterpret_cast<const float4*>(c->blob + c->convw[i].w_off[0]);
-      op.args.bias = c->blob + c->convw[i].b_off;
-    }
-    if (op.type == OP_WBLOCK) {
-      op.wargs.w1 = reinterpret_cast<const float4*>(c->blob + c->convw[i].w_off[0]);
-      op.wargs.b1 = c->blob + c->convw[i].b_off;
-    }
-  }
-  return FPC_OK;
+  return finish_plan(c, bo);
 }
 
 // Rows H* of FPC_BF16_KINDS must mirror rows S* one for one.  (Round 1, gdb.log: with the two H*_1x1 rows still
@@ -1714,87 +1700,28 @@ static int build_plan(fpc_ctx* c) {
   const int H = c->H, W = c->W, B = c->B;
   const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, Hc = H / 8, Wc = W / 8, H16 = H / 16, W16 = W / 16;
   const bool de = c->cfg.descriptor_enabled != 0;
-  // ---- carve the slab
+  // ---- carve the slab: this network's activations, then what both networks share
   Carver cv;
   cv.zones = &c->guards;
   cv.guard = c->guard_zones ? GUARD_BYTES : 0;
-  const size_t o_stem = cv.take<float>((size_t)B * H2 * W2 * 64);
-  const size_t o_x0 = cv.take<float>((size_t)B * H4 * W4 * 64), o_h4 = cv.take<float>((size_t)B * H4 * W4 * 64);
-  const size_t o_x1 = cv.take<float>((size_t)B * H4 * W4 * 64), o_x2 = cv.take<float>((size_t)B * H4 * W4 * 64);
-  const size_t npix8 = (size_t)B * Hc * Wc, npix16 = (size_t)B * H16 * W16;
-  const size_t o_h8 = cv.take<float>(npix8 * 128), o_x3 = cv.take<float>(npix8 * 128);
-  const size_t o_cat = cv.take<float>(npix8 * 256);
-  const size_t o_dh = cv.take<float>(npix8 * 72), o_dproj = cv.take<float>(npix8 * 72);
-  const size_t o_d0 = cv.take<float>(npix8 * 80), o_lg = cv.take<float>(npix8 * 80);
-  const size_t o_h16 = cv.take<float>(npix16 * 256), o_y16a = cv.take<float>(npix16 * 256);
-  const size_t o_y16b = cv.take<float>(npix16 * 256);
-  const size_t o_loh = cv.take<float>(npix8 * 128), o_lo0 = cv.take<float>(npix8 * 128);
-  const size_t o_desc = cv.take<float>(npix8 * 128), o_descin = cv.take<float>(npix8 * 128);
-  const size_t o_prob = cv.take<float>((size_t)B * H * W);
-  const size_t o_map = cv.take<uint32_t>((size_t)B * H * W), o_cand = cv.take<uint32_t>((size_t)B * H * W);
-  const size_t o_ncand = cv.take<int32_t>(B), o_count = cv.take<int32_t>(B), o_status = cv.take<int32_t>(4 + BLOB_HEADER_FLOATS);   // + the 64-byte tag of fpc_broadcast_weights
-  const size_t o_range = cv.take<uint32_t>((size_t)B * FPC_RANGE_WORDS);   // per-frame range words (kernels_misc.h)
-  const size_t o_rowmax = cv.take<float>((size_t)B * (H / 8));             // largest logit per row of cells (softmax_d2s_kernel)
-  const size_t o_xy = cv.take<int32_t>((size_t)B * c->cap * 2), o_conf = cv.take<float>((size_t)B * c->cap);
-  const size_t o_dout = cv.take<float>(de ? (size_t)B * c->cap * 128 : 64);
-  const size_t o_sort = cv.take<unsigned long long>((size_t)B * c->sort_cap);
-  const size_t o_aux = cv.take<int32_t>((size_t)B * NMS_AUX_INTS);
-  const size_t o_rowbest = cv.take<unsigned long long>(c->cap), o_colbest = cv.take<unsigned long long>(c->cap);
-  const size_t o_mfn = cv.take<float>(de ? (size_t)(B + 1) * c->cap : 64);
-  const size_t o_mft = cv.take<unsigned long long>(de ? (size_t)B * c->cap * 2 : 64);
-  const size_t o_mfc = cv.take<unsigned long long>(de ? (size_t)B * c->cap : 64);
-  const size_t o_hfp = cv.take<float4>((size_t)B * c->cap), o_hfr = cv.take<int32_t>((size_t)B * c->cap);
-  const size_t o_hfn = cv.take<int32_t>(B), o_hfb = cv.take<unsigned long long>(B);
-  const size_t o_gpq = cv.take<int32_t>(de ? (size_t)B * c->cap : 64), o_gpt = cv.take<int32_t>(de ? (size_t)B * c->cap : 64);
-  const size_t o_gbx = cv.take<int4>(de ? (size_t)2 * B * ((c->cap + 63) / 64) : 64);
-  cv.finish();
-  c->slab_bytes = cv.off;
-  if (hipMalloc((void**)&c->slab, c->slab_bytes) != hipSuccess) {
-    g_hip_err = "hipMalloc(workspace " + std::to_string(c->slab_bytes >> 20) + " MiB) failed";
-    return FPC_E_HIP;
-  }
-  HIPCHECK(hipMemset(c->slab, 0, c->slab_bytes));
-  if (int grc = fill_guards(c)) return grc;
-  auto F = [&](size_t o) { return reinterpret_cast<float*>(c->slab + o); };
-  c->stem_out = F(o_stem); c->x0 = F(o_x0); c->h4 = F(o_h4); c->x1 = F(o_x1); c->x2 = F(o_x2);
-  c->h8 = F(o_h8); c->x3 = F(o_x3); c->cat = F(o_cat); c->dh = F(o_dh); c->dproj = F(o_dproj);
-  c->d0 = F(o_d0); c->lg = F(o_lg); c->h16 = F(o_h16); c->y16a = F(o_y16a); c->y16b = F(o_y16b);
-  c->lo_h = F(o_loh); c->lo0 = F(o_lo0); c->desc_map = F(o_desc); c->desc_in_nhwc = F(o_descin);
-  c->prob = F(o_prob);
-  c->nmsmap = reinterpret_cast<uint32_t*>(c->slab + o_map);
-  c->cand = reinterpret_cast<uint32_t*>(c->slab + o_cand);
-  c->ncand = reinterpret_cast<int32_t*>(c->slab + o_ncand);
-  c->count = reinterpret_cast<int32_t*>(c->slab + o_count);
-  c->status = reinterpret_cast<int32_t*>(c->slab + o_status);
-  c->bcast_tag = reinterpret_cast<uint32_t*>(c->status + 4);
-  c->range = reinterpret_cast<uint32_t*>(c->slab + o_range);
-  c->rowmax = reinterpret_cast<float*>(c->slab + o_rowmax);
-  c->xy = reinterpret_cast<int32_t*>(c->slab + o_xy);
-  c->conf = F(o_conf);
-  c->desc_out = F(o_dout);
-  c->sort_scratch = reinterpret_cast<unsigned long long*>(c->slab + o_sort);
-  c->nms_aux = reinterpret_cast<int32_t*>(c->slab + o_aux);
-  c->rowbest = reinterpret_cast<unsigned long long*>(c->slab + o_rowbest);
-  c->colbest = reinterpret_cast<unsigned long long*>(c->slab + o_colbest);
-  c->mf_norms = F(o_mfn);
-  c->mf_top2 = reinterpret_cast<unsigned long long*>(c->slab + o_mft);
-  c->mf_colbest = reinterpret_cast<unsigned long long*>(c->slab + o_mfc);
-  c->hf_pairs = reinterpret_cast<float4*>(c->slab + o_hfp);
-  c->hf_row = reinterpret_cast<int32_t*>(c->slab + o_hfr);
-  c->hf_np = reinterpret_cast<int32_t*>(c->slab + o_hfn);
-  c->hf_best = reinterpret_cast<unsigned long long*>(c->slab + o_hfb);
-  c->mgc_perm_q = reinterpret_cast<int32_t*>(c->slab + o_gpq);
-  c->mgc_perm_t = reinterpret_cast<int32_t*>(c->slab + o_gpt);
-  c->mgc_box = reinterpret_cast<int4*>(c->slab + o_gbx);
+  const size_t npix4 = (size_t)B * H4 * W4, npix8 = (size_t)B * Hc * Wc, npix16 = (size_t)B * H16 * W16;
+  cv.into(&c->stem_out, (size_t)B * H2 * W2 * 64);
+  cv.into(&c->x0, npix4 * 64); cv.into(&c->h4, npix4 * 64); cv.into(&c->x1, npix4 * 64); cv.into(&c->x2, npix4 * 64);
+  cv.into(&c->h8, npix8 * 128); cv.into(&c->x3, npix8 * 128);
+  cv.into(&c->cat, npix8 * 256);
+  cv.into(&c->dh, npix8 * 72); cv.into(&c->dproj, npix8 * 72);
+  cv.into(&c->d0, npix8 * 80); cv.into(&c->lg, npix8 * 80);
+  cv.into(&c->h16, npix16 * 256); cv.into(&c->y16a, npix16 * 256); cv.into(&c->y16b, npix16 * 256);
+  cv.into(&c->lo_h, npix8 * 128); cv.into(&c->lo0, npix8 * 128);
+  cv.into(&c->desc_map, npix8 * 128); cv.into(&c->desc_in_nhwc, npix8 * 128);
+  if (int rc = carve_results(c, cv)) return rc;
 
   // ---- ops
   size_t bo = BLOB_HEADER_FLOATS;  // blob offset in floats (the tag of the packed format comes first)
   c->ops.clear();
   c->convw.clear();
   {
-    Op op;
-    op.type = OP_STEM;
-    op.name = "encoder.conv1+bn1+relu";
+    Op& op = push_op(c, OP_STEM, "encoder.conv1+bn1+relu");
     op.flops_per_frame = 2.0 * H2 * W2 * 64 * 147;  // of the reference's 3-channel convolution, also for gray frames
     op.mfma_flops_per_frame = 2.0 * ((H2 + 15) / 16) * ((W2 + 15) / 16) * 256.0 * 64 * 152;
     op.bytes_per_frame = 4.0 * (double)c->cin * H * W + (c->bf16 ? 2.0 : 4.0) * 64.0 * H4 * W4;   // frame in, pooled map out
@@ -1802,18 +1729,12 @@ static int build_plan(fpc_ctx* c) {
       op.mfma_flops_per_frame = (c->bf16 ? 1 : c->split_f16 ? 3 : 6) * 2.0 * ((H2 + 15) / 16) * ((W2 + 15) / 16) * 256.0 * 64 * 16.0 * ((c->cin * 7 + 1) / 2);
     if (c->bf16)              // stem_bf16_kernel: 8 x 7 pooled pixels per tile, 8 blocks of 32 pixels x 64 channels x K16 steps
       op.mfma_flops_per_frame = 2.0 * ((H4 + SB2_PH - 1) / SB2_PH) * ((W4 + SB2_PW - 1) / SB2_PW) * 256.0 * 64 * 16.0 * ((c->cin * 7 + 1) / 2);
-    c->ops.push_back(op);
-    c->convw.push_back({});
     c->stem_w_off = bo;
     // + two zero groups: the fused kernel prefetches ahead; the split-operand stem needs 13 steps x 3 planes
     bo += std::max<size_t>((size_t)(STEM_KG + 2) * 2 * 64 * 4, (size_t)13 * 3 * 2 * 64 * 4);
     c->stem_b_off = bo;
     bo += 64;
-    op = Op();
-    op.type = OP_POOL;
-    op.name = "encoder.max_pool";
-    c->ops.push_back(op);
-    c->convw.push_back({});
+    push_op(c, OP_POOL, "encoder.max_pool");
   }
   auto block = [&](const std::string& p, Kind k3, Kind k1, int stride, const float* x, int csx, int cin, int cinp,
                    int Hx, int Wx, float* h, int csh, int cout, int coutp, float* y, int csy, bool proj,
@@ -1908,13 +1829,7 @@ static int build_plan(fpc_ctx* c) {
   }
   block("detector.layer.1", K_T620_3x3_K72_N96, K_T620_1x1_K72_N96, 1, c->d0, 72, 65, 72, Hc, Wc, c->dh, 72, 65, 72,
         c->lg, 72, false, false, BK_B620_s1_K72_C72);
-  {
-    Op op;
-    op.type = OP_SOFTMAX;
-    op.name = "exp-softmax+depth_to_space+threshold";
-    c->ops.push_back(op);
-    c->convw.push_back({});
-  }
+  push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
   if (de) {
     block("descriptor.layer_in.0", K_T620_3x3s2_K32_N128, K_T620_1x1_K64_N128, 2, feat, 256, 128, 128, Hc, Wc, c->h16,
           256, 256, 256, c->y16a, 256, true, true, BK_B320_s2_K32_C256);
@@ -1993,51 +1908,7 @@ static int build_plan(fpc_ctx* c) {
   }
   }
 postproc:
-  {
-    Op op;
-    op.type = OP_NMS;
-    op.name = "nms+sort+border_crop";
-    c->ops.push_back(op);
-    c->convw.push_back({});
-    if (de) {
-      op.type = OP_DESC;
-      op.name = "descriptor_sample+l2norm";
-      c->ops.push_back(op);
-      c->convw.push_back({});
-    }
-  }
-  for (Op& op : c->ops)
-    if (op.type == OP_SOFTMAX) op.bytes_per_frame = 4.0 * (65.0 * Hc * Wc + 2.0 * H * W);   // logits in; prob + NMS state map out
-  c->blob_floats = bo;
-  HIPCHECK(hipMalloc((void**)&c->blob, c->blob_floats * sizeof(float)));
-  HIPCHECK(hipMemset(c->blob, 0, c->blob_floats * sizeof(float)));
-  // resolve weight pointers
-  for (size_t i = 0; i < c->ops.size(); ++i) {
-    Op& op = c->ops[i];
-    if (op.type == OP_WBLOCK) {
-      op.wargs.w1 = reinterpret_cast<const float4*>(c->blob + c->convw[i].w_off[0]);
-      op.wargs.b1 = c->blob + c->convw[i].b_off;
-      op.wargs.w2 = reinterpret_cast<const float4*>(c->blob + c->convw[i].w_off[1]);
-      op.wargs.b2 = c->blob + c->convw[i].b2_off;
-      op.wargs.dust = g_wkinds[op.wkind].dust ? c->blob + c->convw[i].w_off[2] : nullptr;
-    }
-    if (op.type == OP_BF16) {
-      op.fargs.w1 = reinterpret_cast<const uint4*>(c->blob + c->convw[i].w_off[0]);
-      op.fargs.b1 = c->blob + c->convw[i].b_off;
-      op.fargs.w2 = reinterpret_cast<const uint4*>(c->blob + c->convw[i].w_off[1]);
-      op.fargs.b2 = c->blob + c->convw[i].b2_off;
-    }
-    if (op.type == OP_BLOCK) {
-      op.bargs.w1 = reinterpret_cast<const float4*>(c->blob + c->convw[i].w_off[0]);
-      op.bargs.b1 = c->blob + c->convw[i].b_off;
-      op.bargs.w2 = reinterpret_cast<const float4*>(c->blob + c->convw[i].w_off[1]);
-      op.bargs.b2 = c->blob + c->convw[i].b2_off;
-    }
-    if (op.type != OP_CONV) continue;
-    for (int z = 0; z < op.grid_z; ++z)
-      op.args.sub[z].wfrag = reinterpret_cast<const float4*>(c->blob + c->convw[i].w_off[z]);
-    op.args.bias = c->blob + c->convw[i].b_off;
-  }
+  if (int rc = finish_plan(c, bo)) return rc;
   c->stem.wfrag = reinterpret_cast<const float4*>(c->blob + c->stem_w_off);
   c->stem.bias = c->blob + c->stem_b_off;
   c->stem.out = c->stem_out;
@@ -2192,84 +2063,154 @@ static int pack_all(fpc_ctx* c, const TensorMap& m, std::string* missing) {
   if (rc == FPC_OK) fill_blob_header(c, reinterpret_cast<uint32_t*>(c->host_blob.data()));
   return rc;
 }
-static int pack_all_impl(fpc_ctx* c, const TensorMap& m, std::string* missing, bool& range_bad) {
-  std::vector<float>& blob = c->host_blob;
-  blob.assign(c->blob_floats, 0.f);
-  auto need = [&](const std::string& k, std::initializer_list<int64_t> shp) -> const float* {
+// What every packer below works with: the context and its host blob, the checkpoint, where the first missing key goes.
+struct Packer {
+  fpc_ctx* c;
+  const TensorMap& m;
+  std::string* missing;
+  bool& range_bad;
+  const float* need(const std::string& k, std::initializer_list<int64_t> shp) const {
     if (!has_shape(m, k, shp)) {
       if (missing->empty()) *missing = k;
       return nullptr;
     }
     return m.at(k).data;
-  };
-  if (c->vgg) {  // superpoint::SPModel: Conv2d weights + biases, no BatchNorm (cpp/src/model.cc:4-58)
-    static const std::vector<double> ones(256, 1.0);
-    for (size_t i = 0; i < c->ops.size(); ++i) {
-      const Op& op = c->ops[i];
-      if (op.type == OP_VCONV0) {
-        const float* w = need(op.prefix + ".weight", {64, 1, 3, 3});
-        const float* bv = need(op.prefix + ".bias", {64});
-        if (!w || !bv) return FPC_E_MISSING_KEY;
-        float* dst = blob.data() + c->vconv0_off;
-        for (int t = 0; t < 9; ++t)
-          for (int n = 0; n < 64; ++n) dst[t * 64 + n] = w[n * 9 + t];
-        for (int n = 0; n < 64; ++n) dst[576 + n] = bv[n];
-        continue;
-      }
-      if (!op.plain_conv || op.type == OP_WBLOCK) continue;   // Winograd conv-only launches: generic loop below
-      const int ci = op.cin, co = op.cout, kk = op.ksize * op.ksize;
-      const float* w = need(op.prefix + ".weight", {co, ci, op.ksize, op.ksize});
-      const float* bv = need(op.prefix + ".bias", {co});
-      if (!w || !bv) return FPC_E_MISSING_KEY;
-      const fpc_ctx::ConvW& cw = c->convw[i];
-      PackSource src{ci, ci, kk, [&](int n, int cc, int t) { return (double)w[((size_t)n * ci + cc) * kk + t]; }, &ones};
-      std::vector<float> frag;
-      if (op.type == OP_BF16) {
-        const FKindInfo& k = g_fkinds[op.fkind];
-        frag = pack_conv_bf16({src}, co, k.WN * k.NB, k.KC, k.planes, &range_bad);
-      } else {
-        frag = pack_conv({src}, co, op.args.nbt, g_kinds[op.kind].KC);
-      }
-      memcpy(blob.data() + cw.w_off[0], frag.data(), frag.size() * sizeof(float));
-      for (int n = 0; n < co; ++n) blob[cw.b_off + n] = bv[n];
-    }
   }
-  // stem
-  if (!c->vgg) {
-    const float* w = need("encoder.conv1.weight", {64, 3, 7, 7});
-    Fold f;
-    if (!w || !fold_bn(m, "encoder.bn1", 64, &f, missing)) return FPC_E_MISSING_KEY;
-    float* dst = blob.data() + c->stem_w_off;
-    const int kreal = c->cin * 49, kg = (kreal + 7) / 8;
-    if (c->split || c->bf16) {  // stem_pool_x3_kernel: [step][plane][nb][lane] x 8 bf16; k = (row = 2*step + half, kx = j)
-      uint16_t* d16 = reinterpret_cast<uint16_t*>(dst);
-      const int rows = c->cin * 7, steps = (rows + 1) / 2;
-      for (int st = 0; st < steps; ++st)
-        for (int nb = 0; nb < 2; ++nb)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-              const int row = 2 * st + (lane >> 5), n = nb * 32 + (lane & 31);
-              double v = 0.0;
-              if (row < rows && j > 0) {     // j = 0: the zero-weight pad (LDS column 0 is one pixel left of the window)
-                const int k = row * 7 + j - 1;  // (c, ky, kx = j - 1) flattened exactly as conv1.weight[n]
-                if (c->cin == 3) v = (double)w[n * 147 + k];
-                else v = (double)w[n * 147 + k] + (double)w[n * 147 + 49 + k] + (double)w[n * 147 + 98 + k];
-              }
-              const float wv = (float)(v * f.s[n]);
-              if (c->bf16) {
-                d16[(((size_t)st * 2 + nb) * 64 + lane) * 8 + j] = host_f2bf(wv);
-              } else if (c->split_f16) {
-                if (!(std::fabs(wv) <= 65504.f)) range_bad = true;
-                uint16_t t2[2];
-                host_split2_f16(wv, t2);
-                for (int pl = 0; pl < 2; ++pl) d16[((((size_t)st * 2 + pl) * 2 + nb) * 64 + lane) * 8 + j] = t2[pl];
-              } else {
-                uint16_t t3[3];
-                host_split3(wv, t3);
-                for (int pl = 0; pl < 3; ++pl) d16[((((size_t)st * 3 + pl) * 2 + nb) * 64 + lane) * 8 + j] = t3[pl];
-              }
+  float* at(size_t off) const { return c->host_blob.data() + off; }
+  void put(const std::vector<float>& frag, size_t off) const { memcpy(at(off), frag.data(), frag.size() * sizeof(float)); }
+};
+
+// A ResNetBlock's checkpoint entries under `p`: conv1, conv2, the optional projection shortcut, their folded BatchNorms
+// and the bias behind conv2 (bn2's, plus the projection's bn's)
+struct BlockWeights {
+  const float *w1 = nullptr, *w2 = nullptr, *wp = nullptr;
+  Fold f1, f2, fp;
+  std::vector<double> bias;
+};
+static bool load_block(const Packer& pk, const std::string& p, int ci, int co, bool proj, BlockWeights* b) {
+  b->w1 = pk.need(p + ".conv1.weight", {co, ci, 3, 3});
+  b->w2 = pk.need(p + ".conv2.weight", {co, co, 1, 1});
+  if (!b->w1 || !b->w2 || !fold_bn(pk.m, p + ".bn1", co, &b->f1, pk.missing) || !fold_bn(pk.m, p + ".bn2", co, &b->f2, pk.missing))
+    return false;
+  b->bias = b->f2.t;
+  if (!proj) return true;
+  b->wp = pk.need(p + ".identity_downsample.0.weight", {co, ci, 1, 1});
+  if (!b->wp || !fold_bn(pk.m, p + ".identity_downsample.1", co, &b->fp, pk.missing)) return false;
+  for (int n = 0; n < co; ++n) b->bias[n] += b->fp.t[n];
+  return true;
+}
+// The K sources of a block's 1x1 stage: conv2 over h (padded to `hpad` channels) and, with `xpad`, the projection over x
+static std::vector<PackSource> block_1x1_sources(const BlockWeights& b, int ci, int co, int hpad, int xpad) {
+  std::vector<PackSource> srcs;
+  srcs.push_back({co, hpad, 1, [&b, co](int n, int c_, int) { return (double)b.w2[(size_t)n * co + c_]; }, &b.f2.s});
+  if (b.wp && xpad > 0)
+    srcs.push_back({ci, xpad, 1, [&b, ci](int n, int c_, int) { return (double)b.wp[(size_t)n * ci + c_]; }, &b.fp.s});
+  return srcs;
+}
+
+// Generation-1 Winograd fragments (wblock_mfma.h): U [nn][ci][16] as [chunk][xi][k8][nb][lane] float4
+static void pack_w8_winograd(const std::vector<double>& U, int nn, int ci, const WKindInfo& k, int nchunk, float* dst) {
+  const int nbt = k.NBT, K8 = k.KC / 8;
+  for (int ch = 0; ch < nchunk; ++ch)
+    for (int xi = 0; xi < 16; ++xi)
+      for (int k8 = 0; k8 < K8; ++k8)
+        for (int nb = 0; nb < nbt; ++nb)
+          for (int lane = 0; lane < 64; ++lane) {
+            const int n = nb * 32 + (lane & 31), half = lane >> 5;
+            float* d4 = dst + (((((size_t)ch * 16 + xi) * K8 + k8) * nbt + nb) * 64 + lane) * 4;
+            for (int j = 0; j < 4; ++j) {
+              const int cc = ch * k.KC + k8 * 8 + 4 * half + j;
+              d4[j] = (n < nn && cc < ci) ? (float)U[((size_t)n * ci + cc) * 16 + xi] : 0.f;
             }
-    } else
+          }
+}
+// Winograd-domain filters U of output channels 0 .. nn - 1 in the layout of the op's generation
+static void pack_winograd(const std::vector<double>& U, int nn, int ci, const WKindInfo& k, int nchunk, float* dst) {
+  if (k.gen == 3) pack_w36_winograd(U, nn, ci, k, nchunk, dst);
+  else if (k.gen == 2) pack_w16_winograd(U, nn, ci, k.NCG, nchunk, dst);
+  else pack_w8_winograd(U, nn, ci, k, nchunk, dst);
+}
+
+// ConvTranspose2d(k3, s2, p1, op1): the (ky, kx) of output-parity phase `ph`, in the order add_conv / add_fconvT laid its taps out
+static std::vector<std::pair<int, int>> convt_phase_taps(int ph) {
+  const int py = ph >> 1, px = ph & 1;
+  std::vector<std::pair<int, int>> taps;
+  for (int iy = 0; iy < (py ? 2 : 1); ++iy)
+    for (int ix = 0; ix < (px ? 2 : 1); ++ix) taps.push_back({py ? (iy == 0 ? 0 : 2) : 1, px ? (ix == 0 ? 0 : 2) : 1});
+  return taps;
+}
+
+// superpoint::SPModel: Conv2d weights + biases, no BatchNorm (cpp/src/model.cc:4-58) -- every layer that is not a
+// Winograd launch (those: pack_wblock)
+static int pack_vgg_convs(const Packer& pk) {
+  fpc_ctx* c = pk.c;
+  static const std::vector<double> ones(256, 1.0);
+  for (size_t i = 0; i < c->ops.size(); ++i) {
+    const Op& op = c->ops[i];
+    if (op.type == OP_VCONV0) {
+      const float* w = pk.need(op.prefix + ".weight", {64, 1, 3, 3});
+      const float* bv = pk.need(op.prefix + ".bias", {64});
+      if (!w || !bv) return FPC_E_MISSING_KEY;
+      float* dst = pk.at(c->vconv0_off);
+      for (int t = 0; t < 9; ++t)
+        for (int n = 0; n < 64; ++n) dst[t * 64 + n] = w[n * 9 + t];
+      for (int n = 0; n < 64; ++n) dst[576 + n] = bv[n];
+      continue;
+    }
+    if (!op.plain_conv || op.type == OP_WBLOCK) continue;
+    const int ci = op.cin, co = op.cout, kk = op.ksize * op.ksize;
+    const float* w = pk.need(op.prefix + ".weight", {co, ci, op.ksize, op.ksize});
+    const float* bv = pk.need(op.prefix + ".bias", {co});
+    if (!w || !bv) return FPC_E_MISSING_KEY;
+    const fpc_ctx::ConvW& cw = c->convw[i];
+    PackSource src{ci, ci, kk, [&](int n, int cc, int t) { return (double)w[((size_t)n * ci + cc) * kk + t]; }, &ones};
+    if (op.type == OP_BF16) {
+      const FKindInfo& k = g_fkinds[op.fkind];
+      pk.put(pack_conv_bf16({src}, co, k.WN * k.NB, k.KC, k.planes, &pk.range_bad), cw.w_off[0]);
+    } else {
+      pk.put(pack_conv({src}, co, op.args.nbt, g_kinds[op.kind].KC), cw.w_off[0]);
+    }
+    for (int n = 0; n < co; ++n) pk.at(cw.b_off)[n] = bv[n];
+  }
+  return FPC_OK;
+}
+
+static int pack_stem(const Packer& pk) {
+  fpc_ctx* c = pk.c;
+  const float* w = pk.need("encoder.conv1.weight", {64, 3, 7, 7});
+  Fold f;
+  if (!w || !fold_bn(pk.m, "encoder.bn1", 64, &f, pk.missing)) return FPC_E_MISSING_KEY;
+  float* dst = pk.at(c->stem_w_off);
+  const int kreal = c->cin * 49, kg = (kreal + 7) / 8;
+  if (c->split || c->bf16) {  // stem_pool_x3_kernel: [step][plane][nb][lane] x 8 bf16; k = (row = 2*step + half, kx = j)
+    uint16_t* d16 = reinterpret_cast<uint16_t*>(dst);
+    const int rows = c->cin * 7, steps = (rows + 1) / 2;
+    for (int st = 0; st < steps; ++st)
+      for (int nb = 0; nb < 2; ++nb)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 8; ++j) {
+            const int row = 2 * st + (lane >> 5), n = nb * 32 + (lane & 31);
+            double v = 0.0;
+            if (row < rows && j > 0) {     // j = 0: the zero-weight pad (LDS column 0 is one pixel left of the window)
+              const int k = row * 7 + j - 1;  // (c, ky, kx = j - 1) flattened exactly as conv1.weight[n]
+              if (c->cin == 3) v = (double)w[n * 147 + k];
+              else v = (double)w[n * 147 + k] + (double)w[n * 147 + 49 + k] + (double)w[n * 147 + 98 + k];
+            }
+            const float wv = (float)(v * f.s[n]);
+            if (c->bf16) {
+              d16[(((size_t)st * 2 + nb) * 64 + lane) * 8 + j] = host_f2bf(wv);
+            } else if (c->split_f16) {
+              if (!(std::fabs(wv) <= 65504.f)) pk.range_bad = true;
+              uint16_t t2[2];
+              host_split2_f16(wv, t2);
+              for (int pl = 0; pl < 2; ++pl) d16[((((size_t)st * 2 + pl) * 2 + nb) * 64 + lane) * 8 + j] = t2[pl];
+            } else {
+              uint16_t t3[3];
+              host_split3(wv, t3);
+              for (int pl = 0; pl < 3; ++pl) d16[((((size_t)st * 3 + pl) * 2 + nb) * 64 + lane) * 8 + j] = t3[pl];
+            }
+          }
+  } else {
     for (int g = 0; g < kg; ++g)
       for (int nb = 0; nb < 2; ++nb)
         for (int lane = 0; lane < 64; ++lane)
@@ -2288,300 +2229,231 @@ static int pack_all_impl(fpc_ctx* c, const TensorMap& m, std::string* missing, b
             }
             dst[(((size_t)g * 2 + nb) * 64 + lane) * 4 + j] = (float)(v * f.s[n]);
           }
-    for (int n = 0; n < 64; ++n) blob[c->stem_b_off + n] = (float)f.t[n];
   }
+  for (int n = 0; n < 64; ++n) pk.at(c->stem_b_off)[n] = (float)f.t[n];
+  return FPC_OK;
+}
+
+static int pack_wblock(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw) {
+  const WKindInfo& k = g_wkinds[op.wkind];
+  const WBlockArgs& a = op.wargs;
+  const std::string& p = op.prefix;
+  const int ci = op.cin, co = op.cout, nbt = k.NBT, P = k.gen == 3 ? 36 : 16;
+  if (op.wconv) {  // conv-only launch: U = G g G^T of output channels n0 .. n0 + CMID - 1
+    const float* w1 = pk.need(p + (op.plain_conv ? ".weight" : ".conv1.weight"), {co, ci, 3, 3});
+    Fold f1;
+    if (!w1) return FPC_E_MISSING_KEY;
+    if (op.plain_conv) {
+      const float* bv = pk.need(p + ".bias", {co});
+      if (!bv) return FPC_E_MISSING_KEY;
+      f1.s.assign(co, 1.0);
+      f1.t.assign(bv, bv + co);
+    } else if (!fold_bn(pk.m, p + ".bn1", co, &f1, pk.missing)) {
+      return FPC_E_MISSING_KEY;
+    }
+    const int nn = std::min(k.CMID, co - op.n0);
+    pack_winograd(winograd_filters(w1, op.n0, nn, ci, f1.s, P), nn, ci, k, a.nchunk, pk.at(cw.w_off[0]));
+    for (int n = 0; n < nn; ++n) pk.at(cw.b_off)[n] = (float)f1.t[op.n0 + n];
+    return FPC_OK;
+  }
+  BlockWeights b;
+  if (!load_block(pk, p, ci, co, a.k8_x > 0, &b)) return FPC_E_MISSING_KEY;
+  // U = G (g * s) G^T in double, rounded once
+  const std::vector<double> U = winograd_filters(b.w1, 0, co, ci, b.f1.s, P);
+  pack_winograd(U, co, ci, k, a.nchunk, pk.at(cw.w_off[0]));
+  for (int n = 0; n < std::min(co, nbt * 32); ++n) pk.at(cw.b_off)[n] = (float)b.f1.t[n];
+  const std::vector<PackSource> srcs = block_1x1_sources(b, ci, co, a.k8_h * 8, a.k8_x * 8);
+  if (k.gen >= 2) pack_w16_1x1(srcs, co, k.NCG, pk.at(cw.w_off[1]));
+  else pk.put(pack_conv(srcs, co, nbt, 8), cw.w_off[1]);
+  for (int n = 0; n < std::min(co, nbt * 32); ++n) pk.at(cw.b2_off)[n] = (float)b.bias[n];
+  if (k.dust) {   // the 65th channel's weights (W36Dust, wblock36_mfma.h)
+    float* d = pk.at(cw.w_off[2]);
+    for (int n = 0; n < 64; ++n) d[W36Dust::W2ROW + n] = (float)((double)b.w2[(size_t)n * co + 64] * b.f2.s[n]);
+    for (int kk = 0; kk < 65; ++kk) d[W36Dust::W2COL + kk] = (float)((double)b.w2[(size_t)64 * co + kk] * b.f2.s[64]);
+    if (b.wp)
+      for (int cc = 0; cc < ci; ++cc) d[W36Dust::WPCOL + cc] = (float)((double)b.wp[(size_t)64 * ci + cc] * b.fp.s[64]);
+    d[W36Dust::B1] = (float)b.f1.t[64];
+    d[W36Dust::B2] = (float)b.bias[64];
+    if (a.dust_in) {
+      for (int pp = 0; pp < 36; ++pp) d[W36Dust::UIN64 + pp] = (float)U[((size_t)64 * ci + 64) * 36 + pp];
+      for (int cg = 0; cg < 4; ++cg)
+        for (int pp = 0; pp < 36; ++pp)
+          for (int n16 = 0; n16 < 16; ++n16)
+            d[W36Dust::UIN + (cg * 36 + pp) * 16 + n16] = (float)U[((size_t)(16 * cg + n16) * ci + 64) * 36 + pp];
+    }
+    for (int ch = 0; ch < a.nchunk; ++ch)
+      for (int pp = 0; pp < 36; ++pp)
+        for (int kk = 0; kk < 16; ++kk)
+          d[W36Dust::UOUT + (ch * 36 + pp) * 16 + kk] = 16 * ch + kk < ci ? (float)U[((size_t)64 * ci + 16 * ch + kk) * 36 + pp] : 0.f;
+  }
+  return FPC_OK;
+}
+
+// OP_BF16: a block, or the transposed convolution (one launch or one parity phase), on bf16 / split operands
+static int pack_fblock(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw) {
+  const FKindInfo& k = g_fkinds[op.fkind];
+  const BlockBfArgs& a = op.fargs;
+  const std::string& p = op.prefix;
+  const int ci = op.cin, co = op.cout, nbt = k.WN * k.NB;
+  if (op.phase >= 0) {  // ConvTranspose
+    const float* w = pk.need("descriptor.up_sample.weight", {256, 128, 3, 3});
+    const float* bct = pk.need("descriptor.up_sample.bias", {128});
+    Fold f;
+    if (!w || !bct || !fold_bn(pk.m, "descriptor.bn", 128, &f, pk.missing)) return FPC_E_MISSING_KEY;
+    if (op.phase == 4) {   // convt_bf16_kernel: all nine taps per step of 16 channels, in ConvTTaps' order
+      PackSource s{ci, ci, 9,
+                   [&](int n, int cc, int t) { return (double)w[((cc * 128 + n) * 3 + ConvTTaps::ky(t)) * 3 + ConvTTaps::kx(t)]; },
+                   &f.s};
+      pk.put(pack_conv_bf16({s}, co, k.CMIDP / 32, 16, 1, &pk.range_bad), cw.w_off[0]);
+    } else {
+      const std::vector<std::pair<int, int>> taps = convt_phase_taps(op.phase);
+      PackSource s{ci, a.nchunk * k.KC, (int)taps.size(),
+                   [&](int n, int cc, int t) { return (double)w[((cc * 128 + n) * 3 + taps[t].first) * 3 + taps[t].second]; },
+                   &f.s};
+      pk.put(pack_conv_bf16({s}, co, nbt, k.KC, k.planes, &pk.range_bad), cw.w_off[0]);
+    }
+    for (int n = 0; n < co; ++n) pk.at(cw.b_off)[n] = (float)((double)bct[n] * f.s[n] + f.t[n]);
+    return FPC_OK;
+  }
+  BlockWeights b;
+  if (!load_block(pk, p, ci, co, a.k16_x > 0, &b)) return FPC_E_MISSING_KEY;
+  const bool sc_in_w1 = k.planes == 1;   // (add_fblock)
+  const std::vector<double> ones(co, 1.0);
+  // taps 0..8: conv1 x bn1's scale; tap 9 (FPC_BF16): the shortcut on the same channels -- the projection x its bn's
+  // scale, or the unit matrix
+  PackSource s1{ci, a.nchunk * k.KC, sc_in_w1 ? 10 : 9,
+                [&](int n, int c_, int t) {
+                  if (t < 9) return (double)b.w1[((size_t)(n * ci + c_)) * 9 + t] * b.f1.s[n];
+                  return b.wp ? (double)b.wp[(size_t)n * ci + c_] * b.fp.s[n] : (n == c_ ? 1.0 : 0.0);
+                },
+                &ones};
+  pk.put(pack_conv_bf16({s1}, co, nbt, k.KC, k.planes, &pk.range_bad), cw.w_off[0]);
+  for (int n = 0; n < co; ++n) pk.at(cw.b_off)[n] = (float)b.f1.t[n];
+  pk.put(pack_conv_bf16(block_1x1_sources(b, ci, co, a.k16_h * 16, sc_in_w1 ? 0 : a.k16_x * 16), co, nbt, 16, k.planes, &pk.range_bad),
+         cw.w_off[1]);
+  for (int n = 0; n < co; ++n) pk.at(cw.b2_off)[n] = (float)b.bias[n];
+  return FPC_OK;
+}
+
+static int pack_block(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw) {
+  const BKindInfo& k = g_bkinds[op.bkind];
+  const BlockArgs& a = op.bargs;
+  const int ci = op.cin, co = op.cout, nbt = k.WN * k.NB;
+  BlockWeights b;
+  if (!load_block(pk, op.prefix, ci, co, a.k8_x > 0, &b)) return FPC_E_MISSING_KEY;
+  PackSource s1{ci, a.nchunk * k.KC, 9, [&](int n, int c_, int t) { return (double)b.w1[((size_t)(n * ci + c_)) * 9 + t]; }, &b.f1.s};
+  pk.put(pack_conv({s1}, co, nbt, k.KC), cw.w_off[0]);
+  for (int n = 0; n < co; ++n) pk.at(cw.b_off)[n] = (float)b.f1.t[n];
+  pk.put(pack_conv(block_1x1_sources(b, ci, co, a.k8_h * 8, a.k8_x * 8), co, nbt, 8), cw.w_off[1]);
+  for (int n = 0; n < co; ++n) pk.at(cw.b2_off)[n] = (float)b.bias[n];
+  return FPC_OK;
+}
+
+// OP_CONV of the Python network: one half of an unfused block, the detector's separate shortcut, or the transposed
+// convolution -- the checkpoint prefix and the role are recovered from the op name
+static int pack_conv_op(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw) {
+  const TensorMap& m = pk.m;
+  std::string* missing = pk.missing;
+  const KindInfo& k = g_kinds[op.kind];
+  const ConvArgs& a = op.args;
+  const std::string& nm = op.name;
+  const size_t dot = nm.find(".conv1+");
+  const size_t dot2 = nm.find(".conv2+");
+  const int cin0p = a.nchunk0 * k.KC, cin1p = a.nchunk1 * k.KC;
+  Fold f, fp;
+  std::vector<double> bias(a.nbt * 32, 0.0);
+  if (nm == "descriptor.up_sample+bn+relu") {
+    const float* w = pk.need("descriptor.up_sample.weight", {256, 128, 3, 3});
+    const float* bct = pk.need("descriptor.up_sample.bias", {128});
+    if (!w || !bct || !fold_bn(m, "descriptor.bn", 128, &f, missing)) return FPC_E_MISSING_KEY;
+    for (int ph = 0; ph < 4; ++ph) {
+      const std::vector<std::pair<int, int>> taps = convt_phase_taps(ph);
+      PackSource s{256, cin0p, (int)taps.size(),
+                   [&](int n, int ci, int t) { return (double)w[((ci * 128 + n) * 3 + taps[t].first) * 3 + taps[t].second]; },
+                   &f.s};
+      pk.put(pack_conv({s}, 128, a.nbt, k.KC), cw.w_off[ph]);
+    }
+    for (int n = 0; n < 128; ++n) bias[n] = (double)bct[n] * f.s[n] + f.t[n];
+  } else if (nm == "detector.layer.0.identity_downsample") {
+    const float* w = pk.need("detector.layer.0.identity_downsample.0.weight", {65, 128, 1, 1});
+    if (!w || !fold_bn(m, "detector.layer.0.identity_downsample.1", 65, &f, missing)) return FPC_E_MISSING_KEY;
+    PackSource s{128, cin0p, 1, [&](int n, int ci, int) { return (double)w[n * 128 + ci]; }, &f.s};
+    pk.put(pack_conv({s}, 65, a.nbt, k.KC), cw.w_off[0]);
+    for (int n = 0; n < 65; ++n) bias[n] = f.t[n];
+  } else if (dot != std::string::npos) {  // 3x3 conv1 + bn1
+    const std::string p = nm.substr(0, dot);
+    auto it = m.find(p + ".conv1.weight");
+    if (it == m.end() || it->second.shape.size() != 4 || it->second.shape[2] != 3) {
+      if (missing->empty()) *missing = p + ".conv1.weight";
+      return FPC_E_MISSING_KEY;
+    }
+    const int co = (int)it->second.shape[0], ci = (int)it->second.shape[1];
+    const float* w = it->second.data;
+    if (ci > cin0p || co > a.nbt * 32 || !w) {
+      *missing = p + ".conv1.weight";
+      return FPC_E_MISSING_KEY;
+    }
+    if (!fold_bn(m, p + ".bn1", co, &f, missing)) return FPC_E_MISSING_KEY;
+    PackSource s{ci, cin0p, 9, [&](int n, int c_, int t) { return (double)w[((size_t)(n * ci + c_)) * 9 + t]; }, &f.s};
+    pk.put(pack_conv({s}, co, a.nbt, k.KC), cw.w_off[0]);
+    for (int n = 0; n < co; ++n) bias[n] = f.t[n];
+  } else if (dot2 != std::string::npos) {  // 1x1 conv2 + bn2 (+ projection shortcut as a second K source)
+    const std::string p = nm.substr(0, dot2);
+    auto it = m.find(p + ".conv2.weight");
+    if (it == m.end() || it->second.shape.size() != 4 || !it->second.data) {
+      if (missing->empty()) *missing = p + ".conv2.weight";
+      return FPC_E_MISSING_KEY;
+    }
+    const int co = (int)it->second.shape[0];
+    const float* w = it->second.data;
+    if ((int)it->second.shape[1] != co || co > cin0p || co > a.nbt * 32) {
+      *missing = p + ".conv2.weight";
+      return FPC_E_MISSING_KEY;
+    }
+    if (!fold_bn(m, p + ".bn2", co, &f, missing)) return FPC_E_MISSING_KEY;
+    std::vector<PackSource> srcs;
+    srcs.push_back({co, cin0p, 1, [&, co](int n, int c_, int) { return (double)w[(size_t)n * co + c_]; }, &f.s});
+    for (int n = 0; n < co; ++n) bias[n] = f.t[n];
+    const float* wp = nullptr;
+    int cip = 0;
+    if (a.in1) {
+      auto ip = m.find(p + ".identity_downsample.0.weight");
+      if (ip == m.end() || ip->second.shape.size() != 4 || (int)ip->second.shape[0] != co || !ip->second.data ||
+          (int)ip->second.shape[1] > cin1p) {
+        if (missing->empty()) *missing = p + ".identity_downsample.0.weight";
+        return FPC_E_MISSING_KEY;
+      }
+      wp = ip->second.data;
+      cip = (int)ip->second.shape[1];
+      if (!fold_bn(m, p + ".identity_downsample.1", co, &fp, missing)) return FPC_E_MISSING_KEY;
+      srcs.push_back({cip, cin1p, 1, [&, cip](int n, int c_, int) { return (double)wp[(size_t)n * cip + c_]; }, &fp.s});
+      for (int n = 0; n < co; ++n) bias[n] += fp.t[n];
+    }
+    pk.put(pack_conv(srcs, co, a.nbt, k.KC), cw.w_off[0]);
+  } else {
+    *missing = "internal: unknown op " + nm;
+    return FPC_E_INVALID;
+  }
+  for (int n = 0; n < a.nbt * 32; ++n) pk.at(cw.b_off)[n] = (float)bias[n];
+  return FPC_OK;
+}
+
+static int pack_all_impl(fpc_ctx* c, const TensorMap& m, std::string* missing, bool& range_bad) {
+  c->host_blob.assign(c->blob_floats, 0.f);
+  const Packer pk{c, m, missing, range_bad};
+  if (int rc = c->vgg ? pack_vgg_convs(pk) : pack_stem(pk)) return rc;
   for (size_t i = 0; i < c->ops.size(); ++i) {
     const Op& op = c->ops[i];
     if (c->vgg && op.type != OP_WBLOCK) continue;  // packed above
-    if (op.type == OP_WBLOCK) {
-      const WKindInfo& k = g_wkinds[op.wkind];
-      const WBlockArgs& a = op.wargs;
-      const fpc_ctx::ConvW& cw = c->convw[i];
-      const std::string& p = op.prefix;
-      const int ci = op.cin, co = op.cout, nbt = k.NBT, K8 = k.KC / 8;
-      if (op.wconv) {  // conv-only launch: U = G g G^T of output channels n0 .. n0 + CMID - 1
-        const float* w1 = need(p + (op.plain_conv ? ".weight" : ".conv1.weight"), {co, ci, 3, 3});
-        Fold f1;
-        if (!w1) return FPC_E_MISSING_KEY;
-        if (op.plain_conv) {
-          const float* bv = need(p + ".bias", {co});
-          if (!bv) return FPC_E_MISSING_KEY;
-          f1.s.assign(co, 1.0);
-          f1.t.assign(bv, bv + co);
-        } else if (!fold_bn(m, p + ".bn1", co, &f1, missing)) {
-          return FPC_E_MISSING_KEY;
-        }
-        float* dst = blob.data() + cw.w_off[0];
-        const int nn = std::min(k.CMID, co - op.n0);
-        const std::vector<double> U = winograd_filters(w1, op.n0, nn, ci, f1.s, k.gen == 3 ? 36 : 16);
-        if (k.gen == 3) pack_w36_winograd(U, nn, ci, k, a.nchunk, dst);
-        else if (k.gen == 2) pack_w16_winograd(U, nn, ci, k.NCG, a.nchunk, dst);
-        else
-        for (int ch = 0; ch < a.nchunk; ++ch)
-          for (int xi = 0; xi < 16; ++xi)
-            for (int k8 = 0; k8 < K8; ++k8)
-              for (int nb = 0; nb < nbt; ++nb)
-                for (int lane = 0; lane < 64; ++lane) {
-                  const int n = nb * 32 + (lane & 31), half = lane >> 5;
-                  float* d4 = dst + (((((size_t)ch * 16 + xi) * K8 + k8) * nbt + nb) * 64 + lane) * 4;
-                  for (int j = 0; j < 4; ++j) {
-                    const int cc = ch * k.KC + k8 * 8 + 4 * half + j;
-                    d4[j] = (n < nn && cc < ci) ? (float)U[((size_t)n * ci + cc) * 16 + xi] : 0.f;
-                  }
-                }
-        for (int n = 0; n < nn; ++n) blob[cw.b_off + n] = (float)f1.t[op.n0 + n];
-        continue;
-      }
-      const float* w1 = need(p + ".conv1.weight", {co, ci, 3, 3});
-      const float* w2 = need(p + ".conv2.weight", {co, co, 1, 1});
-      Fold f1, f2, fp;
-      if (!w1 || !w2 || !fold_bn(m, p + ".bn1", co, &f1, missing) || !fold_bn(m, p + ".bn2", co, &f2, missing))
-        return FPC_E_MISSING_KEY;
-      // U = G (g * s) G^T in double, rounded once; generation 1: [chunk][xi][k8][nb][lane] float4
-      const std::vector<double> U = winograd_filters(w1, 0, co, ci, f1.s, k.gen == 3 ? 36 : 16);
-      float* dst = blob.data() + cw.w_off[0];
-      if (k.gen == 3) pack_w36_winograd(U, co, ci, k, a.nchunk, dst);
-      else if (k.gen == 2) pack_w16_winograd(U, co, ci, k.NCG, a.nchunk, dst);
-      else
-      for (int ch = 0; ch < a.nchunk; ++ch)
-        for (int xi = 0; xi < 16; ++xi)
-          for (int k8 = 0; k8 < K8; ++k8)
-            for (int nb = 0; nb < nbt; ++nb)
-              for (int lane = 0; lane < 64; ++lane) {
-                const int n = nb * 32 + (lane & 31), half = lane >> 5;
-                float* d4 = dst + (((((size_t)ch * 16 + xi) * K8 + k8) * nbt + nb) * 64 + lane) * 4;
-                for (int j = 0; j < 4; ++j) {
-                  const int cc = ch * k.KC + k8 * 8 + 4 * half + j;
-                  d4[j] = (n < co && cc < ci) ? (float)U[((size_t)n * ci + cc) * 16 + xi] : 0.f;
-                }
-              }
-      for (int n = 0; n < std::min(co, nbt * 32); ++n) blob[cw.b_off + n] = (float)f1.t[n];
-      std::vector<PackSource> srcs;
-      srcs.push_back({co, a.k8_h * 8, 1, [&](int n, int c_, int) { return (double)w2[(size_t)n * co + c_]; }, &f2.s});
-      std::vector<double> bias(f2.t);
-      const float* wp = nullptr;
-      if (a.k8_x > 0) {
-        wp = need(p + ".identity_downsample.0.weight", {co, ci, 1, 1});
-        if (!wp || !fold_bn(m, p + ".identity_downsample.1", co, &fp, missing)) return FPC_E_MISSING_KEY;
-        srcs.push_back({ci, a.k8_x * 8, 1, [&](int n, int c_, int) { return (double)wp[(size_t)n * ci + c_]; }, &fp.s});
-        for (int n = 0; n < co; ++n) bias[n] += fp.t[n];
-      }
-      if (k.gen >= 2) {
-        pack_w16_1x1(srcs, co, k.NCG, blob.data() + cw.w_off[1]);
-      } else {
-        std::vector<float> frag = pack_conv(srcs, co, nbt, 8);
-        memcpy(blob.data() + cw.w_off[1], frag.data(), frag.size() * sizeof(float));
-      }
-      for (int n = 0; n < std::min(co, nbt * 32); ++n) blob[cw.b2_off + n] = (float)bias[n];
-      if (k.dust) {   // the 65th channel's weights (W36Dust, wblock36_mfma.h)
-        float* d = blob.data() + cw.w_off[2];
-        for (int n = 0; n < 64; ++n) d[W36Dust::W2ROW + n] = (float)((double)w2[(size_t)n * co + 64] * f2.s[n]);
-        for (int kk = 0; kk < 65; ++kk) d[W36Dust::W2COL + kk] = (float)((double)w2[(size_t)64 * co + kk] * f2.s[64]);
-        if (wp)
-          for (int cc = 0; cc < ci; ++cc) d[W36Dust::WPCOL + cc] = (float)((double)wp[(size_t)64 * ci + cc] * fp.s[64]);
-        d[W36Dust::B1] = (float)f1.t[64];
-        d[W36Dust::B2] = (float)bias[64];
-        if (a.dust_in) {
-          for (int pp = 0; pp < 36; ++pp) d[W36Dust::UIN64 + pp] = (float)U[((size_t)64 * ci + 64) * 36 + pp];
-          for (int cg = 0; cg < 4; ++cg)
-            for (int pp = 0; pp < 36; ++pp)
-              for (int n16 = 0; n16 < 16; ++n16)
-                d[W36Dust::UIN + (cg * 36 + pp) * 16 + n16] = (float)U[((size_t)(16 * cg + n16) * ci + 64) * 36 + pp];
-        }
-        for (int ch = 0; ch < a.nchunk; ++ch)
-          for (int pp = 0; pp < 36; ++pp)
-            for (int kk = 0; kk < 16; ++kk)
-              d[W36Dust::UOUT + (ch * 36 + pp) * 16 + kk] = 16 * ch + kk < ci ? (float)U[((size_t)64 * ci + 16 * ch + kk) * 36 + pp] : 0.f;
-      }
-      continue;
+    int rc = FPC_OK;
+    switch (op.type) {
+      case OP_WBLOCK: rc = pack_wblock(pk, op, c->convw[i]); break;
+      case OP_BF16: rc = pack_fblock(pk, op, c->convw[i]); break;
+      case OP_BLOCK: rc = pack_block(pk, op, c->convw[i]); break;
+      case OP_CONV: rc = pack_conv_op(pk, op, c->convw[i]); break;
+      default: break;
     }
-    if (op.type == OP_BF16) {
-      const FKindInfo& k = g_fkinds[op.fkind];
-      const BlockBfArgs& a = op.fargs;
-      const fpc_ctx::ConvW& cw = c->convw[i];
-      const std::string& p = op.prefix;
-      const int ci = op.cin, co = op.cout, nbt = k.WN * k.NB;
-      if (op.phase >= 0) {  // ConvTranspose phase
-        const float* w = need("descriptor.up_sample.weight", {256, 128, 3, 3});
-        const float* bct = need("descriptor.up_sample.bias", {128});
-        Fold f;
-        if (!w || !bct || !fold_bn(m, "descriptor.bn", 128, &f, missing)) return FPC_E_MISSING_KEY;
-        if (op.phase == 4) {   // convt_bf16_kernel: all nine taps per step of 16 channels, in ConvTTaps' order
-          PackSource s{ci, ci, 9,
-                       [&](int n, int cc, int t) { return (double)w[((cc * 128 + n) * 3 + ConvTTaps::ky(t)) * 3 + ConvTTaps::kx(t)]; },
-                       &f.s};
-          std::vector<float> frag = pack_conv_bf16({s}, co, k.CMIDP / 32, 16, 1, &range_bad);
-          memcpy(blob.data() + cw.w_off[0], frag.data(), frag.size() * sizeof(float));
-          for (int n = 0; n < co; ++n) blob[cw.b_off + n] = (float)((double)bct[n] * f.s[n] + f.t[n]);
-          continue;
-        }
-        const int py = op.phase >> 1, px = op.phase & 1;
-        std::vector<std::pair<int, int>> taps;  // (ky, kx) in the order add_fconvT laid the taps out
-        for (int iy = 0; iy < (py ? 2 : 1); ++iy)
-          for (int ix = 0; ix < (px ? 2 : 1); ++ix) taps.push_back({py ? (iy == 0 ? 0 : 2) : 1, px ? (ix == 0 ? 0 : 2) : 1});
-        PackSource s{ci, a.nchunk * k.KC, (int)taps.size(),
-                     [&](int n, int cc, int t) { return (double)w[((cc * 128 + n) * 3 + taps[t].first) * 3 + taps[t].second]; },
-                     &f.s};
-        std::vector<float> frag = pack_conv_bf16({s}, co, nbt, k.KC, k.planes, &range_bad);
-        memcpy(blob.data() + cw.w_off[0], frag.data(), frag.size() * sizeof(float));
-        for (int n = 0; n < co; ++n) blob[cw.b_off + n] = (float)((double)bct[n] * f.s[n] + f.t[n]);
-        continue;
-      }
-      const float* w1 = need(p + ".conv1.weight", {co, ci, 3, 3});
-      const float* w2 = need(p + ".conv2.weight", {co, co, 1, 1});
-      Fold f1, f2, fp;
-      if (!w1 || !w2 || !fold_bn(m, p + ".bn1", co, &f1, missing) || !fold_bn(m, p + ".bn2", co, &f2, missing))
-        return FPC_E_MISSING_KEY;
-      const bool sc_in_w1 = k.planes == 1;   // (add_fblock)
-      std::vector<double> bias(f2.t);
-      const float* wp = nullptr;
-      if (a.k16_x > 0) {
-        wp = need(p + ".identity_downsample.0.weight", {co, ci, 1, 1});
-        if (!wp || !fold_bn(m, p + ".identity_downsample.1", co, &fp, missing)) return FPC_E_MISSING_KEY;
-        for (int n = 0; n < co; ++n) bias[n] += fp.t[n];
-      }
-      const std::vector<double> ones(co, 1.0);
-      // taps 0..8: conv1 x bn1's scale; tap 9 (FPC_BF16): the shortcut on the same channels -- the projection x its bn's
-      // scale, or the unit matrix
-      PackSource s1{ci, a.nchunk * k.KC, sc_in_w1 ? 10 : 9,
-                    [&](int n, int c_, int t) {
-                      if (t < 9) return (double)w1[((size_t)(n * ci + c_)) * 9 + t] * f1.s[n];
-                      return wp ? (double)wp[(size_t)n * ci + c_] * fp.s[n] : (n == c_ ? 1.0 : 0.0);
-                    },
-                    &ones};
-      std::vector<float> frag = pack_conv_bf16({s1}, co, nbt, k.KC, k.planes, &range_bad);
-      memcpy(blob.data() + cw.w_off[0], frag.data(), frag.size() * sizeof(float));
-      for (int n = 0; n < co; ++n) blob[cw.b_off + n] = (float)f1.t[n];
-      std::vector<PackSource> srcs;
-      srcs.push_back({co, a.k16_h * 16, 1, [&](int n, int c_, int) { return (double)w2[(size_t)n * co + c_]; }, &f2.s});
-      if (wp && !sc_in_w1)
-        srcs.push_back({ci, a.k16_x * 16, 1, [&](int n, int c_, int) { return (double)wp[(size_t)n * ci + c_]; }, &fp.s});
-      frag = pack_conv_bf16(srcs, co, nbt, 16, k.planes, &range_bad);
-      memcpy(blob.data() + cw.w_off[1], frag.data(), frag.size() * sizeof(float));
-      for (int n = 0; n < co; ++n) blob[cw.b2_off + n] = (float)bias[n];
-      continue;
-    }
-    if (op.type == OP_BLOCK) {
-      const BKindInfo& k = g_bkinds[op.bkind];
-      const BlockArgs& a = op.bargs;
-      const fpc_ctx::ConvW& cw = c->convw[i];
-      const std::string& p = op.prefix;
-      const int ci = op.cin, co = op.cout, nbt = k.WN * k.NB;
-      const float* w1 = need(p + ".conv1.weight", {co, ci, 3, 3});
-      const float* w2 = need(p + ".conv2.weight", {co, co, 1, 1});
-      Fold f1, f2, fp;
-      if (!w1 || !w2 || !fold_bn(m, p + ".bn1", co, &f1, missing) || !fold_bn(m, p + ".bn2", co, &f2, missing))
-        return FPC_E_MISSING_KEY;
-      PackSource s1{ci, a.nchunk * k.KC, 9, [&](int n, int c_, int t) { return (double)w1[((size_t)(n * ci + c_)) * 9 + t]; }, &f1.s};
-      std::vector<float> frag = pack_conv({s1}, co, nbt, k.KC);
-      memcpy(blob.data() + cw.w_off[0], frag.data(), frag.size() * sizeof(float));
-      for (int n = 0; n < co; ++n) blob[cw.b_off + n] = (float)f1.t[n];
-      std::vector<PackSource> srcs;
-      srcs.push_back({co, a.k8_h * 8, 1, [&](int n, int c_, int) { return (double)w2[(size_t)n * co + c_]; }, &f2.s});
-      std::vector<double> bias(f2.t);
-      const float* wp = nullptr;
-      if (a.k8_x > 0) {
-        wp = need(p + ".identity_downsample.0.weight", {co, ci, 1, 1});
-        if (!wp || !fold_bn(m, p + ".identity_downsample.1", co, &fp, missing)) return FPC_E_MISSING_KEY;
-        srcs.push_back({ci, a.k8_x * 8, 1, [&](int n, int c_, int) { return (double)wp[(size_t)n * ci + c_]; }, &fp.s});
-        for (int n = 0; n < co; ++n) bias[n] += fp.t[n];
-      }
-      frag = pack_conv(srcs, co, nbt, 8);
-      memcpy(blob.data() + cw.w_off[1], frag.data(), frag.size() * sizeof(float));
-      for (int n = 0; n < co; ++n) blob[cw.b2_off + n] = (float)bias[n];
-      continue;
-    }
-    if (op.type != OP_CONV) continue;
-    const KindInfo& k = g_kinds[op.kind];
-    const ConvArgs& a = op.args;
-    const fpc_ctx::ConvW& cw = c->convw[i];
-    // recover the checkpoint prefix and role from the op name
-    const std::string& nm = op.name;
-    const size_t dot = nm.find(".conv1+");
-    const size_t dot2 = nm.find(".conv2+");
-    const int cin0p = a.nchunk0 * k.KC, cin1p = a.nchunk1 * k.KC;
-    Fold f, fp;
-    std::vector<double> bias(a.nbt * 32, 0.0);
-    if (nm == "descriptor.up_sample+bn+relu") {
-      const float* w = need("descriptor.up_sample.weight", {256, 128, 3, 3});
-      const float* bct = need("descriptor.up_sample.bias", {128});
-      if (!w || !bct || !fold_bn(m, "descriptor.bn", 128, &f, missing)) return FPC_E_MISSING_KEY;
-      for (int ph = 0; ph < 4; ++ph) {
-        const int py = ph >> 1, px = ph & 1;
-        std::vector<std::pair<int, int>> taps;  // (ky, kx) in the order add_conv laid the taps out
-        for (int iy = 0; iy < (py ? 2 : 1); ++iy)
-          for (int ix = 0; ix < (px ? 2 : 1); ++ix) taps.push_back({py ? (iy == 0 ? 0 : 2) : 1, px ? (ix == 0 ? 0 : 2) : 1});
-        PackSource s{256, cin0p, (int)taps.size(),
-                     [&](int n, int ci, int t) { return (double)w[((ci * 128 + n) * 3 + taps[t].first) * 3 + taps[t].second]; },
-                     &f.s};
-        std::vector<float> frag = pack_conv({s}, 128, a.nbt, k.KC);
-        memcpy(blob.data() + cw.w_off[ph], frag.data(), frag.size() * sizeof(float));
-      }
-      for (int n = 0; n < 128; ++n) bias[n] = (double)bct[n] * f.s[n] + f.t[n];
-    } else if (nm == "detector.layer.0.identity_downsample") {
-      const float* w = need("detector.layer.0.identity_downsample.0.weight", {65, 128, 1, 1});
-      if (!w || !fold_bn(m, "detector.layer.0.identity_downsample.1", 65, &f, missing)) return FPC_E_MISSING_KEY;
-      PackSource s{128, cin0p, 1, [&](int n, int ci, int) { return (double)w[n * 128 + ci]; }, &f.s};
-      std::vector<float> frag = pack_conv({s}, 65, a.nbt, k.KC);
-      memcpy(blob.data() + cw.w_off[0], frag.data(), frag.size() * sizeof(float));
-      for (int n = 0; n < 65; ++n) bias[n] = f.t[n];
-    } else if (dot != std::string::npos) {  // 3x3 conv1 + bn1
-      const std::string p = nm.substr(0, dot);
-      auto it = m.find(p + ".conv1.weight");
-      if (it == m.end() || it->second.shape.size() != 4 || it->second.shape[2] != 3) {
-        if (missing->empty()) *missing = p + ".conv1.weight";
-        return FPC_E_MISSING_KEY;
-      }
-      const int co = (int)it->second.shape[0], ci = (int)it->second.shape[1];
-      const float* w = it->second.data;
-      if (ci > cin0p || co > a.nbt * 32 || !w) {
-        *missing = p + ".conv1.weight";
-        return FPC_E_MISSING_KEY;
-      }
-      if (!fold_bn(m, p + ".bn1", co, &f, missing)) return FPC_E_MISSING_KEY;
-      PackSource s{ci, cin0p, 9, [&](int n, int c_, int t) { return (double)w[((size_t)(n * ci + c_)) * 9 + t]; }, &f.s};
-      std::vector<float> frag = pack_conv({s}, co, a.nbt, k.KC);
-      memcpy(blob.data() + cw.w_off[0], frag.data(), frag.size() * sizeof(float));
-      for (int n = 0; n < co; ++n) bias[n] = f.t[n];
-    } else if (dot2 != std::string::npos) {  // 1x1 conv2 + bn2 (+ projection shortcut as a second K source)
-      const std::string p = nm.substr(0, dot2);
-      auto it = m.find(p + ".conv2.weight");
-      if (it == m.end() || it->second.shape.size() != 4 || !it->second.data) {
-        if (missing->empty()) *missing = p + ".conv2.weight";
-        return FPC_E_MISSING_KEY;
-      }
-      const int co = (int)it->second.shape[0];
-      const float* w = it->second.data;
-      if ((int)it->second.shape[1] != co || co > cin0p || co > a.nbt * 32) {
-        *missing = p + ".conv2.weight";
-        return FPC_E_MISSING_KEY;
-      }
-      if (!fold_bn(m, p + ".bn2", co, &f, missing)) return FPC_E_MISSING_KEY;
-      std::vector<PackSource> srcs;
-      srcs.push_back({co, cin0p, 1, [&, co](int n, int c_, int) { return (double)w[(size_t)n * co + c_]; }, &f.s});
-      for (int n = 0; n < co; ++n) bias[n] = f.t[n];
-      const float* wp = nullptr;
-      int cip = 0;
-      if (a.in1) {
-        auto ip = m.find(p + ".identity_downsample.0.weight");
-        if (ip == m.end() || ip->second.shape.size() != 4 || (int)ip->second.shape[0] != co || !ip->second.data ||
-            (int)ip->second.shape[1] > cin1p) {
-          if (missing->empty()) *missing = p + ".identity_downsample.0.weight";
-          return FPC_E_MISSING_KEY;
-        }
-        wp = ip->second.data;
-        cip = (int)ip->second.shape[1];
-        if (!fold_bn(m, p + ".identity_downsample.1", co, &fp, missing)) return FPC_E_MISSING_KEY;
-        srcs.push_back({cip, cin1p, 1, [&, cip](int n, int c_, int) { return (double)wp[(size_t)n * cip + c_]; }, &fp.s});
-        for (int n = 0; n < co; ++n) bias[n] += fp.t[n];
-      }
-      std::vector<float> frag = pack_conv(srcs, co, a.nbt, k.KC);
-      memcpy(blob.data() + cw.w_off[0], frag.data(), frag.size() * sizeof(float));
-    } else {
-      *missing = "internal: unknown op " + nm;
-      return FPC_E_INVALID;
-    }
-    for (int n = 0; n < a.nbt * 32; ++n) blob[cw.b_off + n] = (float)bias[n];
+    if (rc != FPC_OK) return rc;
   }
   return FPC_OK;
 }
@@ -2639,10 +2511,234 @@ static int op_index(const fpc_ctx* c, OpType t) {
 }
 
 // which: 0 = encoder, 1 = detector head, 2 = descriptor head
+// The diagnostic build's in-kernel stamps for the launch FPC_STAMP_OP names (a no-op in the product library)
+template <typename Args>
+static void diag_stamp(fpc_ctx* c, const Op& op, Args& a, int tiles) {
+#ifdef FPC_DIAG
+  a.stamps = nullptr;
+  if (const char* e = getenv("FPC_STAMP_OP"))
+    if (op.name.find(e) != std::string::npos) {
+      if (!c->diag_stamps) hipHostMalloc((void**)&c->diag_stamps, (size_t)65536 * 8 * sizeof(unsigned long long));
+      memset(c->diag_stamps, 0, (size_t)65536 * 8 * sizeof(unsigned long long));
+      a.stamps = c->diag_stamps;
+      c->diag_n = tiles;
+    }
+#endif
+}
+
+// The stem's kernel: chosen HERE, for the launch and for the name fpc_get_timings reports alike
+enum StemKind { STEM_PLAIN, STEM_POOL, STEM_POOL2, STEM_X3, STEM_X3_F16, STEM_BF16 };
+static StemKind stem_kind(const fpc_ctx* c) {
+  if (!(c->fuse_stem_pool || c->cin == 1 || c->bf16)) return STEM_PLAIN;   // conv1 alone: OP_POOL follows
+  if (c->split_f16) return STEM_X3_F16;
+  if (c->bf16) return STEM_BF16;   // bf16 operands like every other layer of the mode, bf16 out, no atomics
+  if (c->split) return STEM_X3;
+  return c->stem2 ? STEM_POOL2 : STEM_POOL;
+}
+
+// Launches the stem for `sb`'s frames -- unless `sb` is null: the name alone -- and returns its symbol
+static const char* launch_stem(fpc_ctx* c, const Op& op, int i, const float* frames, const Sub* sb) {
+  static const char* const symbol[] = {"stem_kernel", "stem_pool_kernel", "stem_pool2_kernel", "stem_pool_x3_kernel",
+                                       "stem_pool_x3_kernel", "stem_bf16_kernel"};
+  const StemKind kind = stem_kind(c);
+  if (!sb) return symbol[kind];
+  const int H = c->H, W = c->W, n = sb->n, f0 = sb->f0;
+  const bool gray = c->cin == 1;
+  if (kind == STEM_PLAIN) {
+    LaunchTimer t(c, i, sb->st, n);
+    StemArgs a = c->stem;
+    a.in = frames + (size_t)f0 * 3 * H * W;
+    a.out = c->stem_out + (size_t)f0 * (H / 2) * (W / 2) * 64;
+    hipLaunchKernelGGL(stem_kernel, dim3(a.tiles_x * a.tiles_y * n), dim3(256), 0, sb->st, a);
+    return symbol[kind];
+  }
+  // the pooled map: fp32, completed across tiles with atomicMax (hence zero-filled); FPC_BF16 writes it once, as bf16
+  float* x0 = c->bf16 ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(c->x0) + (size_t)f0 * (H / 4) * (W / 4) * 64)
+                      : c->x0 + (size_t)f0 * (H / 4) * (W / 4) * 64;
+  // (only the cells that tiles complete for each other with atomicMax need the zero: kernels_misc.h)
+  if (!c->bf16) stem_border_clear_kernel<<<(n * (H / 4) + 7) / 8, 256, 0, sb->st>>>(reinterpret_cast<float4*>(x0), H / 4, W / 4, n * (H / 4));
+  LaunchTimer t(c, i, sb->st, n);
+  StemPoolArgs a{};
+  a.in = frames + (size_t)f0 * c->cin * H * W;
+  a.wfrag = c->stem.wfrag;
+  a.bias = c->stem.bias;
+  a.out = x0;
+  a.H = H; a.W = W; a.Ho = H / 2; a.Wo = W / 2; a.Hp = H / 4; a.Wp = W / 4;
+  a.tiles_x = c->stem.tiles_x; a.tiles_y = c->stem.tiles_y;
+  a.range = c->range + (size_t)f0 * FPC_RANGE_WORDS;
+  const dim3 grid(a.tiles_x * a.tiles_y * n);
+  if (kind == STEM_X3 || kind == STEM_X3_F16 || kind == STEM_BF16) {
+    StemX3Args x{};
+    x.in = a.in; x.wfrag = reinterpret_cast<const uint4*>(a.wfrag); x.bias = a.bias; x.out = a.out;
+    x.H = H; x.W = W; x.Ho = a.Ho; x.Wo = a.Wo; x.Hp = a.Hp; x.Wp = a.Wp; x.tiles_x = a.tiles_x; x.tiles_y = a.tiles_y;
+    x.range_flag = c->split_f16 ? c->status + 1 : nullptr;
+    diag_stamp(c, op, x, a.tiles_x * a.tiles_y * n);
+    if (kind == STEM_X3_F16) {
+      if (gray) hipLaunchKernelGGL((stem_pool_x3_kernel<1, 2>), grid, dim3(256), 0, sb->st, x);
+      else hipLaunchKernelGGL((stem_pool_x3_kernel<3, 2>), grid, dim3(256), 0, sb->st, x);
+    } else if (kind == STEM_BF16) {
+      x.frames = n;
+      x.tiles_x = (x.Wp + SB2_PW - 1) / SB2_PW;   // stem_bf16.h: 8 x 7 pooled pixels per tile
+      x.tiles_y = (x.Hp + SB2_PH - 1) / SB2_PH;
+      const int T = x.tiles_x * x.tiles_y * n;
+      const dim3 pg(std::min((T + 7) / 8 * 8, std::max(8, 2 * c->num_cus / 8 * 8)));  // two workgroups per CU, a multiple of 8
+      if (gray) hipLaunchKernelGGL(stem_bf16_kernel<1>, pg, dim3(SB2_THREADS), StemB2Cfg<1>::LDS_BYTES, sb->st, x);
+      else hipLaunchKernelGGL(stem_bf16_kernel<3>, pg, dim3(SB2_THREADS), StemB2Cfg<3>::LDS_BYTES, sb->st, x);
+    } else {
+      if (gray) hipLaunchKernelGGL((stem_pool_x3_kernel<1, 3>), grid, dim3(256), 0, sb->st, x);
+      else hipLaunchKernelGGL((stem_pool_x3_kernel<3, 3>), grid, dim3(256), 0, sb->st, x);
+    }
+    return symbol[kind];
+  }
+  if (kind == STEM_POOL2) {
+    if (gray) hipLaunchKernelGGL(stem_pool2_kernel<1>, grid, dim3(256), 0, sb->st, a);
+    else hipLaunchKernelGGL(stem_pool2_kernel<3>, grid, dim3(256), 0, sb->st, a);
+  } else {
+    if (gray) hipLaunchKernelGGL(stem_pool_kernel<1>, grid, dim3(256), 0, sb->st, a);
+    else hipLaunchKernelGGL(stem_pool_kernel<3>, grid, dim3(256), 0, sb->st, a);
+  }
+  return symbol[kind];
+}
+
+static void launch_pool(fpc_ctx* c, int i, const Sub& sb) {
+  if (stem_kind(c) != STEM_PLAIN) return;   // the stem pooled its own map
+  const int H = c->H, W = c->W, n = sb.n, f0 = sb.f0;
+  LaunchTimer t(c, i, sb.st, n);
+  const size_t total = (size_t)n * (H / 4) * (W / 4) * 16;
+  hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sb.st,
+                     reinterpret_cast<const float4*>(c->stem_out + (size_t)f0 * (H / 2) * (W / 2) * 64),
+                     reinterpret_cast<float4*>(c->x0 + (size_t)f0 * (H / 4) * (W / 4) * 64), n, H / 2, W / 2, H / 4, W / 4);
+}
+
+static void launch_wblock(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
+  const int n = sb.n, f0 = sb.f0;
+  LaunchTimer t(c, i, sb.st, n);
+  WBlockArgs a = op.wargs;
+  a.frame0 = f0;
+  diag_stamp(c, op, a, a.tiles_x * a.tiles_y * n);
+  a.total = a.tiles_x * a.tiles_y * n;
+  a.xcd_order = c->xcd_order ? 1 : 0;
+  {  // range of the input's buffer descriptor: frames 0 .. f0 + n - 1 of the tensor, from `x` (already offset to its first channel)
+    const unsigned long long xb = (unsigned long long)(f0 + n) * a.H * a.W * a.csx * sizeof(float);
+    a.x_bytes = xb > 0xfffffff0ull ? 0xfffffff0u : (unsigned)xb;
+  }
+  // persistent (one workgroup per CU walking the tiles) when a workgroup gets enough tiles to
+  // amortise; otherwise one workgroup per tile
+  int grid = (c->persist_min_tiles > 0 && a.total >= c->persist_min_tiles * c->num_cus) ? c->num_cus : a.total;
+  if (g_wkinds[op.wkind].gen == 3) {
+    // Pointers to the launch's first frame, as many frames per launch as stay below W36_MARKER bytes (all of them,
+    // except at the C++ network's full-resolution layers: 78.6 MB per VGA frame and tensor).
+    const int fpl = w36_frames_per_launch(a.H, a.W, a.csx, a.cso);
+    const float* x0 = a.x;
+    float* o0 = a.out;
+    const int Hf = a.H, tx_f = a.tiles_x, ty_f = a.tiles_y;
+    const WKind sk = c->tiles_round6 ? w36_stacked_kind(op.wkind) : WK_COUNT;
+    double mf = 0.0;
+    for (int g0 = 0; g0 < n; g0 += fpl) {
+      const int gn = std::min(fpl, n - g0);
+      a.frame0 = 0;
+      a.x = x0 + (size_t)(f0 + g0) * Hf * a.W * a.csx;
+      a.out = o0 + (size_t)(f0 + g0) * Hf * a.W * a.cso;
+      a.x_bytes = (unsigned)((unsigned long long)gn * Hf * a.W * a.csx * sizeof(float));
+      // round 6: the launch's frames as ONE image of gn x Hf rows where that is fewer tiles (wblock36s_kernel)
+      const int srows = w36_stacked_rows(Hf, a.W, gn, sk, tx_f * ty_f);
+      const WKind lk = srows ? sk : op.wkind;
+      a.H = srows ? gn * Hf : Hf;
+      a.frame_h = srows ? Hf : 0;
+      a.tiles_x = srows ? (a.W + g_wkinds[sk].TW - 1) / g_wkinds[sk].TW : tx_f;
+      a.tiles_y = srows ? srows : ty_f;
+      a.total = srows ? a.tiles_x * srows : tx_f * ty_f * gn;
+      if (srows) t.wkind = sk;
+      mf += srows ? wkind_mfma_flops(g_wkinds[sk], a.total, a.nchunk, a.k8_h + a.k8_x) : op.mfma_flops_per_frame * gn;
+      // One workgroup per CU (137 KB of LDS), so a launch lasts ceil(tiles / CUs) tile times whatever the grid: take
+      // the SMALLEST grid that still finishes in that many rounds (a multiple of 8: the tile walk is per XCD) and
+      // leave the other CUs to the launches of the other sub-batch's stream -- 640 tiles: 216 workgroups x 3 rounds
+      // instead of 256 of which 128 idle through the third; 320 tiles: 160 x 2.
+      // (a launch of gridDim.y parts shares the CUs between them: each part's tile walk gets CUs / parts)
+      const int cus_cap = c->w36_cus > 0 ? std::min(c->num_cus, c->w36_cus) : c->num_cus;
+      const int cus8 = std::max(1, cus_cap / 8 / std::max(1, op.grid_y)), per_xcd = (a.total + 7) / 8;
+      const int rounds = (per_xcd + cus8 - 1) / cus8;
+      const int grid3 = 8 * std::min(cus8, (per_xcd + rounds - 1) / rounds);
+      g_wkinds[lk].launch(a, dim3(std::min(a.total, grid3), op.grid_y), sb.st);
+    }
+    if (t.wkind >= 0) t.mfma_flops = mf;
+    return;
+  }
+  g_wkinds[op.wkind].launch(a, dim3(std::min(a.total, grid), op.grid_y), sb.st);
+}
+
+static void launch_block(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
+  LaunchTimer t(c, i, sb.st, sb.n);
+  BlockArgs a = op.bargs;
+  a.frame0 = sb.f0;
+  diag_stamp(c, op, a, a.tiles_x * a.tiles_y * sb.n);
+  g_bkinds[op.bkind].launch(a, dim3(a.tiles_x * a.tiles_y * sb.n), sb.st);
+}
+
+static void launch_fblock(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
+  const int n = sb.n, f0 = sb.f0;
+  LaunchTimer t(c, i, sb.st, n);
+  BlockBfArgs a = op.fargs;
+  a.frame0 = f0;
+  a.range_flag = c->split_f16 ? c->status + 1 : nullptr;
+  diag_stamp(c, op, a, a.tiles_x * a.tiles_y * n);
+  if (g_fkinds[op.fkind].planes != 1) {
+    g_fkinds[op.fkind].launch(a, dim3(a.tiles_x * a.tiles_y * n), sb.st);
+    return;
+  }
+  // block_bf16_kernel: persistent grid, a multiple of 8 (block_bf16.h)
+  a.total_tiles = a.tiles_x * a.tiles_y * n;
+  if (sb.fuse_softmax && op.fused_softmax_capable) {
+    const size_t HW = (size_t)c->H * c->W;
+    hipMemsetAsync(c->ncand + f0, 0, sizeof(int32_t) * n, sb.st);
+    a.softmax = 1;
+    a.thresh = c->cfg.conf_thresh;
+    a.nmsmap = c->nmsmap + f0 * HW;
+    a.cand = c->cand + f0 * HW;
+    a.ncand = c->ncand + f0;
+  }
+  // (op.grid_y parts -- convt_bf16_kernel's output-channel halves -- share the CUs)
+  const int g = std::min((a.total_tiles + 7) / 8 * 8, std::max(8, c->fkind_blocks_per_cu[op.fkind] * c->num_cus / op.grid_y / 8 * 8));
+  g_fkinds[op.fkind].launch(a, dim3(g, op.grid_y), sb.st);
+}
+
+static void launch_conv(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
+  LaunchTimer t(c, i, sb.st, sb.n);
+  ConvArgs a = op.args;
+  a.frame0 = sb.f0;
+  const dim3 grid(a.tiles_x * a.tiles_y * sb.n, op.grid_y, op.grid_z);
+  if (op.lean) lean_kind(op.kind)->launch(a, grid, sb.st);
+  else g_kinds[op.kind].launch(a, grid, sb.st);
+}
+
+// The C++ network's own layers: its first convolution, its max-pools, the descriptor normalisation
+static void launch_vconv0(fpc_ctx* c, const Op& op, int i, const float* frames, const Sub& sb) {
+  LaunchTimer t(c, i, sb.st, sb.n);
+  VggConv0Args a{};
+  a.in = frames;
+  a.w = c->blob + c->vconv0_off;
+  a.out = op.pout;
+  a.H = c->H; a.W = c->W; a.frame0 = sb.f0;
+  hipLaunchKernelGGL(vgg_conv0_kernel, dim3((unsigned)((size_t)sb.n * c->H * c->W / 64)), dim3(256), 0, sb.st, a);
+}
+static void launch_pool2(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
+  LaunchTimer t(c, i, sb.st, sb.n);
+  const size_t tot = (size_t)sb.n * (op.pH / 2) * (op.pW / 2) * (op.pC / 4);
+  hipLaunchKernelGGL(maxpool2_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, sb.st,
+                     reinterpret_cast<const float4*>(op.pin), reinterpret_cast<float4*>(op.pout), sb.n, op.pH, op.pW,
+                     op.pC / 4, sb.f0);
+}
+static void launch_l2norm(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
+  LaunchTimer t(c, i, sb.st, sb.n);
+  const size_t npix = (size_t)sb.n * c->Hc * c->Wc;
+  hipLaunchKernelGGL(l2norm256_kernel, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, sb.st,
+                     op.pout + (size_t)sb.f0 * c->Hc * c->Wc * 256, npix);
+}
+
+// which: 0 = encoder, 1 = detector head, 2 = descriptor head
 static void run_network(fpc_ctx* c, const float* frames, const Sub& sb0, int which, hipStream_t st) {
   Sub sb = sb0;
   sb.st = st;
-  const int H = c->H, W = c->W, n = sb.n, f0 = sb.f0;
   for (size_t i = 0; i < c->ops.size(); ++i) {
     const Op& op = c->ops[i];
     const int br = op.descriptor_branch ? 2 : (op.name.compare(0, 8, "detector") == 0 ? 1 : 0);
@@ -2651,230 +2747,16 @@ static void run_network(fpc_ctx* c, const float* frames, const Sub& sb0, int whi
     if (op.when == 1 && !sb.small) continue;   // variants of a layer for small / large calls
     if (op.when == 2 && sb.small) continue;
     switch (op.type) {
-      case OP_STEM: {
-        if (c->fuse_stem_pool || c->cin == 1 || c->bf16) {
-          // the pooled map: fp32, completed across tiles with atomicMax (hence zero-filled); FPC_BF16 writes it once, as bf16
-          float* x0 = c->bf16 ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(c->x0) + (size_t)f0 * (H / 4) * (W / 4) * 64)
-                              : c->x0 + (size_t)f0 * (H / 4) * (W / 4) * 64;
-          // (only the cells that tiles complete for each other with atomicMax need the zero: kernels_misc.h)
-          if (!c->bf16) stem_border_clear_kernel<<<(n * (H / 4) + 7) / 8, 256, 0, sb.st>>>(reinterpret_cast<float4*>(x0), H / 4, W / 4, n * (H / 4));
-          LaunchTimer t(c, (int)i, sb.st, n);
-          StemPoolArgs a{};
-          a.in = frames + (size_t)f0 * c->cin * H * W;
-          a.wfrag = c->stem.wfrag;
-          a.bias = c->stem.bias;
-          a.out = x0;
-          a.H = H; a.W = W; a.Ho = H / 2; a.Wo = W / 2; a.Hp = H / 4; a.Wp = W / 4;
-          a.tiles_x = c->stem.tiles_x; a.tiles_y = c->stem.tiles_y;
-          a.range = c->range + (size_t)f0 * FPC_RANGE_WORDS;
-          if (c->split || c->bf16) {
-            StemX3Args x{};
-            x.in = a.in; x.wfrag = reinterpret_cast<const uint4*>(a.wfrag); x.bias = a.bias; x.out = a.out;
-            x.H = H; x.W = W; x.Ho = a.Ho; x.Wo = a.Wo; x.Hp = a.Hp; x.Wp = a.Wp; x.tiles_x = a.tiles_x; x.tiles_y = a.tiles_y;
-            x.range_flag = c->split_f16 ? c->status + 1 : nullptr;
-#ifdef FPC_DIAG
-            x.stamps = nullptr;
-            if (const char* e = getenv("FPC_STAMP_OP"))
-              if (op.name.find(e) != std::string::npos) {
-                if (!c->diag_stamps) hipHostMalloc((void**)&c->diag_stamps, (size_t)65536 * 8 * sizeof(unsigned long long));
-                memset(c->diag_stamps, 0, (size_t)65536 * 8 * sizeof(unsigned long long));
-                x.stamps = c->diag_stamps;
-                c->diag_n = a.tiles_x * a.tiles_y * n;
-              }
-#endif
-            const dim3 grid(a.tiles_x * a.tiles_y * n);
-            if (c->split_f16) {
-              if (c->cin == 1) hipLaunchKernelGGL((stem_pool_x3_kernel<1, 2>), grid, dim3(256), 0, sb.st, x);
-              else hipLaunchKernelGGL((stem_pool_x3_kernel<3, 2>), grid, dim3(256), 0, sb.st, x);
-            } else if (c->bf16) {  // bf16 mode: bf16 operands like every other layer of the mode, bf16 out, no atomics
-              x.frames = n;
-              x.tiles_x = (x.Wp + SB2_PW - 1) / SB2_PW;   // stem_bf16.h: 8 x 7 pooled pixels per tile
-              x.tiles_y = (x.Hp + SB2_PH - 1) / SB2_PH;
-              const int T = x.tiles_x * x.tiles_y * n;
-              const dim3 pg(std::min((T + 7) / 8 * 8, std::max(8, 2 * c->num_cus / 8 * 8)));  // two workgroups per CU, a multiple of 8
-              if (c->cin == 1) hipLaunchKernelGGL(stem_bf16_kernel<1>, pg, dim3(SB2_THREADS), StemB2Cfg<1>::LDS_BYTES, sb.st, x);
-              else hipLaunchKernelGGL(stem_bf16_kernel<3>, pg, dim3(SB2_THREADS), StemB2Cfg<3>::LDS_BYTES, sb.st, x);
-            } else {
-              if (c->cin == 1) hipLaunchKernelGGL((stem_pool_x3_kernel<1, 3>), grid, dim3(256), 0, sb.st, x);
-              else hipLaunchKernelGGL((stem_pool_x3_kernel<3, 3>), grid, dim3(256), 0, sb.st, x);
-            }
-          } else if (c->stem2) {
-            if (c->cin == 1) hipLaunchKernelGGL(stem_pool2_kernel<1>, dim3(a.tiles_x * a.tiles_y * n), dim3(256), 0, sb.st, a);
-            else hipLaunchKernelGGL(stem_pool2_kernel<3>, dim3(a.tiles_x * a.tiles_y * n), dim3(256), 0, sb.st, a);
-          } else if (c->cin == 1)
-            hipLaunchKernelGGL(stem_pool_kernel<1>, dim3(a.tiles_x * a.tiles_y * n), dim3(256), 0, sb.st, a);
-          else
-            hipLaunchKernelGGL(stem_pool_kernel<3>, dim3(a.tiles_x * a.tiles_y * n), dim3(256), 0, sb.st, a);
-          break;
-        }
-        LaunchTimer t(c, (int)i, sb.st, n);
-        StemArgs a = c->stem;
-        a.in = frames + (size_t)f0 * 3 * H * W;
-        a.out = c->stem_out + (size_t)f0 * (H / 2) * (W / 2) * 64;
-        hipLaunchKernelGGL(stem_kernel, dim3(a.tiles_x * a.tiles_y * n), dim3(256), 0, sb.st, a);
-        break;
-      }
-      case OP_POOL: {
-        if (c->fuse_stem_pool || c->cin == 1 || c->bf16) break;
-        LaunchTimer t(c, (int)i, sb.st, n);
-        const size_t total = (size_t)n * (H / 4) * (W / 4) * 16;
-        hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sb.st,
-                           reinterpret_cast<const float4*>(c->stem_out + (size_t)f0 * (H / 2) * (W / 2) * 64),
-                           reinterpret_cast<float4*>(c->x0 + (size_t)f0 * (H / 4) * (W / 4) * 64), n, H / 2, W / 2, H / 4,
-                           W / 4);
-        break;
-      }
-      case OP_WBLOCK: {
-        LaunchTimer t(c, (int)i, sb.st, n);
-        WBlockArgs a = op.wargs;
-        a.frame0 = f0;
-#ifdef FPC_DIAG
-        a.stamps = nullptr;
-        if (const char* e = getenv("FPC_STAMP_OP"))
-          if (op.name.find(e) != std::string::npos) {
-            if (!c->diag_stamps) hipHostMalloc((void**)&c->diag_stamps, (size_t)65536 * 8 * sizeof(unsigned long long));
-            memset(c->diag_stamps, 0, (size_t)65536 * 8 * sizeof(unsigned long long));
-            a.stamps = c->diag_stamps;
-            c->diag_n = a.tiles_x * a.tiles_y * n;
-          }
-#endif
-        a.total = a.tiles_x * a.tiles_y * n;
-        a.xcd_order = c->xcd_order ? 1 : 0;
-        {  // range of the input's buffer descriptor: frames 0 .. f0 + n - 1 of the tensor, from `x` (already offset to its first channel)
-          const unsigned long long xb = (unsigned long long)(f0 + n) * a.H * a.W * a.csx * sizeof(float);
-          a.x_bytes = xb > 0xfffffff0ull ? 0xfffffff0u : (unsigned)xb;
-        }
-        // persistent (one workgroup per CU walking the tiles) when a workgroup gets enough tiles to
-        // amortise; otherwise one workgroup per tile
-        int grid = (c->persist_min_tiles > 0 && a.total >= c->persist_min_tiles * c->num_cus) ? c->num_cus : a.total;
-        if (g_wkinds[op.wkind].gen == 3) {
-          // Pointers to the launch's first frame, as many frames per launch as stay below W36_MARKER bytes (all of them,
-          // except at the C++ network's full-resolution layers: 78.6 MB per VGA frame and tensor).
-          const int fpl = w36_frames_per_launch(a.H, a.W, a.csx, a.cso);
-          const float* x0 = a.x;
-          float* o0 = a.out;
-          const int Hf = a.H, tx_f = a.tiles_x, ty_f = a.tiles_y;
-          const WKind sk = c->tiles_round6 ? w36_stacked_kind(op.wkind) : WK_COUNT;
-          double mf = 0.0;
-          for (int g0 = 0; g0 < n; g0 += fpl) {
-            const int gn = std::min(fpl, n - g0);
-            a.frame0 = 0;
-            a.x = x0 + (size_t)(f0 + g0) * Hf * a.W * a.csx;
-            a.out = o0 + (size_t)(f0 + g0) * Hf * a.W * a.cso;
-            a.x_bytes = (unsigned)((unsigned long long)gn * Hf * a.W * a.csx * sizeof(float));
-            // round 6: the launch's frames as ONE image of gn x Hf rows where that is fewer tiles (wblock36s_kernel)
-            const int srows = w36_stacked_rows(Hf, a.W, gn, sk, tx_f * ty_f);
-            const WKind lk = srows ? sk : op.wkind;
-            a.H = srows ? gn * Hf : Hf;
-            a.frame_h = srows ? Hf : 0;
-            a.tiles_x = srows ? (a.W + g_wkinds[sk].TW - 1) / g_wkinds[sk].TW : tx_f;
-            a.tiles_y = srows ? srows : ty_f;
-            a.total = srows ? a.tiles_x * srows : tx_f * ty_f * gn;
-            if (srows) t.wkind = sk;
-            mf += srows ? wkind_mfma_flops(g_wkinds[sk], a.total, a.nchunk, a.k8_h + a.k8_x) : op.mfma_flops_per_frame * gn;
-            // One workgroup per CU (137 KB of LDS), so a launch lasts ceil(tiles / CUs) tile times whatever the grid: take
-            // the SMALLEST grid that still finishes in that many rounds (a multiple of 8: the tile walk is per XCD) and
-            // leave the other CUs to the launches of the other sub-batch's stream -- 640 tiles: 216 workgroups x 3 rounds
-            // instead of 256 of which 128 idle through the third; 320 tiles: 160 x 2.
-            // (a launch of gridDim.y parts shares the CUs between them: each part's tile walk gets CUs / parts)
-            const int cus_cap = c->w36_cus > 0 ? std::min(c->num_cus, c->w36_cus) : c->num_cus;
-            const int cus8 = std::max(1, cus_cap / 8 / std::max(1, op.grid_y)), per_xcd = (a.total + 7) / 8;
-            const int rounds = (per_xcd + cus8 - 1) / cus8;
-            const int grid3 = 8 * std::min(cus8, (per_xcd + rounds - 1) / rounds);
-            g_wkinds[lk].launch(a, dim3(std::min(a.total, grid3), op.grid_y), sb.st);
-          }
-          if (t.wkind >= 0) t.mfma_flops = mf;
-          break;
-        }
-        g_wkinds[op.wkind].launch(a, dim3(std::min(a.total, grid), op.grid_y), sb.st);
-        break;
-      }
-      case OP_BLOCK: {
-        LaunchTimer t(c, (int)i, sb.st, n);
-        BlockArgs a = op.bargs;
-        a.frame0 = f0;
-#ifdef FPC_DIAG
-        a.stamps = nullptr;
-        if (const char* e = getenv("FPC_STAMP_OP"))
-          if (op.name.find(e) != std::string::npos) {
-            if (!c->diag_stamps) hipHostMalloc((void**)&c->diag_stamps, (size_t)65536 * 8 * sizeof(unsigned long long));
-            memset(c->diag_stamps, 0, (size_t)65536 * 8 * sizeof(unsigned long long));
-            a.stamps = c->diag_stamps;
-            c->diag_n = a.tiles_x * a.tiles_y * n;
-          }
-#endif
-        g_bkinds[op.bkind].launch(a, dim3(a.tiles_x * a.tiles_y * n), sb.st);
-        break;
-      }
-      case OP_BF16: {
-        LaunchTimer t(c, (int)i, sb.st, n);
-        BlockBfArgs a = op.fargs;
-        a.frame0 = f0;
-        a.range_flag = c->split_f16 ? c->status + 1 : nullptr;
-#ifdef FPC_DIAG
-        a.stamps = nullptr;
-        if (const char* e = getenv("FPC_STAMP_OP"))
-          if (op.name.find(e) != std::string::npos) {
-            if (!c->diag_stamps) hipHostMalloc((void**)&c->diag_stamps, (size_t)65536 * 8 * sizeof(unsigned long long));
-            memset(c->diag_stamps, 0, (size_t)65536 * 8 * sizeof(unsigned long long));
-            a.stamps = c->diag_stamps;
-            c->diag_n = a.tiles_x * a.tiles_y * n;
-          }
-#endif
-        if (g_fkinds[op.fkind].planes == 1) {   // block_bf16_kernel: persistent grid, a multiple of 8 (block_bf16.h)
-          a.total_tiles = a.tiles_x * a.tiles_y * n;
-          if (sb.fuse_softmax && op.fused_softmax_capable) {
-            const size_t HW = (size_t)c->H * c->W;
-            hipMemsetAsync(c->ncand + f0, 0, sizeof(int32_t) * n, sb.st);
-            a.softmax = 1;
-            a.thresh = c->cfg.conf_thresh;
-            a.nmsmap = c->nmsmap + f0 * HW;
-            a.cand = c->cand + f0 * HW;
-            a.ncand = c->ncand + f0;
-          }
-          // (op.grid_y parts -- convt_bf16_kernel's output-channel halves -- share the CUs)
-          const int g = std::min((a.total_tiles + 7) / 8 * 8, std::max(8, c->fkind_blocks_per_cu[op.fkind] * c->num_cus / op.grid_y / 8 * 8));
-          g_fkinds[op.fkind].launch(a, dim3(g, op.grid_y), sb.st);
-        } else {
-          g_fkinds[op.fkind].launch(a, dim3(a.tiles_x * a.tiles_y * n), sb.st);
-        }
-        break;
-      }
-      case OP_VCONV0: {
-        LaunchTimer t(c, (int)i, sb.st, n);
-        VggConv0Args a{};
-        a.in = frames;
-        a.w = c->blob + c->vconv0_off;
-        a.out = op.pout;
-        a.H = H; a.W = W; a.frame0 = f0;
-        hipLaunchKernelGGL(vgg_conv0_kernel, dim3((unsigned)((size_t)n * H * W / 64)), dim3(256), 0, sb.st, a);
-        break;
-      }
-      case OP_POOL2: {
-        LaunchTimer t(c, (int)i, sb.st, n);
-        const size_t tot = (size_t)n * (op.pH / 2) * (op.pW / 2) * (op.pC / 4);
-        hipLaunchKernelGGL(maxpool2_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, sb.st,
-                           reinterpret_cast<const float4*>(op.pin), reinterpret_cast<float4*>(op.pout), n, op.pH, op.pW,
-                           op.pC / 4, f0);
-        break;
-      }
-      case OP_L2NORM: {
-        LaunchTimer t(c, (int)i, sb.st, n);
-        const size_t npix = (size_t)n * c->Hc * c->Wc;
-        hipLaunchKernelGGL(l2norm256_kernel, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, sb.st,
-                           op.pout + (size_t)f0 * c->Hc * c->Wc * 256, npix);
-        break;
-      }
-      case OP_CONV: {
-        LaunchTimer t(c, (int)i, sb.st, n);
-        ConvArgs a = op.args;
-        a.frame0 = f0;
-        if (op.lean) lean_kind(op.kind)->launch(a, dim3(a.tiles_x * a.tiles_y * n, op.grid_y, op.grid_z), sb.st);
-        else g_kinds[op.kind].launch(a, dim3(a.tiles_x * a.tiles_y * n, op.grid_y, op.grid_z), sb.st);
-        break;
-      }
-      default:
-        break;  // post-processing ops are issued by the callers
+      case OP_STEM: launch_stem(c, op, (int)i, frames, &sb); break;
+      case OP_POOL: launch_pool(c, (int)i, sb); break;
+      case OP_WBLOCK: launch_wblock(c, op, (int)i, sb); break;
+      case OP_BLOCK: launch_block(c, op, (int)i, sb); break;
+      case OP_BF16: launch_fblock(c, op, (int)i, sb); break;
+      case OP_CONV: launch_conv(c, op, (int)i, sb); break;
+      case OP_VCONV0: launch_vconv0(c, op, (int)i, frames, sb); break;
+      case OP_POOL2: launch_pool2(c, op, (int)i, sb); break;
+      case OP_L2NORM: launch_l2norm(c, op, (int)i, sb); break;
+      default: break;  // post-processing ops are issued by the callers
     }
   }
 }
@@ -4951,7 +4833,7 @@ int fpc_get_timings(fpc_ctx* c, int cap, const char** names, const char** kernel
     if (kernels) {
       const char* k = "?";
       if (op) switch (op->type) {
-          case OP_STEM: k = c->bf16 ? "stem_bf16_kernel" : c->split ? "stem_pool_x3_kernel" : c->stem2 ? "stem_pool2_kernel" : c->fuse_stem_pool ? "stem_pool_kernel" : "stem_kernel"; break;
+          case OP_STEM: k = launch_stem(c, *op, t.op, nullptr, nullptr); break;   // (no Sub: the name alone)
           case OP_POOL: k = "maxpool_kernel"; break;
           case OP_CONV: k = op->lean ? lean_kind(op->kind)->symbol : g_kinds[op->kind].symbol; break;
           case OP_BLOCK: k = g_bkinds[op->bkind].symbol; break;

@@ -22,7 +22,7 @@
 //     the tail is one pass (no halves): 1x1 over h (+ projection over x, staged 64 channels at a time), each wave eight
 //     pixel blocks of its channel group; epilogue through LDS into 16-byte stores.
 // Same WBlockArgs, same packed weights, same results up to the order of two additions as wblock36_kernel<1, TYT, TXT>.
-// The detector's 65-channel blocks (the DUST instance) stay on the one-wave kernel.
+// The detector's 65-channel blocks run on the DUST instance of this kernel (wblock36p_dust_kernel, WK_W36PD_*).
 #pragma once
 #include "wblock36_mfma.h"
 
