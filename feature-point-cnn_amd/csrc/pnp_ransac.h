@@ -1,23 +1,25 @@
 // Batched RANSAC perspective-n-point (fpc_ransac_pnp / fpc_pnp_frames / fpc_pnp_bank; the rule is stated in include/fpc.h and
-// restated in float64 by tests/test_pnp_ransac.py).  The hash, the (count << 32) | ~t selection and hf_block_sum are
-// ransac_homography.h's, the Jacobi routine is ransac_fundamental.h's.
+// restated in float64 by tests/test_pnp_ransac.py).  This header holds the pose's model -- the DLT rows, the polar step, the
+// Gauss-Newton sums and pose update, the reprojection tests -- its pair records and the landmark kernels; the sampler, the
+// selection key, the compaction, the LDS solve and the score and refit skeletons are ransac_parts.h's, the Jacobi routine is
+// ransac_fundamental.h's.  The full-pivot elimination inside pnp_solve6 is fm_solve8's at another size, written out again
+// (ransac_fundamental.h says why).
 //
 //   pnp_pack_kernel / pnp_gather_kernel   twins of hf_pack_kernel / hf_gather_kernel: every problem's pair list as 32-byte
 //                     records [x, y, X, Y | Z, row, -, -] (two float4; `row` is the mask row of the pair, as int bits), the
-//                     pair count, and the zeroed best key and mask.  The gather is the same order-preserving compaction
-//                     (ballot + popcount prefix, no atomics); a landmark's validity (its w, or valid[] and the finiteness
-//                     of its coordinates) is part of the pair test.
-//   pnp_score_kernel  grid ceil(T / 64) x n, one thread per hypothesis: draws its 6 pairs and solves the normalised 6-point
-//                     DLT in fp64 by Gaussian elimination with full pivoting.  The 11 x 12 system needs dynamic row and
-//                     column indices, so it lives in LDS, struct-of-arrays (sys[132][64]); the column permutation is twelve
-//                     nibbles of one 64-bit register.  132 doubles x 64 lanes = 66 KiB: ONE wave per workgroup, so that
+//                     pair count, and the zeroed best key and mask.  The gather is the same gather_body; a landmark's
+//                     validity (its w, or valid[] and the finiteness of its coordinates) is part of the pair test.
+//   pnp_score_kernel  score_body at 64 hypotheses per workgroup: the normalised 6-point DLT in fp64 by Gaussian elimination
+//                     with full pivoting.  The 11 x 12 system needs dynamic row and column indices, so it lives in LDS,
+//                     struct-of-arrays (sys[132][64]); the column permutation is twelve nibbles of one 64-bit register.
+//                     132 doubles x 64 lanes = 66 KiB: ONE wave per workgroup, so that
 //                     two workgroups share a CU's 160 KiB (128 lanes would need 132 KiB and run alone).  P then sits in 12
-//                     fp32 VGPRs and the pair list is walked through the same LDS in 1 024-record chunks (32 KiB), every
-//                     lane reading the same record: the broadcast case.
+//                     fp32 VGPRs and the pair list is walked through the same LDS in 1 024-record chunks (32 KiB).
 //   pnp_refit_kernel  one workgroup of 256 per problem: one lane re-derives the best sample's P with the same device
-//                     function and takes its polar step (fm_jacobi at N = 3); then `refits` times one pass over the pairs
-//                     (the 21 + 6 sums of J^T J and J^T r, and the count, in fp64 through hf_block_sum) and one lane's
-//                     6 x 6 elimination in LDS; writes R, t, the inlier count and the mask of the pose it returns.
+//                     function and takes its polar step (fm_jacobi at N = 3; refit_head); then `refits` times one pass over
+//                     the pairs (the 21 + 6 sums of J^T J and J^T r, and the count, in fp64 through hf_block_sum) and one
+//                     lane's 6 x 6 solve_lds; through refit_tail it writes R, t, the inlier count and the mask of the pose
+//                     it returns.
 //   pnp_landmarks_store_kernel / pnp_landmarks_invalidate_kernel   element-wise, over one slot's rows (or every slot's).
 #pragma once
 #include "ransac_fundamental.h"
@@ -26,7 +28,7 @@ constexpr int PNP_DRAWS = 32;          // draw budget of one sample
 constexpr int PNP_SAMPLE = 6;
 constexpr int PNP_THREADS = 64;        // hypotheses per workgroup of pnp_score_kernel: 66 KiB of LDS, two workgroups per CU
 constexpr int PNP_ROWS = 11, PNP_COLS = 12;
-constexpr int PNP_CHUNK = 1024;        // records staged per LDS chunk (32 KiB)
+constexpr int PNP_CHUNK = HF_CHUNK;    // records staged per LDS chunk (32 KiB)
 constexpr double PNP_PIVOT = 1e-10;    // last pivot / first pivot below which a sample is degenerate
 constexpr double PNP_RANK = 1e-12;     // lambda_min / lambda_max of A^T A at or below which P has no rotation
 constexpr double PNP_SINGULAR = 1e-14; // pivot / largest diagonal entry of J^T J at or below which a refit is singular
@@ -52,11 +54,6 @@ __device__ __forceinline__ PnpPair pnp_load(const float4* __restrict__ rec, int 
 
 __device__ __forceinline__ bool pnp_finite3(float X, float Y, float Z) {
   return fabsf(X) <= 3.402823466e38f && fabsf(Y) <= 3.402823466e38f && fabsf(Z) <= 3.402823466e38f;   // (false for NaN)
-}
-
-// the sampler of include/fpc.h: the first 6 distinct of 32 draws
-__device__ __forceinline__ bool pnp_sample(uint32_t seed, uint32_t f, uint32_t t, uint32_t M, uint32_t (&idx)[PNP_SAMPLE]) {
-  return hf_sample_distinct<PNP_SAMPLE, PNP_DRAWS>(seed, f, t, M, idx);
 }
 
 // The 6-point DLT.  sys: this thread's 11 x 12 system, element (r, c) at sys[(r * 12 + c) * S] (LDS).  Image points in
@@ -230,8 +227,7 @@ struct PnpTrain {
 // one workgroup per frame; rows i < count[f] with 0 <= match < the train count and a valid landmark, in ascending i
 __global__ __launch_bounds__(256) void pnp_gather_kernel(PnpArgs a, const int32_t* __restrict__ xy, const int32_t* __restrict__ count,
                                                          const int32_t* __restrict__ match, uint8_t* mask, const PnpTrain tr) {
-  __shared__ int wsum[4];
-  const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cap = a.cap;
+  const int f = blockIdx.x, cap = a.cap;
   const int cnt = hf_clamp(count[f], cap);
   const float4* lm = nullptr;
   int nt = 0;
@@ -244,102 +240,72 @@ __global__ __launch_bounds__(256) void pnp_gather_kernel(PnpArgs a, const int32_
   } else {
     nt = hf_clamp(tr.nkey[0], cap);
   }
-  const int32_t* qxy = xy + (size_t)f * cap * 2;
-  const int end = mask ? cap : cnt;
-  int base = 0;
-  for (int i0 = 0; i0 < end; i0 += 256) {
-    const int i = i0 + tid;
-    int m = -1;
-    if (i < cnt) m = match[(size_t)f * cap + i];
-    bool flag = m >= 0 && m < nt;
-    float X = 0.f, Y = 0.f, Z = 0.f;
-    if (flag) {
+  // gather_body's Source: row i of frame f is a pair when its match is a row of the train set with a valid landmark, which
+  // `pair` keeps for `write`
+  struct {
+    const PnpArgs& a;
+    const PnpTrain& tr;
+    const int32_t* qxy;
+    const float4* lm;
+    int f, nt;
+    float X, Y, Z;
+    __device__ __forceinline__ bool pair(int m) {
+      X = Y = Z = 0.f;
+      if (!(m >= 0 && m < nt)) return false;
       if (tr.slot) {
         const float4 p = lm[m];
         X = p.x; Y = p.y; Z = p.z;
-        flag = p.w != 0.f;
-      } else {
-        X = tr.key_xyz[3 * (size_t)m]; Y = tr.key_xyz[3 * (size_t)m + 1]; Z = tr.key_xyz[3 * (size_t)m + 2];
-        flag = (!tr.key_valid || tr.key_valid[m] != 0) && pnp_finite3(X, Y, Z);
+        return p.w != 0.f;
       }
+      X = tr.key_xyz[3 * (size_t)m]; Y = tr.key_xyz[3 * (size_t)m + 1]; Z = tr.key_xyz[3 * (size_t)m + 2];
+      return (!tr.key_valid || tr.key_valid[m] != 0) && pnp_finite3(X, Y, Z);
     }
-    if (mask && i < cap) mask[(size_t)f * cap + i] = 0;
-    const unsigned long long b = __ballot(flag);
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();
-    if (lane == 0) wsum[wave] = __popcll(b);
-    __syncthreads();
-    int off = base + before;
-    for (int w = 0; w < 4; ++w) {
-      if (w < wave) off += wsum[w];
-      base += wsum[w];
-    }
-    if (flag) {
-      float4* out = a.rec + ((size_t)f * cap + off) * 2;
+    __device__ __forceinline__ void write(int off, int i, int) {
+      float4* out = a.rec + ((size_t)f * a.cap + off) * 2;
       out[0] = make_float4((float)qxy[2 * i], (float)qxy[2 * i + 1], X, Y);
       out[1] = make_float4(Z, __int_as_float(i), 0.f, 0.f);
     }
-  }
-  if (tid == 0) {
-    a.np[f] = base;
-    a.best[f] = 0ull;
-  }
+  } src{a, tr, xy + (size_t)f * cap * 2, lm, f, nt, 0.f, 0.f, 0.f};
+  gather_body(src, f, cnt, cap, match, mask, a.np, a.best);
 }
 
 // ---- scoring ----------------------------------------------------------------------------------------------------------
+// score_body's Model.  P sits in twelve named registers on purpose: an indexed store becomes scratch.  (A degenerate
+// hypothesis keeps P = 0: w = 0 is never > 0, it counts nothing.)
+struct PnpModel {
+  static constexpr int SAMPLE = PNP_SAMPLE, DRAWS = PNP_DRAWS, REC = 2;
+  float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f, p4 = 0.f, p5 = 0.f, p6 = 0.f, p7 = 0.f, p8 = 0.f, p9 = 0.f, p10 = 0.f, p11 = 0.f;
+  float thr;
+  __device__ __forceinline__ explicit PnpModel(const PnpArgs& a) : thr(a.thr) {}
+  static __device__ __forceinline__ const float4* records(const PnpArgs& a, int f) { return a.rec + (size_t)f * a.cap * 2; }
+  static __device__ __forceinline__ int frame(const PnpArgs&, int f) { return f; }
+  __device__ __forceinline__ bool solve(const PnpArgs& a, const float4* __restrict__ rec, const uint32_t (&idx)[PNP_SAMPLE],
+                                        double* sys) {
+    double P[12];
+    PnpPair first;
+    float P32[12];
+    if (!(pnp_solve6<PNP_THREADS>(sys + threadIdx.x, rec, idx, a, P, first) && pnp_hypothesis(P, a, first, P32))) return false;
+    p0 = P32[0]; p1 = P32[1]; p2 = P32[2]; p3 = P32[3]; p4 = P32[4]; p5 = P32[5];
+    p6 = P32[6]; p7 = P32[7]; p8 = P32[8]; p9 = P32[9]; p10 = P32[10]; p11 = P32[11];
+    return true;
+  }
+  __device__ __forceinline__ bool counts(const float4* r) const {
+    const float4 q = r[0];
+    const float Z = r[1].x;
+    const float w = fmaf(p10, Z, fmaf(p9, q.w, fmaf(p8, q.z, p11)));
+    const float u = fmaf(p2, Z, fmaf(p1, q.w, fmaf(p0, q.z, p3)));
+    const float v = fmaf(p6, Z, fmaf(p5, q.w, fmaf(p4, q.z, p7)));
+    const float ex = fmaf(-w, q.x, u), ey = fmaf(-w, q.y, v);
+    const float tw = thr * w;
+    return w > 0.f && fmaf(ex, ex, ey * ey) < tw * tw;
+  }
+};
+
 __global__ __launch_bounds__(PNP_THREADS) void pnp_score_kernel(PnpArgs a) {
   __shared__ double sys[PNP_ROWS * PNP_COLS * PNP_THREADS];  // the systems; afterwards the staged pair chunk
   static_assert(sizeof(double) * PNP_ROWS * PNP_COLS * PNP_THREADS >= sizeof(float4) * 2 * PNP_CHUNK,
                 "the pair chunk reuses the systems' LDS");
-  float4* stage = reinterpret_cast<float4*>(sys);
-  const int f = blockIdx.y, tid = threadIdx.x;
-  const int M = hf_clamp(a.np[f], a.cap);
-  if (M < PNP_SAMPLE) return;
-  const float4* __restrict__ rec = a.rec + (size_t)f * a.cap * 2;
-  const uint32_t t = blockIdx.x * (uint32_t)PNP_THREADS + tid;
-  float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f, p4 = 0.f, p5 = 0.f, p6 = 0.f, p7 = 0.f, p8 = 0.f, p9 = 0.f, p10 = 0.f, p11 = 0.f;
-  bool ok = t < (uint32_t)a.T;
-  if (ok) {
-    uint32_t idx[PNP_SAMPLE];
-    ok = pnp_sample(a.seed, (uint32_t)f, t, (uint32_t)M, idx);
-    if (ok) {
-      double P[12];
-      PnpPair first;
-      float P32[12];
-      ok = pnp_solve6<PNP_THREADS>(sys + tid, rec, idx, a, P, first) && pnp_hypothesis(P, a, first, P32);
-      if (ok) {
-        p0 = P32[0]; p1 = P32[1]; p2 = P32[2]; p3 = P32[3]; p4 = P32[4]; p5 = P32[5];
-        p6 = P32[6]; p7 = P32[7]; p8 = P32[8]; p9 = P32[9]; p10 = P32[10]; p11 = P32[11];
-      }
-    }
-  }
-  // (a degenerate hypothesis keeps P = 0: w = 0 is never > 0, it counts nothing; such lanes still meet the barriers)
-  const float thr = a.thr;
-  int cnt = 0;
-  for (int c0 = 0; c0 < M; c0 += PNP_CHUNK) {
-    const int m = min(PNP_CHUNK, M - c0);
-    __syncthreads();
-    for (int i = tid; i < 2 * m; i += PNP_THREADS) stage[i] = rec[2 * c0 + i];
-    __syncthreads();
-#pragma unroll 4
-    for (int k = 0; k < m; ++k) {
-      const float4 q = stage[2 * k];
-      const float Z = stage[2 * k + 1].x;
-      const float w = fmaf(p10, Z, fmaf(p9, q.w, fmaf(p8, q.z, p11)));
-      const float u = fmaf(p2, Z, fmaf(p1, q.w, fmaf(p0, q.z, p3)));
-      const float v = fmaf(p6, Z, fmaf(p5, q.w, fmaf(p4, q.z, p7)));
-      const float ex = fmaf(-w, q.x, u), ey = fmaf(-w, q.y, v);
-      const float tw = thr * w;
-      cnt += (w > 0.f && fmaf(ex, ex, ey * ey) < tw * tw) ? 1 : 0;
-    }
-  }
-  unsigned long long key = (ok && cnt > 0) ? (((unsigned long long)(uint32_t)cnt << 32) | (unsigned long long)(~t)) : 0ull;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long other = __shfl_xor(key, o);
-    key = other > key ? other : key;
-  }
-  if (tid == 0 && key) atomicMax(a.best + f, key);
+  score_body<PNP_THREADS, PnpModel>(a, reinterpret_cast<float4*>(sys), sys);
 }
 
 // ---- refit ------------------------------------------------------------------------------------------------------------
@@ -402,24 +368,17 @@ __global__ __launch_bounds__(256) void pnp_refit_kernel(PnpArgs a, float* __rest
   const double thr2 = (double)a.thr * (double)a.thr;
   const double fx = a.fx, fy = a.fy, cx = a.cx, cy = a.cy;
   double R[9], t[3];
-  bool ok = M >= PNP_SAMPLE && key != 0ull;
-  if (ok) {                                     // (uniform) one lane re-derives the best sample's P: same function, same bits
-    if (tid == 0) {
-      uint32_t idx[PNP_SAMPLE];
-      double P[12];
-      PnpPair first;
-      int good = pnp_sample(a.seed, (uint32_t)f, ~(uint32_t)key, (uint32_t)M, idx) && pnp_solve6<1>(sys, rec, idx, a, P, first);
-      if (good) {
+  bool ok = refit_head(M >= PNP_SAMPLE && key != 0ull, &solved, [&]() {
+    uint32_t idx[PNP_SAMPLE];
+    double P[12];
+    PnpPair first;
+    if (!(hf_sample_distinct<PNP_SAMPLE, PNP_DRAWS>(a.seed, (uint32_t)f, ~(uint32_t)key, (uint32_t)M, idx) &&
+          pnp_solve6<1>(sys, rec, idx, a, P, first)))
+      return false;
 #pragma unroll
-        for (int i = 0; i < 12; ++i) pw[i] = P[i];
-        good = pnp_polar(pw, jm, jv, jw, pose);
-      }
-      solved = good;
-    }
-    __syncthreads();
-    ok = solved != 0;
-  }
-  int total = 0;
+    for (int i = 0; i < 12; ++i) pw[i] = P[i];
+    return pnp_polar(pw, jm, jv, jw, pose);
+  });
   if (ok) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = pose[i];
@@ -460,31 +419,8 @@ __global__ __launch_bounds__(256) void pnp_refit_kernel(PnpArgs a, float* __rest
           sm[i][6] = -s28[21 + i];
           dmax = fmax(dmax, fabs(sm[i][i]));
         }
-        // Gaussian elimination with partial pivoting, in LDS (dynamic indices must not become scratch)
-        int good = 1;
-        const double tiny = PNP_SINGULAR * dmax;
-        for (int c = 0; c < 6 && good; ++c) {
-          int pr = c;
-          double pv = fabs(sm[c][c]);
-          for (int i = c + 1; i < 6; ++i) {
-            const double v = fabs(sm[i][c]);
-            if (v > pv) { pv = v; pr = i; }
-          }
-          if (!(pv > tiny)) { good = 0; break; }
-          if (pr != c)
-            for (int j = c; j < 7; ++j) { const double tmp = sm[c][j]; sm[c][j] = sm[pr][j]; sm[pr][j] = tmp; }
-          const double ip = 1.0 / sm[c][c];
-          for (int i = c + 1; i < 6; ++i) {
-            const double fct = sm[i][c] * ip;
-            for (int j = c; j < 7; ++j) sm[i][j] -= fct * sm[c][j];
-          }
-        }
+        int good = solve_lds<6>(sm, PNP_SINGULAR * dmax) ? 1 : 0;
         if (good) {
-          for (int i = 5; i >= 0; --i) {
-            double acc = sm[i][6];
-            for (int j = i + 1; j < 6; ++j) acc -= sm[i][j] * sm[j][6];
-            sm[i][6] = acc / sm[i][i];
-          }
           const double w0 = sm[0][6], w1 = sm[1][6], w2 = sm[2][6], v0 = sm[3][6], v1 = sm[4][6], v2 = sm[5][6];
           const double th2 = w0 * w0 + w1 * w1 + w2 * w2;
           double A = 1.0, B = 0.5;
@@ -520,28 +456,18 @@ __global__ __launch_bounds__(256) void pnp_refit_kernel(PnpArgs a, float* __rest
 #pragma unroll
       for (int i = 0; i < 3; ++i) t[i] = pose[9 + i];
     }
-    double c1[1] = {0.0};
-    for (int k = tid; k < M; k += 256) {
-      double xa, xb, xc;
-      c1[0] += pnp_inlier(R, t, a, pnp_load(rec, k), thr2, xa, xb, xc) ? 1.0 : 0.0;
-    }
-    hf_block_sum<1>(c1, red);
-    total = (int)c1[0];
-    ok = total >= a.min_inliers;
   }
-  if (ok && mask)                                                           // (the pack / gather kernel zeroed the mask)
-    for (int k = tid; k < M; k += 256) {
-      const PnpPair p = pnp_load(rec, k);
-      double xa, xb, xc;
-      if (pnp_inlier(R, t, a, p, thr2, xa, xb, xc)) mask[(size_t)f * mstride + p.row] = 1;
-    }
-  __syncthreads();
+  ok = refit_tail(ok, M, a.min_inliers, red, mask, ninl + f,
+                  [&](int k) {
+                    double xa, xb, xc;
+                    return pnp_inlier(R, t, a, pnp_load(rec, k), thr2, xa, xb, xc);
+                  },
+                  [&](int k) { return (size_t)f * mstride + pnp_load(rec, k).row; });
   if (tid == 0) {                                                           // (through LDS: R[tid] would be scratch)
 #pragma unroll
     for (int i = 0; i < 9; ++i) pose[i] = ok ? R[i] : 0.0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) pose[9 + i] = ok ? t[i] : 0.0;
-    ninl[f] = ok ? total : 0;
   }
   __syncthreads();
   if (tid < 9) Rout[f * 9 + tid] = (float)pose[tid];

@@ -1,6 +1,7 @@
 // Relative pose from a fundamental matrix (fpc_pose_fundamental / fpc_pose_frames / fpc_pose_bank; the rule is stated in
-// include/fpc.h and restated in float64 by tests/test_pose_epipolar.py).  The pair records, their pack / gather kernels, the
-// workspace and hf_block_sum are ransac_homography.h's; the Sampson test and the Jacobi routine are ransac_fundamental.h's.
+// include/fpc.h and restated in float64 by tests/test_pose_epipolar.py).  The pair records, their pack / gather kernels and
+// the workspace are ransac_homography.h's, hf_clamp and hf_block_sum are ransac_parts.h's; the Sampson test and the Jacobi
+// routine are ransac_fundamental.h's.
 //
 //   pose_kernel   one workgroup of 256 per frame.  One lane forms E = K_t^T F K_q, diagonalises E^T E by fm_jacobi at N = 3
 //                 and builds the two rotations and the translation direction; whatever is indexed dynamically (the Jacobi

@@ -1,17 +1,21 @@
 // Batched RANSAC fundamental matrices (fpc_ransac_fundamental / fpc_fundamental_frames / fpc_fundamental_bank; the rule is
 // stated in include/fpc.h and restated in float64 by tests/test_fundamental_ransac.py).  The pair records, their pack /
-// gather kernels, the workspace, the hash, the (count << 32) | ~t selection and hf_block_sum are ransac_homography.h's.
+// gather kernels and the workspace are ransac_homography.h's.  This header holds the fundamental matrix's model -- the
+// 8-point rows, the rank-2 projection and the finish, the Sampson tests -- and fm_jacobi, which pose_epipolar.h and
+// pnp_ransac.h use too; the sampler, the selection key, the score and refit skeletons and the Hartley moments are
+// ransac_parts.h's.  The full-pivot elimination inside fm_solve8 is written out here and again in pnp_solve6: as one shared
+// function template it returned the same bits and cost both score kernels 6 % of their time.
 //
-//   fm_score_kernel   grid ceil(T / 128) x n, one thread per hypothesis: draws its 8 pairs, solves the normalised 8-point
-//                     system in fp64 by Gaussian elimination with full pivoting.  The 8 x 9 system needs dynamic row and
-//                     column indices, which in registers would become scratch, so it lives in LDS, struct-of-arrays
-//                     (sys[72][128]: lanes doing the same step hit consecutive banks); the column permutation is nine
-//                     nibbles of one 64-bit register.  F then sits in 9 fp32 VGPRs and the pair list is walked as in
-//                     ransac_score_kernel, staged in 1 024-record chunks through the LDS the system occupied.
-//   fm_refit_kernel   one workgroup per problem: one lane re-derives the best sample's F with the same device function,
-//                     then `refits` times two passes over the pairs (moments; the 36 sums of M = sum a a^T, a = q (x) p)
-//                     in fp64 through hf_block_sum, and one lane's cyclic Jacobi in LDS (N = 9 for the eigenvector,
-//                     N = 3 for the rank-2 projection); writes F, the inlier count and the mask of the F it returns.
+//   fm_score_kernel   score_body at 128 hypotheses per workgroup: the normalised 8-point system in fp64 by Gaussian
+//                     elimination with full pivoting.  The 8 x 9 system needs dynamic row and column indices, which in
+//                     registers would become scratch, so it lives in LDS, struct-of-arrays (sys[72][128]: lanes doing the
+//                     same step hit consecutive banks); the column permutation is nine nibbles of one 64-bit register.
+//                     F then sits in 9 fp32 VGPRs and the pair list is staged through the LDS the systems occupied.
+//   fm_refit_kernel   one workgroup per problem: one lane re-derives the best sample's F with the same device function
+//                     (refit_head), then `refits` times two passes over the pairs (hartley_moments; the 36 sums of
+//                     M = sum a a^T, a = q (x) p) in fp64 through hf_block_sum, and one lane's cyclic Jacobi in LDS (N = 9
+//                     for the eigenvector, N = 3 for the rank-2 projection); through refit_tail it writes F, the inlier
+//                     count and the mask of the F it returns.
 #pragma once
 #include "ransac_homography.h"
 
@@ -21,14 +25,6 @@ constexpr int FM_THREADS = 128;       // hypotheses per workgroup of fm_score_ke
 constexpr double FM_PIVOT = 1e-10;    // last pivot / first pivot below which a sample is degenerate
 constexpr int FM_SWEEPS = 10;         // cyclic Jacobi sweeps
 constexpr int FM_NSUM = 36;
-
-// the sampler of include/fpc.h: the first 8 distinct of 32 draws
-__device__ __forceinline__ bool fm_sample(uint32_t seed, uint32_t f, uint32_t t, uint32_t M, uint32_t (&idx)[FM_SAMPLE]) {
-  return hf_sample_distinct<FM_SAMPLE, FM_DRAWS>(seed, f, t, M, idx);
-}
-
-// Hartley normalisation of one side: centroid and the scale that brings the RMS distance to sqrt(2)
-struct FmNorm { double cx, cy, ss, cu, cv, sd; };
 
 // F = Td^T Fn Ts,  Ts = [ss 0 -ss cx; 0 ss -ss cy; 0 0 1],  Td = [sd 0 -sd cu; 0 sd -sd cv; 0 0 1]
 __device__ __forceinline__ void fm_denormalise(const double (&n)[9], const FmNorm& w, double (&F)[9]) {
@@ -157,61 +153,43 @@ __device__ __forceinline__ bool fm_hypothesis(const double (&Fn)[9], const FmNor
 }
 
 // ---- scoring ----------------------------------------------------------------------------------------------------------
+// score_body's Model; F is only ever indexed by constants (fully unrolled), so it stays in registers.  (A degenerate
+// hypothesis keeps F = 0: 0 < 0 is false, it counts nothing.  At T = 1, 127 of 128 lanes per frame are such lanes or beyond
+// T: correct and idle, their loop costs what their wave's costs anyway.)
+struct FmModel {
+  static constexpr int SAMPLE = FM_SAMPLE, DRAWS = FM_DRAWS, REC = 1;
+  float F[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float thr2;
+  __device__ __forceinline__ explicit FmModel(const HfArgs& a) : thr2(a.thr * a.thr) {}
+  static __device__ __forceinline__ const float4* records(const HfArgs& a, int f) { return a.pairs + (size_t)f * a.cap; }
+  static __device__ __forceinline__ int frame(const HfArgs& a, int f) { return hf_frame(a.per_frame, f); }
+  __device__ __forceinline__ bool solve(const HfArgs&, const float4* __restrict__ pairs, const uint32_t (&idx)[FM_SAMPLE],
+                                        double* sys) {
+    double Fn[9];
+    FmNorm w;
+    float F32[9];
+    if (!(fm_solve8<FM_THREADS>(sys + threadIdx.x, pairs, idx, Fn, w) && fm_hypothesis(Fn, w, F32))) return false;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) F[i] = F32[i];
+    return true;
+  }
+  __device__ __forceinline__ bool counts(const float4* r) const {
+    const float4 p = r[0];
+    const float l0 = fmaf(F[1], p.y, fmaf(F[0], p.x, F[2]));
+    const float l1 = fmaf(F[4], p.y, fmaf(F[3], p.x, F[5]));
+    const float l2 = fmaf(F[7], p.y, fmaf(F[6], p.x, F[8]));
+    const float e = fmaf(p.w, l1, fmaf(p.z, l0, l2));
+    const float m0 = fmaf(F[3], p.w, fmaf(F[0], p.z, F[6]));
+    const float m1 = fmaf(F[4], p.w, fmaf(F[1], p.z, F[7]));
+    const float g = fmaf(m1, m1, fmaf(m0, m0, fmaf(l1, l1, l0 * l0)));
+    return e * e < thr2 * g;
+  }
+};
+
 __global__ __launch_bounds__(FM_THREADS) void fm_score_kernel(HfArgs a) {
   __shared__ double sys[72 * FM_THREADS];                    // the systems; afterwards the staged pair chunk
   static_assert(sizeof(double) * 72 * FM_THREADS >= sizeof(float4) * HF_CHUNK, "the pair chunk reuses the systems' LDS");
-  float4* rec = reinterpret_cast<float4*>(sys);
-  const int f = blockIdx.y, tid = threadIdx.x;
-  const int M = hf_clamp(a.np[f], a.cap);
-  if (M < FM_SAMPLE) return;
-  const float4* __restrict__ pairs = a.pairs + (size_t)f * a.cap;
-  const uint32_t t = blockIdx.x * (uint32_t)FM_THREADS + tid;
-  float F[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  bool ok = t < (uint32_t)a.T;
-  if (ok) {
-    uint32_t idx[FM_SAMPLE];
-    ok = fm_sample(a.seed, (uint32_t)hf_frame(a, f), t, (uint32_t)M, idx);
-    if (ok) {
-      double Fn[9];
-      FmNorm w;
-      float F32[9];
-      ok = fm_solve8<FM_THREADS>(sys + tid, pairs, idx, Fn, w) && fm_hypothesis(Fn, w, F32);
-      if (ok) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) F[i] = F32[i];
-      }
-    }
-  }
-  // (a degenerate hypothesis keeps F = 0: 0 < 0 is false, it counts nothing.  Such lanes, and the lanes with t >= T of the
-  // last workgroup, still walk every chunk: they stage records and meet the barriers, and their loop costs what their
-  // wave's costs anyway -- at T = 1 that is 127 of 128 lanes per frame, correct and idle.)
-  const float thr2 = a.thr * a.thr;
-  int cnt = 0;
-  for (int c0 = 0; c0 < M; c0 += HF_CHUNK) {
-    const int m = min(HF_CHUNK, M - c0);
-    __syncthreads();
-    for (int i = tid; i < m; i += FM_THREADS) rec[i] = pairs[c0 + i];
-    __syncthreads();
-#pragma unroll 4
-    for (int k = 0; k < m; ++k) {
-      const float4 p = rec[k];
-      const float l0 = fmaf(F[1], p.y, fmaf(F[0], p.x, F[2]));
-      const float l1 = fmaf(F[4], p.y, fmaf(F[3], p.x, F[5]));
-      const float l2 = fmaf(F[7], p.y, fmaf(F[6], p.x, F[8]));
-      const float e = fmaf(p.w, l1, fmaf(p.z, l0, l2));
-      const float m0 = fmaf(F[3], p.w, fmaf(F[0], p.z, F[6]));
-      const float m1 = fmaf(F[4], p.w, fmaf(F[1], p.z, F[7]));
-      const float g = fmaf(m1, m1, fmaf(m0, m0, fmaf(l1, l1, l0 * l0)));
-      cnt += (e * e < thr2 * g) ? 1 : 0;
-    }
-  }
-  unsigned long long key = (ok && cnt > 0) ? (((unsigned long long)(uint32_t)cnt << 32) | (unsigned long long)(~t)) : 0ull;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long other = __shfl_xor(key, o);
-    key = other > key ? other : key;
-  }
-  if ((tid & 63) == 0 && key) atomicMax(a.best + f, key);
+  score_body<FM_THREADS, FmModel>(a, reinterpret_cast<float4*>(sys), sys);
 }
 
 // ---- refit ------------------------------------------------------------------------------------------------------------
@@ -318,46 +296,24 @@ __global__ __launch_bounds__(256) void fm_refit_kernel(HfArgs a, float* __restri
   const float4* __restrict__ pairs = a.pairs + (size_t)f * a.cap;
   const double thr2 = (double)a.thr * (double)a.thr;
   double F[9];
-  bool ok = M >= FM_SAMPLE && key != 0ull;
-  if (ok) {                                     // (uniform) one lane re-derives the best sample's F: same function, same bits
-    if (tid == 0) {
-      uint32_t idx[FM_SAMPLE];
-      double Fn[9];
-      FmNorm w;
-      int good = fm_sample(a.seed, (uint32_t)hf_frame(a, f), ~(uint32_t)key, (uint32_t)M, idx) &&
-                 fm_solve8<1>(sys, pairs, idx, Fn, w);
-      if (good) {                               // the sample's F as it is returned: rank 2 in its normalised coordinates
+  bool ok = refit_head(M >= FM_SAMPLE && key != 0ull, &solved, [&]() {
+    uint32_t idx[FM_SAMPLE];
+    double Fn[9];
+    FmNorm w;
+    if (!(hf_sample_distinct<FM_SAMPLE, FM_DRAWS>(a.seed, (uint32_t)hf_frame(a.per_frame, f), ~(uint32_t)key, (uint32_t)M, idx) &&
+          fm_solve8<1>(sys, pairs, idx, Fn, w)))
+      return false;
 #pragma unroll
-        for (int i = 0; i < 9; ++i) fw[i] = Fn[i];
-        fm_rank2(fw, jm, jv);
-        good = fm_finish(fw, w, fnew);
-      }
-      solved = good;
-    }
-    __syncthreads();
-    ok = solved != 0;
-  }
-  int total = 0;
+    for (int i = 0; i < 9; ++i) fw[i] = Fn[i];  // the sample's F as it is returned: rank 2 in its normalised coordinates
+    fm_rank2(fw, jm, jv);
+    return fm_finish(fw, w, fnew);
+  });
   if (ok) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) F[i] = fnew[i];
     for (int r = 0; r < a.refits; ++r) {
-      // normalisation moments of the inlier set: n, sum x, y, x^2 + y^2, u, v, u^2 + v^2
-      double mo[7] = {0, 0, 0, 0, 0, 0, 0};
-      for (int k = tid; k < M; k += 256) {
-        const float4 p = pairs[k];
-        if (fm_inlier(F, p, thr2)) {
-          const double x = p.x, y = p.y, u = p.z, v = p.w;
-          mo[0] += 1.0; mo[1] += x; mo[2] += y; mo[3] += x * x + y * y; mo[4] += u; mo[5] += v; mo[6] += u * u + v * v;
-        }
-      }
-      hf_block_sum<7>(mo, red);
-      if (mo[0] < 8.0) break;
       FmNorm w;
-      w.cx = mo[1] / mo[0]; w.cy = mo[2] / mo[0]; w.cu = mo[4] / mo[0]; w.cv = mo[5] / mo[0];
-      const double vs = mo[3] / mo[0] - w.cx * w.cx - w.cy * w.cy, vd = mo[6] / mo[0] - w.cu * w.cu - w.cv * w.cv;
-      if (!(vs > 1e-12) || !(vd > 1e-12)) break;
-      w.ss = sqrt(2.0 / vs); w.sd = sqrt(2.0 / vd);                        // RMS distance to the centroid -> sqrt(2)
+      if (!hartley_moments(pairs, M, 8.0, red, [&](const float4& p) { return fm_inlier(F, p, thr2); }, w)) break;
       // M = sum a a^T with a = q (x) p: s[6 qq + pp], qq in (uu uv u vv v 1), pp in (xx xy x yy y 1)
       double s[FM_NSUM];
 #pragma unroll
@@ -390,20 +346,12 @@ __global__ __launch_bounds__(256) void fm_refit_kernel(HfArgs a, float* __restri
 #pragma unroll
       for (int i = 0; i < 9; ++i) F[i] = fnew[i];                           // (the next write of fnew is behind hf_block_sum's barriers)
     }
-    double c1[1] = {0.0};
-    for (int k = tid; k < M; k += 256) c1[0] += fm_inlier(F, pairs[k], thr2) ? 1.0 : 0.0;
-    hf_block_sum<1>(c1, red);
-    total = (int)c1[0];
-    ok = total >= a.min_inliers;
   }
-  if (ok && mask)                                                           // (the pack / gather kernel zeroed the mask)
-    for (int k = tid; k < M; k += 256)
-      if (fm_inlier(F, pairs[k], thr2)) mask[(size_t)f * mstride + a.row[(size_t)f * a.cap + k]] = 1;
-  __syncthreads();
+  ok = refit_tail(ok, M, a.min_inliers, red, mask, ninl + f, [&](int k) { return fm_inlier(F, pairs[k], thr2); },
+                  [&](int k) { return (size_t)f * mstride + a.row[(size_t)f * a.cap + k]; });
   if (tid == 0) {                                                           // (through LDS: F[tid] would be scratch)
 #pragma unroll
     for (int i = 0; i < 9; ++i) fnew[i] = ok ? F[i] : 0.0;
-    ninl[f] = ok ? total : 0;
   }
   __syncthreads();
   if (tid < 9) Fout[f * 9 + tid] = (float)fnew[tid];

@@ -1,29 +1,26 @@
 // Batched RANSAC homography estimation (fpc_ransac_homography / fpc_homography_frames; the rule is stated in
-// include/fpc.h and restated in float64 by tests/test_homography_ransac.py).
+// include/fpc.h and restated in float64 by tests/test_homography_ransac.py).  This header holds the homography's model --
+// the 4-point closed form, the refit's normal equations and denormalisation, the two inlier tests -- and the pair records
+// every family shares; the sampler, the selection key, the compaction, the score and refit skeletons, the LDS solve and the
+// Hartley moments are ransac_parts.h's.
 //
 //   hf_pack_kernel / hf_gather_kernel   build every frame's pair list [x, y, u, v] (float32, 16-byte records), the row of
 //                          the caller's mask each pair belongs to, the pair count, and zero the best key and the mask.
-//                          The gather is an order-preserving compaction (ballot + popcount prefix, no atomics), so the
-//                          list is in ascending row order; from here on both entry points run the same kernels on the
-//                          same records, which is what makes them bit-identical on equal pairs.
-//   ransac_score_kernel    grid ceil(T / 256) x n, one thread per hypothesis: draws its 4 pairs, solves the 4-point
-//                          homography in fp64 registers (closed form through the projective basis: cross products and
-//                          adjugates, no pivoting, no division), keeps it in 9 fp32 VGPRs and walks the pair list, which
-//                          is staged through LDS in chunks -- every lane reads the same 16-byte record (the broadcast
-//                          case, conflict-free).  The best (count, lowest t) per frame is a 64-bit atomicMax on
-//                          (count << 32) | ~t: integer keys, so the result does not depend on the execution order.
+//                          The gather is gather_body's order-preserving compaction, so the list is in ascending row
+//                          order; from here on both entry points run the same kernels on the same records, which is
+//                          what makes them bit-identical on equal pairs.
+//   ransac_score_kernel    score_body at 256 hypotheses per workgroup: the 4-point homography in fp64 registers (closed
+//                          form through the projective basis: cross products and adjugates, no pivoting, no division),
+//                          kept in 9 fp32 VGPRs for the walk over the staged pair list.
 //   ransac_refit_kernel    one workgroup per frame: re-derives the best sample's H, then `refits` times a Hartley-
-//                          normalised least-squares fit over the current inliers -- moments and normal equations
-//                          accumulated in fp64 per thread over a fixed stride and summed by a fixed-shape butterfly /
-//                          4-wave tree (no floating-point atomics), solved by one lane in LDS -- and writes H, the
-//                          inlier count and the mask of the H it returns.
+//                          normalised least-squares fit over the current inliers -- hartley_moments, then the normal
+//                          equations accumulated in fp64 per thread over a fixed stride and summed by hf_block_sum (no
+//                          floating-point atomics), solved by one lane with solve_lds -- and, through refit_tail, writes
+//                          H, the inlier count and the mask of the H it returns.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "ransac_parts.h"
 
-constexpr int HF_MAX_ITERATIONS = 4096;
 constexpr int HF_DRAWS = 16;          // draw budget of one sample
-constexpr int HF_CHUNK = 1024;        // records staged per LDS chunk (16 KiB)
 constexpr double HF_COLLINEAR = 0.5;  // doubled triangle area (px^2) below which three points count as collinear
 
 struct HfArgs {
@@ -40,49 +37,6 @@ struct HfArgs {
   // the sampler.  0 (every other entry point): one problem per frame, p = f.
   int per_frame;
 };
-
-__device__ __forceinline__ int hf_frame(const HfArgs& a, int p) { return a.per_frame > 1 ? p / a.per_frame : p; }
-
-__device__ __forceinline__ int hf_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// the sampler of include/fpc.h
-__device__ __forceinline__ uint32_t hf_mix(uint32_t a) {
-  a ^= a >> 16; a *= 0x7feb352du; a ^= a >> 15; a *= 0x846ca68bu; a ^= a >> 16;
-  return a;
-}
-__device__ __forceinline__ bool hf_sample(uint32_t seed, uint32_t f, uint32_t t, uint32_t M, uint32_t& i0, uint32_t& i1,
-                                          uint32_t& i2, uint32_t& i3) {
-  i0 = i1 = i2 = i3 = M;
-  int got = 0;
-  for (uint32_t k = 0; k < (uint32_t)HF_DRAWS && got < 4; ++k) {
-    const uint32_t r = hf_mix(seed ^ hf_mix((f * (uint32_t)HF_MAX_ITERATIONS + t) * (uint32_t)HF_DRAWS + k)) % M;
-    const bool fresh = r != i0 && r != i1 && r != i2;           // (selects, not an indexed store: that becomes scratch)
-    i0 = (fresh && got == 0) ? r : i0;
-    i1 = (fresh && got == 1) ? r : i1;
-    i2 = (fresh && got == 2) ? r : i2;
-    i3 = (fresh && got == 3) ? r : i3;
-    got += fresh ? 1 : 0;
-  }
-  return got == 4;
-}
-// ... and of the 8-point (fundamental) and 6-point (PnP) solvers: the first N distinct of DRAWS draws (selects, not an indexed
-// store: that becomes scratch)
-template <int N, int DRAWS>
-__device__ __forceinline__ bool hf_sample_distinct(uint32_t seed, uint32_t f, uint32_t t, uint32_t M, uint32_t (&idx)[N]) {
-#pragma unroll
-  for (int j = 0; j < N; ++j) idx[j] = M;
-  int got = 0;
-  for (uint32_t k = 0; k < (uint32_t)DRAWS && got < N; ++k) {
-    const uint32_t r = hf_mix(seed ^ hf_mix((f * (uint32_t)HF_MAX_ITERATIONS + t) * (uint32_t)DRAWS + k)) % M;
-    bool fresh = true;
-#pragma unroll
-    for (int j = 0; j < N; ++j) fresh = fresh && r != idx[j];
-#pragma unroll
-    for (int j = 0; j < N; ++j) idx[j] = (fresh && got == j) ? r : idx[j];
-    got += fresh ? 1 : 0;
-  }
-  return got == N;
-}
 
 struct HfV3 { double x, y, z; };
 __device__ __forceinline__ HfV3 hf_cross(const HfV3& a, const HfV3& b) {
@@ -158,9 +112,8 @@ __global__ __launch_bounds__(256) void hf_gather_kernel(HfArgs a, const int32_t*
                                                         int pairing, const int32_t* __restrict__ key_xy,
                                                         const int32_t* __restrict__ nkey, const int32_t* __restrict__ match,
                                                         uint8_t* mask, const HfBank bank) {
-  __shared__ int wsum[4];
-  const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cap = a.cap;
-  const int fq = hf_frame(a, f);               // the frame whose keypoints are the query side
+  const int f = blockIdx.x, cap = a.cap;
+  const int fq = hf_frame(a.per_frame, f);     // the frame whose keypoints are the query side
   const int cnt = hf_clamp(count[fq], cap);
   const int32_t* txy = nullptr;
   int nt = 0;
@@ -177,107 +130,53 @@ __global__ __launch_bounds__(256) void hf_gather_kernel(HfArgs a, const int32_t*
     txy = key_xy;
     nt = hf_clamp(nkey[0], cap);
   }
-  const int32_t* qxy = xy + (size_t)fq * cap * 2;
-  const int end = mask ? cap : cnt;
-  int base = 0;
-  for (int i0 = 0; i0 < end; i0 += 256) {
-    const int i = i0 + tid;
-    int m = -1;
-    if (i < cnt) m = match[(size_t)f * cap + i];
-    const bool flag = m >= 0 && m < nt;
-    if (mask && i < cap) mask[(size_t)f * cap + i] = 0;
-    const unsigned long long b = __ballot(flag);
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();
-    if (lane == 0) wsum[wave] = __popcll(b);
-    __syncthreads();
-    int off = base + before;
-    for (int w = 0; w < 4; ++w) {
-      if (w < wave) off += wsum[w];
-      base += wsum[w];
+  // gather_body's Source: row i of problem f is a pair when its match is a row of the train set
+  struct {
+    const HfArgs& a;
+    const int32_t *qxy, *txy;
+    int f, nt;
+    __device__ __forceinline__ bool pair(int m) { return m >= 0 && m < nt; }
+    __device__ __forceinline__ void write(int off, int i, int m) {
+      a.pairs[(size_t)f * a.cap + off] = make_float4((float)qxy[2 * i], (float)qxy[2 * i + 1], (float)txy[2 * m], (float)txy[2 * m + 1]);
+      a.row[(size_t)f * a.cap + off] = i;
     }
-    if (flag) {
-      a.pairs[(size_t)f * cap + off] = make_float4((float)qxy[2 * i], (float)qxy[2 * i + 1], (float)txy[2 * m], (float)txy[2 * m + 1]);
-      a.row[(size_t)f * cap + off] = i;
-    }
-  }
-  if (tid == 0) {
-    a.np[f] = base;
-    a.best[f] = 0ull;
-  }
+  } src{a, xy + (size_t)fq * cap * 2, txy, f, nt};
+  gather_body(src, f, cnt, cap, match, mask, a.np, a.best);
 }
 
 // ---- scoring ----------------------------------------------------------------------------------------------------------
+// score_body's Model.  H sits in nine named registers on purpose: an indexed store becomes scratch.  (A degenerate
+// hypothesis keeps H = 0: w = 0 is never > 0, it counts nothing.)
+struct HfModel {
+  static constexpr int SAMPLE = 4, DRAWS = HF_DRAWS, REC = 1;
+  float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f, h4 = 0.f, h5 = 0.f, h6 = 0.f, h7 = 0.f, h8 = 0.f;
+  float thr;
+  __device__ __forceinline__ explicit HfModel(const HfArgs& a) : thr(a.thr) {}
+  static __device__ __forceinline__ const float4* records(const HfArgs& a, int f) { return a.pairs + (size_t)f * a.cap; }
+  static __device__ __forceinline__ int frame(const HfArgs& a, int f) { return hf_frame(a.per_frame, f); }
+  __device__ __forceinline__ bool solve(const HfArgs&, const float4* __restrict__ pairs, const uint32_t (&idx)[4], double*) {
+    double H[9];
+    if (!hf_solve4(pairs[idx[0]], pairs[idx[1]], pairs[idx[2]], pairs[idx[3]], H)) return false;
+    h0 = (float)H[0]; h1 = (float)H[1]; h2 = (float)H[2]; h3 = (float)H[3]; h4 = (float)H[4];
+    h5 = (float)H[5]; h6 = (float)H[6]; h7 = (float)H[7]; h8 = (float)H[8];
+    return true;
+  }
+  __device__ __forceinline__ bool counts(const float4* r) const {
+    const float4 p = r[0];
+    const float w = fmaf(h7, p.y, fmaf(h6, p.x, h8));
+    const float ex = fmaf(-w, p.z, fmaf(h1, p.y, fmaf(h0, p.x, h2)));
+    const float ey = fmaf(-w, p.w, fmaf(h4, p.y, fmaf(h3, p.x, h5)));
+    const float tw = thr * w;
+    return w > 0.f && fmaf(ex, ex, ey * ey) < tw * tw;
+  }
+};
+
 __global__ __launch_bounds__(256) void ransac_score_kernel(HfArgs a) {
   __shared__ float4 rec[HF_CHUNK];
-  const int f = blockIdx.y, tid = threadIdx.x;
-  const int M = hf_clamp(a.np[f], a.cap);
-  if (M < 4) return;
-  const float4* __restrict__ pairs = a.pairs + (size_t)f * a.cap;
-  const uint32_t t = blockIdx.x * 256u + tid;
-  float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f, h4 = 0.f, h5 = 0.f, h6 = 0.f, h7 = 0.f, h8 = 0.f;
-  bool ok = t < (uint32_t)a.T;
-  if (ok) {
-    uint32_t i0, i1, i2, i3;
-    ok = hf_sample(a.seed, (uint32_t)hf_frame(a, f), t, (uint32_t)M, i0, i1, i2, i3);
-    if (ok) {
-      double H[9];
-      ok = hf_solve4(pairs[i0], pairs[i1], pairs[i2], pairs[i3], H);
-      if (ok) {
-        h0 = (float)H[0]; h1 = (float)H[1]; h2 = (float)H[2]; h3 = (float)H[3]; h4 = (float)H[4];
-        h5 = (float)H[5]; h6 = (float)H[6]; h7 = (float)H[7]; h8 = (float)H[8];
-      }
-    }
-  }
-  // (a degenerate hypothesis keeps H = 0: w = 0 is never > 0, it counts nothing)
-  const float thr = a.thr;
-  int cnt = 0;
-  for (int c0 = 0; c0 < M; c0 += HF_CHUNK) {
-    const int m = min(HF_CHUNK, M - c0);
-    __syncthreads();
-    for (int i = tid; i < m; i += 256) rec[i] = pairs[c0 + i];
-    __syncthreads();
-#pragma unroll 4
-    for (int k = 0; k < m; ++k) {
-      const float4 p = rec[k];
-      const float w = fmaf(h7, p.y, fmaf(h6, p.x, h8));
-      const float ex = fmaf(-w, p.z, fmaf(h1, p.y, fmaf(h0, p.x, h2)));
-      const float ey = fmaf(-w, p.w, fmaf(h4, p.y, fmaf(h3, p.x, h5)));
-      const float tw = thr * w;
-      cnt += (w > 0.f && fmaf(ex, ex, ey * ey) < tw * tw) ? 1 : 0;
-    }
-  }
-  unsigned long long key = (ok && cnt > 0) ? (((unsigned long long)(uint32_t)cnt << 32) | (unsigned long long)(~t)) : 0ull;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long other = __shfl_xor(key, o);
-    key = other > key ? other : key;
-  }
-  if ((tid & 63) == 0 && key) atomicMax(a.best + f, key);
+  score_body<256, HfModel>(a, rec, nullptr);
 }
 
 // ---- refit ------------------------------------------------------------------------------------------------------------
-// Sum of every thread's v[i] over the workgroup (256 threads), the same in every thread: xor butterfly inside a wave, then
-// the four waves' sums in wave order.
-template <int N>
-__device__ __forceinline__ void hf_block_sum(double (&v)[N], double* red /* [4][N] */) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double x = v[i];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
-    v[i] = x;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) red[(threadIdx.x >> 6) * N + i] = v[i];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = ((red[i] + red[N + i]) + red[2 * N + i]) + red[3 * N + i];
-}
-
 // |H p - q| < thr without the division, in fp64 (sign-free: the plain reprojection test of include/fpc.h)
 __device__ __forceinline__ bool hf_inlier(const double (&H)[9], const float4& p, double thr2) {
   const double x = p.x, y = p.y;
@@ -302,32 +201,19 @@ __global__ __launch_bounds__(256) void ransac_refit_kernel(HfArgs a, float* __re
   double H[9];
   bool ok = M >= 4 && key != 0ull;
   if (ok) {                                   // (uniform) every thread re-derives the best sample's H: same code, same bits
-    uint32_t i0, i1, i2, i3;
-    ok = hf_sample(a.seed, (uint32_t)hf_frame(a, f), ~(uint32_t)key, (uint32_t)M, i0, i1, i2, i3) &&
-         hf_solve4(pairs[i0], pairs[i1], pairs[i2], pairs[i3], H);
+    uint32_t idx[4];
+    ok = hf_sample_distinct<4, HF_DRAWS>(a.seed, (uint32_t)hf_frame(a.per_frame, f), ~(uint32_t)key, (uint32_t)M, idx) &&
+         hf_solve4(pairs[idx[0]], pairs[idx[1]], pairs[idx[2]], pairs[idx[3]], H);
   }
-  int total = 0;
   if (ok) {
     const double inv = 1.0 / H[8];
 #pragma unroll
     for (int i = 0; i < 9; ++i) H[i] = (double)(float)(H[i] * inv);        // the H that would be returned: fp32 values
     H[8] = 1.0;
     for (int r = 0; r < a.refits; ++r) {
-      // normalisation moments of the inlier set: n, sum x, y, x^2 + y^2, u, v, u^2 + v^2
-      double mo[7] = {0, 0, 0, 0, 0, 0, 0};
-      for (int k = tid; k < M; k += 256) {
-        const float4 p = pairs[k];
-        if (hf_inlier(H, p, thr2)) {
-          const double x = p.x, y = p.y, u = p.z, v = p.w;
-          mo[0] += 1.0; mo[1] += x; mo[2] += y; mo[3] += x * x + y * y; mo[4] += u; mo[5] += v; mo[6] += u * u + v * v;
-        }
-      }
-      hf_block_sum<7>(mo, red);
-      if (mo[0] < 4.0) break;
-      const double cx = mo[1] / mo[0], cy = mo[2] / mo[0], cu = mo[4] / mo[0], cv = mo[5] / mo[0];
-      const double vs = mo[3] / mo[0] - cx * cx - cy * cy, vd = mo[6] / mo[0] - cu * cu - cv * cv;
-      if (!(vs > 1e-12) || !(vd > 1e-12)) break;
-      const double ss = sqrt(2.0 / vs), sd = sqrt(2.0 / vd);              // RMS distance to the centroid -> sqrt(2)
+      FmNorm w;
+      if (!hartley_moments(pairs, M, 4.0, red, [&](const float4& p) { return hf_inlier(H, p, thr2); }, w)) break;
+      const double cx = w.cx, cy = w.cy, ss = w.ss, cu = w.cu, cv = w.cv, sd = w.sd;
       // normal equations of [x y 1 0 0 0 -ux -uy | u], [0 0 0 x y 1 -vx -vy | v] in the normalised coordinates
       double s[HF_NSUM];
 #pragma unroll
@@ -360,31 +246,8 @@ __global__ __launch_bounds__(256) void ransac_refit_kernel(HfArgs a, float* __re
         sm[7][7] = s[20]; sm[7][8] = -s[22];
         for (int i = 1; i < 8; ++i)
           for (int j = 0; j < i; ++j) sm[i][j] = sm[j][i];
-        // Gaussian elimination with partial pivoting, in LDS (dynamic indices must not become scratch)
-        int good = 1;
-        const double tiny = 1e-10 * s[5];
-        for (int c = 0; c < 8 && good; ++c) {
-          int pr = c;
-          double pv = fabs(sm[c][c]);
-          for (int i = c + 1; i < 8; ++i) {
-            const double v = fabs(sm[i][c]);
-            if (v > pv) { pv = v; pr = i; }
-          }
-          if (!(pv > tiny)) { good = 0; break; }
-          if (pr != c)
-            for (int j = c; j < 9; ++j) { const double tmp = sm[c][j]; sm[c][j] = sm[pr][j]; sm[pr][j] = tmp; }
-          const double ip = 1.0 / sm[c][c];
-          for (int i = c + 1; i < 8; ++i) {
-            const double fct = sm[i][c] * ip;
-            for (int j = c; j < 9; ++j) sm[i][j] -= fct * sm[c][j];
-          }
-        }
+        int good = solve_lds<8>(sm, 1e-10 * s[5]) ? 1 : 0;
         if (good) {
-          for (int i = 7; i >= 0; --i) {
-            double acc = sm[i][8];
-            for (int j = i + 1; j < 8; ++j) acc -= sm[i][j] * sm[j][8];
-            sm[i][8] = acc / sm[i][i];
-          }
           const double n0 = sm[0][8], n1 = sm[1][8], n2 = sm[2][8], n3 = sm[3][8], n4 = sm[4][8], n5 = sm[5][8],
                        n6 = sm[6][8], n7 = sm[7][8];
           // H = Td^-1 Hn Ts,  Ts = [ss 0 -ss cx; 0 ss -ss cy; 0 0 1],  Td^-1 = [1/sd 0 cu; 0 1/sd cv; 0 0 1]
@@ -413,20 +276,12 @@ __global__ __launch_bounds__(256) void ransac_refit_kernel(HfArgs a, float* __re
 #pragma unroll
       for (int i = 0; i < 9; ++i) H[i] = hnew[i];
     }
-    double c1[1] = {0.0};
-    for (int k = tid; k < M; k += 256) c1[0] += hf_inlier(H, pairs[k], thr2) ? 1.0 : 0.0;
-    hf_block_sum<1>(c1, red);
-    total = (int)c1[0];
-    ok = total >= a.min_inliers;
   }
-  if (ok && mask)                                                           // (the pack / gather kernel zeroed the mask)
-    for (int k = tid; k < M; k += 256)
-      if (hf_inlier(H, pairs[k], thr2)) mask[(size_t)f * mstride + a.row[(size_t)f * a.cap + k]] = 1;
-  __syncthreads();
+  ok = refit_tail(ok, M, a.min_inliers, red, mask, ninl + f, [&](int k) { return hf_inlier(H, pairs[k], thr2); },
+                  [&](int k) { return (size_t)f * mstride + a.row[(size_t)f * a.cap + k]; });
   if (tid == 0) {                                                           // (through LDS: H[tid] would be scratch)
 #pragma unroll
     for (int i = 0; i < 9; ++i) hnew[i] = ok ? H[i] : 0.0;
-    ninl[f] = ok ? total : 0;
   }
   __syncthreads();
   if (tid < 9) Hout[f * 9 + tid] = (float)hnew[tid];

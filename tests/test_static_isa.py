@@ -388,3 +388,32 @@ def test_guided_strip_kernels_keep_their_registers(code_object):
         assert m["group_segment_fixed_size"] == lds, (name, m)
         assert m["agpr_count"] <= agpr and m["vgpr_count"] <= vgpr, (name, m)
         assert m["vgpr_count"] - m["agpr_count"] <= vgpr - agpr, (name, m)
+
+
+# The geometry chain's ten kernels (csrc/ransac_parts.h and the three model headers): `.group_segment_fixed_size` in the
+# code object of commit 1b707a5, before the kernels were built from shared parts (DESIGN.md section 7 has both builds'
+# registers).  Shared parts must not cost a kernel its LDS budget or push anything into scratch.
+RANSAC_KERNELS = {
+    "_Z14hf_pack_kernel6HfArgsPKfS1_PKiiPh": 0,
+    "_Z16hf_gather_kernel6HfArgsPKiS1_iS1_S1_S1_Ph6HfBank": 16,
+    "_Z15pnp_pack_kernel7PnpArgsPKfS1_PKiiPh": 0,
+    "_Z17pnp_gather_kernel7PnpArgsPKiS1_S1_Ph8PnpTrain": 16,
+    "_Z19ransac_score_kernel6HfArgs": 16384,
+    "_Z15fm_score_kernel6HfArgs": 73728,
+    "_Z16pnp_score_kernel7PnpArgs": 67584,
+    "_Z19ransac_refit_kernel6HfArgsPfPiPhi": 1392,
+    "_Z15fm_refit_kernel6HfArgsPfPiPhi": 3112,
+    "_Z16pnp_refit_kernel7PnpArgsPfS0_PiPhi": 2456,
+}
+
+
+def test_ransac_kernels_keep_their_lds_and_stay_out_of_scratch(code_object):
+    """ransac_homography.h / ransac_fundamental.h / pnp_ransac.h: the pack, gather, score and refit kernels keep their LDS
+    sizes, hold nothing in scratch and spill nothing, as in commit 1b707a5."""
+    _, meta = code_object
+    for name, lds in RANSAC_KERNELS.items():
+        assert name in meta, name
+        m = meta[name]
+        assert m["private_segment_fixed_size"] == 0, (name, m)
+        assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (name, m)
+        assert m["group_segment_fixed_size"] == lds, (name, m)
