@@ -196,6 +196,75 @@ def bf16_emulated_layer(name, inputs, sd):
     return y if out_f32 else round_bf16(y)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# The fp32 twins of the two functions above: ONE layer of the fp32 plans on given input tensor(s), nothing rounded to
+# bf16.  Weights are BatchNorm-folded as weights.h packs them ((float)(w * s), the product taken in double), every
+# convolution accumulates in double and is rounded to float once, bias / shortcut / ReLU are float.  Fed with a layer's
+# own input as the device holds it, the result bounds that layer alone: nothing compounds across layers.
+# ---------------------------------------------------------------------------------------------------------------
+LAYERS = BF16_LAYERS        # the layer graph is the network's, not the mode's
+_BLOCKS = _BF16_BLOCKS
+
+
+def _wf(w, s):
+    """BN-folded fp32 weight as the product packs it: (float)(w * s), the product in double."""
+    return (w.astype(np.float64) * s[:, None, None, None]).astype(np.float32)
+
+
+def f32_folded_weights(name, sd):
+    """The folded float weights and biases f32_layer uses for `name`, for a caller that runs the same layer with another
+    convolution (tests: torch's fp32 one).  "pool": the stem's (w [64,3,7,7], bias [64]); "up": (wt [256,128,3,3],
+    bias [128]); a block: (w1, b1, w2, wp or None, b2 (+ the projection's)), stride."""
+    if name == "pool":
+        s, t = _fold(sd, "encoder.bn1")
+        return _wf(sd["encoder.conv1.weight"], s), t.astype(np.float32)
+    if name == "up":
+        s, t = _fold(sd, "descriptor.bn")
+        wt = (sd["descriptor.up_sample.weight"].astype(np.float64) * s[None, :, None, None]).astype(np.float32)
+        return wt, (sd["descriptor.up_sample.bias"].astype(np.float64) * s + t).astype(np.float32)
+    p, stride, proj, _ = _BLOCKS[name]
+    s1, t1 = _fold(sd, p + ".bn1")
+    s2, t2 = _fold(sd, p + ".bn2")
+    wp = None
+    if proj:
+        sp, tp = _fold(sd, p + ".identity_downsample.1")
+        wp, t2 = _wf(sd[p + ".identity_downsample.0.weight"], sp), t2 + tp
+    return (_wf(sd[p + ".conv1.weight"], s1), t1.astype(np.float32), _wf(sd[p + ".conv2.weight"], s2), wp,
+            t2.astype(np.float32)), stride
+
+
+def f32_stem(image, sd):
+    """frames [B,3,H,W] -> the pooled stem output ("pool") of the fp32 plans: 7 x 7 stride-2 convolution with folded
+    weights (double accumulation), bias, ReLU, 3 x 3 stride-2 max-pool."""
+    image = np.ascontiguousarray(image, np.float32)
+    b, _, hh, ww = image.shape
+    w, t = f32_folded_weights("pool", sd)
+    st = _relu(_conv2d(image, w, 2, 3) + t[None, :, None, None])
+    x0 = np.empty((b, 64, hh // 4, ww // 4), np.float32)
+    lib().oracle_maxpool3s2(_p(np.ascontiguousarray(st)), _p(x0), b, 64, hh // 2, ww // 2)
+    return x0
+
+
+def f32_layer(name, inputs, sd):
+    """ONE layer of the fp32 plans on given float32 input tensor(s) [B,C,h,w]: the ten ResNet blocks and "up"
+    (ConvTranspose2d + bn + relu).  bf16_emulated_layer's structure without a single bf16 rounding."""
+    x = np.ascontiguousarray(np.concatenate(inputs, 1) if len(inputs) > 1 else inputs[0], np.float32)
+    if name == "up":
+        wt, bt = f32_folded_weights(name, sd)
+        b, _, h, w = x.shape
+        up = np.empty((b, 128, 2 * h, 2 * w), np.float32)
+        lib().oracle_conv_transpose2d(_p(x), _p(np.ascontiguousarray(wt)), _p(bt), _p(up), b, 256, h, w, 128)
+        return _relu(up)
+    (w1, b1, w2, wp, b2), stride = f32_folded_weights(name, sd)
+    h = _relu(_conv2d(x, w1, stride, 1) + b1[None, :, None, None])
+    y = _conv2d(h, w2, 1, 0)
+    if wp is not None:
+        y = y + _conv2d(x, wp, stride, 0) + b2[None, :, None, None]
+    else:
+        y = y + b2[None, :, None, None] + x
+    return _relu(y)
+
+
 def forward_bf16_emulated(image, sd, descriptor_enabled=True, with_taps=False):
     """image float32 [B,3,H,W] -> (prob_map, desc, logits[, taps]) as `forward`, with FPC_BF16's roundings."""
     image = np.ascontiguousarray(image, np.float32)
