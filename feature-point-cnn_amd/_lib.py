@@ -41,6 +41,7 @@ SYMBOLS = [
     "fpc_default_pose_params", "fpc_pose_fundamental", "fpc_pose_frames", "fpc_pose_bank",
     "fpc_default_pnp_params", "fpc_pnp_reserve", "fpc_bank_landmarks_reserve", "fpc_bank_store_landmarks",
     "fpc_bank_landmarks_get", "fpc_ransac_pnp", "fpc_pnp_frames", "fpc_pnp_bank",
+    "fpc_match_frames_guided_pose", "fpc_match_bank_guided_pose",
 ]
 
 ABI_VERSION = 4
@@ -229,6 +230,9 @@ def load():
     l.fpc_match_bank_guided_epipolar.argtypes = list(l.fpc_match_bank_guided.argtypes)
     l.fpc_match_frames_guided_epipolar_cells.argtypes = list(l.fpc_match_frames_guided_cells.argtypes)   # likewise
     l.fpc_match_bank_guided_epipolar_cells.argtypes = list(l.fpc_match_bank_guided_cells.argtypes)
+    cf = ctypes.c_float
+    l.fpc_match_frames_guided_pose.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, cf, vp, vp]
+    l.fpc_match_bank_guided_pose.argtypes = [vp, ci, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, cf, vp, vp]
     l.fpc_bank_topk_reserve.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_size_t)]
     l.fpc_match_bank_topk.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp, vp]
     l.fpc_homography_bank_topk.argtypes = [vp, ci, ci, vp, vp, rp, vp, vp, vp, vp, vp]

@@ -40,6 +40,7 @@
 #include "match_guided.h"
 #include "match_guided_cells.h"
 #include "match_guided_epipolar.h"
+#include "match_guided_pose.h"
 #include "ransac_homography.h"
 #include "ransac_fundamental.h"
 #include "pose_epipolar.h"
@@ -4567,8 +4568,8 @@ int fpc_homography_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot,
   return launched();
 }
 
-// ---- guided matching: plain, cell-ordered and epipolar (include/fpc.h; two strip skeletons and two gates in match_guided.h,
-// ---- match_guided_cells.h and match_guided_epipolar.h, four kernels) ------------------------------------------------------------
+// ---- guided matching: plain, cell-ordered, epipolar and under a pose (include/fpc.h; two strip skeletons and three gates in
+// ---- match_guided.h, match_guided_cells.h, match_guided_epipolar.h and match_guided_pose.h, five kernels) -----------------------
 // 32-px cells wherever the order is public; a frame of more cells than the order kernel's histogram holds (beyond
 // 16.7 MPx) is ordered in coarser cells by the guided calls, whose output does not depend on the order.
 static CellOrderArgs cell_order_args(fpc_ctx* c, int shift) {
@@ -4615,16 +4616,17 @@ static MatchCellsArgs cell_order_passes(fpc_ctx* c, const MatchFramesArgs& a, co
   return MatchCellsArgs{c->mgc_perm_q, c->mgc_box, c->mgc_perm_t, box_t, nbox, stats};
 }
 
-// The eight guided entry points run on fpc_match_frames' workspace (norms, top-2, column minima: [max_batch][cap], and the
+// The ten guided entry points run on fpc_match_frames' workspace (norms, top-2, column minima: [max_batch][cap], and the
 // bank's rows <= cap), carved at fpc_create: nothing of their own.  One sequence for all: the column minima and the stats
 // reset, the norms (a bf16 bank: its rounding pass, match_bank_bf16.h), the variant's strip kernel (the four fp32 ones are
-// mg_strip / mgc_strip with the homography or the epipolar gate; the cell-ordered ones run behind their order passes), the
-// finalize kernel.  norm_blocks: n + 1 with the key's block, n against the bank, whose
-// norms are its own.
-enum GuidedStrip { GUIDED_PLAIN, GUIDED_CELLS, GUIDED_BANK_BF16, GUIDED_EPIPOLAR, GUIDED_EPIPOLAR_CELLS };
+// mg_strip / mgc_strip with the homography or the epipolar gate; the cell-ordered ones run behind their order passes; the
+// pose strip is mg_strip with the pose gate and takes its own arguments, `pose`, in place of g), the finalize kernel.
+// norm_blocks: n + 1 with the key's block, n against the bank, whose norms are its own.
+enum GuidedStrip { GUIDED_PLAIN, GUIDED_CELLS, GUIDED_BANK_BF16, GUIDED_EPIPOLAR, GUIDED_EPIPOLAR_CELLS, GUIDED_POSE };
 
 static int match_guided_launch(fpc_ctx* c, GuidedStrip strip, MatchFramesArgs a, const MatchGuidedArgs& g, int norm_blocks,
-                               float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
+                               float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats,
+                               const MatchPoseArgs* pose = nullptr) {
   const dim3 norms((c->cap + 127) / 128, norm_blocks), strips((c->cap + MF_ROWS - 1) / MF_ROWS, a.n);
   if (a.cross_check)
     HIPCHECK(hipMemsetAsync(c->mf_colbest, 0xff, sizeof(unsigned long long) * a.n * c->cap, c->stream));
@@ -4644,6 +4646,8 @@ static int match_guided_launch(fpc_ctx* c, GuidedStrip strip, MatchFramesArgs a,
     hipLaunchKernelGGL(match_guided_epipolar_cells_kernel, strips, dim3(256), 0, c->stream, a, g, m);     // (g.H holds F)
   } else if (strip == GUIDED_EPIPOLAR) {
     hipLaunchKernelGGL(match_guided_epipolar_kernel, strips, dim3(256), 0, c->stream, a, g);     // (g.H holds F)
+  } else if (strip == GUIDED_POSE) {
+    hipLaunchKernelGGL(match_guided_pose_kernel, strips, dim3(256), 0, c->stream, a, *pose);
   } else {
     hipLaunchKernelGGL(match_guided_kernel, strips, dim3(256), 0, c->stream, a, g);
   }
@@ -4735,6 +4739,54 @@ int fpc_match_frames_guided_epipolar_cells(fpc_ctx* c, int n, int pairing, const
 int fpc_match_bank_guided_epipolar_cells(fpc_ctx* c, int n, const int32_t* slot, const float* F, float radius, int cross_check,
                                          float max_dist, float ratio, int32_t* match, float* dist, int32_t* stats) {
   return match_bank_guided(c, GUIDED_EPIPOLAR_CELLS, n, slot, F, radius, cross_check, max_dist, ratio, match, dist, stats);
+}
+
+// fpc_match_frames_guided_pose / fpc_match_bank_guided_pose: the gate reads the train set's landmarks -- the key's, or the
+// bank's (null without a landmark reservation: no row is valid) -- and no train pixels
+static bool pose_options_ok(const float* R, const float* t, float fx, float fy, float cx, float cy, float radius,
+                            float max_dist, float ratio, const int32_t* match) {
+  return t && guided_options_ok(R, radius, max_dist, ratio, match) && camera_ok(fx, fy, cx, cy);
+}
+
+static MatchPoseArgs match_pose_args(fpc_ctx* c, const float* R, const float* t, float fx, float fy, float cx, float cy,
+                                     float radius) {
+  MatchPoseArgs g{};
+  g.R = R; g.t = t; g.xy = c->xy;
+  g.fx = fx; g.fy = fy; g.cx = cx; g.cy = cy;
+  g.r2 = (double)radius * (double)radius;
+  return g;
+}
+
+int fpc_match_frames_guided_pose(fpc_ctx* c, int n, const float* key, const int32_t* nkey, const float* key_xyz,
+                                 const uint8_t* key_valid, const float* R, const float* t, float fx, float fy, float cx,
+                                 float cy, float radius, int cross_check, float max_dist, float ratio, int32_t* match,
+                                 float* dist) {
+  if (!c || !key || !nkey || !key_xyz || !pose_options_ok(R, t, fx, fy, cx, cy, radius, max_dist, ratio, match))
+    return FPC_E_INVALID;
+  if (int rc = match_frames_check(c, n, key, nkey)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  MatchFramesArgs a = match_frames_args(c, n, key, nkey);
+  a.pairing = FPC_PAIR_KEY;
+  a.cross_check = cross_check != 0;
+  MatchPoseArgs g = match_pose_args(c, R, t, fx, fy, cx, cy, radius);
+  g.key_xyz = key_xyz; g.key_valid = key_valid;
+  return match_guided_launch(c, GUIDED_POSE, a, MatchGuidedArgs{}, n + 1, max_dist, ratio, match, dist, nullptr, &g);
+}
+
+int fpc_match_bank_guided_pose(fpc_ctx* c, int n, const int32_t* slot, const float* R, const float* t, float fx, float fy,
+                               float cx, float cy, float radius, int cross_check, float max_dist, float ratio, int32_t* match,
+                               float* dist) {
+  if (!c || !c->bank_slab || !slot || !pose_options_ok(R, t, fx, fy, cx, cy, radius, max_dist, ratio, match))
+    return FPC_E_INVALID;
+  if (c->bank_format != FPC_BANK_F32) return FPC_E_INVALID;     // (the bf16 bank's pose gate: not built yet)
+  if (int rc = match_frames_check(c, n, nullptr, nullptr)) return rc;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  MatchFramesArgs a = match_frames_args(c, n, nullptr, nullptr);
+  a.cross_check = cross_check != 0;
+  bank_as_train(a, c->bank, slot);
+  MatchPoseArgs g = match_pose_args(c, R, t, fx, fy, cx, cy, radius);
+  g.lm = c->lm_xyzw;                                            // (null without a landmark reservation)
+  return match_guided_launch(c, GUIDED_POSE, a, MatchGuidedArgs{}, n, max_dist, ratio, match, dist, nullptr, &g);
 }
 
 int fpc_results(fpc_ctx* c, fpc_device_results* out) {

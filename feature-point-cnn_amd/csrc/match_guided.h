@@ -14,7 +14,9 @@
 //                          double[64] LDS arrays of the skeleton (in ascending LDS order: each gate keeps the layout
 //                          its kernel had), one value per query row of the strip, filled once by row(); column()
 //                          keeps what it needs of a train pixel, pass() is the pair test, box() / reach() the tile cull
-//                          of the ordered skeleton.
+//                          of the ordered skeleton.  The plain skeleton asks the gate for the train side it reads
+//                          (train(): these two take the train pixels, mg_train_xy; MgPose of match_guided_pose.h takes
+//                          the train set's landmarks) and is templated on the gate's argument struct for that.
 //   mg_pass_mask           a lane's 64 pairs of the MFMA C/D layout (2 train columns x 32 query rows) as a 64-bit mask.
 //   mg_tile                mf_strip's tile behind that mask -- the same 2 x 2 v_mfma_f32_32x32x2_f32 blocks, K order, d^2
 //                          expression and clamp, so a candidate pair's d^2 has fpc_match_frames' bits -- with the pairs
@@ -60,6 +62,10 @@ struct MgHomography {
   const MatchGuidedArgs& g;
   const int f;
   double *s_px, *s_py, *s_w, *s_rw;             // LDS, [64] each
+  typedef const int32_t* Train;                 // what column() reads of frame f's train set: its pixels
+  static __device__ __forceinline__ Train train(const MatchFramesArgs& a, const MatchGuidedArgs& g, int f) {
+    return mg_train_xy(a, g, f);
+  }
 
   __device__ __forceinline__ MgHomography(const MatchGuidedArgs& g, int f, double* l0, double* l1, double* l2, double* l3)
       : g(g), f(f), s_px(l1), s_py(l2), s_w(l0), s_rw(l3) {}
@@ -197,9 +203,10 @@ __device__ __forceinline__ void mg_merge(const unsigned long long (*s_top)[64][2
   o[1] = m2;
 }
 
-// The plain skeleton: one workgroup (256 threads), the 64-row strip blockIdx.x of frame blockIdx.y.
-template <class Gate>
-__device__ __forceinline__ void mg_strip(const MatchFramesArgs& a, const MatchGuidedArgs& g) {
+// The plain skeleton: one workgroup (256 threads), the 64-row strip blockIdx.x of frame blockIdx.y.  GArgs: the gate's
+// arguments, with the frames' pixels in `xy`.
+template <class Gate, class GArgs = MatchGuidedArgs>
+__device__ __forceinline__ void mg_strip(const MatchFramesArgs& a, const GArgs& g) {
   __shared__ __attribute__((aligned(16))) float s_d2[4][64 * MF_PITCH];
   __shared__ unsigned long long s_top[4][64][2];
   __shared__ float s_qn[64];
@@ -207,7 +214,7 @@ __device__ __forceinline__ void mg_strip(const MatchFramesArgs& a, const MatchGu
   const int f = blockIdx.y, q0 = blockIdx.x * MF_ROWS;
   const MfSets s = mf_sets(a, f);
   if (q0 >= s.nq || s.nt == 0) return;       // (the finalize kernel reads nq / nt itself)
-  const int32_t* txy = mg_train_xy(a, g, f);
+  const typename Gate::Train txy = Gate::train(a, g, f);
   const int32_t* qxy = g.xy + (size_t)f * a.cap * 2;
   unsigned long long* top2 = a.top2 + (size_t)f * a.cap * 2;
   unsigned long long* colbest = a.colbest + (size_t)f * a.cap;

@@ -882,6 +882,25 @@ class Engine:
         rm, ni, mask = self._ransac_out(n, stride=stride)
         return rm, torch.empty((n, 3), dtype=torch.float32, device=self.torch_device), ni, mask
 
+    def _key_landmarks(self, key_xyz, key_valid):
+        """A key frame's 3-D points -> (xyz float32 [k,3], valid uint8 [k] or None, device count) on the device.  key_xyz:
+        float32 [k,3] (device or host), or a device pair (xyz, count), used as it is."""
+        if isinstance(key_xyz, tuple):
+            kx, kc = key_xyz
+        else:
+            kx = torch.as_tensor(key_xyz).to(self.torch_device, torch.float32).contiguous()
+            kc = torch.tensor([kx.shape[0]], dtype=torch.int32, device=self.torch_device)
+        if kx.device != self.torch_device or kx.dtype != torch.float32 or kx.dim() != 2 or kx.shape[1] != 3 \
+                or kc.device != self.torch_device or kc.dtype != torch.int32:
+            raise ValueError("key_xyz must be float32 [k,3], or device tensors (float32 [k,3], int32 [1])")
+        kx = kx.contiguous()
+        kv = None
+        if key_valid is not None:
+            kv = self._dev_uint8(key_valid)
+            if kv.dim() != 1 or kv.shape[0] < kx.shape[0]:
+                raise ValueError("key_valid must be [k]")
+        return kx, kv, kc
+
     def ransac_pnp_async(self, xy, xyz, npairs, K=None, **params):
         """fpc_ransac_pnp: xy float32 [n,stride,2] pixels, xyz float32 [n,stride,3] points and npairs int32 [n] (device
         tensors or host arrays) -> device tensors (R float32 [n,3,3] and t float32 [n,3] with X_cam = R X + t, ninliers
@@ -901,20 +920,7 @@ class Engine:
         pair (xyz, count)) and key_valid (bool / uint8 [k], None: every row) -> device tensors (R [n,3,3], t [n,3],
         ninliers [n], inlier bool [n,cap] by query row).  Does not synchronise."""
         p = self._pnp_params(K, params)
-        if isinstance(key_xyz, tuple):
-            kx, kc = key_xyz
-        else:
-            kx = torch.as_tensor(key_xyz).to(self.torch_device, torch.float32).contiguous()
-            kc = torch.tensor([kx.shape[0]], dtype=torch.int32, device=self.torch_device)
-        if kx.device != self.torch_device or kx.dtype != torch.float32 or kx.dim() != 2 or kx.shape[1] != 3 \
-                or kc.device != self.torch_device or kc.dtype != torch.int32:
-            raise ValueError("key_xyz must be float32 [k,3], or device tensors (float32 [k,3], int32 [1])")
-        kx = kx.contiguous()
-        kv = None
-        if key_valid is not None:
-            kv = self._dev_uint8(key_valid)
-            if kv.dim() != 1 or kv.shape[0] < kx.shape[0]:
-                raise ValueError("key_valid must be [k]")
+        kx, kv, kc = self._key_landmarks(key_xyz, key_valid)
         match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
         return self._solve("fpc_pnp_frames", n, (kx, kv, kc, match), p, self._pnp_out(n))
 
@@ -1138,6 +1144,56 @@ class Engine:
         """match_bank_guided_epipolar_cells_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
         return self._per_frame(n, *self.match_bank_guided_epipolar_cells_async(n, slot, F, radius, cross_check, max_dist,
                                                                                ratio))
+
+    # -- pose-guided matching: the match once more under the estimated absolute poses, "search by projection"
+    # -- (fpc_match_*_guided_pose)
+    def _guided_pose(self, name, n, train, R, t, radius, K, cross_check, max_dist, ratio):
+        """fpc_<name>(ctx, n, *train, R, t, fx, fy, cx, cy, radius, ...): what both pose-guided calls do behind their
+        train set's checks."""
+        rm = self._guided_h(n, R, "R")
+        tv = torch.as_tensor(t).to(self.torch_device, torch.float32).contiguous()
+        if tuple(tv.shape) != (n, 3):
+            raise ValueError("t must be [n,3]")
+        p = self._pnp_params(K, {})
+        m, d = self._table(n)
+        self._call(name, n, *train, rm, tv, float(p.fx), float(p.fy), float(p.cx), float(p.cy), float(radius),
+                   int(bool(cross_check)), float(max_dist), float(ratio), m, d, inputs=(*train, rm, tv))
+        return m, d
+
+    def match_frames_guided_pose_async(self, n, R, t, radius, key, key_xyz, key_valid=None, K=None, cross_check=True,
+                                       max_dist=0.0, ratio=0.0):
+        """fpc_match_frames_guided_pose: match_frames_async against `key` over the key rows whose 3-D point -- key_xyz /
+        key_valid as in pnp_frames_async -- projects within `radius` pixels of the query row under the frame's pose: R
+        (float32 [n,3,3] or [n,9]) and t (float32 [n,3]) with X_cam = R X + t, pnp_frames_async's output, device or
+        host.  K: the camera as in ransac_pnp_async -> (match int32 [n,cap], dist float32 [n,cap]) on the device; a frame
+        with R = t = 0 is all -1.  Does not synchronise."""
+        kd, kc = self._key(key)
+        if kd is None:
+            raise ValueError("the pose-guided match needs a key")
+        kx, kv, _ = self._key_landmarks(key_xyz, key_valid)
+        if kx.shape[0] < kd.shape[0]:
+            raise ValueError("a key needs key_xyz with a row for each of its rows")
+        return self._guided_pose("fpc_match_frames_guided_pose", n, (kd, kc, kx, kv), R, t, radius, K, cross_check,
+                                 max_dist, ratio)
+
+    def match_frames_guided_pose(self, n, R, t, radius, key, key_xyz, key_valid=None, K=None, cross_check=True,
+                                 max_dist=0.0, ratio=0.0):
+        """match_frames_guided_pose_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        return self._per_frame(n, *self.match_frames_guided_pose_async(n, R, t, radius, key, key_xyz, key_valid, K,
+                                                                       cross_check, max_dist, ratio))
+
+    def match_bank_guided_pose_async(self, n, slot, R, t, radius, K=None, cross_check=True, max_dist=0.0, ratio=0.0):
+        """fpc_match_bank_guided_pose: match_frames_guided_pose_async with frame f's train set and landmarks taken from bank
+        slot slot[f] (as match_bank_guided_async) and R, t pnp_bank_async's output; an "f32" bank only (a "bf16" bank is
+        refused); a bank without landmarks gives all -1.  Does not synchronise."""
+        self._bank_info()
+        slot = self._dev_int32("slot", slot, "[n]", n)
+        return self._guided_pose("fpc_match_bank_guided_pose", n, (slot,), R, t, radius, K, cross_check, max_dist, ratio)
+
+    def match_bank_guided_pose(self, n, slot, R, t, radius, K=None, cross_check=True, max_dist=0.0, ratio=0.0):
+        """match_bank_guided_pose_async, then per frame (match int32 [K_f], dist float32 [K_f])."""
+        return self._per_frame(n, *self.match_bank_guided_pose_async(n, slot, R, t, radius, K, cross_check, max_dist,
+                                                                     ratio))
 
     # -- timing ----------------------------------------------------------------------
     def check_guards(self):

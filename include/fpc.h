@@ -1019,6 +1019,60 @@ int fpc_pnp_frames(fpc_ctx* ctx, int n, const float* key_xyz_dev, const uint8_t*
 int fpc_pnp_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const fpc_pnp_params* params,
                  float* R_dev, float* t_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
 
+/* --- pose-guided matching: the match once more, under the estimated absolute poses as the gate ----------------------------
+ * The third model's second pass, "search by projection": with one (R, t) per frame -- what fpc_pnp_frames / fpc_pnp_bank
+ * wrote, passed on unchanged, or the previous frame's pose as a motion prior -- the train set's landmarks are projected into
+ * the frame and a row is matched only against the landmarks that project next to it.  The gate knows a landmark's depth:
+ * two landmarks on one viewing ray of the key camera share their epipolar line, and this gate still tells them apart.
+ *
+ * fpc_match_frames_guided_pose / fpc_match_bank_guided_pose.  Query sets, counts, cap and the output shapes are
+ * fpc_match_frames' for the same n.
+ *  - Frames variant: the train set is the key, key_dev float32 [nkey][D] with nkey_dev[0] read on the device and clamped to
+ *    the capacity; its landmarks are key_xyz_dev float32 [nkey][3] and key_valid_dev uint8 [nkey] or NULL -- the arguments
+ *    and the validity rule of fpc_pnp_frames: landmark j is valid when key_valid_dev[j] != 0 (NULL: every row) and its three
+ *    coordinates are finite.  There is no pairing argument and no key_xy_dev: a predecessor frame has no landmarks, and the
+ *    gate does not read train pixels.
+ *  - Bank variant: frame f's train set is desc[slot[f]], count[slot[f]] of the bank, its landmarks the bank's float4 row
+ *    (w != 0: valid).  slot_dev is read on the device; a slot outside [0, slots) gives the frame no train rows.  A bank
+ *    without a landmark reservation leaves every row -1 / +inf, as fpc_pnp_bank leaves such a frame without pairs.
+ *  - R_dev float32 [n][9] row-major and t_dev float32 [n][3] with X_cam = R X + t: the direction and layout fpc_ransac_pnp /
+ *    fpc_pnp_frames / fpc_pnp_bank write.  The camera is four host floats, the fx, fy, cx, cy of fpc_pnp_params.
+ *  - Gate: query row i at the integer pixel (x, y), train row j with landmark (X, Y, Z); in fp64 from the fp32 R and t
+ *        a = R0 X + R1 Y + R2 Z + t0,   b = R3 X + R4 Y + R5 Z + t1,   c = R6 X + R7 Y + R8 Z + t2
+ *        ex = fx a - (x - cx) c,        ey = fy b - (y - cy) c
+ *    and row j is a CANDIDATE of row i iff landmark j is valid, c > 0 and ex^2 + ey^2 < radius^2 c^2.  No division.  This
+ *    is the inlier test of the PnP calls with radius in the place of reproj_threshold: a pair that a PnP call marks as an
+ *    inlier at threshold t is a candidate at radius t.  A failed frame's zeros give c = 0: no candidates, every row
+ *    -1 / +inf.  The same holds for an R or t with any non-finite entry.  R is used as given; it is not orthonormalised.
+ *  - Result: fpc_match_frames' rule over the candidates only: the nearest candidate in (d^2, index) order, dist = its
+ *    distance, max_dist and ratio as there with the second-nearest CANDIDATE as d2 (fewer than two candidates: the ratio
+ *    test fails).  Cross check: row i survives iff i is the (d^2, index)-nearest among the query rows that have j as a
+ *    candidate.  A row without a candidate: -1 / +inf; rows count[f] <= i < cap: -1 / +inf.
+ *  - Bits: for a candidate pair d^2 is the value fpc_match_frames computes for that pair (the same norms, K order,
+ *    expression and clamp), so where the guided winner equals the unguided winner dist is bit-equal, and under a radius at
+ *    which EVERY pair of a frame is a candidate the frame's output is fpc_match_frames' / the fpc_match_bank table's, bit
+ *    for bit.  That needs every train landmark valid with c > 0; the radius that admits every pair depends on the pose.
+ *  - Execution: asynchronous on the ctx stream, no host synchronisation, no device-to-host copy, no allocation (the
+ *    workspace is fpc_match_frames', carved at fpc_create; nothing new is carved, the plan hash and the guard zones are what
+ *    they were, nothing is added to the bank's or the landmarks' allocation; no fpc_pnp_reserve is needed); every count and
+ *    slot is read on the device; deterministic (bit-identical outputs on repeated calls).  fpc_detect, fpc_match_bank,
+ *    fpc_pnp_bank, fpc_match_bank_guided_pose, fpc_pnp_bank needs no host call in between; the same holds with a key
+ *    through fpc_match_frames, fpc_pnp_frames, fpc_match_frames_guided_pose, fpc_pnp_frames.
+ * FPC_E_INVALID (nothing is written): everything fpc_match_frames refuses; NULL R_dev, t_dev or match_dev; radius not finite
+ * or not > 0; fx or fy not > 0 or a non-finite intrinsic; frames variant: NULL key_dev, nkey_dev or key_xyz_dev; bank
+ * variant: no bank, NULL slot_dev, or a FPC_BANK_BF16 bank (that format's pose gate is a follow-up, as its epipolar one).
+ * The cell-ordered variant is a follow-up too: its train order would have to follow the PROJECTED pixels, which differ per
+ * frame and pose. */
+int fpc_match_frames_guided_pose(fpc_ctx* ctx, int n, const float* key_dev, const int32_t* nkey_dev,
+                                 const float* key_xyz_dev, const uint8_t* key_valid_dev,
+                                 const float* R_dev, const float* t_dev, float fx, float fy, float cx, float cy,
+                                 float radius, int cross_check, float max_dist, float ratio,
+                                 int32_t* match_dev, float* dist_dev);
+int fpc_match_bank_guided_pose(fpc_ctx* ctx, int n, const int32_t* slot_dev,
+                               const float* R_dev, const float* t_dev, float fx, float fy, float cx, float cy,
+                               float radius, int cross_check, float max_dist, float ratio,
+                               int32_t* match_dev, float* dist_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
