@@ -42,6 +42,7 @@ SYMBOLS = [
     "fpc_default_pnp_params", "fpc_pnp_reserve", "fpc_bank_landmarks_reserve", "fpc_bank_store_landmarks",
     "fpc_bank_landmarks_get", "fpc_ransac_pnp", "fpc_pnp_frames", "fpc_pnp_bank",
     "fpc_match_frames_guided_pose", "fpc_match_bank_guided_pose",
+    "fpc_default_landmark_params", "fpc_landmarks_pairs", "fpc_landmarks_frames", "fpc_landmarks_bank",
 ]
 
 ABI_VERSION = 4
@@ -106,7 +107,14 @@ class FpcPnpParams(ctypes.Structure):
                 ("refits", ctypes.c_int), ("min_inliers", ctypes.c_int)]
 
 
-BANK_MAX_SLOTS = 1024         # include/fpc.h FPC_BANK_MAX_SLOTS
+class FpcLandmarkParams(ctypes.Structure):
+    """fpc_landmark_params (include/fpc.h)."""
+    _fields_ = [("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
+                ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
+                ("reproj_threshold", ctypes.c_float), ("min_parallax_deg", ctypes.c_float)]
+
+
+BANK_MAX_SLOTS = 1024        # include/fpc.h FPC_BANK_MAX_SLOTS
 BANK_TOPK_MAX = 16            # include/fpc.h FPC_BANK_TOPK_MAX
 
 
@@ -233,7 +241,13 @@ def load():
     cf = ctypes.c_float
     l.fpc_match_frames_guided_pose.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, cf, vp, vp]
     l.fpc_match_bank_guided_pose.argtypes = [vp, ci, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, cf, vp, vp]
-    l.fpc_bank_topk_reserve.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_size_t)]
+    lp = ctypes.POINTER(FpcLandmarkParams)
+    l.fpc_default_landmark_params.argtypes = [lp]
+    # a pair source, then (R_dev, t_dev, params, xyz_dev, kind_dev, counts_dev)
+    l.fpc_landmarks_pairs.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, lp, vp, vp, vp]
+    l.fpc_landmarks_frames.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, lp, vp, vp, vp]
+    l.fpc_landmarks_bank.argtypes = [vp, ci, vp, vp, vp, vp, lp, vp, vp, vp]
+    l.fpc_bank_topk_reserve.argtypes =[vp, ci, ctypes.POINTER(ctypes.c_size_t)]
     l.fpc_match_bank_topk.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp, vp]
     l.fpc_homography_bank_topk.argtypes = [vp, ci, ci, vp, vp, rp, vp, vp, vp, vp, vp]
     l.fpc_sample_descriptors.argtypes = [vp, vp, vp, ci, vp]

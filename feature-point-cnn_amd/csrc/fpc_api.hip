@@ -46,6 +46,7 @@
 #include "pose_epipolar.h"
 #include "match_bank_topk.h"
 #include "pnp_ransac.h"
+#include "landmarks.h"
 #include "homography.h"
 #include "weights.h"
 
@@ -4787,6 +4788,71 @@ int fpc_match_bank_guided_pose(fpc_ctx* c, int n, const int32_t* slot, const flo
   MatchPoseArgs g = match_pose_args(c, R, t, fx, fy, cx, cy, radius);
   g.lm = c->lm_xyzw;                                            // (null without a landmark reservation)
   return match_guided_launch(c, GUIDED_POSE, a, MatchGuidedArgs{}, n, max_dist, ratio, match, dist, nullptr, &g);
+}
+
+// ---- landmarks for a new key frame from its PnP pose (include/fpc.h; kernel in landmarks.h) -----------------------------------
+// One launch per call: the kernel reads every row straight from its source, so there is no pair list, no workspace and no
+// reservation behind these calls.
+int fpc_default_landmark_params(fpc_landmark_params* p) {
+  if (!p) return FPC_E_INVALID;
+  p->q_fx = p->q_fy = p->t_fx = p->t_fy = 500.0f;
+  p->q_cx = p->t_cx = 320.0f;
+  p->q_cy = p->t_cy = 240.0f;
+  p->reproj_threshold = 3.0f;
+  p->min_parallax_deg = 1.0f;
+  return FPC_OK;
+}
+
+static bool landmark_params_ok(const fpc_landmark_params* p) {
+  return p && camera_ok(p->q_fx, p->q_fy, p->q_cx, p->q_cy) && camera_ok(p->t_fx, p->t_fy, p->t_cx, p->t_cy) &&
+         threshold_ok(p->reproj_threshold) && p->min_parallax_deg >= 0.f && p->min_parallax_deg < 90.f;   // (a NaN fails)
+}
+
+// what the three calls share behind their source's own checks: the arguments every source has, then the launch; S rows of
+// xyz / kind per frame
+extern "C++" template <class Source>    // (this block is extern "C")
+static int landmarks_launch(fpc_ctx* c, int n, const Source& src, const float* R, const float* t, const fpc_landmark_params* p,
+                            float* xyz, uint8_t* kind, int32_t* counts, int S) {
+  if (!R || !t || !xyz || !kind || !landmark_params_ok(p)) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  LmArgs a{};
+  a.q_fx = p->q_fx; a.q_fy = p->q_fy; a.q_cx = p->q_cx; a.q_cy = p->q_cy;
+  a.t_fx = p->t_fx; a.t_fy = p->t_fy; a.t_cx = p->t_cx; a.t_cy = p->t_cy;
+  a.thr = p->reproj_threshold;
+  const double s = std::sin((double)p->min_parallax_deg * (3.14159265358979323846 / 180.0));
+  a.parallax = p->min_parallax_deg > 0.f ? s * s : POSE_PARALLEL;
+  hipLaunchKernelGGL(landmarks_kernel<Source>, dim3(n), dim3(256), 0, c->stream, src, a, R, t, xyz, kind, counts, S);
+  return launched();
+}
+
+int fpc_landmarks_pairs(fpc_ctx* c, int n, const float* q_xy, const float* t_xy, const float* t_xyz, const uint8_t* t_valid,
+                        const int32_t* npairs, int stride, const float* R, const float* t, const fpc_landmark_params* p,
+                        float* xyz, uint8_t* kind, int32_t* counts) {
+  if (!c || !q_xy || !t_xy || !npairs || !explicit_ok(c, n, stride)) return FPC_E_INVALID;
+  LmExplicit src{};
+  src.q_xy = q_xy; src.t_xy = t_xy; src.t_xyz = t_xyz; src.t_valid = t_valid; src.npairs = npairs; src.stride = stride;
+  return landmarks_launch(c, n, src, R, t, p, xyz, kind, counts, stride);
+}
+
+int fpc_landmarks_frames(fpc_ctx* c, int n, const int32_t* key_xy, const int32_t* nkey, const float* key_xyz,
+                         const uint8_t* key_valid, const int32_t* match, const float* R, const float* t,
+                         const fpc_landmark_params* p, float* xyz, uint8_t* kind, int32_t* counts) {
+  if (!c || !key_xy || !nkey || !match || !frames_ok(c, n)) return FPC_E_INVALID;
+  LmKey src{};
+  src.q = LmFrames{c->xy, c->count, match, c->cap};
+  src.key_xy = key_xy; src.nkey = nkey; src.key_xyz = key_xyz; src.key_valid = key_valid;
+  return landmarks_launch(c, n, src, R, t, p, xyz, kind, counts, c->cap);
+}
+
+int fpc_landmarks_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const float* R, const float* t,
+                       const fpc_landmark_params* p, float* xyz, uint8_t* kind, int32_t* counts) {
+  if (!c || !bank_ok(c, n, slot, match)) return FPC_E_INVALID;
+  LmBank src{};
+  src.q = LmFrames{c->xy, c->count, match, c->cap};
+  src.slot = slot; src.bank_xy = c->bank.xy; src.bank_count = c->bank.count;
+  src.bank_lm = c->lm_xyzw;                                      // (null without a landmark reservation: triangulation only)
+  src.rows = c->bank.rows; src.slots = c->bank.slots;
+  return landmarks_launch(c, n, src, R, t, p, xyz, kind, counts, c->cap);
 }
 
 int fpc_results(fpc_ctx* c, fpc_device_results* out) {

@@ -772,14 +772,19 @@ class Engine:
             return tuple(float(v) for v in k)
         raise ValueError("%s must be a 3 x 3 matrix or (fx, fy, cx, cy)" % name)
 
-    def _pose_params(self, K_query, K_train, params):
+    def _two_camera_params(self, struct, default, fields, word, K_query, K_train, params):
+        """_params for a struct that starts with the query and the train camera (q_fx .. t_cy)."""
         cameras = (("q", self._intrinsics(K_query, "K_query")), ("t", self._intrinsics(K_train, "K_train")))
-        p = self._params(_lib.FpcPoseParams, "fpc_default_pose_params", ("reproj_threshold", "min_front"), "pose", params)
+        p = self._params(struct, default, fields, word, params)
         for side, k in cameras:
             if k is not None:
                 for field, v in zip(("fx", "fy", "cx", "cy"), k):
                     setattr(p, "%s_%s" % (side, field), v)
         return p
+
+    def _pose_params(self, K_query, K_train, params):
+        return self._two_camera_params(_lib.FpcPoseParams, "fpc_default_pose_params", ("reproj_threshold", "min_front"),
+                                       "pose", K_query, K_train, params)
 
     def _pose_out(self, n, stride, points):
         """Empty pose outputs (R float32 [n,3,3], t float32 [n,3], nfront int32 [n], xyz float32 [n,stride,3], front uint8
@@ -938,6 +943,86 @@ class Engine:
     def pnp_bank(self, n, slot, match, K=None, **params):
         """pnp_bank_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""
         return self._host(self.pnp_bank_async(n, slot, match, K, **params))
+
+    # -- map growth: landmarks for a new key frame from its PnP pose (fpc_landmarks_pairs / _frames / _bank) -----------------
+    def _landmark_params(self, K_query, K_train, params):
+        return self._two_camera_params(_lib.FpcLandmarkParams, "fpc_default_landmark_params",
+                                       ("reproj_threshold", "min_parallax_deg"), "landmark", K_query, K_train, params)
+
+    def _landmarks(self, name, n, pairs, R, t, p, stride):
+        """fpc_<name>(ctx, n, *pairs, R, t, params, xyz, kind, counts) -> (xyz float32 [n,stride,3], kind uint8 [n,stride],
+        counts int32 [n,2]) on the device."""
+        rm = self._guided_h(n, R, "R")
+        tv = torch.as_tensor(t).to(self.torch_device, torch.float32).contiguous()
+        if tuple(tv.shape) != (n, 3):
+            raise ValueError("t must be [n,3]")
+        xyz = torch.empty((n, stride, 3), dtype=torch.float32, device=self.torch_device)
+        kind = torch.empty((n, stride), dtype=torch.uint8, device=self.torch_device)
+        counts = self._int32(n, 2)
+        self._call(name, n, *pairs, rm, tv, ctypes.byref(p), xyz, kind, counts, inputs=(*pairs, rm, tv))
+        return xyz, kind, counts
+
+    def landmarks_pairs_async(self, q_xy, t_xy, npairs, R, t, t_xyz=None, t_valid=None, K_query=None, K_train=None,
+                              **params):
+        """fpc_landmarks_pairs: per pair the query pixel q_xy and the train pixel t_xy (float32 [n,stride,2]), the train
+        row's 3-D point t_xyz (float32 [n,stride,3]; None: no row has one) and its flag t_valid (bool / uint8 [n,stride];
+        None: every finite row), npairs int32 [n] -- device tensors or host arrays -- under the poses R (float32 [n,3,3] or
+        [n,9]) and t (float32 [n,3]) with X_query = R X_train + t, the PnP calls' output -> device tensors (xyz float32
+        [n,stride,3] in the query camera's frame, kind uint8 [n,stride]: 1 carried over, 2 triangulated, 0 neither; counts
+        int32 [n,2] of kinds 1 and 2).  K_query / K_train: 3 x 3 camera matrices or (fx, fy, cx, cy).  Parameters:
+        reproj_threshold, min_parallax_deg.  A frame with a failed pose is all zeros.  Does not synchronise."""
+        p = self._landmark_params(K_query, K_train, params)
+        n, (a, b, npairs, stride) = self._explicit_pairs(q_xy, t_xy, npairs, 2,
+                                                         "q_xy and t_xy must be [n,stride,2] and npairs [n]")
+        lm = vl = None
+        if t_xyz is not None:
+            lm = torch.as_tensor(t_xyz).to(self.torch_device, torch.float32).contiguous()
+            if tuple(lm.shape) != (n, stride, 3):
+                raise ValueError("t_xyz must be [n,stride,3]")
+        if t_valid is not None:
+            vl = self._dev_uint8(t_valid)
+            if tuple(vl.shape) != (n, stride):
+                raise ValueError("t_valid must be [n,stride]")
+        return self._landmarks("fpc_landmarks_pairs", n, (a, b, lm, vl, npairs, stride), R, t, p, stride)
+
+    def landmarks_pairs(self, q_xy, t_xy, npairs, R, t, t_xyz=None, t_valid=None, K_query=None, K_train=None, **params):
+        """landmarks_pairs_async, then host arrays (xyz [n,stride,3], kind uint8 [n,stride], counts [n,2])."""
+        return self._host(self.landmarks_pairs_async(q_xy, t_xy, npairs, R, t, t_xyz, t_valid, K_query, K_train, **params))
+
+    def landmarks_frames_async(self, n, match, R, t, key_xy, key_xyz=None, key_valid=None, K_query=None, K_train=None,
+                               **params):
+        """fpc_landmarks_frames: the rows (xy[f][i], key row match[f][i]) of every frame of the last detect, `match` being
+        match_frames_async's table against the key frame whose pixels are key_xy (keep_frame_points, or an (xy, count)
+        device pair) and whose rows' 3-D points are key_xyz / key_valid as in pnp_frames_async (None: the key has none, every
+        row is triangulated); R, t: pnp_frames_async's output -> device tensors (xyz [n,cap,3], kind uint8 [n,cap] by query
+        row, counts [n,2]); `xyz[f]`, `kind[f]` go into bank_store_landmarks as they are.  Does not synchronise."""
+        p = self._landmark_params(K_query, K_train, params)
+        kx, kc = self._key_xy(key_xy)
+        if kx is None:
+            raise ValueError("landmarks_frames needs key_xy")
+        lm = vl = None
+        if key_xyz is not None:
+            lm, vl, _ = self._key_landmarks(key_xyz, key_valid)
+            if lm.shape[0] < kx.shape[0]:
+                raise ValueError("key_xyz needs a row for each row of key_xy")
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        return self._landmarks("fpc_landmarks_frames", n, (kx, kc, lm, vl, match), R, t, p, self.capacity)
+
+    def landmarks_frames(self, n, match, R, t, key_xy, key_xyz=None, key_valid=None, K_query=None, K_train=None, **params):
+        """landmarks_frames_async, then host arrays (xyz [n,cap,3], kind uint8 [n,cap], counts [n,2])."""
+        return self._host(self.landmarks_frames_async(n, match, R, t, key_xy, key_xyz, key_valid, K_query, K_train, **params))
+
+    def landmarks_bank_async(self, n, slot, match, R, t, K_query=None, K_train=None, **params):
+        """fpc_landmarks_bank: landmarks_frames_async with frame f's key pixels and landmarks taken from bank slot slot[f]
+        (as pnp_bank_async, whose R, t go in as they are) on a bank of either format; a frame with slot -1 is all zeros; a
+        bank without landmarks triangulates every row.  bank_store(f, s) and bank_store_landmarks(s, xyz[f], kind[f]) behind
+        it make frame f the next key frame, at the map's scale.  Does not synchronise."""
+        p, pairs = self._bank_pairs(n, slot, match, self._landmark_params, K_query, K_train, params)
+        return self._landmarks("fpc_landmarks_bank", n, pairs, R, t, p, self.capacity)
+
+    def landmarks_bank(self, n, slot, match, R, t, K_query=None, K_train=None, **params):
+        """landmarks_bank_async, then host arrays (xyz [n,cap,3], kind uint8 [n,cap], counts [n,2])."""
+        return self._host(self.landmarks_bank_async(n, slot, match, R, t, K_query, K_train, **params))
 
     # -- verified relocalisation: the k best slots per frame, each checked by RANSAC (fpc_*_bank_topk) ------------------
     def bank_topk_reserve(self, kmax):

@@ -1073,6 +1073,82 @@ int fpc_match_bank_guided_pose(fpc_ctx* ctx, int n, const int32_t* slot_dev,
                                float radius, int cross_check, float max_dist, float ratio,
                                int32_t* match_dev, float* dist_dev);
 
+/* --- map growth: landmarks for a new key frame from its PnP pose ----------------------------------------------------------
+ * fpc_pose_* is the only call above that creates 3-D points, from two views and at the scale |t| = 1 of that pair.  A frame
+ * that fpc_pnp_frames / fpc_pnp_bank has localised has an R, t at the MAP's scale; the calls below give that frame its own
+ * landmarks at that scale, so that it can be stored as the next key frame: a row that matched a train row WITH a landmark
+ * gets that landmark carried over into its own camera frame, a row that matched a train row WITHOUT one gets a new point,
+ * triangulated under the known pose.  fpc_landmarks_pairs, fpc_landmarks_frames and fpc_landmarks_bank mirror
+ * fpc_ransac_pnp, fpc_pnp_frames and fpc_pnp_bank: explicit pairs, the frames of the last detect against one key set, and
+ * those frames against bank slots.
+ *  - Convention: X_query = R X_train + t, the direction the PnP calls write; R_dev float32 [n][9] row-major and t_dev float32
+ *    [n][3] are passed on unchanged.  An R, t from fpc_pose_* has the OPPOSITE direction (X_train = R X_query + t) and does
+ *    not go in as it is.  R is used as given; it is not orthonormalised.
+ *  - Rows.  Explicit: pair k < npairs[f] (clamped to [0, stride]) is the query pixel q_xy[f][k], the train pixel t_xy[f][k]
+ *    (both float32 [n][stride][2]) and the train row's landmark t_xyz[f][k] (float32 [n][stride][3]) with its flag
+ *    t_valid[f][k] (uint8 [n][stride]; NULL: every row).  Frames and bank: query row i < count[f] with
+ *    0 <= j = match[f][i] < the train count; the query pixel is xy[f][i] of the results, the train pixel and landmark are row
+ *    j of the key (key_xy_dev int32 [nkey][2], key_xyz_dev float32 [nkey][3], key_valid_dev uint8 [nkey] or NULL; nkey_dev[0]
+ *    clamped to the capacity) or of bank slot slot[f].  Counts, clamping, the slot rules and the key rules are those of
+ *    fpc_pnp_frames / fpc_pnp_bank.  A landmark is valid by the rule of fpc_bank_store_landmarks: its flag is set and its
+ *    three coordinates are finite.  A NULL t_xyz_dev / key_xyz_dev, or a bank without a landmark reservation, means that no
+ *    train row has a landmark.  Everything below is fp64, computed from the fp32 R, t and from integer or fp32 pixels.
+ *  - Failed pose: a frame whose R is all zero (a failed frame of the PnP calls), or whose R or t holds a non-finite entry,
+ *    and a bank slot outside [0, slots): every kind row 0, every xyz row zero, counts (0, 0).
+ *  - Transfer (kind 1), where the train row has a valid landmark X: (a, b, c) = R X + t; the row is kept iff c > 0 and
+ *        (q_fx a - (x - q_cx) c)^2 + (q_fy b - (y - q_cy) c)^2 < reproj_threshold^2 c^2
+ *    with (x, y) the query pixel: the inlier test of the PnP calls.  xyz = (a, b, c) rounded to fp32.  A row that fails gets
+ *    kind 0; it is NOT triangulated: the map contradicts the match.
+ *  - Triangulation (kind 2), where the train row has no valid landmark: p^ = ((x - q_cx) / q_fx, (y - q_cy) / q_fy, 1), q^
+ *    likewise from the train pixel (u, v) and the train camera; a = p^, b = R q^;
+ *        det = (a.a)(b.b) - (a.b)^2,
+ *        lam = ((a.t)(b.b) - (a.b)(b.t)) / det,      mu = ((a.b)(a.t) - (a.a)(b.t)) / det
+ *    (the parameters at which the rays lam a and t + mu b are closest); X = (lam a + t + mu b) / 2, the midpoint, in the query
+ *    camera's frame, and Y = R^T (X - t), the same point in the train camera's frame.  The row is kept iff
+ *        det > sin^2(min_parallax_deg) (a.a)(b.b)   (sin^2 formed by the host in double; at 0 degrees the floor of the pose
+ *                                                     calls instead: det > 1e-12 (a.a)(b.b)),
+ *        lam > 0 and mu > 0,
+ *        X passes the test above against the query pixel and the query camera,
+ *        Y passes it against the train pixel and the train camera,
+ *    all of them on the fp64 X, before rounding.  xyz = X rounded to fp32.
+ *  - Outputs: xyz_dev float32 [n][S][3], kind_dev uint8 [n][S], counts_dev int32 [n][2] (may be NULL); S is `stride` for
+ *    fpc_landmarks_pairs and the capacity for the other two; a row is a pair (explicit) or a query row (frames, bank).  Every
+ *    row of the call's frames is written: nothing needs to be cleared beforehand.  A row that is no pair, lies past the
+ *    count or failed a test holds kind 0 and three zeros.  counts[f] = (rows of kind 1, rows of kind 2): integer sums,
+ *    independent of the execution order.  kind_dev + f S goes into fpc_bank_store_landmarks as valid_dev unchanged (it tests
+ *    != 0) and xyz_dev + f S 3 as xyz_dev, right behind fpc_bank_store(f, slot): fpc_detect, fpc_match_bank, fpc_pnp_bank,
+ *    fpc_landmarks_bank, fpc_bank_store, fpc_bank_store_landmarks needs no host call in between, and the map grows at one
+ *    scale.
+ *  - Execution: asynchronous on the ctx stream, no host synchronisation, no device-to-host copy, no allocation.  One launch
+ *    reads every row straight from its source: nothing is carved, the RANSAC and PnP pair-list workspaces are not touched, so
+ *    no fpc_pnp_reserve is needed; the plan hash and the guard zones are what they were.  Every count and slot is read on the
+ *    device.  Deterministic: bit-identical outputs on repeated calls; the three entry points give bit-identical outputs on
+ *    equal lists, and fpc_landmarks_bank is bit-identical to fpc_landmarks_frames with that slot's own storage as the key.
+ *    It works on a FPC_BANK_BF16 bank: it reads only xy, counts and landmarks.
+ *  - Not here: fusing repeated observations of one landmark, bundle adjustment, a cell-ordered variant.
+ * FPC_E_INVALID (nothing is written): everything the PnP twins refuse for the arguments they share (n, stride, a NULL pair
+ * array, npairs_dev, match_dev); NULL params, R_dev, t_dev, xyz_dev or kind_dev; fx or fy not > 0 or a non-finite intrinsic on
+ * either side; reproj_threshold not > 0 (or not below 1e18); min_parallax_deg not in [0, 90); fpc_landmarks_frames: a NULL
+ * key_xy_dev or nkey_dev; fpc_landmarks_bank: no bank or a NULL slot_dev. */
+typedef struct fpc_landmark_params {
+  float q_fx, q_fy, q_cx, q_cy;   /* camera of the frames being promoted (query), pixels, fx, fy > 0                      */
+  float t_fx, t_fy, t_cx, t_cy;   /* camera of the key frame (train)                                                      */
+  float reproj_threshold;         /* px, > 0, below 1e18                                                                  */
+  float min_parallax_deg;         /* >= 0, < 90: the least angle between the two rays of a triangulated row               */
+} fpc_landmark_params;
+/* fx = fy = 500, centre (320, 240) on both sides, reproj_threshold 3.0, min_parallax_deg 1.0 */
+int fpc_default_landmark_params(fpc_landmark_params* params);
+int fpc_landmarks_pairs(fpc_ctx* ctx, int n, const float* q_xy_dev, const float* t_xy_dev, const float* t_xyz_dev,
+                        const uint8_t* t_valid_dev, const int32_t* npairs_dev, int stride, const float* R_dev,
+                        const float* t_dev, const fpc_landmark_params* params, float* xyz_dev, uint8_t* kind_dev,
+                        int32_t* counts_dev);
+int fpc_landmarks_frames(fpc_ctx* ctx, int n, const int32_t* key_xy_dev, const int32_t* nkey_dev, const float* key_xyz_dev,
+                         const uint8_t* key_valid_dev, const int32_t* match_dev, const float* R_dev, const float* t_dev,
+                         const fpc_landmark_params* params, float* xyz_dev, uint8_t* kind_dev, int32_t* counts_dev);
+int fpc_landmarks_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const float* R_dev,
+                       const float* t_dev, const fpc_landmark_params* params, float* xyz_dev, uint8_t* kind_dev,
+                       int32_t* counts_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
