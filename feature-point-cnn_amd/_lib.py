@@ -43,6 +43,7 @@ SYMBOLS = [
     "fpc_bank_landmarks_get", "fpc_ransac_pnp", "fpc_pnp_frames", "fpc_pnp_bank",
     "fpc_match_frames_guided_pose", "fpc_match_bank_guided_pose",
     "fpc_default_landmark_params", "fpc_landmarks_pairs", "fpc_landmarks_frames", "fpc_landmarks_bank",
+    "fpc_default_sim3_params", "fpc_ransac_sim3", "fpc_sim3_frames", "fpc_sim3_bank",
 ]
 
 ABI_VERSION = 4
@@ -112,6 +113,14 @@ class FpcLandmarkParams(ctypes.Structure):
     _fields_ = [("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
                 ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
                 ("reproj_threshold", ctypes.c_float), ("min_parallax_deg", ctypes.c_float)]
+
+
+class FpcSim3Params(ctypes.Structure):
+    """fpc_sim3_params (include/fpc.h)."""
+    _fields_ = [("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
+                ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
+                ("iterations", ctypes.c_int), ("reproj_threshold", ctypes.c_float), ("seed", ctypes.c_uint32),
+                ("refits", ctypes.c_int), ("min_inliers", ctypes.c_int), ("fix_scale", ctypes.c_int)]
 
 
 BANK_MAX_SLOTS = 1024        # include/fpc.h FPC_BANK_MAX_SLOTS
@@ -247,6 +256,11 @@ def load():
     l.fpc_landmarks_pairs.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, lp, vp, vp, vp]
     l.fpc_landmarks_frames.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, lp, vp, vp, vp]
     l.fpc_landmarks_bank.argtypes = [vp, ci, vp, vp, vp, vp, lp, vp, vp, vp]
+    sp = ctypes.POINTER(FpcSim3Params)
+    l.fpc_default_sim3_params.argtypes = [sp]
+    l.fpc_ransac_sim3.argtypes = [vp, ci, vp, vp, vp, ci, sp, vp, vp, vp, vp, vp]
+    l.fpc_sim3_frames.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, sp, vp, vp, vp, vp, vp]
+    l.fpc_sim3_bank.argtypes = [vp, ci, vp, vp, vp, vp, sp, vp, vp, vp, vp, vp]
     l.fpc_bank_topk_reserve.argtypes =[vp, ci, ctypes.POINTER(ctypes.c_size_t)]
     l.fpc_match_bank_topk.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp, vp]
     l.fpc_homography_bank_topk.argtypes = [vp, ci, ci, vp, vp, rp, vp, vp, vp, vp, vp]

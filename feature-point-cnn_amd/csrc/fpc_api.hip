@@ -46,6 +46,7 @@
 #include "pose_epipolar.h"
 #include "match_bank_topk.h"
 #include "pnp_ransac.h"
+#include "sim3_ransac.h"
 #include "landmarks.h"
 #include "homography.h"
 #include "weights.h"
@@ -4489,6 +4490,87 @@ int fpc_pnp_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, c
   // (without landmark storage lm is null: no frame has pairs)
   return pnp_gather(c, n, PnpTrain{nullptr, nullptr, nullptr, slot, c->lm_xyzw, c->bank.count, c->bank.rows, c->bank.slots},
                     match, p, R, t, ninliers, inlier);
+}
+
+// ---- Sim(3) alignment between two frames' landmarks (include/fpc.h; kernels in sim3_ransac.h) ----------------------------------
+int fpc_default_sim3_params(fpc_sim3_params* p) {
+  if (!p) return FPC_E_INVALID;
+  p->q_fx = p->q_fy = p->t_fx = p->t_fy = 500.0f;
+  p->q_cx = p->t_cx = 320.0f;
+  p->q_cy = p->t_cy = 240.0f;
+  p->iterations = 1024;
+  p->reproj_threshold = 3.0f;
+  p->seed = 0;
+  p->refits = 4;
+  p->min_inliers = 12;
+  p->fix_scale = 0;
+  return FPC_OK;
+}
+
+static bool sim3_params_ok(const fpc_sim3_params* p) {
+  return p && camera_ok(p->q_fx, p->q_fy, p->q_cx, p->q_cy) && camera_ok(p->t_fx, p->t_fy, p->t_cx, p->t_cy) &&
+         ransac_fields_ok(p->iterations, p->reproj_threshold, p->refits, p->min_inliers, SIM3_SAMPLE) &&
+         (p->fix_scale == 0 || p->fix_scale == 1);
+}
+
+// the records, counts and best keys are the PnP reservation's (the records have the PnP records' size)
+static Sim3Args sim3_args(fpc_ctx* c, int n, const fpc_sim3_params* p) {
+  Sim3Args a{};
+  a.rec = c->pnp_rec; a.np = c->pnp_np; a.best = c->pnp_best;
+  a.cap = c->cap; a.n = n;
+  a.T = p->iterations; a.refits = p->refits; a.min_inliers = p->min_inliers; a.fix_scale = p->fix_scale;
+  a.thr = p->reproj_threshold; a.seed = p->seed;
+  a.qfx = p->q_fx; a.qfy = p->q_fy; a.tfx = p->t_fx; a.tfy = p->t_fy;
+  return a;
+}
+
+// the solver step behind the pair list
+static int sim3_launch(fpc_ctx* c, const Sim3Args& a, float* s, float* R, float* t, int32_t* ninliers, uint8_t* inlier,
+                       int mstride) {
+  hipLaunchKernelGGL(sim3_score_kernel, dim3((a.T + SIM3_THREADS - 1) / SIM3_THREADS, a.n), dim3(SIM3_THREADS), 0, c->stream, a);
+  hipLaunchKernelGGL(sim3_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, s, R, t, ninliers, inlier, mstride);
+  return launched();
+}
+
+// fpc_sim3_frames / fpc_sim3_bank: the gather kernel over either train set, then the solver
+static int sim3_gather(fpc_ctx* c, int n, const float* q_xyz, const uint8_t* q_valid, const PnpTrain& tr, const int32_t* match,
+                       const fpc_sim3_params* p, float* s, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const Sim3Args a = sim3_args(c, n, p);
+  hipLaunchKernelGGL(sim3_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, q_xyz, q_valid, c->count, match, inlier, tr);
+  return sim3_launch(c, a, s, R, t, ninliers, inlier, c->cap);
+}
+
+int fpc_ransac_sim3(fpc_ctx* c, int n, const float* q_xyz, const float* t_xyz, const int32_t* npairs, int stride,
+                    const fpc_sim3_params* p, float* s, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->pnp_slab || !q_xyz || !t_xyz || !npairs || !s || !R || !t || !ninliers || !sim3_params_ok(p) ||
+      !explicit_ok(c, n, stride))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const Sim3Args a = sim3_args(c, n, p);
+  hipLaunchKernelGGL(sim3_pack_kernel, dim3((stride + 255) / 256, n), dim3(256), 0, c->stream, a, q_xyz, t_xyz, npairs, stride,
+                     inlier);
+  return sim3_launch(c, a, s, R, t, ninliers, inlier, stride);
+}
+
+int fpc_sim3_frames(fpc_ctx* c, int n, const float* q_xyz, const uint8_t* q_valid, const float* key_xyz, const uint8_t* key_valid,
+                    const int32_t* nkey, const int32_t* match, const fpc_sim3_params* p, float* s, float* R, float* t,
+                    int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->pnp_slab || !q_xyz || !key_xyz || !nkey || !match || !s || !R || !t || !ninliers || !sim3_params_ok(p) ||
+      !frames_ok(c, n))
+    return FPC_E_INVALID;
+  return sim3_gather(c, n, q_xyz, q_valid, PnpTrain{key_xyz, key_valid, nkey, nullptr, nullptr, nullptr, 0, 0}, match, p, s, R,
+                     t, ninliers, inlier);
+}
+
+int fpc_sim3_bank(fpc_ctx* c, int n, const float* q_xyz, const uint8_t* q_valid, const int32_t* slot, const int32_t* match,
+                  const fpc_sim3_params* p, float* s, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->pnp_slab || !q_xyz || !s || !R || !t || !ninliers || !sim3_params_ok(p) || !bank_ok(c, n, slot, match))
+    return FPC_E_INVALID;
+  // (without landmark storage lm is null: no frame has pairs)
+  return sim3_gather(c, n, q_xyz, q_valid,
+                     PnpTrain{nullptr, nullptr, nullptr, slot, c->lm_xyzw, c->bank.count, c->bank.rows, c->bank.slots}, match, p,
+                     s, R, t, ninliers, inlier);
 }
 
 // ---- top-K candidates of the bank, each verified by RANSAC (include/fpc.h; kernels in match_bank_topk.h) -------------------

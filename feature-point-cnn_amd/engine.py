@@ -552,13 +552,13 @@ class Engine:
     def _ransac_params(self, params):
         return self._params(_lib.FpcRansacParams, "fpc_default_ransac_params", self._RANSAC_FIELDS, "RANSAC", params)
 
-    def _explicit_pairs(self, a, b, npairs, width=2, text="src and dst must be [n,stride,2] and npairs [n]"):
-        """Explicit pairs on the device: a float32 [n,stride,2], b float32 [n,stride,width], npairs int32 [n] -> (n, the
+    def _explicit_pairs(self, a, b, npairs, width=2, text="src and dst must be [n,stride,2] and npairs [n]", first=2):
+        """Explicit pairs on the device: a float32 [n,stride,first], b float32 [n,stride,width], npairs int32 [n] -> (n, the
         calls' arguments (a, b, npairs, stride))."""
         a = torch.as_tensor(a).to(self.torch_device, torch.float32).contiguous()
         b = torch.as_tensor(b).to(self.torch_device, torch.float32).contiguous()
         npairs = torch.as_tensor(npairs).to(self.torch_device, torch.int32).contiguous()
-        if a.dim() != 3 or a.shape[2] != 2 or b.shape != (*a.shape[:2], width) or npairs.shape != (a.shape[0],):
+        if a.dim() != 3 or a.shape[2] != first or b.shape != (*a.shape[:2], width) or npairs.shape != (a.shape[0],):
             raise ValueError(text)
         return int(a.shape[0]), (a, b, npairs, int(a.shape[1]))
 
@@ -1023,6 +1023,74 @@ class Engine:
     def landmarks_bank(self, n, slot, match, R, t, K_query=None, K_train=None, **params):
         """landmarks_bank_async, then host arrays (xyz [n,cap,3], kind uint8 [n,cap], counts [n,2])."""
         return self._host(self.landmarks_bank_async(n, slot, match, R, t, K_query, K_train, **params))
+
+    # -- Sim(3) alignment between two frames' landmarks (fpc_ransac_sim3 / fpc_sim3_frames / fpc_sim3_bank) ---------------------
+    def _sim3_params(self, K_query, K_train, params):
+        return self._two_camera_params(_lib.FpcSim3Params, "fpc_default_sim3_params", self._RANSAC_FIELDS + ("fix_scale",),
+                                       "Sim(3)", K_query, K_train, params)
+
+    def _sim3_out(self, n, stride=None):
+        """Empty Sim(3) outputs (s float32 [n], R float32 [n,3,3], t float32 [n,3], ninliers int32 [n], mask uint8
+        [n,stride or cap])."""
+        rm, tv, ni, mask = self._pnp_out(n, stride)
+        return torch.empty((n,), dtype=torch.float32, device=self.torch_device), rm, tv, ni, mask
+
+    def _query_landmarks(self, n, q_xyz, q_valid):
+        """The frames' own landmarks -> (xyz float32 [n,cap,3], valid uint8 [n,cap] or None) on the device: xyz and kind of
+        landmarks_*_async, used as they are."""
+        cap = self.capacity
+        qx = torch.as_tensor(q_xyz).to(self.torch_device, torch.float32).contiguous()
+        if tuple(qx.shape) != (n, cap, 3):
+            raise ValueError("q_xyz must be [n,%d,3]" % cap)
+        qv = None
+        if q_valid is not None:
+            qv = self._dev_uint8(q_valid)
+            if tuple(qv.shape) != (n, cap):
+                raise ValueError("q_valid must be [n,%d]" % cap)
+        return qx, qv
+
+    def ransac_sim3_async(self, q_xyz, t_xyz, npairs, K_query=None, K_train=None, **params):
+        """fpc_ransac_sim3: q_xyz and t_xyz float32 [n,stride,3], the pairs' points in the query and the train camera's
+        frame, and npairs int32 [n] (device tensors or host arrays) -> device tensors (s float32 [n], R float32 [n,3,3] and
+        t float32 [n,3] with X_query = s R X_train + t, ninliers int32 [n], inlier bool [n,stride]); a failed frame is all
+        zeros.  K_query / K_train: 3 x 3 camera matrices or (fx, fy, cx, cy).  Parameters: the other fields of
+        fpc_sim3_params.  Needs pnp_reserve().  Does not synchronise."""
+        p = self._sim3_params(K_query, K_train, params)
+        n, pairs = self._explicit_pairs(q_xyz, t_xyz, npairs, 3, "q_xyz and t_xyz must be [n,stride,3] and npairs [n]", 3)
+        return self._solve("fpc_ransac_sim3", n, pairs, p, self._sim3_out(n, pairs[3]))
+
+    def ransac_sim3(self, q_xyz, t_xyz, npairs, K_query=None, K_train=None, **params):
+        """ransac_sim3_async, then host arrays (s [n], R [n,3,3], t [n,3], ninliers [n], inlier bool [n,stride])."""
+        return self._host(self.ransac_sim3_async(q_xyz, t_xyz, npairs, K_query, K_train, **params))
+
+    def sim3_frames_async(self, n, match, q_xyz, q_valid, key_xyz, key_valid=None, K_query=None, K_train=None, **params):
+        """fpc_sim3_frames: the pairs (q_xyz[f][i], key_xyz[match[f][i]]) of every frame of the last detect: q_xyz float32
+        [n,cap,3] and q_valid (bool / uint8 [n,cap], None: every row) the frames' own landmarks -- xyz and kind of
+        landmarks_*_async as they are --, `match` match_frames_async's table against the key frame whose landmarks are
+        key_xyz / key_valid as in pnp_frames_async -> device tensors (s [n], R [n,3,3], t [n,3], ninliers [n], inlier bool
+        [n,cap] by query row).  Does not synchronise."""
+        p = self._sim3_params(K_query, K_train, params)
+        qx, qv = self._query_landmarks(n, q_xyz, q_valid)
+        kx, kv, kc = self._key_landmarks(key_xyz, key_valid)
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        return self._solve("fpc_sim3_frames", n, (qx, qv, kx, kv, kc, match), p, self._sim3_out(n))
+
+    def sim3_frames(self, n, match, q_xyz, q_valid, key_xyz, key_valid=None, K_query=None, K_train=None, **params):
+        """sim3_frames_async, then host arrays (s [n], R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""
+        return self._host(self.sim3_frames_async(n, match, q_xyz, q_valid, key_xyz, key_valid, K_query, K_train, **params))
+
+    def sim3_bank_async(self, n, slot, match, q_xyz, q_valid=None, K_query=None, K_train=None, **params):
+        """fpc_sim3_bank: sim3_frames_async with frame f's train landmarks taken from bank slot slot[f] (int32 [n], device;
+        a loop candidate of match_bank_topk_async, say) and `match` the table against that slot, on a bank of either format;
+        a frame with slot -1, or a bank without landmarks, fails (zeros).  s is the ratio of the frame's scale to the
+        slot's: the drift between the two.  Does not synchronise."""
+        p, pairs = self._bank_pairs(n, slot, match, self._sim3_params, K_query, K_train, params)
+        qx, qv = self._query_landmarks(n, q_xyz, q_valid)
+        return self._solve("fpc_sim3_bank", n, (qx, qv, *pairs), p, self._sim3_out(n))
+
+    def sim3_bank(self, n, slot, match, q_xyz, q_valid=None, K_query=None, K_train=None, **params):
+        """sim3_bank_async, then host arrays (s [n], R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""
+        return self._host(self.sim3_bank_async(n, slot, match, q_xyz, q_valid, K_query, K_train, **params))
 
     # -- verified relocalisation: the k best slots per frame, each checked by RANSAC (fpc_*_bank_topk) ------------------
     def bank_topk_reserve(self, kmax):

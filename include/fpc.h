@@ -1149,6 +1149,110 @@ int fpc_landmarks_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32
                        const float* t_dev, const fpc_landmark_params* params, float* xyz_dev, uint8_t* kind_dev,
                        int32_t* counts_dev);
 
+/* --- Sim(3) alignment: RANSAC similarity between two frames' landmarks ----------------------------------------------------
+ * Every key frame carries landmarks in its own camera frame, at the scale it inherited from the key frame it was localised
+ * against.  A frame that HAS landmarks of its own (what fpc_landmarks_* wrote) and matches an old bank slot -- a loop
+ * candidate of fpc_match_bank_topk -- has 3-D <-> 3-D pairs, and the similarity between the two sets is the edge a pose graph
+ * or a map merge needs: R and t as fpc_pnp_bank gives them, and the ratio s of the two scales, the drift a monocular map
+ * accumulates (Horn 1987, scored by reprojection in both cameras).  fpc_ransac_sim3, fpc_sim3_frames and fpc_sim3_bank mirror
+ * fpc_ransac_pnp, fpc_pnp_frames and fpc_pnp_bank: explicit pairs, the frames of the last detect against one key set, and
+ * those frames against bank slots.  The rule below is pinned by planted scenes and by a float64 restatement
+ * (tests/test_sim3_ransac.py).
+ *  - Convention: X_query = s R X_train + t with det R = +1 and s > 0: the direction the PnP calls write, with the scale
+ *    added.  s_dev float32 [n], R_dev float32 [n][9] row-major, t_dev float32 [n][3].  With both sets at one scale this is the
+ *    PnP pose; with the train set stored at 1 / sigma of the query's scale it is (sigma, R, sigma t_pnp).
+ *  - Pairs.  Explicit: pair k < npairs[f] (clamped to [0, stride]) is (q_xyz[f][k], t_xyz[f][k]), both float32
+ *    [n][stride][3].  A pair with a non-finite coordinate on either side is still a pair, a record like any other; it can
+ *    never be an inlier (below).  Frames and bank: query row i < count[f] with 0 <= j = match[f][i] < the train count.
+ *    q_xyz_dev is float32 [n][capacity][3] and q_valid_dev uint8 [n][capacity] or NULL (every row): the xyz_dev and kind_dev of
+ *    a fpc_landmarks_* call, unchanged.  The train landmarks are the key's (key_xyz_dev float32 [nkey][3], key_valid_dev uint8
+ *    [nkey] or NULL, nkey_dev[0] clamped to the capacity) or bank slot slot[f]'s float4 rows.  The row is a pair iff BOTH
+ *    landmarks are valid by the rule of fpc_bank_store_landmarks: the flag is != 0 and the three coordinates are finite.
+ *    Pairs come in ascending i.  The slot rules, the clamping, a bank without a landmark reservation (no frame has pairs) and
+ *    the mask's indexing (uint8 [n][stride] by pair, or [n][capacity] by query row; may be NULL) are fpc_pnp_bank's.
+ *  - Workspace: the pair records are two float4 each, (Qx, Qy, Qz, Tx), (Ty, Tz, row, -): the size and shape of the PnP
+ *    records, so the calls use the fpc_pnp_reserve reservation for records, counts and best keys.  They allocate nothing and
+ *    carve nothing; the plan hash, the packed size, the guard zones and the bank's allocations stay what they are.  A Sim(3)
+ *    call overwrites the PnP pair list and the other way round; both are stream-ordered and each call packs its own list
+ *    first, so neither sees the other's.
+ *  - Inliers: the rule of the RETURNED model, in fp64 from the fp32 s, R, t.  With Q the query point and T the train point,
+ *    Y = s R T + t and T' = R^T (Q - t) / s.  The pair is an inlier iff every coordinate of Q, T, Y and T' is finite,
+ *    Yz > 0, Qz > 0, T'z > 0 and Tz > 0, and
+ *        (q_fx (Yx Qz - Qx Yz))^2 + (q_fy (Yy Qz - Qy Yz))^2 < thr^2 Yz^2 Qz^2
+ *        (t_fx (T'x Tz - Tx T'z))^2 + (t_fy (T'y Tz - Ty T'z))^2 < thr^2 T'z^2 Tz^2.
+ *    The first asks that the transferred train point and the query's own point project within thr pixels of each other in the
+ *    query camera, the second is the same test in the train camera.  No division by a depth, and in pixels: the test does not
+ *    depend on either set's scale.  The principal points cancel; they stay in the struct for symmetry and are checked finite.
+ *  - Sampling: mix() as above with a budget of 16 draws: r = mix(seed ^ mix((f * 4096 + t) * 16 + k)) % M; the first 3
+ *    distinct indices are the sample, in that order; a hypothesis that has not found 3 within its 16 draws is degenerate.
+ *  - Minimal solve, three pairs, fp64, closed form.  On each side the triad of (p0, p1, p2): d1 = p1 - p0, d2 = p2 - p0,
+ *    x = d1 / |d1|, c = d1 x d2, z = c / |c|, y = z x x.  The sample is degenerate when c.c is not > 1e-12 |d1|^2 |d2|^2 on
+ *    either side, or when anything is not finite.  R = [x y z]_query [x y z]_train^T (columns x, y, z).  With Qm, Tm the means
+ *    of the three points, s = sqrt(sum |Q_i - Qm|^2 / sum |T_i - Tm|^2) (fix_scale: s = 1) and t = Qm - s R Tm.
+ *  - Scoring: the hypothesis is rounded to fp32 as 24 values, A = s R, t, B = R^T / s and u = -R^T t / s (formed in fp64; a
+ *    value that is not finite in fp32 makes the hypothesis degenerate).  Hypothesis t counts the pairs with, in fp32 (fmaf,
+ *    the products added in the order x, y, z onto the translation), Y = A T + t, W = B Q + u, and both of
+ *        Yz > 0, Qz > 0, (q_fx fmaf(Yx, Qz, -(Qx Yz)))^2 + (q_fy fmaf(Yy, Qz, -(Qy Yz)))^2 < (thr (Yz Qz))^2
+ *        Wz > 0, Tz > 0, (t_fx fmaf(Wx, Tz, -(Tx Wz)))^2 + (t_fy fmaf(Wy, Tz, -(Ty Wz)))^2 < (thr (Wz Tz))^2
+ *    where e_x^2 + e_y^2 is fmaf(e_x, e_x, e_y e_y).  Selection: the largest count; ties go to the lower t.
+ *  - The best sample's model is its s, R, t rounded to fp32.  Refit, `refits` times, in fp64 (Horn's closed form): over the
+ *    inliers of the current fp32 model, a first pass gives their number n and the centroids Qm, Tm; a second pass gives
+ *    S = sum a b^T (9 sums), sum |a|^2 and sum |b|^2 with a = T - Tm, b = Q - Qm, accumulated in a fixed order (no
+ *    floating-point atomics).  With S's entries named Sxx .. Szz (row: a's component, column: b's) the symmetric matrix
+ *        N = [Sxx+Syy+Szz  Syz-Szy       Szx-Sxz       Sxy-Syx    ]
+ *            [             Sxx-Syy-Szz   Sxy+Syx       Szx+Sxz    ]
+ *            [                          -Sxx+Syy-Szz   Syz+Szy    ]
+ *            [                                        -Sxx-Syy+Szz]
+ *    is diagonalised by the cyclic Jacobi of the fundamental section at N = 4; the eigenvector of the largest eigenvalue
+ *    lambda0 (ties: the lowest index), normalised, is the unit quaternion (w, x, y, z), and
+ *        R = [w^2+x^2-y^2-z^2  2(xy-wz)         2(xz+wy)        ]
+ *            [2(xy+wz)         w^2-x^2+y^2-z^2  2(yz-wx)        ]
+ *            [2(xz-wy)         2(yz+wx)         w^2-x^2-y^2+z^2 ],
+ *    s = sqrt(sum |b|^2 / sum |a|^2) (fix_scale: 1), t = Qm - s R Tm; all rounded to fp32.  The sums are unweighted.  The
+ *    refit is singular with n < 3, with sum |a|^2 or sum |b|^2 not > 0, with lambda0 - lambda1 not > 1e-12 sqrt(sum |a|^2
+ *    sum |b|^2) (lambda1 the second largest: collinear inliers leave the rotation about their line free), or with a result
+ *    that is not finite or an s that is not > 0 in fp32.  A singular refit keeps the model and ends the refits.
+ *    A refit that returns the model it started from, value for value, also ends the refits: the same model has the same
+ *    inliers and the same sums, so every further refit would return it again -- the result is that of all `refits` refits.
+ *    MONOTONE GUARD: the refitted model replaces the current one only if its inlier count is not below the current model's;
+ *    otherwise the current model stays and the refits end.  (A least-squares fit over inliers of noisy 3-D points can lose
+ *    pairs the best sample had; the guard makes the returned count a maximum over the models visited.)
+ *  - Failure: a frame with fewer than 3 pairs, with no non-degenerate sample, or with fewer than min_inliers inliers after the
+ *    last refit gets s = 0, nine zeros, three zeros, ninliers = 0 and an all-zero mask.
+ *  - Determinism, execution: as for the PnP calls.  The three entry points give bit-identical outputs on equal pair lists,
+ *    and fpc_sim3_bank is bit-identical to fpc_sim3_frames with that slot's landmarks at the SAME frame index.  Asynchronous
+ *    on the ctx stream: no host synchronisation, no device-to-host copy, no allocation; every count and slot is read on the
+ *    device.  They work on a FPC_BANK_BF16 bank: they read counts and landmarks only.  fpc_detect, fpc_match_bank,
+ *    fpc_pnp_bank, fpc_landmarks_bank (the frame's own landmarks), fpc_match_bank against the loop candidate, fpc_sim3_bank
+ *    needs no host call in between.
+ * FPC_E_INVALID (nothing is written): everything the PnP twins refuse for the arguments they share (n, stride, npairs_dev,
+ * match_dev, no PnP reservation); NULL params, q_xyz_dev, s_dev, R_dev, t_dev or ninliers_dev; fpc_ransac_sim3: a NULL
+ * t_xyz_dev; a focal length that is not > 0 or a non-finite intrinsic on either side; iterations outside 1 .. 4096;
+ * reproj_threshold not > 0 (or not below 1e18); refits outside 0 .. 4; min_inliers < 3; fix_scale not 0 or 1;
+ * fpc_sim3_frames: a NULL key_xyz_dev or nkey_dev; fpc_sim3_bank: no bank or a NULL slot_dev. */
+typedef struct fpc_sim3_params {
+  float q_fx, q_fy, q_cx, q_cy;   /* camera of the query side, pixels, fx, fy > 0                                         */
+  float t_fx, t_fy, t_cx, t_cy;   /* camera of the train side                                                             */
+  int iterations;                 /* 1 .. 4096                                                                            */
+  float reproj_threshold;         /* px, > 0, below 1e18                                                                  */
+  uint32_t seed;
+  int refits;                     /* 0 .. 4 Horn refits on the inlier set                                                 */
+  int min_inliers;                /* >= 3                                                                                 */
+  int fix_scale;                  /* 0: estimate s;  1: s = 1 (rigid alignment, two sets at one scale)                    */
+} fpc_sim3_params;
+/* fx = fy = 500, centre (320, 240) on both sides, 1024 iterations, 3.0 px, seed 0, 4 refits, 12 inliers, fix_scale 0 */
+int fpc_default_sim3_params(fpc_sim3_params* params);
+int fpc_ransac_sim3(fpc_ctx* ctx, int n, const float* q_xyz_dev, const float* t_xyz_dev, const int32_t* npairs_dev, int stride,
+                    const fpc_sim3_params* params, float* s_dev, float* R_dev, float* t_dev, int32_t* ninliers_dev,
+                    uint8_t* inlier_dev);
+int fpc_sim3_frames(fpc_ctx* ctx, int n, const float* q_xyz_dev, const uint8_t* q_valid_dev, const float* key_xyz_dev,
+                    const uint8_t* key_valid_dev, const int32_t* nkey_dev, const int32_t* match_dev,
+                    const fpc_sim3_params* params, float* s_dev, float* R_dev, float* t_dev, int32_t* ninliers_dev,
+                    uint8_t* inlier_dev);
+int fpc_sim3_bank(fpc_ctx* ctx, int n, const float* q_xyz_dev, const uint8_t* q_valid_dev, const int32_t* slot_dev,
+                  const int32_t* match_dev, const fpc_sim3_params* params, float* s_dev, float* R_dev, float* t_dev,
+                  int32_t* ninliers_dev, uint8_t* inlier_dev);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
