@@ -375,11 +375,27 @@ static const WKindInfo g_wkinds[WK_COUNT] = {
 #undef X
 };
 
-// blob floats of a generation-2 / generation-3 kernel's conv1 fragments: [channel group][chunk of 16][position][64 lanes]
-// float4 + zero positions behind every group (the fragment rings read ahead)
+// ---- blob floats of every fragment layout: one function each, shared by the plan builder that reserves the region and
+// the packer that fills it
+// pack_conv (weights.h): `steps` K steps of 8 channels for `nbt` blocks of 32 output channels, and the two zero steps the
+// kernels prefetch
+static size_t conv_floats(size_t steps, int nbt) { return (steps + 2) * nbt * 64 * 4; }
+// pack_conv_bf16: steps of 16 channels, `planes` terms per element
+static size_t conv_bf16_floats(size_t steps, int nbt, int planes) { return (steps + 2) * planes * nbt * 64 * 4; }
+static size_t bias_floats(int nbt) { return (size_t)nbt * 32; }
+// a Winograd kernel's conv1 fragments.  Generations 2, 3: [channel group][chunk of 16][position][64 lanes] float4 + zero
+// positions behind every group (the fragment rings read ahead); generation 1: pack_conv's order with 16 positions for
+// taps, and a chunk of zeros
 static size_t w1_floats(const WKindInfo& k, int nchunk) {
   if (k.gen == 3) return (size_t)k.NCG * ((size_t)nchunk * 36 + (k.NCG == 8 ? W36Cfg<2, 4, 4>::WPAD : W36Cfg<1, 4, 4>::WPAD)) * 256;
-  return (size_t)k.NCG * ((size_t)nchunk * 16 + W16Cfg<8>::WPAD) * 256;
+  if (k.gen == 2) return (size_t)k.NCG * ((size_t)nchunk * 16 + W16Cfg<8>::WPAD) * 256;
+  return conv_floats(((size_t)nchunk + 1) * 16 * (k.KC / 8), k.NBT);
+}
+// ... and its 1x1 stage's, over `k8` steps of 8 channels of [h | x]: [channel group][step of 16][lane] float4 (pack_w16_1x1),
+// generation 1: pack_conv's
+static size_t w2_floats(const WKindInfo& k, int k8) {
+  if (k.gen >= 2) return (size_t)k.NCG * ((size_t)k8 / 2 + W16Cfg<8>::WPAD) * 256;
+  return conv_floats(k8, k.NBT);
 }
 // MFMA FLOPs one frame's tiles issue: positions x Winograd tiles x channels x K for the 3x3, pixels x channels x K for the 1x1
 static double wkind_mfma_flops(const WKindInfo& k, int tiles, int nchunk, int k8_1x1) {
@@ -523,7 +539,7 @@ struct Op {
   BlockBfArgs fargs{};
   int phase = -1;              // ConvTranspose output-parity phase of a bf16 conv-only op
   int when = 0;                // 0: always; 1: only in calls of a few frames; 2: only in larger calls
-  bool shadow = false;         // packed like any op but never launched: the second half of a merged two-half launch (see add_wconv)
+  bool shadow = false;         // packed like any op but never launched: part 1 .. G - 1 of a conv-only launch of G parts (add_wconv merges them into part 0's op)
   bool wconv = false;          // conv-only Winograd launch: 3x3 conv + (BN or bias) + ReLU, output channels n0 .. n0+127
   int n0 = 0;
   bool plain_conv = false;     // a Conv2d + bias (+ ReLU) of the C++ network: weights `prefix`.weight / .bias, no BN
@@ -540,6 +556,12 @@ struct Op {
   bool fused_softmax_capable = false;   // FPC_BF16's detector.layer.1 (block_bf16.h: fused exp-softmax epilogue)
   double bytes_per_frame = 0;       // algorithmic HBM bytes: the launch's input tensor(s) read once + its output written once
   bool descriptor_branch = false;
+};
+
+// `len` floats of the packed blob from float `off`: what a plan builder reserved for one fragment or bias vector (reserve);
+// the packers write no more into it (Packer).  plan_hash mixes the offsets alone.
+struct Region {
+  size_t off = 0, len = 0;
 };
 
 struct Timing {
@@ -687,7 +709,7 @@ struct fpc_ctx {
   StemArgs stem{};
   size_t stem_w_off = 0, stem_b_off = 0;
   struct ConvW {
-    size_t w_off[4] = {0, 0, 0, 0}, b_off = 0, b2_off = 0;
+    Region w[4], b, b2;   // fragments (OP_CONV: one per grid z; blocks: conv1, the 1x1 stage, the dust block), biases
   };
   std::vector<ConvW> convw;  // parallel to ops (unused entries for non-conv ops)
 
@@ -849,7 +871,7 @@ static Op& push_op(fpc_ctx* c, OpType type, const std::string& name) {
 }
 
 // The end of either network's plan: the post-processing ops, the blob, and every op's weight pointers into it.
-// (A conv-only Winograd or split-operand op has no second stage: its w_off[1] and b2_off are 0, so w2 / b2 point at the
+// (A conv-only Winograd or split-operand op has no second stage: its w[1] and b2 are empty at offset 0, so w2 / b2 point at the
 // blob's tag, in bounds, and the kernels do not read them under conv_only.)
 static int finish_plan(fpc_ctx* c, size_t blob_floats) {
   push_op(c, OP_NMS, "nms+sort+border_crop");
@@ -862,12 +884,12 @@ static int finish_plan(fpc_ctx* c, size_t blob_floats) {
   for (size_t i = 0; i < c->ops.size(); ++i) {
     Op& op = c->ops[i];
     const fpc_ctx::ConvW& cw = c->convw[i];
-    const float *w1 = c->blob + cw.w_off[0], *w2 = c->blob + cw.w_off[1], *b1 = c->blob + cw.b_off, *b2 = c->blob + cw.b2_off;
+    const float *w1 = c->blob + cw.w[0].off, *w2 = c->blob + cw.w[1].off, *b1 = c->blob + cw.b.off, *b2 = c->blob + cw.b2.off;
     switch (op.type) {
       case OP_WBLOCK:
         op.wargs.w1 = reinterpret_cast<const float4*>(w1); op.wargs.b1 = b1;
         op.wargs.w2 = reinterpret_cast<const float4*>(w2); op.wargs.b2 = b2;
-        op.wargs.dust = g_wkinds[op.wkind].dust ? c->blob + cw.w_off[2] : nullptr;
+        op.wargs.dust = g_wkinds[op.wkind].dust ? c->blob + cw.w[2].off : nullptr;
         break;
       case OP_BF16:
         op.fargs.w1 = reinterpret_cast<const uint4*>(w1); op.fargs.b1 = b1;
@@ -879,7 +901,7 @@ static int finish_plan(fpc_ctx* c, size_t blob_floats) {
         break;
       case OP_CONV:
         for (int z = 0; z < op.grid_z; ++z)
-          op.args.sub[z].wfrag = reinterpret_cast<const float4*>(c->blob + cw.w_off[z]);
+          op.args.sub[z].wfrag = reinterpret_cast<const float4*>(c->blob + cw.w[z].off);
         op.args.bias = b1;
         break;
       default:
@@ -889,11 +911,46 @@ static int finish_plan(fpc_ctx* c, size_t blob_floats) {
   return FPC_OK;
 }
 
+// The next `n` floats of the blob become region `r`
+static void reserve(size_t* blob_off, Region& r, size_t n) {
+  r = {*blob_off, n};
+  *blob_off += n;
+}
+// An op with weights: what the packers and the reports read of it, whichever kernel family runs it
+static Op weight_op(OpType type, const std::string& name, const std::string& prefix, int cin, int cout, bool desc_branch) {
+  Op op;
+  op.type = type; op.name = name; op.prefix = prefix;
+  op.cin = cin; op.cout = cout; op.descriptor_branch = desc_branch;
+  return op;
+}
+static void push_op(fpc_ctx* c, const Op& op, const fpc_ctx::ConvW& cw) {
+  c->ops.push_back(op);
+  c->convw.push_back(cw);
+}
+// A layer's two variants: the ops from `i0` on run only in calls of a few frames (when = 1) or only in larger calls (2)
+static void mark_when(fpc_ctx* c, size_t i0, int when) {
+  for (size_t k = i0; k < c->ops.size(); ++k) c->ops[k].when = when;
+}
+static unsigned x_bytes(const fpc_ctx* c, int H, int W, int csx, int elem) {
+  return (unsigned)std::min<size_t>((size_t)c->B * H * W * csx * elem, 0xffffff00u);
+}
+
+// ConvTranspose2d(k3, s2, p1, op1) as four output-parity phases over the INPUT grid: the taps of phase `ph` = 2 py + px in
+// the order the plan lays them out and the packers fill them -- input pixel (dy, dx) of the halo under weight (ky, kx)
+struct ConvTTap { int dy, dx, ky, kx; };
+static std::vector<ConvTTap> convt_phase_taps(int ph) {
+  const int py = ph >> 1, px = ph & 1;
+  std::vector<ConvTTap> taps;
+  for (int iy = 0; iy < (py ? 2 : 1); ++iy)
+    for (int ix = 0; ix < (px ? 2 : 1); ++ix)   // py=1: (dy=1,ky=0), (dy=0,ky=2)
+      taps.push_back({py ? 1 - iy : 0, px ? 1 - ix : 0, py ? (iy == 0 ? 0 : 2) : 1, px ? (ix == 0 ? 0 : 2) : 1});
+  return taps;
+}
+
 struct ConvSpec {
   std::string name;
   Kind kind;
   int ksize;             // 3, 1, or 2 (= ConvTranspose phase set)
-  int stride;
   const float* in0;      // source 0
   int cs0, cin0, cin0_pad, H0, W0;
   const float* in1 = nullptr;  // optional second K source (1x1)
@@ -925,25 +982,11 @@ static void add_conv(fpc_ctx* c, const ConvSpec& s, size_t* blob_off) {
   const int N = k.WN * k.NB * 32;
   const int nbt = (s.cout + N - 1) / N * (N / 32);
   op.grid_y = nbt * 32 / N;
-  a.in0 = s.in0;
-  a.cs0 = s.cs0;
-  a.nchunk0 = s.cin0_pad / k.KC;
-  a.in1 = s.in1;
-  a.cs1 = s.cs1;
-  a.nchunk1 = s.in1 ? s.cin1_pad / k.KC : 0;
-  a.s1 = s.s1;
-  a.H1 = s.H1;
-  a.W1 = s.W1;
-  a.H = s.H0;
-  a.W = s.W0;
+  a.in0 = s.in0; a.cs0 = s.cs0; a.nchunk0 = s.cin0_pad / k.KC; a.H = s.H0; a.W = s.W0;
+  a.in1 = s.in1; a.cs1 = s.cs1; a.nchunk1 = s.in1 ? s.cin1_pad / k.KC : 0; a.s1 = s.s1; a.H1 = s.H1; a.W1 = s.W1;
   a.pad = s.ksize == 3 ? 1 : 0;
-  a.res = s.res;
-  a.csr = s.csr;
-  a.out = s.out;
-  a.cso = s.cso;
-  a.nstore = s.nstore;
-  a.relu = s.relu;
-  a.nbt = nbt;
+  a.res = s.res; a.csr = s.csr;
+  a.out = s.out; a.cso = s.cso; a.nstore = s.nstore; a.relu = s.relu; a.nbt = nbt;
   const int HWp = (k.TW - 1) * k.S + k.EXT, ROW4 = k.KC / 4 + 1;
   fpc_ctx::ConvW cw;
   const int K8 = k.KC / 8;
@@ -956,18 +999,12 @@ static void add_conv(fpc_ctx* c, const ConvSpec& s, size_t* blob_off) {
     a.oys = a.oxs = 2;
     double macs = 0;
     for (int ph = 0; ph < 4; ++ph) {
-      const int py = ph >> 1, px = ph & 1;
       ConvSub& sp = a.sub[ph];
-      sp.oy0 = py;
-      sp.ox0 = px;
+      sp.oy0 = ph >> 1;
+      sp.ox0 = ph & 1;
       sp.ntaps = 0;
-      for (int iy = 0; iy < (py ? 2 : 1); ++iy)
-        for (int ix = 0; ix < (px ? 2 : 1); ++ix) {
-          const int dy = py ? 1 - iy : 0, dx = px ? 1 - ix : 0;  // py=1: (dy=1,ky=0), (dy=0,ky=2)
-          sp.tapoff4[sp.ntaps++] = (dy * HWp + dx) * ROW4;
-        }
-      cw.w_off[ph] = *blob_off;
-      *blob_off += ((size_t)a.nchunk0 * sp.ntaps * K8 + 2) * nbt * 64 * 4;
+      for (const ConvTTap& t : convt_phase_taps(ph)) sp.tapoff4[sp.ntaps++] = (t.dy * HWp + t.dx) * ROW4;
+      reserve(blob_off, cw.w[ph], conv_floats((size_t)a.nchunk0 * sp.ntaps * K8, nbt));
       macs += (double)sp.ntaps;
     }
     op.flops_per_frame = 2.0 * macs * s.H0 * s.W0 * s.cin0 * s.cout;
@@ -981,22 +1018,19 @@ static void add_conv(fpc_ctx* c, const ConvSpec& s, size_t* blob_off) {
     sp.ntaps = s.ksize * s.ksize;
     for (int ky = 0; ky < s.ksize; ++ky)
       for (int kx = 0; kx < s.ksize; ++kx) sp.tapoff4[ky * s.ksize + kx] = (ky * HWp + kx) * ROW4;
-    cw.w_off[0] = *blob_off;
-    *blob_off += ((size_t)(a.nchunk0 * sp.ntaps + a.nchunk1) * K8 + 2) * nbt * 64 * 4;
+    reserve(blob_off, cw.w[0], conv_floats((size_t)(a.nchunk0 * sp.ntaps + a.nchunk1) * K8, nbt));
     op.flops_per_frame = 2.0 * s.Ho * s.Wo * s.cout * ((double)s.cin0 * sp.ntaps + s.cin1);
     op.mfma_flops_per_frame = 2.0 * ((s.Ho + k.TH - 1) / k.TH) * ((s.Wo + k.TW - 1) / k.TW) * (k.WM * k.MB * 32.0) * (nbt * 32.0) *
                               ((double)a.nchunk0 * k.KC * sp.ntaps + (double)a.nchunk1 * k.KC);
   }
-  cw.b_off = *blob_off;
-  *blob_off += (size_t)nbt * 32;
+  reserve(blob_off, cw.b, bias_floats(nbt));
   // conv2_mfma_kernel: one K source, every workgroup stores all of its N channels as float4s
   op.lean = conv_is_lean(c, op);
   a.tiles_x = (a.Wo + k.TW - 1) / k.TW;
   a.tiles_y = (a.Ho + k.TH - 1) / k.TH;
   op.bytes_per_frame = 4.0 * ((double)s.cin0 * s.H0 * s.W0 + (s.in1 ? (double)s.cin1 * s.H1 * s.W1 : 0.0) +
                               (s.res ? (double)s.cout * s.Ho * s.Wo : 0.0) + (double)s.cout * s.Ho * s.Wo);
-  c->ops.push_back(op);
-  c->convw.push_back(cw);
+  push_op(c, op, cw);
 }
 
 struct BlockSpec {
@@ -1009,27 +1043,32 @@ struct BlockSpec {
   bool proj, desc_branch;
 };
 
+// A fused block on instance `kind`: the instance's halo taps, its tiles over the output, the MFMA work they issue
+static void tile_block(Op& o, BKind kind) {
+  const BKindInfo& k = g_bkinds[kind];
+  o.bkind = kind;
+  BlockArgs& a = o.bargs;
+  const int HWp = (k.TW - 1) * k.S + 3, ROW4 = k.KC / 4 + 1;
+  for (int ky = 0; ky < 3; ++ky)
+    for (int kx = 0; kx < 3; ++kx) a.tapoff4[ky * 3 + kx] = (ky * HWp + kx) * ROW4;
+  a.tiles_x = (a.Wo + k.TW - 1) / k.TW;
+  a.tiles_y = (a.Ho + k.TH - 1) / k.TH;
+  o.mfma_flops_per_frame = 2.0 * a.tiles_x * a.tiles_y * (k.WM * k.MB * 32.0) * (k.WN * k.NB * 32.0) *
+                           ((double)a.nchunk * k.KC * 9 + (a.k8_h + a.k8_x) * 8.0);
+}
+
 static void add_block(fpc_ctx* c, const BlockSpec& s, size_t* blob_off) {
   const BKindInfo& k = g_bkinds[s.kind];
-  Op op;
-  op.type = OP_BLOCK;
-  op.name = s.prefix + (s.proj ? " [conv1+bn1+relu+conv2+bn2+proj+relu]" : " [conv1+bn1+relu+conv2+bn2+identity+relu]");
-  op.prefix = s.prefix;
-  op.bkind = s.kind;
-  op.cin = s.cin;
-  op.cout = s.cout;
-  op.descriptor_branch = s.desc_branch;
+  Op op = weight_op(OP_BLOCK, s.prefix + (s.proj ? " [conv1+bn1+relu+conv2+bn2+proj+relu]" : " [conv1+bn1+relu+conv2+bn2+identity+relu]"),
+                    s.prefix, s.cin, s.cout, s.desc_branch);
   BlockArgs& a = op.bargs;
   const int nbt = k.WN * k.NB, K8 = k.KC / 8;
   a.x = s.x;
   a.csx = s.csx;
-  a.x_bytes = (unsigned)std::min<size_t>((size_t)c->B * s.H * s.W * s.csx * 4, 0xffffff00u);
+  a.x_bytes = x_bytes(c, s.H, s.W, s.csx, 4);
   a.nchunk = s.cin_pad / k.KC;
   a.H = s.H;
   a.W = s.W;
-  const int HWp = (k.TW - 1) * k.S + 3, ROW4 = k.KC / 4 + 1;
-  for (int ky = 0; ky < 3; ++ky)
-    for (int kx = 0; kx < 3; ++kx) a.tapoff4[ky * 3 + kx] = (ky * HWp + kx) * ROW4;
   a.k8_h = k.CMIDP / 8;
   a.k8_x = s.proj ? s.cin_pad / 8 : 0;   // the kernel walks the projection eight K steps at a time
   if (a.k8_x % 8) { fprintf(stderr, "fpc: fused block %s: projection over %d channels is not a multiple of 64\n", s.prefix.c_str(), s.cin_pad); abort(); }
@@ -1037,24 +1076,16 @@ static void add_block(fpc_ctx* c, const BlockSpec& s, size_t* blob_off) {
   a.cso = s.cso;
   a.Ho = s.H / k.S;
   a.Wo = s.W / k.S;
-  a.tiles_x = (a.Wo + k.TW - 1) / k.TW;
-  a.tiles_y = (a.Ho + k.TH - 1) / k.TH;
   a.nstore = s.cout_pad;
+  tile_block(op, s.kind);
   fpc_ctx::ConvW cw;
-  cw.w_off[0] = *blob_off;
-  *blob_off += ((size_t)a.nchunk * 9 * K8 + 2) * nbt * 64 * 4;
-  cw.b_off = *blob_off;
-  *blob_off += (size_t)nbt * 32;
-  cw.w_off[1] = *blob_off;
-  *blob_off += ((size_t)(a.k8_h + a.k8_x) + 2) * nbt * 64 * 4;
-  cw.b2_off = *blob_off;
-  *blob_off += (size_t)nbt * 32;
+  reserve(blob_off, cw.w[0], conv_floats((size_t)a.nchunk * 9 * K8, nbt));
+  reserve(blob_off, cw.b, bias_floats(nbt));
+  reserve(blob_off, cw.w[1], conv_floats(a.k8_h + a.k8_x, nbt));
+  reserve(blob_off, cw.b2, bias_floats(nbt));
   op.flops_per_frame = 2.0 * a.Ho * a.Wo * s.cout * ((double)s.cin * 9 + s.cout + (s.proj ? s.cin : 0));
-  op.mfma_flops_per_frame = 2.0 * a.tiles_x * a.tiles_y * (k.WM * k.MB * 32.0) * (nbt * 32.0) *
-                            ((double)a.nchunk * k.KC * 9 + (a.k8_h + a.k8_x) * 8.0);
   op.bytes_per_frame = 4.0 * ((double)s.cin * s.H * s.W + (double)s.cout * a.Ho * a.Wo);
-  c->ops.push_back(op);
-  c->convw.push_back(cw);
+  push_op(c, op, cw);
 }
 
 // The op just added moves to a finer tile (an instance that consumes the same fragments: same KC and channel blocking).
@@ -1065,16 +1096,7 @@ static void add_block(fpc_ctx* c, const BlockSpec& s, size_t* blob_off) {
 static void retile_block(fpc_ctx* c, BKind small) {
   const BKindInfo &k0 = g_bkinds[c->ops.back().bkind], &k = g_bkinds[small];
   if (k.KC != k0.KC || k.WN * k.NB != k0.WN * k0.NB || k.S != k0.S || k.CMIDP != k0.CMIDP) { c->plan_error = true; return; }
-  Op& o = c->ops.back();
-  o.bkind = small;
-  BlockArgs& a = o.bargs;
-  const int HWp = (k.TW - 1) * k.S + 3, ROW4 = k.KC / 4 + 1;
-  for (int ky = 0; ky < 3; ++ky)
-    for (int kx = 0; kx < 3; ++kx) a.tapoff4[ky * 3 + kx] = (ky * HWp + kx) * ROW4;
-  a.tiles_x = (a.Wo + k.TW - 1) / k.TW;
-  a.tiles_y = (a.Ho + k.TH - 1) / k.TH;
-  o.mfma_flops_per_frame = 2.0 * a.tiles_x * a.tiles_y * (k.WM * k.MB * 32.0) * (k.WN * k.NB * 32.0) *
-                           ((double)a.nchunk * k.KC * 9 + (a.k8_h + a.k8_x) * 8.0);
+  tile_block(c->ops.back(), small);
 }
 static void retile_last(fpc_ctx* c, BKind small) {
   if (!c->latency_tiles || c->ops.empty() || c->ops.back().type != OP_BLOCK) return;
@@ -1116,20 +1138,34 @@ static void retile_last(fpc_ctx* c, Kind small) {
   o.lean = conv_is_lean(c, o);
 }
 
+// A generation-2 128-channel Winograd op (all of its parts, where it is a conv-only launch of several) on the 4 x 16
+// latency tile, WK_W16_C128H -- the same fragments: the copy shares the op's regions
+static Op half_tile_copy(const Op& op) {
+  const WKindInfo& kh = g_wkinds[WK_W16_C128H];
+  Op oh = op;
+  WBlockArgs& a = oh.wargs;
+  oh.wkind = WK_W16_C128H;
+  a.tiles_y = (a.H + kh.TH - 1) / kh.TH;
+  oh.mfma_flops_per_frame = op.grid_y * wkind_mfma_flops(kh, a.tiles_x * a.tiles_y, a.nchunk, a.k8_h + a.k8_x);
+  return oh;
+}
+
+// What the fused and the conv-only Winograd ops share: the tensors, the map, instance `k`'s tiles over it
+static void fill_wargs(WBlockArgs& a, const WKindInfo& k, const float* x, int csx, int H, int W, float* out, int cso) {
+  a.x = x; a.csx = csx;
+  a.H = H; a.W = W;
+  a.out = out; a.cso = cso;
+  a.tiles_x = (W + k.TW - 1) / k.TW;
+  a.tiles_y = (H + k.TH - 1) / k.TH;
+}
+
 static void add_wblock(fpc_ctx* c, const BlockSpec& s, WKind wk, size_t* blob_off, bool small_only = false) {
   const WKindInfo& k = g_wkinds[wk];
-  Op op;
-  op.type = OP_WBLOCK;
-  op.name = s.prefix + (s.proj ? " [winograd conv1+bn1+relu+conv2+bn2+proj+relu]" : " [winograd conv1+bn1+relu+conv2+bn2+identity+relu]");
-  op.prefix = s.prefix;
+  Op op = weight_op(OP_WBLOCK, s.prefix + (s.proj ? " [winograd conv1+bn1+relu+conv2+bn2+proj+relu]" : " [winograd conv1+bn1+relu+conv2+bn2+identity+relu]"),
+                    s.prefix, s.cin, s.cout, s.desc_branch);
   op.wkind = wk;
-  op.cin = s.cin;
-  op.cout = s.cout;
-  op.descriptor_branch = s.desc_branch;
   WBlockArgs& a = op.wargs;
-  const int K8 = k.KC / 8;
-  a.x = s.x;
-  a.csx = s.csx;
+  fill_wargs(a, k, s.x, s.csx, s.H, s.W, s.out, s.cso);
   a.nchunk = s.cin_pad / k.KC;
   a.dust = nullptr;
   a.dust_in = 0;
@@ -1141,82 +1177,40 @@ static void add_wblock(fpc_ctx* c, const BlockSpec& s, WKind wk, size_t* blob_of
     a.dust_in = s.cin == 65;
     a.nchunk = a.dust_in ? 4 : s.cin_pad / 16;
   } else if (s.cin_pad % k.KC) { c->plan_error = true; return; }
-  a.H = s.H;
-  a.W = s.W;
   a.k8_h = k.CMID / 8;
   a.k8_x = s.proj ? s.cin_pad / 8 : 0;   // the kernel walks the projection four K steps at a time
   if (a.k8_x % 4) { fprintf(stderr, "fpc: winograd block %s: projection over %d channels is not a multiple of 32\n", s.prefix.c_str(), s.cin_pad); abort(); }
-  a.out = s.out;
-  a.cso = s.cso;
-  a.tiles_x = (s.W + k.TW - 1) / k.TW;
-  a.tiles_y = (s.H + k.TH - 1) / k.TH;
+  // generations 2, 3 take an even number of chunks of 16, four at least (wblock16_mfma.h, wblock36_mfma.h)
+  if (k.gen >= 2 && (a.nchunk < 4 || (a.nchunk & 1))) { c->plan_error = true; return; }
   fpc_ctx::ConvW cw;
-  cw.w_off[0] = *blob_off;
-  if (k.gen >= 2) {   // [channel group][chunk of 16][position][64 lanes] float4 + zero pad per group (wblock16_mfma.h, wblock36_mfma.h)
-    if (a.nchunk < 4 || (a.nchunk & 1)) { c->plan_error = true; return; }
-    *blob_off += w1_floats(k, a.nchunk);
-  } else {
-    *blob_off += ((size_t)a.nchunk * 16 * K8 + 16 * K8 + 2) * k.NBT * 64 * 4;
-  }
-  cw.b_off = *blob_off;
-  *blob_off += (size_t)k.NBT * 32;
-  cw.w_off[1] = *blob_off;
-  if (k.gen >= 2) *blob_off += (size_t)k.NCG * ((size_t)(a.k8_h + a.k8_x) / 2 + W16Cfg<8>::WPAD) * 256;
-  else *blob_off += ((size_t)(a.k8_h + a.k8_x) + 2) * k.NBT * 64 * 4;
-  cw.b2_off = *blob_off;
-  *blob_off += (size_t)k.NBT * 32;
-  if (k.dust) {
-    cw.w_off[2] = *blob_off;
-    *blob_off += (size_t)W36Dust::floats(a.nchunk);
-  }
+  reserve(blob_off, cw.w[0], w1_floats(k, a.nchunk));
+  reserve(blob_off, cw.b, bias_floats(k.NBT));
+  reserve(blob_off, cw.w[1], w2_floats(k, a.k8_h + a.k8_x));
+  reserve(blob_off, cw.b2, bias_floats(k.NBT));
+  if (k.dust) reserve(blob_off, cw.w[2], (size_t)W36Dust::floats(a.nchunk));
   op.flops_per_frame = 2.0 * s.H * s.W * s.cout * ((double)s.cin * 9 + s.cout + (s.proj ? s.cin : 0));
   // 16 (36) GEMMs over the tile's Winograd tiles instead of 9 taps over its pixels; then the 1x1 on its pixels
   op.mfma_flops_per_frame = wkind_mfma_flops(k, a.tiles_x * a.tiles_y, a.nchunk, a.k8_h + a.k8_x);
   if (k.dust && a.dust_in) op.mfma_flops_per_frame += 2.0 * a.tiles_x * a.tiles_y * 64.0 * 36 * 16 * 4;   // input channel 64: one K = 4 MFMA per position
   op.bytes_per_frame = 4.0 * ((double)s.cin * s.H * s.W + (double)s.cout * s.H * s.W);
-  if (k.dust) {
-    // calls of a few frames keep the round-1 instance (its own fragments), as the 64- / 128-channel layers keep generation 2
-    op.when = c->latency_tiles ? 2 : 0;
-    c->ops.push_back(op);
-    c->convw.push_back(cw);
-    if (c->latency_tiles) add_wblock(c, s, s.cin == 65 ? WK_W816_K24_C72 : WK_W816_K32_C72, blob_off, true);
-    return;
+  // What calls of a few frames run instead.  With fragments of its own (`own`, added by the call below with small_only):
+  // - the detector's generation-3 instances keep the round-1 instance, as the 64- / 128-channel layers keep generation 2;
+  // - generation 3's tile is 256 pixels: a frame has 20 of them at 60 x 80, and the latency of a single frame's layer is
+  //   one tile's time.  Calls of a few frames keep generation 2 (16 positions instead of 36), on its 4 x 16 latency
+  //   tiles where that instance exists.
+  // On the same fragments (`half`): generation 2's 128-channel layer on 4 x 16 tiles -- under small_only the caller's
+  // large-call op exists already, and only that instance is added.
+  WKind own = WK_COUNT;
+  if (c->latency_tiles && k.dust) own = s.cin == 65 ? WK_W816_K24_C72 : WK_W816_K32_C72;
+  else if (c->latency_tiles && k.gen == 3) own = s.cout == 64 ? WK_W16_C64 : WK_W16_C128;
+  const bool half = wk == WK_W16_C128 && (small_only || c->latency_tiles);
+  op.when = small_only ? 1 : (half || own != WK_COUNT) ? 2 : 0;
+  if (!(small_only && half)) push_op(c, op, cw);
+  if (half) {
+    push_op(c, half_tile_copy(op), cw);
+    c->ops.back().when = 1;
   }
-  if (k.gen == 3 && c->latency_tiles) {
-    // Generation 3's tile is 256 pixels: a frame has 20 of them at 60 x 80, and the latency of a single frame's layer is
-    // one tile's time.  Calls of a few frames keep generation 2 (its own fragments: 16 positions instead of 36), on its
-    // 4 x 16 latency tiles where that instance exists.
-    op.when = 2;
-    c->ops.push_back(op);
-    c->convw.push_back(cw);
-    add_wblock(c, s, s.cout == 64 ? WK_W16_C64 : WK_W16_C128, blob_off, true);
-    return;
-  }
-  if (small_only && wk == WK_W16_C128) {   // (the caller's large-call op exists already: only the 4 x 16 instance)
-    const WKindInfo& kh = g_wkinds[WK_W16_C128H];
-    op.when = 1;
-    op.wkind = WK_W16_C128H;
-    op.wargs.tiles_y = (s.H + kh.TH - 1) / kh.TH;
-    op.mfma_flops_per_frame = wkind_mfma_flops(kh, op.wargs.tiles_x * op.wargs.tiles_y, a.nchunk, a.k8_h + a.k8_x);
-    c->ops.push_back(op);
-    c->convw.push_back(cw);
-    return;
-  }
-  if (small_only) op.when = 1;
-  c->ops.push_back(op);
-  c->convw.push_back(cw);
-  if (wk == WK_W16_C128 && c->latency_tiles) {
-    // the same layer on 4 x 16 tiles for calls of a few frames (same fragments: the blob offsets are shared)
-    const WKindInfo& kh = g_wkinds[WK_W16_C128H];
-    c->ops.back().when = 2;
-    Op oh = c->ops.back();
-    oh.when = 1;
-    oh.wkind = WK_W16_C128H;
-    oh.wargs.tiles_y = (s.H + kh.TH - 1) / kh.TH;
-    oh.mfma_flops_per_frame = wkind_mfma_flops(kh, oh.wargs.tiles_x * oh.wargs.tiles_y, a.nchunk, a.k8_h + a.k8_x);
-    c->ops.push_back(oh);
-    c->convw.push_back(cw);
-  }
+  if (own != WK_COUNT) add_wblock(c, s, own, blob_off, true);
 }
 
 // A 3x3 stride-1 convolution + (folded BN | bias) + ReLU on the Winograd kernel in conv-only form.  Output channels
@@ -1225,42 +1219,23 @@ static void add_wblock(fpc_ctx* c, const BlockSpec& s, WKind wk, size_t* blob_of
 static void add_wconv(fpc_ctx* c, const std::string& prefix, bool bn, WKind wk, const float* x, int csx, int cin, int H,
                       int W, float* out, int cso, int cout, int n0, bool desc_branch, size_t* blob_off) {
   const WKindInfo& k = g_wkinds[wk];
-  Op op;
-  op.type = OP_WBLOCK;
-  op.name = prefix + (bn ? ".conv1+bn1+relu [winograd" : " [winograd conv+bias+relu") +
-            (cout > k.CMID ? ", channels " + std::to_string(n0) + ".." + std::to_string(n0 + k.CMID - 1) : std::string()) + "]";
-  op.prefix = prefix;
+  Op op = weight_op(OP_WBLOCK, prefix + (bn ? ".conv1+bn1+relu [winograd" : " [winograd conv+bias+relu") +
+                    (cout > k.CMID ? ", channels " + std::to_string(n0) + ".." + std::to_string(n0 + k.CMID - 1) : std::string()) + "]",
+                    prefix, cin, cout, desc_branch);
   op.wkind = wk;
   if (wk == WK_W36PC_C64_8x2) op.hash_wkind = w36_kind(64, H, W, true);   // the same fragments: plan_hash as FPC_PLAN_TILES_ROUND5's
   op.wconv = true;
   op.plain_conv = !bn;
   op.n0 = n0;
-  op.cin = cin;
-  op.cout = cout;
-  op.descriptor_branch = desc_branch;
   WBlockArgs& a = op.wargs;
-  const int K8 = k.KC / 8;
-  a.x = x;
-  a.csx = csx;
+  fill_wargs(a, k, x, csx, H, W, out + n0, cso);
   a.nchunk = cin / k.KC;
-  a.H = H;
-  a.W = W;
   a.k8_h = a.k8_x = 0;
   a.conv_only = 1;
-  a.out = out + n0;
-  a.cso = cso;
-  a.tiles_x = (W + k.TW - 1) / k.TW;
-  a.tiles_y = (H + k.TH - 1) / k.TH;
+  if (k.gen >= 2 && (a.nchunk < 4 || (a.nchunk & 1))) { c->plan_error = true; return; }
   fpc_ctx::ConvW cw;
-  cw.w_off[0] = *blob_off;
-  if (k.gen >= 2) {
-    if (a.nchunk < 4 || (a.nchunk & 1)) { c->plan_error = true; return; }
-    *blob_off += w1_floats(k, a.nchunk);
-  } else {
-    *blob_off += ((size_t)a.nchunk * 16 * K8 + 16 * K8 + 2) * k.NBT * 64 * 4;
-  }
-  cw.b_off = *blob_off;
-  *blob_off += (size_t)k.NBT * 32;
+  reserve(blob_off, cw.w[0], w1_floats(k, a.nchunk));
+  reserve(blob_off, cw.b, bias_floats(k.NBT));
   op.flops_per_frame = 2.0 * H * W * (double)k.CMID * cin * 9;
   op.mfma_flops_per_frame = wkind_mfma_flops(k, a.tiles_x * a.tiles_y, a.nchunk, 0);
   op.bytes_per_frame = 4.0 * ((double)cin * H * W + (double)std::min(k.CMID, cout - n0) * H * W);
@@ -1272,7 +1247,7 @@ static void add_wconv(fpc_ctx* c, const std::string& prefix, bool bn, WKind wk, 
     Op& first = c->ops[c->ops.size() - part];
     fpc_ctx::ConvW& cf = c->convw[c->convw.size() - part];
     if (first.wconv && first.prefix == prefix && first.n0 == 0 && first.wkind == wk && first.grid_y == part) {
-      const int ys = (int)((cw.w_off[0] - cf.w_off[0]) / part);
+      const int ys = (int)((cw.w[0].off - cf.w[0].off) / part);
       if (part == 1) first.wargs.ysplit_floats = ys;
       else if (first.wargs.ysplit_floats != ys) { c->plan_error = true; return; }
       first.grid_y = part + 1;
@@ -1284,8 +1259,87 @@ static void add_wconv(fpc_ctx* c, const std::string& prefix, bool bn, WKind wk, 
       op.shadow = true;
     }
   }
-  c->ops.push_back(op);
-  c->convw.push_back(cw);
+  push_op(c, op, cw);
+}
+
+// ---- the Python network, layer by layer -------------------------------------------------------
+// One row per ResNetBlock, and one for the up-sample: what the layer IS -- its checkpoint prefix, its tensors and their
+// channel strides, its real and padded channel counts, its input map and stride -- whatever runs it.  python_layers()
+// fills the rows from the context; which kernel instance runs a row is chosen per arithmetic by build_f32_ops,
+// build_bf16_ops and build_x3_ops, and by nothing else.
+enum LayerId { L_ENC10, L_ENC11, L_ENC20, L_ENC21, L_DET0, L_DET1, L_IN0, L_IN1, L_UP, L_OUT0, L_OUT1, L_COUNT };
+struct Layer {
+  const char* prefix;
+  float* x;              // input [.., csx]: cin channels, padded to cinp, on an H x W map (bf16 elements in FPC_BF16 mode,
+  int csx, cin, cinp;    // as every tensor here -- the strides count elements)
+  int H, W, stride;
+  float* h;              // conv1's output [.., csh], where the block runs as two launches (the fp32 plan)
+  int csh;
+  float* y;              // output [.., csy]: cout channels, padded to coutp
+  int csy, cout, coutp;
+  bool proj, desc;       // projection shortcut; descriptor branch (absent without descriptors)
+};
+
+static void python_layers(fpc_ctx* c, Layer* net) {
+  const int H4 = c->H / 4, W4 = c->W / 4, Hc = c->H / 8, Wc = c->W / 8, H16 = c->H / 16, W16 = c->W / 16;
+  // encoder output lives in channels 128..255 of `cat`; the detector's 65 channels are padded to the logits' stride
+  float* feat = c->bf16 ? reinterpret_cast<float*>(reinterpret_cast<bf16_t*>(c->cat) + 128) : c->cat + 128;
+  const int dc = c->lgcs;
+  net[L_ENC10] = {"encoder.layer1.0", c->x0, 64, 64, 64, H4, W4, 1, c->h4, 64, c->x1, 64, 64, 64, true, false};
+  net[L_ENC11] = {"encoder.layer1.1", c->x1, 64, 64, 64, H4, W4, 1, c->h4, 64, c->x2, 64, 64, 64, false, false};
+  net[L_ENC20] = {"encoder.layer2.0", c->x2, 64, 64, 64, H4, W4, 2, c->h8, 128, c->x3, 128, 128, 128, true, false};
+  net[L_ENC21] = {"encoder.layer2.1", c->x3, 128, 128, 128, Hc, Wc, 1, c->h8, 128, feat, 256, 128, 128, false, false};
+  net[L_DET0] = {"detector.layer.0", feat, 256, 128, 128, Hc, Wc, 1, c->dh, 72, c->d0, dc, 65, dc, true, false};
+  net[L_DET1] = {"detector.layer.1", c->d0, dc, 65, dc, Hc, Wc, 1, c->dh, 72, c->lg, dc, 65, dc, false, false};
+  net[L_IN0] = {"descriptor.layer_in.0", feat, 256, 128, 128, Hc, Wc, 2, c->h16, 256, c->y16a, 256, 256, 256, true, true};
+  net[L_IN1] = {"descriptor.layer_in.1", c->y16a, 256, 256, 256, H16, W16, 1, c->h16, 256, c->y16b, 256, 256, 256, false, true};
+  // ConvTranspose2d(k3, s2, p1, op1) + bn + relu: the H16 x W16 map doubles into channels 0..127 of `cat`
+  net[L_UP] = {"descriptor.up_sample", c->y16b, 256, 256, 256, H16, W16, 1, nullptr, 0, c->cat, 256, 128, 128, false, true};
+  net[L_OUT0] = {"descriptor.layer_out.0", c->cat, 256, 256, 256, Hc, Wc, 1, c->lo_h, 128, c->lo0, 128, 128, 128, true, true};
+  net[L_OUT1] = {"descriptor.layer_out.1", c->lo0, 128, 128, 128, Hc, Wc, 1, c->lo_h, 128, c->desc_map, 128, 128, 128, false, true};
+}
+static int layer_count(const fpc_ctx* c) { return c->cfg.descriptor_enabled ? (int)L_COUNT : (int)L_IN0; }
+
+static BlockSpec block_spec(const Layer& L, BKind kind) {
+  return {L.prefix, kind, L.x, L.csx, L.cin, L.cinp, L.H, L.W, L.y, L.csy, L.cout, L.coutp, L.proj, L.desc};
+}
+// One OP_CONV of `L`: `cin` channels (padded to `cinp`) of `in` on an H x W map -> L's output channels in `out`
+static ConvSpec conv_spec(const Layer& L, const char* role, Kind kind, int ksize, const float* in, int cs,
+                          int cin, int cinp, int H, int W, float* out, int cso, int Ho, int Wo, int relu) {
+  ConvSpec s{};
+  s.name = std::string(L.prefix) + role;
+  s.kind = kind; s.ksize = ksize;
+  s.in0 = in; s.cs0 = cs; s.cin0 = cin; s.cin0_pad = cinp; s.H0 = H; s.W0 = W;
+  s.out = out; s.cso = cso; s.cout = L.cout; s.nstore = L.coutp; s.Ho = Ho; s.Wo = Wo; s.relu = relu;
+  s.desc_branch = L.desc;
+  return s;
+}
+// a block's first half, conv1 + bn1 + relu: x -> h
+static ConvSpec conv1_spec(const Layer& L, Kind kind) {
+  return conv_spec(L, ".conv1+bn1+relu", kind, 3, L.x, L.csx, L.cin, L.cinp, L.H, L.W, L.h, L.csh, L.H / L.stride, L.W / L.stride, 1);
+}
+// ... its second half, conv2 + bn2 + shortcut + relu: h -> y, the projection over x as a second K source or x as the
+// residual -- or `shortcut`, a projection computed apart (laid out as h), as the residual
+static ConvSpec conv2_spec(const Layer& L, Kind kind, const float* shortcut = nullptr) {
+  const int Ho = L.H / L.stride, Wo = L.W / L.stride;
+  ConvSpec t = conv_spec(L, shortcut ? ".conv2+bn2+shortcut+relu" : L.proj ? ".conv2+bn2+proj+relu" : ".conv2+bn2+identity+relu", kind, 1,
+                         L.h, L.csh, L.cout, L.coutp, Ho, Wo, L.y, L.csy, Ho, Wo, 1);
+  if (shortcut) {
+    t.res = shortcut; t.csr = L.csh;
+  } else if (L.proj) {
+    t.in1 = L.x; t.cs1 = L.csx; t.cin1 = L.cin; t.cin1_pad = L.cinp; t.s1 = L.stride; t.H1 = L.H; t.W1 = L.W;
+  } else {
+    t.res = L.x; t.csr = L.csx;
+  }
+  return t;
+}
+// ... its projection shortcut as a launch of its own: x -> out, laid out as h
+static ConvSpec shortcut_spec(const Layer& L, Kind kind, float* out) {
+  return conv_spec(L, ".identity_downsample", kind, 1, L.x, L.csx, L.cin, L.cinp, L.H, L.W, out, L.csh, L.H, L.W, 0);
+}
+// the up-sample (frames are multiples of 16 with descriptors on: the doubled map is the 1/8 map)
+static ConvSpec upsample_spec(const Layer& L, Kind kind) {
+  return conv_spec(L, "+bn+relu", kind, 2, L.x, L.csx, L.cin, L.cinp, L.H, L.W, L.y, L.csy, 2 * L.H, 2 * L.W, 1);
 }
 
 // ---- bf16 plan (block_bf16.h) ---------------------------------------------------------------
@@ -1298,232 +1352,167 @@ struct FBlockSpec {
   int cso, out_f32, cout;
   bool proj, desc_branch;
 };
+// (FPC_BF16 keeps bf16 tensors but for the logits; the split modes the fp32 plan's buffers, all fp32)
+static FBlockSpec fblock_spec(const fpc_ctx* c, const Layer& L, FKind kind) {
+  return {L.prefix, kind, L.x, L.csx, c->split, L.cin, L.cinp, L.H, L.W, L.y, L.csy, c->split || L.y == c->lg, L.cout, L.proj, L.desc};
+}
+
+static const char* fplanes_tag(const FKindInfo& k) { return k.planes == 3 ? "3xbf16" : k.planes == 2 ? "2xfp16" : "bf16"; }
+// split operands: six bf16 (three fp16) MFMAs per product
+static double fplanes_mfmas(const FKindInfo& k) { return k.planes == 3 ? 6.0 : k.planes == 2 ? 3.0 : 1.0; }
+// halo offset of tap (dy, dx) in 16-byte units
+// (halo row pitch: block_bf16_kernel pads it for its bank-conflict-free pixel order, block_bf16.h)
+static int ftap_off(const FKindInfo& k, int dy, int dx) {
+  const int HWp = k.planes == 1 ? bf_halo_pitch(k.TH, k.TW, k.S, k.EXT) : (k.TW - 1) * k.S + k.EXT, ROW16 = k.KC / 8 + 1;
+  return (dy * HWp + dx) * ROW16;
+}
+// What every OP_BF16 launch's arguments share: the tensors, the K chunks, the Ho x Wo grid instance `k`'s tiles walk and
+// where its points land in the output (every `os`-th pixel; a caller with parity phases adds oy0 / ox0)
+static void fill_fargs(BlockBfArgs& a, const FKindInfo& k, const void* x, int csx, int in_f32, int cin_pad, int H, int W,
+                       void* out, int cso, int out_f32, int Ho, int Wo, int os) {
+  a.x = x; a.csx = csx; a.in_f32 = in_f32;
+  a.nchunk = cin_pad / k.KC;
+  a.H = H; a.W = W;
+  a.out = out; a.cso = cso; a.out_f32 = out_f32;
+  a.Ho = Ho; a.Wo = Wo; a.OH = os * Ho; a.OW = os * Wo; a.oys = a.oxs = os;
+  a.tiles_x = (Wo + k.TW - 1) / k.TW;
+  a.tiles_y = (Ho + k.TH - 1) / k.TH;
+}
+// ... a ksize x ksize window's taps
+static void fill_ftaps(BlockBfArgs& a, const FKindInfo& k, int ksize) {
+  a.pad = ksize / 2;
+  a.ntaps = ksize * ksize;
+  for (int ky = 0; ky < ksize; ++ky)
+    for (int kx = 0; kx < ksize; ++kx) a.tapoff16[ky * ksize + kx] = ftap_off(k, ky, kx);
+}
 
 static void add_fblock(fpc_ctx* c, const FBlockSpec& s, size_t* blob_off) {
   if (s.kind >= FK_COUNT) { c->plan_error = true; return; }
   const FKindInfo& k = g_fkinds[s.kind];
-  Op op;
-  op.type = OP_BF16;
-  const std::string tag = k.planes == 3 ? " [3xbf16 " : k.planes == 2 ? " [2xfp16 " : " [bf16 ";
-  op.name = s.prefix + tag + (s.proj ? "conv1+bn1+relu+conv2+bn2+proj+relu]" : "conv1+bn1+relu+conv2+bn2+identity+relu]");
-  op.prefix = s.prefix;
+  Op op = weight_op(OP_BF16, s.prefix + " [" + fplanes_tag(k) + (s.proj ? " conv1+bn1+relu+conv2+bn2+proj+relu]" : " conv1+bn1+relu+conv2+bn2+identity+relu]"),
+                    s.prefix, s.cin, s.cout, s.desc_branch);
   op.fkind = s.kind;
-  op.cin = s.cin;
-  op.cout = s.cout;
-  op.descriptor_branch = s.desc_branch;
   BlockBfArgs& a = op.fargs;
   const int nbt = k.WN * k.NB, K16 = k.KC / 16;
-  a.x = s.x;
-  a.csx = s.csx;
-  a.in_f32 = s.in_f32;
-  a.x_bytes = (unsigned)std::min<size_t>((size_t)c->B * s.H * s.W * s.csx * 2, 0xffffff00u);
-  a.nchunk = s.cin_pad / k.KC;
+  fill_fargs(a, k, s.x, s.csx, s.in_f32, s.cin_pad, s.H, s.W, s.out, s.cso, s.out_f32, s.H / k.S, s.W / k.S, 1);
+  a.x_bytes = x_bytes(c, s.H, s.W, s.csx, 2);
   // block_bf16_one_kernel: the single chunk is a compile-time fact of the instance (block_bf16.h)
   if (strstr(k.symbol, "block_bf16_one_kernel") && a.nchunk != 1) { c->plan_error = true; return; }
   if (strstr(k.symbol, "block_bf16_two_kernel") && a.nchunk != 2) { c->plan_error = true; return; }
-  a.H = s.H;
-  a.W = s.W;
-  a.ntaps = 9;
-  a.pad = 1;
-  // (halo row pitch: block_bf16_kernel pads it for its bank-conflict-free pixel order, block_bf16.h)
-  const int HWp = k.planes == 1 ? bf_halo_pitch(k.TH, k.TW, k.S, k.EXT) : (k.TW - 1) * k.S + k.EXT, ROW16 = k.KC / 8 + 1;
-  for (int ky = 0; ky < 3; ++ky)
-    for (int kx = 0; kx < 3; ++kx) a.tapoff16[ky * 3 + kx] = (ky * HWp + kx) * ROW16;
+  fill_ftaps(a, k, 3);
   a.k16_h = k.CMIDP / 16;
   a.k16_x = s.proj ? s.cin_pad / 16 : 0;
-  a.conv_only = 0;
-  a.out = s.out;
-  a.cso = s.cso;
-  a.out_f32 = s.out_f32;
-  a.Ho = a.OH = s.H / k.S;
-  a.Wo = a.OW = s.W / k.S;
-  a.oys = a.oxs = 1;
-  a.oy0 = a.ox0 = 0;
-  a.tiles_x = (a.Wo + k.TW - 1) / k.TW;
-  a.tiles_y = (a.Ho + k.TH - 1) / k.TH;
   fpc_ctx::ConvW cw;
   // FPC_BF16 (planes == 1): the shortcut's fragments (projection, or the identity as a unit matrix) follow each chunk's
   // conv1 fragments in the w1 stream as a tenth tap (block_bf16.h), and w2 holds conv2 only
   const bool sc_in_w1 = k.planes == 1;
-  cw.w_off[0] = *blob_off;
-  *blob_off += ((size_t)a.nchunk * (sc_in_w1 ? 10 : 9) * K16 + 2) * k.planes * nbt * 64 * 4;
-  cw.b_off = *blob_off;
-  *blob_off += (size_t)nbt * 32;
-  cw.w_off[1] = *blob_off;
-  *blob_off += ((size_t)(a.k16_h + (sc_in_w1 ? 0 : a.k16_x)) + 2) * k.planes * nbt * 64 * 4;
-  cw.b2_off = *blob_off;
-  *blob_off += (size_t)nbt * 32;
+  reserve(blob_off, cw.w[0], conv_bf16_floats((size_t)a.nchunk * (sc_in_w1 ? 10 : 9) * K16, nbt, k.planes));
+  reserve(blob_off, cw.b, bias_floats(nbt));
+  reserve(blob_off, cw.w[1], conv_bf16_floats(a.k16_h + (sc_in_w1 ? 0 : a.k16_x), nbt, k.planes));
+  reserve(blob_off, cw.b2, bias_floats(nbt));
   op.flops_per_frame = 2.0 * a.Ho * a.Wo * s.cout * ((double)s.cin * 9 + s.cout + (s.proj ? s.cin : 0));
-  // split operands: six bf16 MFMAs per product
-  op.mfma_flops_per_frame = (k.planes == 3 ? 6.0 : k.planes == 2 ? 3.0 : 1.0) * 2.0 * a.tiles_x * a.tiles_y * (k.WM * k.MB * 32.0) * (nbt * 32.0) *
+  op.mfma_flops_per_frame = fplanes_mfmas(k) * 2.0 * a.tiles_x * a.tiles_y * (k.WM * k.MB * 32.0) * (nbt * 32.0) *
                             ((double)a.nchunk * k.KC * 9 + (a.k16_h + (sc_in_w1 ? s.cin_pad / 16 : a.k16_x)) * 16.0);
   op.bytes_per_frame = (double)s.cin * s.H * s.W * ((s.in_f32 || k.planes > 1) ? 4.0 : 2.0) +
                        (double)s.cout * a.Ho * a.Wo * ((s.out_f32 || k.planes > 1) ? 4.0 : 2.0);
-  c->ops.push_back(op);
-  c->convw.push_back(cw);
+  push_op(c, op, cw);
 }
 
-// ConvTranspose2d(k3, s2, p1, op1) + bn + relu as four output-parity phases, one launch each
-static void add_fconvT(fpc_ctx* c, FKind kind, const void* x, int csx, int cin, int H, int W, void* out, int cso,
-                       int cout, size_t* blob_off) {
+// The up-sample, ConvTranspose2d(k3, s2, p1, op1) + bn + relu, as four output-parity phases: one launch each, or all in one
+static void add_fconvT(fpc_ctx* c, FKind kind, const Layer& L, size_t* blob_off) {
   if (kind >= FK_COUNT) { c->plan_error = true; return; }
   const FKindInfo& k = g_fkinds[kind];
-  const int nbt = k.WN * k.NB, K16 = k.KC / 16;
-  if (strstr(k.symbol, "convt_bf16_kernel")) {
-    // round 5: ONE launch (convt_bf16.h) -- a workgroup stages a tile's halo chunk once and issues all nine taps on it, the
-    // four parities' accumulators side by side; gridDim.y = the output-channel parts
-    if (cin % k.KC != 0 || cout != k.CMIDP) { c->plan_error = true; return; }
-    Op op;
-    op.type = OP_BF16;
-    op.name = "descriptor.up_sample+bn+relu [bf16, four parities in one launch]";
-    op.prefix = "descriptor.up_sample";
-    op.fkind = kind;
-    op.phase = 4;   // all four
-    op.cin = cin;
-    op.cout = cout;
-    op.descriptor_branch = true;
-    op.grid_y = k.CMIDP / (k.WN * 32);
-    BlockBfArgs& a = op.fargs;
-    a.x = x;
-    a.csx = csx;
-    a.in_f32 = 0;
-    a.x_bytes = (unsigned)std::min<size_t>((size_t)c->B * H * W * csx * 2, 0xffffff00u);
-    a.nchunk = cin / k.KC;
-    a.H = H;
-    a.W = W;
-    a.pad = 0;
-    a.ntaps = 9;
-    a.conv_only = 1;
-    a.out = out;
-    a.cso = cso;
-    a.out_f32 = 0;
-    a.Ho = H;
-    a.Wo = W;
-    a.OH = 2 * H;
-    a.OW = 2 * W;
-    a.oys = a.oxs = 2;
-    a.tiles_x = (W + k.TW - 1) / k.TW;
-    a.tiles_y = (H + k.TH - 1) / k.TH;
-    fpc_ctx::ConvW cw;
-    cw.w_off[0] = *blob_off;
-    *blob_off += ((size_t)(cin / 16) * 9 + 2) * (k.CMIDP / 32) * 64 * 4;   // pack_conv_bf16 with KC = 16: [step of 16 channels][tap][32-channel block][lane]
-    cw.b_off = *blob_off;
-    *blob_off += (size_t)k.CMIDP;
-    op.flops_per_frame = 2.0 * 9 * H * W * cin * cout;
-    op.mfma_flops_per_frame = 2.0 * 9 * a.tiles_x * a.tiles_y * (k.TH * k.TW) * (double)cin * k.CMIDP;
-    op.bytes_per_frame = 2.0 * ((double)cin * H * W + 4.0 * cout * H * W);
-    c->ops.push_back(op);
-    c->convw.push_back(cw);
-    return;
-  }
-  const int HWp = k.planes == 1 ? bf_halo_pitch(k.TH, k.TW, k.S, k.EXT) : (k.TW - 1) * k.S + k.EXT, ROW16 = k.KC / 8 + 1;
-  for (int ph = 0; ph < 4; ++ph) {
-    const int py = ph >> 1, px = ph & 1;
-    Op op;
-    op.type = OP_BF16;
-    op.name = std::string("descriptor.up_sample+bn+relu [") + (k.planes == 3 ? "3xbf16" : k.planes == 2 ? "2xfp16" : "bf16") + " phase " + std::to_string(ph) + "]";
-    op.prefix = "descriptor.up_sample";
+  const int nbt = k.WN * k.NB, K16 = k.KC / 16, H = L.H, W = L.W, cin = L.cin, cout = L.cout;
+  // round 5: ONE launch (convt_bf16.h) -- a workgroup stages a tile's halo chunk once and issues all nine taps on it, the
+  // four parities' accumulators side by side; gridDim.y = the output-channel parts
+  const bool fused = strstr(k.symbol, "convt_bf16_kernel") != nullptr;
+  if (fused && (cin % k.KC != 0 || cout != k.CMIDP)) { c->plan_error = true; return; }
+  for (int ph = fused ? 4 : 0; ph < (fused ? 5 : 4); ++ph) {   // phase 4: all four
+    Op op = weight_op(OP_BF16, std::string(L.prefix) + "+bn+relu [" + fplanes_tag(k) + (fused ? ", four parities in one launch]" : " phase " + std::to_string(ph) + "]"),
+                      L.prefix, cin, cout, L.desc);
     op.fkind = kind;
     op.phase = ph;
-    op.cin = cin;
-    op.cout = cout;
-    op.descriptor_branch = true;
     BlockBfArgs& a = op.fargs;
-    a.x = x;
-    a.csx = csx;
-    a.in_f32 = 0;
-    a.x_bytes = (unsigned)std::min<size_t>((size_t)c->B * H * W * csx * 2, 0xffffff00u);
-    a.nchunk = cin / k.KC;
-    a.H = H;
-    a.W = W;
+    fill_fargs(a, k, L.x, L.csx, 0, cin, H, W, L.y, L.csy, 0, H, W, 2);
+    a.x_bytes = x_bytes(c, H, W, L.csx, 2);
     a.pad = 0;
-    a.ntaps = 0;
-    for (int iy = 0; iy < (py ? 2 : 1); ++iy)
-      for (int ix = 0; ix < (px ? 2 : 1); ++ix) {
-        const int dy = py ? 1 - iy : 0, dx = px ? 1 - ix : 0;
-        a.tapoff16[a.ntaps++] = (dy * HWp + dx) * ROW16;
-      }
     a.conv_only = 1;
-    a.out = out;
-    a.cso = cso;
-    a.out_f32 = 0;
-    a.Ho = H;
-    a.Wo = W;
-    a.OH = 2 * H;
-    a.OW = 2 * W;
-    a.oys = a.oxs = 2;
-    a.oy0 = py;
-    a.ox0 = px;
-    a.tiles_x = (W + k.TW - 1) / k.TW;
-    a.tiles_y = (H + k.TH - 1) / k.TH;
     fpc_ctx::ConvW cw;
-    cw.w_off[0] = *blob_off;
-    *blob_off += ((size_t)a.nchunk * a.ntaps * K16 + 2) * k.planes * nbt * 64 * 4;
-    cw.b_off = *blob_off;
-    *blob_off += (size_t)nbt * 32;
-    op.flops_per_frame = 2.0 * a.ntaps * H * W * cin * cout;
-    op.mfma_flops_per_frame = (k.planes == 3 ? 6.0 : k.planes == 2 ? 3.0 : 1.0) * 2.0 * a.ntaps * a.tiles_x * a.tiles_y * (k.WM * k.MB * 32.0) * (a.nchunk * k.KC) * (nbt * 32.0);
-    // the four phases read the same input: a quarter of it is attributed to each, plus the phase's quarter of the output
-    op.bytes_per_frame = (k.planes > 1 ? 4.0 : 2.0) * ((double)cin * H * W / 4.0 + (double)cout * H * W);
-    c->ops.push_back(op);
-    c->convw.push_back(cw);
+    if (fused) {
+      op.grid_y = k.CMIDP / (k.WN * 32);
+      a.ntaps = 9;
+      reserve(blob_off, cw.w[0], conv_bf16_floats((size_t)(cin / 16) * 9, k.CMIDP / 32, 1));   // pack_conv_bf16 with KC = 16: [step of 16 channels][tap][32-channel block][lane]
+      reserve(blob_off, cw.b, (size_t)k.CMIDP);
+      op.flops_per_frame = 2.0 * 9 * H * W * cin * cout;
+      op.mfma_flops_per_frame = 2.0 * 9 * a.tiles_x * a.tiles_y * (k.TH * k.TW) * (double)cin * k.CMIDP;
+      op.bytes_per_frame = 2.0 * ((double)cin * H * W + 4.0 * cout * H * W);
+    } else {
+      a.ntaps = 0;
+      for (const ConvTTap& t : convt_phase_taps(ph)) a.tapoff16[a.ntaps++] = ftap_off(k, t.dy, t.dx);
+      a.oy0 = ph >> 1;
+      a.ox0 = ph & 1;
+      reserve(blob_off, cw.w[0], conv_bf16_floats((size_t)a.nchunk * a.ntaps * K16, nbt, k.planes));
+      reserve(blob_off, cw.b, bias_floats(nbt));
+      op.flops_per_frame = 2.0 * a.ntaps * H * W * cin * cout;
+      op.mfma_flops_per_frame = fplanes_mfmas(k) * 2.0 * a.ntaps * a.tiles_x * a.tiles_y * (k.WM * k.MB * 32.0) * (a.nchunk * k.KC) * (nbt * 32.0);
+      // the four phases read the same input: a quarter of it is attributed to each, plus the phase's quarter of the output
+      op.bytes_per_frame = (k.planes > 1 ? 4.0 : 2.0) * ((double)cin * H * W / 4.0 + (double)cout * H * W);
+    }
+    push_op(c, op, cw);
   }
 }
 
-static void build_bf16_ops(fpc_ctx* c, size_t* bo) {
-  const int H = c->H, W = c->W;
-  const int H4 = H / 4, W4 = W / 4, Hc = H / 8, Wc = W / 8, H16 = H / 16, W16 = W / 16;
-  const bool de = c->cfg.descriptor_enabled != 0;
-  bf16_t* feat = reinterpret_cast<bf16_t*>(c->cat) + 128;
+// The rows on the bf16 / split-operand instances `kinds`, one per row
+static void add_fnet(fpc_ctx* c, const Layer* net, const FKind* kinds, size_t* bo) {
+  for (int l = 0; l < layer_count(c); ++l) {
+    if (l == L_UP) add_fconvT(c, kinds[l], net[l], bo);
+    else add_fblock(c, fblock_spec(c, net[l], kinds[l]), bo);
+    if (l != L_DET1) continue;
+    if (c->bf16) c->ops.back().fused_softmax_capable = c->fuse_softmax;
+    push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
+  }
+}
+
+static void build_bf16_ops(fpc_ctx* c, const Layer* net, size_t* bo) {
+  FKind kinds[L_COUNT];
   // (layer1 measured the same 0.53 ms per 64 HD frames on 8 x 16 tiles of 2 x 2 waves x (2 x 1) blocks, 16 x 16 tiles of
   // 4 x 1 waves x (2 x 2) and 8 x 16 tiles of 2 x 1 waves x (2 x 2): not a matter of the blocking;
   // single-wave workgroups (4 x 16 tiles, 1 x 1 waves x (2 x 2) blocks: no barrier waits at all) measured 0.55 ms: not
   // the barriers either.  What these kernels run into is operand delivery: at full MFMA rate a CU's four SIMDs would
   // pull 64 B/clk of weight fragments from L2 and 64 B/clk of pixels from LDS for a 2 x 2 register blocking.)
-  add_fblock(c, {"encoder.layer1.0", FK_F816_s1_K64_C64, c->x0, 64, 0, 64, 64, H4, W4, c->x1, 64, 0, 64, true, false}, bo);
-  add_fblock(c, {"encoder.layer1.1", FK_F816_s1_K64_C64, c->x1, 64, 0, 64, 64, H4, W4, c->x2, 64, 0, 64, false, false}, bo);
-  add_fblock(c, {"encoder.layer2.0", FK_F620_s2_K64_C128, c->x2, 64, 0, 64, 64, H4, W4, c->x3, 128, 0, 128, true, false}, bo);
-  add_fblock(c, {"encoder.layer2.1", FK_F816_s1_K128_C128, c->x3, 128, 0, 128, 128, Hc, Wc, feat, 256, 0, 128, false, false}, bo);
+  kinds[L_ENC10] = kinds[L_ENC11] = FK_F816_s1_K64_C64;
+  kinds[L_ENC20] = FK_F620_s2_K64_C128;
+  kinds[L_ENC21] = FK_F816_s1_K128_C128;
   // detector.layer.0 on the 2 x 2 blocking of the 128-wide layers (N = 128 for 65 channels: a quarter of the MFMAs on
   // zeros, but four MFMAs per four operand fetches instead of three per four: 0.47 -> 0.40 ms per 64 HD frames);
   // layer.1 (K = 80) measured the same on both shapes and keeps the narrower one
-  add_fblock(c, {"detector.layer.0", FK_F816_s1_K128_C80w, feat, 256, 0, 128, 128, Hc, Wc, c->d0, 80, 0, 65, true, false}, bo);
-  add_fblock(c, {"detector.layer.1", FK_F816_s1_K80_C80, c->d0, 80, 0, 65, 80, Hc, Wc, c->lg, 80, 1, 65, false, false}, bo);
-  c->ops.back().fused_softmax_capable = c->fuse_softmax;
-  push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
-  if (de) {
-    add_fblock(c, {"descriptor.layer_in.0", FK_F320_s2_K128_C256, feat, 256, 0, 128, 128, Hc, Wc, c->y16a, 256, 0, 256, true, true}, bo);
-    add_fblock(c, {"descriptor.layer_in.1", FK_F416_s1_K128_C256, c->y16a, 256, 0, 256, 256, H16, W16, c->y16b, 256, 0, 256, false, true}, bo);
-    add_fconvT(c, c->convt_fused ? FK_F816_ctf_K64_C128 : FK_F816_ct_K64_C128, c->y16b, 256, 256, H16, W16, c->cat, 256, 128, bo);
-    add_fblock(c, {"descriptor.layer_out.0", FK_F816_s1_K64_C128, c->cat, 256, 0, 256, 256, Hc, Wc, c->lo0, 128, 0, 128, true, true}, bo);
-    // (the descriptor map is bf16 as well -- round 3: descriptor16_kernel<8, true> reads it, fpc_forward / the tap convert it)
-    add_fblock(c, {"descriptor.layer_out.1", FK_F816_s1_K128_C128, c->lo0, 128, 0, 128, 128, Hc, Wc, c->desc_map, 128, 0, 128, false, true}, bo);
-  }
+  kinds[L_DET0] = FK_F816_s1_K128_C80w;
+  kinds[L_DET1] = FK_F816_s1_K80_C80;
+  kinds[L_IN0] = FK_F320_s2_K128_C256;
+  kinds[L_IN1] = FK_F416_s1_K128_C256;
+  kinds[L_UP] = c->convt_fused ? FK_F816_ctf_K64_C128 : FK_F816_ct_K64_C128;
+  kinds[L_OUT0] = FK_F816_s1_K64_C128;
+  // (the descriptor map is bf16 as well -- round 3: descriptor16_kernel<8, true> reads it, fpc_forward / the tap convert it)
+  kinds[L_OUT1] = FK_F816_s1_K128_C128;
+  add_fnet(c, net, kinds, bo);
 }
 
-// dtype = FPC_F32_SPLIT: the fp32 plan's buffers (all fp32), every ResNetBlock / ConvTranspose on block_x3_kernel
 // the fp16 twin of a bf16x3 instance (rows H* follow rows S* in the same order in FPC_BF16_KINDS)
 static FKind split_kind(const fpc_ctx* c, FKind s);
 
-static void build_x3_ops(fpc_ctx* c, size_t* bo) {
-  const int H = c->H, W = c->W;
-  const int H4 = H / 4, W4 = W / 4, Hc = H / 8, Wc = W / 8, H16 = H / 16, W16 = W / 16;
-  const bool de = c->cfg.descriptor_enabled != 0;
-  float* feat = c->cat + 128;
-  add_fblock(c, {"encoder.layer1.0", split_kind(c, FK_S816_s1_K64_C64), c->x0, 64, 1, 64, 64, H4, W4, c->x1, 64, 1, 64, true, false}, bo);
-  add_fblock(c, {"encoder.layer1.1", split_kind(c, FK_S816_s1_K64_C64), c->x1, 64, 1, 64, 64, H4, W4, c->x2, 64, 1, 64, false, false}, bo);
-  add_fblock(c, {"encoder.layer2.0", split_kind(c, FK_S620_s2_K16_C128), c->x2, 64, 1, 64, 64, H4, W4, c->x3, 128, 1, 128, true, false}, bo);
-  add_fblock(c, {"encoder.layer2.1", split_kind(c, FK_S620_s1_K64_C128), c->x3, 128, 1, 128, 128, Hc, Wc, feat, 256, 1, 128, false, false}, bo);
-  add_fblock(c, {"detector.layer.0", split_kind(c, FK_S620_s1_K64_C80), feat, 256, 1, 128, 128, Hc, Wc, c->d0, 80, 1, 65, true, false}, bo);
-  add_fblock(c, {"detector.layer.1", split_kind(c, FK_S620_s1_K16_C80), c->d0, 80, 1, 65, 80, Hc, Wc, c->lg, 80, 1, 65, false, false}, bo);
-  push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
-  if (de) {
-    add_fblock(c, {"descriptor.layer_in.0", split_kind(c, FK_S320_s2_K16_C256), feat, 256, 1, 128, 128, Hc, Wc, c->y16a, 256, 1, 256, true, true}, bo);
-    add_fblock(c, {"descriptor.layer_in.1", split_kind(c, FK_S320_s1_K64_C256), c->y16a, 256, 1, 256, 256, H16, W16, c->y16b, 256, 1, 256, false, true}, bo);
-    add_fconvT(c, split_kind(c, FK_S620_ct_K64_C128), c->y16b, 256, 256, H16, W16, c->cat, 256, 128, bo);
-    add_fblock(c, {"descriptor.layer_out.0", split_kind(c, FK_S620_s1_K64_C128), c->cat, 256, 1, 256, 256, Hc, Wc, c->lo0, 128, 1, 128, true, true}, bo);
-    add_fblock(c, {"descriptor.layer_out.1", split_kind(c, FK_S620_s1_K64_C128), c->lo0, 128, 1, 128, 128, Hc, Wc, c->desc_map, 128, 1, 128, false, true}, bo);
-  }
+// dtype = FPC_F32_SPLIT: the fp32 plan's buffers (all fp32), every ResNetBlock / ConvTranspose on block_x3_kernel
+static void build_x3_ops(fpc_ctx* c, const Layer* net, size_t* bo) {
+  FKind kinds[L_COUNT];
+  kinds[L_ENC10] = kinds[L_ENC11] = FK_S816_s1_K64_C64;
+  kinds[L_ENC20] = FK_S620_s2_K16_C128;
+  kinds[L_ENC21] = kinds[L_OUT0] = kinds[L_OUT1] = FK_S620_s1_K64_C128;
+  kinds[L_DET0] = FK_S620_s1_K64_C80;
+  kinds[L_DET1] = FK_S620_s1_K16_C80;
+  kinds[L_IN0] = FK_S320_s2_K16_C256;
+  kinds[L_IN1] = FK_S320_s1_K64_C256;
+  kinds[L_UP] = FK_S620_ct_K64_C128;
+  for (FKind& k : kinds) k = split_kind(c, k);
+  add_fnet(c, net, kinds, bo);
 }
 
 // ---- the reference's C++ network (superpoint::SPModel, cpp/src/model.cc) -----------------------------
@@ -1534,48 +1523,22 @@ static void add_fconv(fpc_ctx* c, FKind kind, const std::string& prefix, const f
   if (kind >= FK_COUNT) { c->plan_error = true; return; }
   const FKindInfo& k = g_fkinds[kind];
   const int nbt = k.WN * k.NB, K16 = k.KC / 16;
-  const int HWp = k.planes == 1 ? bf_halo_pitch(k.TH, k.TW, k.S, k.EXT) : (k.TW - 1) * k.S + k.EXT, ROW16 = k.KC / 8 + 1;
-  Op op;
-  op.type = OP_BF16;
-  op.name = prefix + (k.planes == 2 ? " [2xfp16 conv+bias" : " [3xbf16 conv+bias") + (relu ? "+relu]" : "]");
-  op.prefix = prefix;
+  Op op = weight_op(OP_BF16, prefix + " [" + fplanes_tag(k) + " conv+bias" + (relu ? "+relu]" : "]"), prefix, cin, cout, desc_branch);
   op.fkind = kind;
   op.plain_conv = true;
   op.ksize = ksize;
-  op.cin = cin;
-  op.cout = cout;
-  op.descriptor_branch = desc_branch;
   BlockBfArgs& a = op.fargs;
-  a.x = x;
-  a.csx = csx;
-  a.in_f32 = 1;
-  a.nchunk = cin_pad / k.KC;
-  a.H = H;
-  a.W = W;
-  a.pad = ksize / 2;
-  a.ntaps = ksize * ksize;
-  for (int ky = 0; ky < ksize; ++ky)
-    for (int kx = 0; kx < ksize; ++kx) a.tapoff16[ky * ksize + kx] = (ky * HWp + kx) * ROW16;
+  fill_fargs(a, k, x, csx, 1, cin_pad, H, W, out, cso, 1, H, W, 1);
+  fill_ftaps(a, k, ksize);
   a.conv_only = 1;
   a.norelu = relu ? 0 : 1;
-  a.out = out;
-  a.cso = cso;
-  a.out_f32 = 1;
-  a.Ho = a.OH = H;
-  a.Wo = a.OW = W;
-  a.oys = a.oxs = 1;
-  a.tiles_x = (W + k.TW - 1) / k.TW;
-  a.tiles_y = (H + k.TH - 1) / k.TH;
   fpc_ctx::ConvW cw;
-  cw.w_off[0] = *blob_off;
-  *blob_off += ((size_t)a.nchunk * a.ntaps * K16 + 2) * k.planes * nbt * 64 * 4;
-  cw.b_off = *blob_off;
-  *blob_off += (size_t)nbt * 32;
+  reserve(blob_off, cw.w[0], conv_bf16_floats((size_t)a.nchunk * a.ntaps * K16, nbt, k.planes));
+  reserve(blob_off, cw.b, bias_floats(nbt));
   op.flops_per_frame = 2.0 * a.ntaps * H * W * (double)cin * cout;
-  op.mfma_flops_per_frame = (k.planes == 2 ? 3.0 : 6.0) * 2.0 * a.ntaps * a.tiles_x * a.tiles_y * (k.WM * k.MB * 32.0) * (a.nchunk * k.KC) * (nbt * 32.0);
+  op.mfma_flops_per_frame = fplanes_mfmas(k) * 2.0 * a.ntaps * a.tiles_x * a.tiles_y * (k.WM * k.MB * 32.0) * (a.nchunk * k.KC) * (nbt * 32.0);
   op.bytes_per_frame = 4.0 * ((double)cin * H * W + (double)cout * H * W);
-  c->ops.push_back(op);
-  c->convw.push_back(cw);
+  push_op(c, op, cw);
 }
 
 static int build_vgg_plan(fpc_ctx* c) {
@@ -1614,7 +1577,7 @@ static int build_vgg_plan(fpc_ctx* c) {
         const size_t i0 = c->ops.size();
         for (int n0 = 0; n0 < cout; n0 += g_wkinds[wk].CMID)
           add_wconv(c, prefix, false, wk, x, cin, cin, Hx, Wx, out, cso, cout, n0, desc, &bo);
-        for (size_t k = i0; k < c->ops.size(); ++k) c->ops[k].when = when;
+        mark_when(c, i0, when);
       };
       if (c->winograd_gen == 3 && w36_fits(c->B, Hx, Wx, cin, cso) && cin % 32 == 0 && cin >= 64) {
         // round 4: F(4x4,3x3) for the C++ network's 3x3 layers too (the conv-only form of wblock36_kernel; 256 outputs in
@@ -1633,7 +1596,7 @@ static int build_vgg_plan(fpc_ctx* c) {
     s.name = prefix + (relu ? " [conv+bias+relu]" : " [conv+bias]");
     if (ksize == 3) s.kind = cout == 64 ? K_T816_3x3_K64_N64 : K_T620_3x3_K64_N128;
     else s.kind = cout == 65 ? K_T620_1x1_K64_N96 : K_T620_1x1_K64_N128;
-    s.ksize = ksize; s.stride = 1;
+    s.ksize = ksize;
     s.in0 = x; s.cs0 = cin; s.cin0 = cin; s.cin0_pad = cin; s.H0 = Hx; s.W0 = Wx;
     s.out = out; s.cso = cso; s.cout = cout; s.nstore = cout == 65 ? cso : cout; s.Ho = Hx; s.Wo = Wx; s.relu = relu ? 1 : 0;
     s.desc_branch = desc;
@@ -1698,11 +1661,132 @@ static FKind split_kind(const fpc_ctx* c, FKind s) {
   return h >= (int)FK_H816_s1_K64_C64 && h < (int)FK_COUNT ? (FKind)h : FK_COUNT;
 }
 
+// ---- fp32 plan: a row as ONE fused launch (direct or Winograd), or as its conv1 / conv2 launches -------------------
+struct F32Kinds {
+  Kind k3, k1;   // unfused: conv1 (the up-sample's only launch) and conv2
+  BKind bk;      // the fused direct block
+};
+
+// The Winograd instance of a fused stride-1 block (WK_COUNT: none, the direct block runs it)
+static WKind wblock_kind(const fpc_ctx* c, const Layer& L) {
+  if (!c->winograd || L.stride != 1) return WK_COUNT;
+  const bool fits = w36_fits(c->B, L.H, L.W, L.csx, L.csy);
+  // generation 3's projection pass walks x in 16-channel steps, 4 or 8 per pass (wblock36_mfma.h: gemm_over advances
+  // by 4): k8_x = cinp / 8 must be a multiple of 8, i.e. cinp of 64 -- true of every layer of both networks; a
+  // layer that is not falls back to generation 2 instead of running extra K steps over stale staging rows
+  const int gen = c->winograd_gen == 3 && (!fits || (L.proj && L.cinp % 64 != 0)) ? 2 : c->winograd_gen;
+  if (L.cinp % 32 == 0 && L.cout == 64) return gen == 3 ? w36_kind(64, L.H, L.W, c->w36_paired) : gen == 2 ? WK_W16_C64 : WK_W816_K32_C64;
+  if (L.cinp % 32 == 0 && L.cout == 128) return gen == 3 ? w36_kind(128, L.H, L.W) : gen == 2 ? WK_W16_C128 : WK_W816_K32_C128;
+  if (!c->winograd_det) return WK_COUNT;
+  if (L.cout == 65 && c->winograd_det_gen3 && c->winograd_gen == 3 && fits &&
+      (L.cin == 65 ? !L.proj : (L.cin == L.cinp && L.cinp % 64 == 0 && L.cinp <= 256)))
+    return w36_kind(65, L.H, L.W, c->w36_paired);
+  if (L.cinp % 32 == 0 && L.coutp == 72) return WK_W816_K32_C72;
+  if (L.cinp == 72 && L.coutp == 72) return WK_W816_K24_C72;
+  return WK_COUNT;
+}
+
+static void add_f32_block(fpc_ctx* c, const Layer& L, const F32Kinds& k, size_t* bo) {
+  if (c->fuse_blocks) {
+    const WKind wk = wblock_kind(c, L);
+    if (wk != WK_COUNT) add_wblock(c, block_spec(L, k.bk), wk, bo);
+    else add_block(c, block_spec(L, k.bk), bo);
+    return;
+  }
+  add_conv(c, conv1_spec(L, k.k3), bo);
+  add_conv(c, conv2_spec(L, k.k1), bo);
+}
+
+// conv1 of `L` as ONE conv-only Winograd launch on `wk`, in parts of that instance's width: x -> h
+static void add_wconv1(fpc_ctx* c, const Layer& L, WKind wk, size_t* bo) {
+  for (int n0 = 0; n0 < L.cout; n0 += g_wkinds[wk].CMID)
+    add_wconv(c, L.prefix, true, wk, L.x, L.csx, L.cin, L.H, L.W, L.h, L.csh, L.cout, n0, L.desc, bo);
+}
+
+// descriptor.layer_in.1 of a fused Winograd plan.  256 channels are too wide for the fused Winograd block (accumulators):
+// conv1 as two conv-only Winograd launches of 128 output channels each, then conv2 + identity + ReLU as a 1x1 launch (h
+// makes one round trip)
+static void add_f32_in1(fpc_ctx* c, const Layer& L, const F32Kinds& k, size_t* bo) {
+  // Generation 3: FOUR parts of 64 channels (the NB = 1 instance, gridDim.y = 4).  A 30 x 40 map is 6 tiles per
+  // frame: 192 tiles x 2 halves were 384 one-tile workgroups = 1.5 rounds of the 256 CUs at the 128-channel tile's
+  // time; 192 x 4 = 768 half-as-long tiles are 3 full rounds (64 workgroups per part walk 3 tiles each).
+  const bool g3 = c->winograd_gen == 3 && w36_fits(c->B, L.H, L.W, L.csx, L.csy);
+  const WKind wk = g3 ? w36_kind(64, L.H, L.W, c->w36_paired, c->tiles_round6) : c->winograd_gen >= 2 ? WK_W16_C128 : WK_W816_K32_C128;
+  const int gen = g_wkinds[wk].gen;
+  const ConvSpec t = conv2_spec(L, k.k1);
+  const size_t ia = c->ops.size();   // [the launch, its shadows, the 1x1]
+  add_wconv1(c, L, wk, bo);
+  add_conv(c, t, bo);
+  retile_last(c, K_T320_1x1_K64_N128);
+  if (c->plan_error) return;
+  if (gen == 2 && c->latency_tiles) {
+    // calls of a few frames: the same two-half launch on 4 x 16 tiles (24 tiles x 2 halves per frame instead of
+    // 12 x 2), then the same 1x1 -- 0.10 ms for one frame against 0.16 ms for the fused direct block on 20 tiles
+    c->ops[ia].when = 2;
+    c->ops.insert(c->ops.begin() + ia + 1, half_tile_copy(c->ops[ia]));
+    c->ops[ia + 1].when = 1;
+    c->convw.insert(c->convw.begin() + ia + 1, fpc_ctx::ConvW(c->convw[ia]));
+  } else if (gen == 3 && c->latency_tiles) {
+    // generation 3's fragments have 36 positions: the small-call variant (generation 2 on 4 x 16 tiles, then the same
+    // 1x1) gets fragments of its own
+    mark_when(c, ia, 2);
+    const size_t ib = c->ops.size();
+    add_wconv1(c, L, WK_W16_C128, bo);
+    add_conv(c, t, bo);
+    retile_last(c, K_T320_1x1_K64_N128);
+    if (c->plan_error) return;
+    c->ops[ib] = half_tile_copy(c->ops[ib]);
+    mark_when(c, ib, 1);
+  } else if (c->latency_tiles || c->winograd_gen == 1) {
+    mark_when(c, ia, 2);
+    // a call of a few frames has 12 tiles per frame here: three dependent launches cost more latency than they save
+    // work, so small calls take the fused direct block instead (its weights sit in the blob next to the others)
+    add_f32_block(c, L, k, bo);
+    c->ops.back().when = 1;
+  }
+}
+
+static void build_f32_ops(fpc_ctx* c, const Layer* net, size_t* bo) {
+  const BKind l1kind = c->layer1_t816 ? BK_B816_s1_K64_C64 : BK_B1616_s1_K32_C64;
+  F32Kinds kinds[L_COUNT];
+  kinds[L_ENC10] = kinds[L_ENC11] = {K_T816_3x3_K64_N64, K_T816_1x1_K64_N64, l1kind};
+  kinds[L_ENC20] = {K_T620_3x3s2_K32_N128, K_T620_1x1_K64_N128, BK_B620_s2_K32_C128};
+  kinds[L_ENC21] = kinds[L_OUT0] = kinds[L_OUT1] = {K_T620_3x3_K64_N128, K_T620_1x1_K64_N128, BK_B620_s1_K64_C128};
+  kinds[L_DET0] = {K_T620_3x3_K64_N96, K_T620_1x1_K72_N96, BK_B620_s1_K64_C72};
+  kinds[L_DET1] = {K_T620_3x3_K72_N96, K_T620_1x1_K72_N96, BK_B620_s1_K72_C72};
+  kinds[L_IN0] = {K_T620_3x3s2_K32_N128, K_T620_1x1_K64_N128, BK_B320_s2_K32_C256};
+  kinds[L_IN1] = {K_T620_3x3_K64_N128, K_T620_1x1_K64_N128, BK_B320_s1_K64_C256};
+  kinds[L_UP] = {K_T620_2x2_K64_N128, K_COUNT, BK_COUNT};
+  for (int l = 0; l < layer_count(c); ++l) {
+    const Layer& L = net[l];
+    const F32Kinds& k = kinds[l];
+    if (l == L_UP) {
+      add_conv(c, upsample_spec(L, k.k3), bo);
+      retile_last(c, K_T320_2x2_K64_N128);
+    } else if (l == L_DET0 && !c->fuse_blocks) {
+      // detector.layer.0: the projection shortcut has K = 128 while conv2 has K = 72 (65 padded):
+      // run the shortcut as its own 1x1 and add it as the residual of conv2
+      add_conv(c, conv1_spec(L, k.k3), bo);
+      add_conv(c, shortcut_spec(L, K_T620_1x1_K64_N96, c->dproj), bo);
+      add_conv(c, conv2_spec(L, k.k1, c->dproj), bo);
+    } else if (l == L_IN1 && c->fuse_blocks && c->winograd && c->winograd_in1) {
+      add_f32_in1(c, L, k, bo);
+    } else {
+      add_f32_block(c, L, k, bo);
+    }
+    if (l == L_ENC20 && c->fuse_blocks) {
+      retile_last(c, BK_B320_s2_K32_C128);
+      retile_rows(c, BK_B416_s2_K32_C128);
+    }
+    if (l == L_IN0 && c->fuse_blocks) retile_last(c, BK_B310_s2_K32_C256);
+    if (l == L_DET1) push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
+  }
+}
+
 static int build_plan(fpc_ctx* c) {
   if (c->vgg) return build_vgg_plan(c);
   const int H = c->H, W = c->W, B = c->B;
   const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, Hc = H / 8, Wc = W / 8, H16 = H / 16, W16 = W / 16;
-  const bool de = c->cfg.descriptor_enabled != 0;
   // ---- carve the slab: this network's activations, then what both networks share
   Carver cv;
   cv.zones = &c->guards;
@@ -1739,178 +1823,11 @@ static int build_plan(fpc_ctx* c) {
     bo += 64;
     push_op(c, OP_POOL, "encoder.max_pool");
   }
-  auto block = [&](const std::string& p, Kind k3, Kind k1, int stride, const float* x, int csx, int cin, int cinp,
-                   int Hx, int Wx, float* h, int csh, int cout, int coutp, float* y, int csy, bool proj,
-                   bool desc, BKind bk = BK_COUNT) {
-    if (c->fuse_blocks && bk != BK_COUNT) {
-      const BlockSpec bs{p, bk, x, csx, cin, cinp, Hx, Wx, y, csy, cout, coutp, proj, desc};
-      WKind wk = WK_COUNT;
-      if (c->winograd && stride == 1) {
-        // generation 3's projection pass walks x in 16-channel steps, 4 or 8 per pass (wblock36_mfma.h: gemm_over advances
-        // by 4): k8_x = cinp / 8 must be a multiple of 8, i.e. cinp of 64 -- true of every layer of both networks; a
-        // layer that is not falls back to generation 2 instead of running extra K steps over stale staging rows
-        const int gen = c->winograd_gen == 3 && (!w36_fits(c->B, Hx, Wx, csx, csy) || (proj && cinp % 64 != 0)) ? 2 : c->winograd_gen;
-        if (cinp % 32 == 0 && cout == 64) wk = gen == 3 ? w36_kind(64, Hx, Wx, c->w36_paired) : gen == 2 ? WK_W16_C64 : WK_W816_K32_C64;
-        else if (cinp % 32 == 0 && cout == 128) wk = gen == 3 ? w36_kind(128, Hx, Wx) : gen == 2 ? WK_W16_C128 : WK_W816_K32_C128;
-        else if (c->winograd_det && cout == 65 && c->winograd_det_gen3 && c->winograd_gen == 3 && w36_fits(c->B, Hx, Wx, csx, csy) &&
-                 (cin == 65 ? !proj : (cin == cinp && cinp % 64 == 0 && cinp <= 256)))
-          wk = w36_kind(65, Hx, Wx, c->w36_paired);
-        else if (c->winograd_det && cinp % 32 == 0 && coutp == 72) wk = WK_W816_K32_C72;
-        else if (c->winograd_det && cinp == 72 && coutp == 72) wk = WK_W816_K24_C72;
-      }
-      if (wk != WK_COUNT)
-        add_wblock(c, bs, wk, &bo);
-      else
-        add_block(c, bs, &bo);
-      return;
-    }
-    const int Ho = Hx / stride, Wo = Wx / stride;
-    ConvSpec s{};
-    s.name = p + ".conv1+bn1+relu";
-    s.kind = k3; s.ksize = 3; s.stride = stride;
-    s.in0 = x; s.cs0 = csx; s.cin0 = cin; s.cin0_pad = cinp; s.H0 = Hx; s.W0 = Wx;
-    s.out = h; s.cso = csh; s.cout = cout; s.nstore = coutp; s.Ho = Ho; s.Wo = Wo; s.relu = 1;
-    s.desc_branch = desc;
-    add_conv(c, s, &bo);
-    ConvSpec t{};
-    t.name = p + (proj ? ".conv2+bn2+proj+relu" : ".conv2+bn2+identity+relu");
-    t.kind = k1; t.ksize = 1; t.stride = 1;
-    t.in0 = h; t.cs0 = csh; t.cin0 = cout; t.cin0_pad = coutp; t.H0 = Ho; t.W0 = Wo;
-    if (proj) {
-      t.in1 = x; t.cs1 = csx; t.cin1 = cin; t.cin1_pad = cinp; t.s1 = stride; t.H1 = Hx; t.W1 = Wx;
-    } else {
-      t.res = x; t.csr = csx;
-    }
-    t.out = y; t.cso = csy; t.cout = cout; t.nstore = coutp; t.Ho = Ho; t.Wo = Wo; t.relu = 1;
-    t.desc_branch = desc;
-    add_conv(c, t, &bo);
-  };
-  float* feat = c->cat + 128;  // encoder output lives in channels 128..255 of `cat`
-  if (c->bf16 || c->split) {
-    if (c->bf16) build_bf16_ops(c, &bo);
-    else build_x3_ops(c, &bo);
-    goto postproc;
-  }
-  {
-  const BKind l1kind = c->layer1_t816 ? BK_B816_s1_K64_C64 : BK_B1616_s1_K32_C64;
-  block("encoder.layer1.0", K_T816_3x3_K64_N64, K_T816_1x1_K64_N64, 1, c->x0, 64, 64, 64, H4, W4, c->h4, 64, 64, 64,
-        c->x1, 64, true, false, l1kind);
-  block("encoder.layer1.1", K_T816_3x3_K64_N64, K_T816_1x1_K64_N64, 1, c->x1, 64, 64, 64, H4, W4, c->h4, 64, 64, 64,
-        c->x2, 64, false, false, l1kind);
-  block("encoder.layer2.0", K_T620_3x3s2_K32_N128, K_T620_1x1_K64_N128, 2, c->x2, 64, 64, 64, H4, W4, c->h8, 128,
-        128, 128, c->x3, 128, true, false, BK_B620_s2_K32_C128);
-  if (c->fuse_blocks) retile_last(c, BK_B320_s2_K32_C128);
-  if (c->fuse_blocks) retile_rows(c, BK_B416_s2_K32_C128);
-  block("encoder.layer2.1", K_T620_3x3_K64_N128, K_T620_1x1_K64_N128, 1, c->x3, 128, 128, 128, Hc, Wc, c->h8, 128,
-        128, 128, feat, 256, false, false, BK_B620_s1_K64_C128);
-  if (c->fuse_blocks) {
-    const BlockSpec bs{"detector.layer.0", BK_B620_s1_K64_C72, feat, 256, 128, 128, Hc, Wc, c->d0, 72, 65, 72, true, false};
-    if (c->winograd && c->winograd_det)
-      add_wblock(c, bs, c->winograd_det_gen3 && c->winograd_gen == 3 && w36_fits(c->B, Hc, Wc, 256, 72) ? w36_kind(65, Hc, Wc, c->w36_paired) : WK_W816_K32_C72, &bo);
-    else add_block(c, bs, &bo);
-  } else {  // detector.layer.0: the projection shortcut has K = 128 while conv2 has K = 72 (65 padded):
-     // run the shortcut as its own 1x1 and add it as the residual of conv2
-    ConvSpec s{};
-    s.name = "detector.layer.0.conv1+bn1+relu";
-    s.kind = K_T620_3x3_K64_N96; s.ksize = 3; s.stride = 1;
-    s.in0 = feat; s.cs0 = 256; s.cin0 = 128; s.cin0_pad = 128; s.H0 = Hc; s.W0 = Wc;
-    s.out = c->dh; s.cso = 72; s.cout = 65; s.nstore = 72; s.Ho = Hc; s.Wo = Wc; s.relu = 1;
-    add_conv(c, s, &bo);
-    ConvSpec p{};
-    p.name = "detector.layer.0.identity_downsample";
-    p.kind = K_T620_1x1_K64_N96; p.ksize = 1; p.stride = 1;
-    p.in0 = feat; p.cs0 = 256; p.cin0 = 128; p.cin0_pad = 128; p.H0 = Hc; p.W0 = Wc;
-    p.out = c->dproj; p.cso = 72; p.cout = 65; p.nstore = 72; p.Ho = Hc; p.Wo = Wc; p.relu = 0;
-    add_conv(c, p, &bo);
-    ConvSpec t{};
-    t.name = "detector.layer.0.conv2+bn2+shortcut+relu";
-    t.kind = K_T620_1x1_K72_N96; t.ksize = 1; t.stride = 1;
-    t.in0 = c->dh; t.cs0 = 72; t.cin0 = 65; t.cin0_pad = 72; t.H0 = Hc; t.W0 = Wc;
-    t.res = c->dproj; t.csr = 72;
-    t.out = c->d0; t.cso = 72; t.cout = 65; t.nstore = 72; t.Ho = Hc; t.Wo = Wc; t.relu = 1;
-    add_conv(c, t, &bo);
-  }
-  block("detector.layer.1", K_T620_3x3_K72_N96, K_T620_1x1_K72_N96, 1, c->d0, 72, 65, 72, Hc, Wc, c->dh, 72, 65, 72,
-        c->lg, 72, false, false, BK_B620_s1_K72_C72);
-  push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
-  if (de) {
-    block("descriptor.layer_in.0", K_T620_3x3s2_K32_N128, K_T620_1x1_K64_N128, 2, feat, 256, 128, 128, Hc, Wc, c->h16,
-          256, 256, 256, c->y16a, 256, true, true, BK_B320_s2_K32_C256);
-    if (c->fuse_blocks) retile_last(c, BK_B310_s2_K32_C256);
-    if (c->fuse_blocks && c->winograd && c->winograd_in1) {
-      // 256 channels are too wide for the fused Winograd block (accumulators): conv1 as two conv-only Winograd
-      // launches of 128 output channels each, then conv2 + identity + ReLU as a 1x1 launch (h makes one round trip)
-      const std::string p = "descriptor.layer_in.1";
-      // Generation 3: FOUR parts of 64 channels (the NB = 1 instance, gridDim.y = 4).  A 30 x 40 map is 6 tiles per
-      // frame: 192 tiles x 2 halves were 384 one-tile workgroups = 1.5 rounds of the 256 CUs at the 128-channel tile's
-      // time; 192 x 4 = 768 half-as-long tiles are 3 full rounds (64 workgroups per part walk 3 tiles each).
-      const bool g3 = c->winograd_gen == 3 && w36_fits(c->B, H16, W16, 256, 256);
-      const int in1_parts = g3 ? 4 : 2;
-      for (int n0 = 0; n0 < 256; n0 += 256 / in1_parts)
-        add_wconv(c, p, true, g3 ? w36_kind(64, H16, W16, c->w36_paired, c->tiles_round6) : c->winograd_gen >= 2 ? WK_W16_C128 : WK_W816_K32_C128, c->y16a, 256, 256, H16, W16, c->h16, 256, 256, n0, true, &bo);
-      const size_t in1_ops = in1_parts + 1;      // [the launch, its shadows, the 1x1 below]
-      ConvSpec t{};
-      t.name = p + ".conv2+bn2+identity+relu";
-      t.kind = K_T620_1x1_K64_N128; t.ksize = 1; t.stride = 1;
-      t.in0 = c->h16; t.cs0 = 256; t.cin0 = 256; t.cin0_pad = 256; t.H0 = H16; t.W0 = W16;
-      t.res = c->y16a; t.csr = 256;
-      t.out = c->y16b; t.cso = 256; t.cout = 256; t.nstore = 256; t.Ho = H16; t.Wo = W16; t.relu = 1;
-      t.desc_branch = true;
-      add_conv(c, t, &bo);
-      retile_last(c, K_T320_1x1_K64_N128);
-      if (g_wkinds[c->ops[c->ops.size() - in1_ops].wkind].gen == 2 && c->latency_tiles) {
-        // calls of a few frames: the same two-half launch on 4 x 16 tiles (24 tiles x 2 halves per frame instead of
-        // 12 x 2), then the same 1x1 -- 0.10 ms for one frame against 0.16 ms for the fused direct block on 20 tiles
-        const size_t ia = c->ops.size() - in1_ops;   // [two-half launch, its shadow, 1x1]
-        c->ops[ia].when = 2;
-        Op oh = c->ops[ia];
-        oh.when = 1;
-        oh.wkind = WK_W16_C128H;
-        oh.wargs.tiles_y = (H16 + 3) / 4;
-        oh.mfma_flops_per_frame = 2 * 2.0 * oh.wargs.tiles_x * oh.wargs.tiles_y * 128.0 * (16.0 * 16 * 256);
-        const fpc_ctx::ConvW cwa = c->convw[ia];
-        c->ops.insert(c->ops.begin() + ia + 1, oh);
-        c->convw.insert(c->convw.begin() + ia + 1, cwa);
-      } else if (g_wkinds[c->ops[c->ops.size() - in1_ops].wkind].gen == 3 && c->latency_tiles) {
-        // generation 3's fragments have 36 positions: the small-call variant (generation 2 on 4 x 16 tiles, then the same
-        // 1x1) gets fragments of its own
-        for (size_t k = c->ops.size() - in1_ops; k < c->ops.size(); ++k) c->ops[k].when = 2;
-        const size_t ib = c->ops.size();
-        for (int n0 = 0; n0 < 256; n0 += 128)
-          add_wconv(c, p, true, WK_W16_C128, c->y16a, 256, 256, H16, W16, c->h16, 256, 256, n0, true, &bo);
-        add_conv(c, t, &bo);
-        retile_last(c, K_T320_1x1_K64_N128);
-        Op& oh = c->ops[ib];
-        oh.wkind = WK_W16_C128H;
-        oh.wargs.tiles_y = (H16 + 3) / 4;
-        oh.mfma_flops_per_frame = 2 * 2.0 * oh.wargs.tiles_x * oh.wargs.tiles_y * 128.0 * (16.0 * 16 * 256);
-        for (size_t k = ib; k < c->ops.size(); ++k) c->ops[k].when = 1;
-      } else if (c->latency_tiles || c->winograd_gen == 1) {
-      for (size_t k = c->ops.size() - in1_ops; k < c->ops.size(); ++k) c->ops[k].when = 2;
-      // a call of a few frames has 12 tiles per frame here: three dependent launches cost more latency than they save
-      // work, so small calls take the fused direct block instead (its weights sit in the blob next to the others)
-      block("descriptor.layer_in.1", K_T620_3x3_K64_N128, K_T620_1x1_K64_N128, 1, c->y16a, 256, 256, 256, H16, W16,
-            c->h16, 256, 256, 256, c->y16b, 256, false, true, BK_B320_s1_K64_C256);
-      c->ops.back().when = 1;
-      }
-    } else
-    block("descriptor.layer_in.1", K_T620_3x3_K64_N128, K_T620_1x1_K64_N128, 1, c->y16a, 256, 256, 256, H16, W16,
-          c->h16, 256, 256, 256, c->y16b, 256, false, true, BK_B320_s1_K64_C256);
-    ConvSpec u{};
-    u.name = "descriptor.up_sample+bn+relu";
-    u.kind = K_T620_2x2_K64_N128; u.ksize = 2; u.stride = 1;
-    u.in0 = c->y16b; u.cs0 = 256; u.cin0 = 256; u.cin0_pad = 256; u.H0 = H16; u.W0 = W16;
-    u.out = c->cat; u.cso = 256; u.cout = 128; u.nstore = 128; u.Ho = Hc; u.Wo = Wc; u.relu = 1;
-    u.desc_branch = true;
-    add_conv(c, u, &bo);
-    retile_last(c, K_T320_2x2_K64_N128);
-    block("descriptor.layer_out.0", K_T620_3x3_K64_N128, K_T620_1x1_K64_N128, 1, c->cat, 256, 256, 256, Hc, Wc,
-          c->lo_h, 128, 128, 128, c->lo0, 128, true, true, BK_B620_s1_K64_C128);
-    block("descriptor.layer_out.1", K_T620_3x3_K64_N128, K_T620_1x1_K64_N128, 1, c->lo0, 128, 128, 128, Hc, Wc,
-          c->lo_h, 128, 128, 128, c->desc_map, 128, false, true, BK_B620_s1_K64_C128);
-  }
-  }
-postproc:
+  Layer net[L_COUNT];
+  python_layers(c, net);
+  if (c->bf16) build_bf16_ops(c, net, &bo);
+  else if (c->split) build_x3_ops(c, net, &bo);
+  else build_f32_ops(c, net, &bo);
   if (int rc = finish_plan(c, bo)) return rc;
   c->stem.wfrag = reinterpret_cast<const float4*>(c->blob + c->stem_w_off);
   c->stem.bias = c->blob + c->stem_b_off;
@@ -1923,6 +1840,7 @@ postproc:
   c->stem2 = c->stem_lean && !c->bf16 && !c->split && !c->vgg && (c->fuse_stem_pool || c->cin == 1) && H2 % 2 == 0 && W2 % STEM_T == 0;
   return FPC_OK;
 }
+
 
 // ---- the packed blob's tag ----------------------------------------------------------------
 // The first 16 words of the blob describe what packed it, so that a blob that travels (fpc_export_packed ->
@@ -1946,8 +1864,8 @@ static uint64_t plan_hash(const fpc_ctx* c) {
     mix((uint64_t)(op.phase + 1)); mix((uint64_t)op.n0);
     for (char ch : op.prefix) mix((uint64_t)(unsigned char)ch);
     const fpc_ctx::ConvW& cw = c->convw[i];
-    for (int z = 0; z < 4; ++z) mix(cw.w_off[z]);
-    mix(cw.b_off); mix(cw.b2_off);
+    for (int z = 0; z < 4; ++z) mix(cw.w[z].off);
+    mix(cw.b.off); mix(cw.b2.off);
   }
   return h;
 }
@@ -2018,9 +1936,9 @@ static void pack_w36_winograd(const std::vector<double>& U, int nn, int ci, cons
 // ---- generation-2 Winograd fragments (wblock16_mfma.h) ---------------------------------------------
 // U: [nn][ci][16] Winograd-domain filters (scaled); dst: [channel group][chunk of 16][position][lane] float4 with
 // lane (n = l & 15, kq = l >> 4) holding { U[16 cg + n][16 chunk + 4 kq + j][pos] }, j = 0..3; WPAD zero steps per group.
-static void pack_w16_winograd(const std::vector<double>& U, int nn, int ci, int ncg, int nchunk, float* dst) {
-  const size_t gstride = ((size_t)nchunk * 16 + W16Cfg<8>::WPAD) * 256;
-  for (int cg = 0; cg < ncg; ++cg)
+static void pack_w16_winograd(const std::vector<double>& U, int nn, int ci, const WKindInfo& k, int nchunk, float* dst) {
+  const size_t gstride = w1_floats(k, nchunk) / k.NCG;
+  for (int cg = 0; cg < k.NCG; ++cg)
     for (int ch = 0; ch < nchunk; ++ch)
       for (int xi = 0; xi < 16; ++xi)
         for (int lane = 0; lane < 64; ++lane) {
@@ -2034,10 +1952,11 @@ static void pack_w16_winograd(const std::vector<double>& U, int nn, int ci, int 
 }
 
 // 1x1 over [h | x]: sources concatenated along K (each a multiple of 16 channels); dst [channel group][step of 16][lane] float4
-static void pack_w16_1x1(const std::vector<PackSource>& srcs, int cout, int ncg, float* dst) {
+static void pack_w16_1x1(const std::vector<PackSource>& srcs, int cout, const WKindInfo& k, float* dst) {
   size_t steps = 0;
   for (auto& s : srcs) steps += (size_t)s.cin_pad / 16;
-  const size_t gstride = (steps + W16Cfg<8>::WPAD) * 256;
+  const int ncg = k.NCG;
+  const size_t gstride = w2_floats(k, (int)(2 * steps)) / ncg;
   size_t step0 = 0;
   for (auto& s : srcs) {
     for (int g = 0; g < s.cin_pad / 16; ++g)
@@ -2080,7 +1999,25 @@ struct Packer {
     return m.at(k).data;
   }
   float* at(size_t off) const { return c->host_blob.data() + off; }
-  void put(const std::vector<float>& frag, size_t off) const { memcpy(at(off), frag.data(), frag.size() * sizeof(float)); }
+  // Writes into an op's region are refused where they are longer than the region: the plan's size function and the packer
+  // disagree, and the floats behind the region are another fragment's.  (Never on a correct plan; a load error, not a
+  // corrupted neighbour.)
+  int fits(const Op& op, const Region& r, size_t n) const {
+    if (n <= r.len) return FPC_OK;
+    *missing = "internal: " + op.name + " packs " + std::to_string(n) + " floats into a region of " + std::to_string(r.len);
+    return FPC_E_INVALID;
+  }
+  int put(const Op& op, const std::vector<float>& frag, const Region& r) const {
+    if (int rc = fits(op, r, frag.size())) return rc;
+    memcpy(at(r.off), frag.data(), frag.size() * sizeof(float));
+    return FPC_OK;
+  }
+  template <typename F>
+  int fill(const Op& op, const Region& r, int n, F v) const {   // v(0) .. v(n - 1): a bias vector
+    if (int rc = fits(op, r, (size_t)std::max(n, 0))) return rc;
+    for (int i = 0; i < n; ++i) at(r.off)[i] = (float)v(i);
+    return FPC_OK;
+  }
 };
 
 // A ResNetBlock's checkpoint entries under `p`: conv1, conv2, the optional projection shortcut, their folded BatchNorms
@@ -2130,17 +2067,8 @@ static void pack_w8_winograd(const std::vector<double>& U, int nn, int ci, const
 // Winograd-domain filters U of output channels 0 .. nn - 1 in the layout of the op's generation
 static void pack_winograd(const std::vector<double>& U, int nn, int ci, const WKindInfo& k, int nchunk, float* dst) {
   if (k.gen == 3) pack_w36_winograd(U, nn, ci, k, nchunk, dst);
-  else if (k.gen == 2) pack_w16_winograd(U, nn, ci, k.NCG, nchunk, dst);
+  else if (k.gen == 2) pack_w16_winograd(U, nn, ci, k, nchunk, dst);
   else pack_w8_winograd(U, nn, ci, k, nchunk, dst);
-}
-
-// ConvTranspose2d(k3, s2, p1, op1): the (ky, kx) of output-parity phase `ph`, in the order add_conv / add_fconvT laid its taps out
-static std::vector<std::pair<int, int>> convt_phase_taps(int ph) {
-  const int py = ph >> 1, px = ph & 1;
-  std::vector<std::pair<int, int>> taps;
-  for (int iy = 0; iy < (py ? 2 : 1); ++iy)
-    for (int ix = 0; ix < (px ? 2 : 1); ++ix) taps.push_back({py ? (iy == 0 ? 0 : 2) : 1, px ? (ix == 0 ? 0 : 2) : 1});
-  return taps;
 }
 
 // superpoint::SPModel: Conv2d weights + biases, no BatchNorm (cpp/src/model.cc:4-58) -- every layer that is not a
@@ -2169,11 +2097,11 @@ static int pack_vgg_convs(const Packer& pk) {
     PackSource src{ci, ci, kk, [&](int n, int cc, int t) { return (double)w[((size_t)n * ci + cc) * kk + t]; }, &ones};
     if (op.type == OP_BF16) {
       const FKindInfo& k = g_fkinds[op.fkind];
-      pk.put(pack_conv_bf16({src}, co, k.WN * k.NB, k.KC, k.planes, &pk.range_bad), cw.w_off[0]);
+      if (int rc = pk.put(op, pack_conv_bf16({src}, co, k.WN * k.NB, k.KC, k.planes, &pk.range_bad), cw.w[0])) return rc;
     } else {
-      pk.put(pack_conv({src}, co, op.args.nbt, g_kinds[op.kind].KC), cw.w_off[0]);
+      if (int rc = pk.put(op, pack_conv({src}, co, op.args.nbt, g_kinds[op.kind].KC), cw.w[0])) return rc;
     }
-    for (int n = 0; n < co; ++n) pk.at(cw.b_off)[n] = bv[n];
+    if (int rc = pk.fill(op, cw.b, co, [&](int n) { return bv[n]; })) return rc;
   }
   return FPC_OK;
 }
@@ -2255,22 +2183,28 @@ static int pack_wblock(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw)
       return FPC_E_MISSING_KEY;
     }
     const int nn = std::min(k.CMID, co - op.n0);
-    pack_winograd(winograd_filters(w1, op.n0, nn, ci, f1.s, P), nn, ci, k, a.nchunk, pk.at(cw.w_off[0]));
-    for (int n = 0; n < nn; ++n) pk.at(cw.b_off)[n] = (float)f1.t[op.n0 + n];
-    return FPC_OK;
+    if (int rc = pk.fits(op, cw.w[0], w1_floats(k, a.nchunk))) return rc;
+    pack_winograd(winograd_filters(w1, op.n0, nn, ci, f1.s, P), nn, ci, k, a.nchunk, pk.at(cw.w[0].off));
+    return pk.fill(op, cw.b, nn, [&](int n) { return f1.t[op.n0 + n]; });
   }
   BlockWeights b;
   if (!load_block(pk, p, ci, co, a.k8_x > 0, &b)) return FPC_E_MISSING_KEY;
   // U = G (g * s) G^T in double, rounded once
   const std::vector<double> U = winograd_filters(b.w1, 0, co, ci, b.f1.s, P);
-  pack_winograd(U, co, ci, k, a.nchunk, pk.at(cw.w_off[0]));
-  for (int n = 0; n < std::min(co, nbt * 32); ++n) pk.at(cw.b_off)[n] = (float)b.f1.t[n];
+  if (int rc = pk.fits(op, cw.w[0], w1_floats(k, a.nchunk))) return rc;
+  pack_winograd(U, co, ci, k, a.nchunk, pk.at(cw.w[0].off));
+  if (int rc = pk.fill(op, cw.b, std::min(co, nbt * 32), [&](int n) { return b.f1.t[n]; })) return rc;
   const std::vector<PackSource> srcs = block_1x1_sources(b, ci, co, a.k8_h * 8, a.k8_x * 8);
-  if (k.gen >= 2) pack_w16_1x1(srcs, co, k.NCG, pk.at(cw.w_off[1]));
-  else pk.put(pack_conv(srcs, co, nbt, 8), cw.w_off[1]);
-  for (int n = 0; n < std::min(co, nbt * 32); ++n) pk.at(cw.b2_off)[n] = (float)b.bias[n];
+  if (k.gen >= 2) {
+    if (int rc = pk.fits(op, cw.w[1], w2_floats(k, a.k8_h + a.k8_x))) return rc;
+    pack_w16_1x1(srcs, co, k, pk.at(cw.w[1].off));
+  } else if (int rc = pk.put(op, pack_conv(srcs, co, nbt, 8), cw.w[1])) {
+    return rc;
+  }
+  if (int rc = pk.fill(op, cw.b2, std::min(co, nbt * 32), [&](int n) { return b.bias[n]; })) return rc;
   if (k.dust) {   // the 65th channel's weights (W36Dust, wblock36_mfma.h)
-    float* d = pk.at(cw.w_off[2]);
+    if (int rc = pk.fits(op, cw.w[2], (size_t)W36Dust::floats(a.nchunk))) return rc;
+    float* d = pk.at(cw.w[2].off);
     for (int n = 0; n < 64; ++n) d[W36Dust::W2ROW + n] = (float)((double)b.w2[(size_t)n * co + 64] * b.f2.s[n]);
     for (int kk = 0; kk < 65; ++kk) d[W36Dust::W2COL + kk] = (float)((double)b.w2[(size_t)64 * co + kk] * b.f2.s[64]);
     if (b.wp)
@@ -2307,20 +2241,19 @@ static int pack_fblock(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw)
       PackSource s{ci, ci, 9,
                    [&](int n, int cc, int t) { return (double)w[((cc * 128 + n) * 3 + ConvTTaps::ky(t)) * 3 + ConvTTaps::kx(t)]; },
                    &f.s};
-      pk.put(pack_conv_bf16({s}, co, k.CMIDP / 32, 16, 1, &pk.range_bad), cw.w_off[0]);
+      if (int rc = pk.put(op, pack_conv_bf16({s}, co, k.CMIDP / 32, 16, 1, &pk.range_bad), cw.w[0])) return rc;
     } else {
-      const std::vector<std::pair<int, int>> taps = convt_phase_taps(op.phase);
+      const std::vector<ConvTTap> taps = convt_phase_taps(op.phase);
       PackSource s{ci, a.nchunk * k.KC, (int)taps.size(),
-                   [&](int n, int cc, int t) { return (double)w[((cc * 128 + n) * 3 + taps[t].first) * 3 + taps[t].second]; },
+                   [&](int n, int cc, int t) { return (double)w[((cc * 128 + n) * 3 + taps[t].ky) * 3 + taps[t].kx]; },
                    &f.s};
-      pk.put(pack_conv_bf16({s}, co, nbt, k.KC, k.planes, &pk.range_bad), cw.w_off[0]);
+      if (int rc = pk.put(op, pack_conv_bf16({s}, co, nbt, k.KC, k.planes, &pk.range_bad), cw.w[0])) return rc;
     }
-    for (int n = 0; n < co; ++n) pk.at(cw.b_off)[n] = (float)((double)bct[n] * f.s[n] + f.t[n]);
-    return FPC_OK;
+    return pk.fill(op, cw.b, co, [&](int n) { return (double)bct[n] * f.s[n] + f.t[n]; });
   }
   BlockWeights b;
   if (!load_block(pk, p, ci, co, a.k16_x > 0, &b)) return FPC_E_MISSING_KEY;
-  const bool sc_in_w1 = k.planes == 1;   // (add_fblock)
+  const bool sc_in_w1 = k.planes == 1;   // (as add_fblock laid the regions out)
   const std::vector<double> ones(co, 1.0);
   // taps 0..8: conv1 x bn1's scale; tap 9 (FPC_BF16): the shortcut on the same channels -- the projection x its bn's
   // scale, or the unit matrix
@@ -2330,12 +2263,12 @@ static int pack_fblock(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw)
                   return b.wp ? (double)b.wp[(size_t)n * ci + c_] * b.fp.s[n] : (n == c_ ? 1.0 : 0.0);
                 },
                 &ones};
-  pk.put(pack_conv_bf16({s1}, co, nbt, k.KC, k.planes, &pk.range_bad), cw.w_off[0]);
-  for (int n = 0; n < co; ++n) pk.at(cw.b_off)[n] = (float)b.f1.t[n];
-  pk.put(pack_conv_bf16(block_1x1_sources(b, ci, co, a.k16_h * 16, sc_in_w1 ? 0 : a.k16_x * 16), co, nbt, 16, k.planes, &pk.range_bad),
-         cw.w_off[1]);
-  for (int n = 0; n < co; ++n) pk.at(cw.b2_off)[n] = (float)b.bias[n];
-  return FPC_OK;
+  if (int rc = pk.put(op, pack_conv_bf16({s1}, co, nbt, k.KC, k.planes, &pk.range_bad), cw.w[0])) return rc;
+  if (int rc = pk.fill(op, cw.b, co, [&](int n) { return b.f1.t[n]; })) return rc;
+  if (int rc = pk.put(op, pack_conv_bf16(block_1x1_sources(b, ci, co, a.k16_h * 16, sc_in_w1 ? 0 : a.k16_x * 16), co, nbt, 16, k.planes, &pk.range_bad),
+                      cw.w[1]))
+    return rc;
+  return pk.fill(op, cw.b2, co, [&](int n) { return b.bias[n]; });
 }
 
 static int pack_block(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw) {
@@ -2345,11 +2278,10 @@ static int pack_block(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw) 
   BlockWeights b;
   if (!load_block(pk, op.prefix, ci, co, a.k8_x > 0, &b)) return FPC_E_MISSING_KEY;
   PackSource s1{ci, a.nchunk * k.KC, 9, [&](int n, int c_, int t) { return (double)b.w1[((size_t)(n * ci + c_)) * 9 + t]; }, &b.f1.s};
-  pk.put(pack_conv({s1}, co, nbt, k.KC), cw.w_off[0]);
-  for (int n = 0; n < co; ++n) pk.at(cw.b_off)[n] = (float)b.f1.t[n];
-  pk.put(pack_conv(block_1x1_sources(b, ci, co, a.k8_h * 8, a.k8_x * 8), co, nbt, 8), cw.w_off[1]);
-  for (int n = 0; n < co; ++n) pk.at(cw.b2_off)[n] = (float)b.bias[n];
-  return FPC_OK;
+  if (int rc = pk.put(op, pack_conv({s1}, co, nbt, k.KC), cw.w[0])) return rc;
+  if (int rc = pk.fill(op, cw.b, co, [&](int n) { return b.f1.t[n]; })) return rc;
+  if (int rc = pk.put(op, pack_conv(block_1x1_sources(b, ci, co, a.k8_h * 8, a.k8_x * 8), co, nbt, 8), cw.w[1])) return rc;
+  return pk.fill(op, cw.b2, co, [&](int n) { return b.bias[n]; });
 }
 
 // OP_CONV of the Python network: one half of an unfused block, the detector's separate shortcut, or the transposed
@@ -2370,18 +2302,18 @@ static int pack_conv_op(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw
     const float* bct = pk.need("descriptor.up_sample.bias", {128});
     if (!w || !bct || !fold_bn(m, "descriptor.bn", 128, &f, missing)) return FPC_E_MISSING_KEY;
     for (int ph = 0; ph < 4; ++ph) {
-      const std::vector<std::pair<int, int>> taps = convt_phase_taps(ph);
+      const std::vector<ConvTTap> taps = convt_phase_taps(ph);
       PackSource s{256, cin0p, (int)taps.size(),
-                   [&](int n, int ci, int t) { return (double)w[((ci * 128 + n) * 3 + taps[t].first) * 3 + taps[t].second]; },
+                   [&](int n, int ci, int t) { return (double)w[((ci * 128 + n) * 3 + taps[t].ky) * 3 + taps[t].kx]; },
                    &f.s};
-      pk.put(pack_conv({s}, 128, a.nbt, k.KC), cw.w_off[ph]);
+      if (int rc = pk.put(op, pack_conv({s}, 128, a.nbt, k.KC), cw.w[ph])) return rc;
     }
     for (int n = 0; n < 128; ++n) bias[n] = (double)bct[n] * f.s[n] + f.t[n];
   } else if (nm == "detector.layer.0.identity_downsample") {
     const float* w = pk.need("detector.layer.0.identity_downsample.0.weight", {65, 128, 1, 1});
     if (!w || !fold_bn(m, "detector.layer.0.identity_downsample.1", 65, &f, missing)) return FPC_E_MISSING_KEY;
     PackSource s{128, cin0p, 1, [&](int n, int ci, int) { return (double)w[n * 128 + ci]; }, &f.s};
-    pk.put(pack_conv({s}, 65, a.nbt, k.KC), cw.w_off[0]);
+    if (int rc = pk.put(op, pack_conv({s}, 65, a.nbt, k.KC), cw.w[0])) return rc;
     for (int n = 0; n < 65; ++n) bias[n] = f.t[n];
   } else if (dot != std::string::npos) {  // 3x3 conv1 + bn1
     const std::string p = nm.substr(0, dot);
@@ -2398,7 +2330,7 @@ static int pack_conv_op(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw
     }
     if (!fold_bn(m, p + ".bn1", co, &f, missing)) return FPC_E_MISSING_KEY;
     PackSource s{ci, cin0p, 9, [&](int n, int c_, int t) { return (double)w[((size_t)(n * ci + c_)) * 9 + t]; }, &f.s};
-    pk.put(pack_conv({s}, co, a.nbt, k.KC), cw.w_off[0]);
+    if (int rc = pk.put(op, pack_conv({s}, co, a.nbt, k.KC), cw.w[0])) return rc;
     for (int n = 0; n < co; ++n) bias[n] = f.t[n];
   } else if (dot2 != std::string::npos) {  // 1x1 conv2 + bn2 (+ projection shortcut as a second K source)
     const std::string p = nm.substr(0, dot2);
@@ -2432,13 +2364,12 @@ static int pack_conv_op(const Packer& pk, const Op& op, const fpc_ctx::ConvW& cw
       srcs.push_back({cip, cin1p, 1, [&, cip](int n, int c_, int) { return (double)wp[(size_t)n * cip + c_]; }, &fp.s});
       for (int n = 0; n < co; ++n) bias[n] += fp.t[n];
     }
-    pk.put(pack_conv(srcs, co, a.nbt, k.KC), cw.w_off[0]);
+    if (int rc = pk.put(op, pack_conv(srcs, co, a.nbt, k.KC), cw.w[0])) return rc;
   } else {
     *missing = "internal: unknown op " + nm;
     return FPC_E_INVALID;
   }
-  for (int n = 0; n < a.nbt * 32; ++n) pk.at(cw.b_off)[n] = (float)bias[n];
-  return FPC_OK;
+  return pk.fill(op, cw.b, a.nbt * 32, [&](int n) { return bias[n]; });
 }
 
 static int pack_all_impl(fpc_ctx* c, const TensorMap& m, std::string* missing, bool& range_bad) {

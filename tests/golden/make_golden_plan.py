@@ -8,7 +8,6 @@ four-frame fpc_forward.  Needs the GPU and a built libfpc.so (FPC_LIB_PATH picks
 Run it on the build whose plan is meant to be the pinned one: for a change that must not move the plan, that is the
 build of the commit BEFORE the change, never the changed one.
 """
-import json
 import os
 import sys
 
@@ -16,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 import fpc_amd  # noqa: E402,F401
-from tests.test_gpu_plan_pins import FIXTURE, cases, record  # noqa: E402
+from tests.test_gpu_plan_pins import FIXTURE, cases, dump_pins, record  # noqa: E402
 
 if __name__ == "__main__":
     out = sys.argv[1] if len(sys.argv) > 1 else FIXTURE
@@ -25,7 +24,5 @@ if __name__ == "__main__":
         pins[case[0]] = record(*case[1:])
         print(case[0], pins[case[0]]["plan_hash"], pins[case[0]]["packed_size"], len(pins[case[0]]["launches_1"]),
               len(pins[case[0]]["launches_4"]), flush=True)
-    with open(out, "w") as f:
-        json.dump(pins, f, indent=1, sort_keys=True)
-        f.write("\n")
+    dump_pins(pins, out)
     print("wrote", out, len(pins), "cases")

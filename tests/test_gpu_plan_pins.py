@@ -22,17 +22,61 @@ GEOMETRIES = ((32, 48), (160, 64))     # ragged tiles both ways; a 20-row 1/8 ma
 MAX_BATCH = 4
 DTYPES = {"resnet": ("f32", "bf16", "f32_split", "f32_split_f16"), "vgg": ("f32", "f32_split", "f32_split_f16")}
 F32_PLANS = ("winograd_gen1", "winograd_gen2", "no_fused_blocks", "tiles_round5")
+# Created with min_sub_batch = 2, so that the four-frame call is a LARGE call (n >= 2 * min_sub_batch) and launches the
+# large-call variants of the plan -- the default min_sub_batch of 8 makes both pinned calls of the cases above few-frame
+# calls.  (arch, dtype, plan flags, further Engine keyword arguments): the builder branches the cases above never enter.
+LARGE_CALL = (
+    [("resnet", "f32", (), {})] +
+    [("resnet", "f32", flags, {}) for flags in (
+        ("no_latency_tiles",), ("no_winograd",), ("no_winograd", "layer1_tile_8x16"), ("no_winograd_detector",),
+        ("no_winograd_layer_in1",), ("detector_gen1",), ("w36_one_wave",), ("conv_round1",), ("stem_round3",))] +
+    [("resnet", "f32", (), {"descriptor_enabled": False}), ("resnet", "f32", (), {"in_channels": 1}),
+     ("resnet", "bf16", (), {}), ("resnet", "bf16", ("convt_phases",), {}), ("resnet", "bf16", ("no_fused_softmax",), {}),
+     ("resnet", "bf16", (), {"descriptor_enabled": False}), ("resnet", "f32_split", (), {}),
+     ("vgg", "f32", (), {}), ("vgg", "f32", (), {"descriptor_enabled": False})])
 
 
 def cases():
-    """(id, arch, dtype, plan flag or None, height, width): the default plan of each architecture x dtype, and the
-    Python network's FPC_F32 plan under the flags that change its kernels or its blob, at both geometries."""
+    """(id, arch, dtype, plan flags, height, width, Engine keyword arguments): the default plan of each architecture x
+    dtype, the Python network's FPC_F32 plan under the flags that change its kernels or its blob, and the large-call
+    cases, at both geometries."""
     out = []
     for h, w in GEOMETRIES:
         for arch, dtypes in DTYPES.items():
-            out += [("%s-%s-%dx%d" % (arch, dt, h, w), arch, dt, None, h, w) for dt in dtypes]
-        out += [("resnet-f32-%s-%dx%d" % (flag, h, w), "resnet", "f32", flag, h, w) for flag in F32_PLANS]
+            out += [("%s-%s-%dx%d" % (arch, dt, h, w), arch, dt, (), h, w, {}) for dt in dtypes]
+        out += [("resnet-f32-%s-%dx%d" % (flag, h, w), "resnet", "f32", (flag,), h, w, {}) for flag in F32_PLANS]
+        for arch, dt, flags, kw in LARGE_CALL:
+            tags = list(flags) + ["%s_%d" % (k, int(v)) for k, v in sorted(kw.items())]
+            out.append(("-".join([arch, dt, "sub2"] + tags + ["%dx%d" % (h, w)]), arch, dt, flags, h, w,
+                        dict(kw, min_sub_batch=2)))
     return out
+
+
+def load_pins(path=FIXTURE):
+    """Case id -> record.  The file holds the records of the few-frame cases in full, as it always has; those of the
+    large-call cases sit under "large_call" with their launch lists as indexes into ONE table of (layer name, kernel
+    symbol) pairs -- the same lists, a line per case."""
+    with open(path) as f:
+        pins = json.load(f)
+    packed = pins.pop("large_call", {"launch_table": [], "cases": {}})
+    table = packed["launch_table"]
+    for cid, rec in packed["cases"].items():
+        pins[cid] = {k: [table[i] for i in v] if k.startswith("launches_") else v for k, v in rec.items()}
+    return pins
+
+
+def dump_pins(pins, path=FIXTURE):
+    """The inverse of load_pins (tests/golden/make_golden_plan.py)."""
+    large = {c[0] for c in cases() if "min_sub_batch" in c[6]}
+    table = sorted({tuple(l) for cid in large for k, v in pins[cid].items() if k.startswith("launches_") for l in v})
+    index = {l: i for i, l in enumerate(table)}
+    text = json.dumps({cid: rec for cid, rec in pins.items() if cid not in large}, indent=1, sort_keys=True)
+    rows = ["   %s: %s" % (json.dumps(cid), json.dumps(
+        {k: [index[tuple(l)] for l in v] if k.startswith("launches_") else v for k, v in pins[cid].items()}, sort_keys=True))
+        for cid in sorted(large)]
+    with open(path, "w") as f:
+        f.write(text[:text.rindex("}")].rstrip("\n") + ',\n "large_call": {\n  "launch_table": [\n' +
+                ",\n".join("   " + json.dumps(list(l)) for l in table) + '\n  ],\n  "cases": {\n' + ",\n".join(rows) + "\n  }\n }\n}\n")
 
 
 _cache = {}
@@ -44,16 +88,17 @@ def _shared(key, make, *args, **kw):
     return _cache[key]
 
 
-def record(arch, dtype, flag, h, w):
+def record(arch, dtype, flags, h, w, kw):
     """What the fixture holds for one case, from the library the package loads."""
     from fpc_amd.engine import Engine
 
     vgg = arch == "vgg"
-    eng = Engine(h, w, max_batch=MAX_BATCH, in_channels=1 if vgg else 3, dtype=dtype, arch=arch,
-                 plan_flags=[flag] if flag else ())
+    kw = dict(kw)
+    cin = kw.pop("in_channels", 1 if vgg else 3)
+    eng = Engine(h, w, max_batch=MAX_BATCH, in_channels=cin, dtype=dtype, arch=arch, plan_flags=list(flags), **kw)
     try:
         eng.load_state_dict(_shared(("sd", arch), synth.make_vgg_state_dict if vgg else synth.make_state_dict, seed=0))
-        frames = _shared(("frames", vgg, h, w), synth.make_batch, 11, MAX_BATCH, h, w, gray=vgg)[:, :1 if vgg else 3].copy()
+        frames = _shared(("frames", cin == 1, h, w), synth.make_batch, 11, MAX_BATCH, h, w, gray=cin == 1)[:, :cin].copy()
         rec = {"plan_hash": "%016x" % eng.plan_hash(), "packed_size": int(eng.packed_size()),
                "blob_sha256": hashlib.sha256(eng.export_packed().tobytes()).hexdigest()}
         for n in (1, MAX_BATCH):
@@ -69,8 +114,7 @@ def record(arch, dtype, flag, h, w):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", cases(), ids=lambda c: c[0])
 def test_plan_pins(case):
-    with open(FIXTURE) as f:
-        want = json.load(f)[case[0]]
+    want = _shared("pins", load_pins)[case[0]]
     got = record(*case[1:])
     for key in want:
         assert got[key] == want[key], "%s: %s differs from tests/golden/plan_pins.json" % (case[0], key)
