@@ -414,6 +414,15 @@ static int w36_frames_per_launch(int H, int W, int cs_in, int cs_out) {
   const unsigned long long fb = (unsigned long long)H * W * (unsigned long long)std::max(cs_in, cs_out) * sizeof(float);
   return (int)std::max<unsigned long long>(1, ((unsigned long long)W36_MARKER - 1) / fb);
 }
+// Generation 2 (wblock16_kernel) reads its input through ONE buffer descriptor that starts at the tensor's frame 0, with
+// unsigned 32-bit byte offsets (wblock16_mfma.h: load_halo; launch_wblock clamps the descriptor's range to W16_REACH): a
+// frame that ends beyond W16_REACH bytes would read zeros or, past 2^32, the pixels of an earlier frame.  The Python
+// network's widest generation-2 input has 16 bytes per frame pixel, which fpc_create's 2^28-pixel limit keeps in reach;
+// the C++ network's full-resolution layers have 256.  The frames of an H x W tensor with `cs` channels that are in reach:
+static const unsigned long long W16_REACH = 0xfffffff0ull;
+static int w16_frames_in_reach(int H, int W, int cs) {
+  return (int)std::min<unsigned long long>(1u << 30, W16_REACH / ((unsigned long long)H * W * cs * sizeof(float)));
+}
 // conv-only layers wider than one instance: two 128-channel parts or four 64-channel ones (NB = 1 tiles take 0.53 of an
 // NB = 2 tile's time) -- whichever needs fewer tile times on `cus` CUs for `tiles` tiles per part
 static int w36_conv_part(int cout, int tiles, int cus) {
@@ -581,7 +590,8 @@ struct fpc_ctx {
   int H = 0, W = 0, B = 0, Hc = 0, Wc = 0;
   bool vgg = false;                  // cfg.arch == FPC_ARCH_VGG: superpoint::SPModel (cpp/src/model.cc)
   int D = 128;                       // descriptor length: 128 (python net) / 256 (C++ net, settings.h:25)
-  std::vector<float*> vbuf;          // VGG activation buffers
+  struct VTap { const char* name; const float* p; int cs, C, H, W; };   // a tensor of the C++ network: buffer, channel stride, shape
+  std::vector<VTap> vtaps;           // ... by the reference's module names (build_vgg_plan; fpc_read_activation)
   size_t vconv0_off = 0;
   bool bf16 = false;                 // cfg.dtype == FPC_BF16
   bool split = false;                // cfg.dtype == FPC_F32_SPLIT or FPC_F32_SPLIT_F16
@@ -603,6 +613,7 @@ struct fpc_ctx {
   bool nms_aside = true;             // FPC_NMS_ASIDE=0: NMS in line on the sub-batch stream
   bool split_heads = false;          // FPC_SPLIT_HEADS=1: detector head + NMS of a sub-batch on a side stream next to its descriptor head
   hipEvent_t ev_fork = nullptr;
+  int small_reach = 1 << 30;         // the C++ network: the largest call the latency plan's generation-2 launches can address (build_vgg_plan)
   int min_sub = 8;                   // smallest sub-batch worth its own stream (FPC_MIN_SUB); calls below twice this take the latency plan
   int num_cus = 256;
   int fkind_blocks_per_cu[64] = {};   // resident workgroups per CU of every bf16 / split-operand instance (fpc_create)
@@ -1544,6 +1555,17 @@ static void add_fconv(fpc_ctx* c, FKind kind, const std::string& prefix, const f
 static int build_vgg_plan(fpc_ctx* c) {
   const int H = c->H, W = c->W, B = c->B, Hc = H / 8, Wc = W / 8;
   const size_t npix8 = (size_t)B * Hc * Wc;
+  if (!c->split && c->winograd) {
+    // Where generation 2 runs the full-resolution 64-channel layers -- this network's widest tensors, 256 bytes per frame
+    // pixel -- every frame it is handed must lie in its reach (w16_frames_in_reach).  A plan that runs it in every call
+    // (FPC_PLAN_WINOGRAD_GEN2; generation 3 with a frame too large for W36_MARKER) addresses the whole batch from frame 0:
+    // refused here, before anything is allocated, where max_batch frames do not fit.  The default plan runs it only in
+    // calls of a few frames, from the call's frame 0: a call of more frames than fit takes the batch plan instead.
+    const int reach = w16_frames_in_reach(H, W, 64);
+    const bool every_call = c->winograd_gen == 2 || (c->winograd_gen == 3 && !w36_fits(B, H, W, 64, 64));
+    if (every_call && B > reach) return FPC_E_INVALID;
+    if (c->winograd_gen == 3 && c->latency_tiles) c->small_reach = reach;
+  }
   Carver cv;
   cv.zones = &c->guards;
   cv.guard = c->guard_zones ? GUARD_BYTES : 0;
@@ -1558,6 +1580,22 @@ static int build_vgg_plan(fpc_ctx* c) {
   cv.into(&det_a, npix8 * 256); cv.into(&desc_a, npix8 * 256);
   cv.into(&c->lg, npix8 * 80); cv.into(&c->desc_map, npix8 * 256); cv.into(&c->desc_in_nhwc, npix8 * 256);
   if (int rc = carve_results(c, cv)) return rc;
+  // what fpc_read_activation serves: superpoint::SPModel's modules (cpp/src/model.cc).  "det_b" is the logits; "desc_b" the
+  // descriptor map as l2norm256_kernel leaves it (normalised in place)
+  static const char* const enc_names[4][3] = {{"conv0_a", "conv0_b", "pool0"}, {"conv1_a", "conv1_b", "pool1"},
+                                              {"conv2_a", "conv2_b", "pool2"}, {"conv3_a", "conv3_b", nullptr}};
+  c->vtaps.clear();
+  for (int i = 0; i < 4; ++i) {
+    c->vtaps.push_back({enc_names[i][0], act_a[i], ac[i], ac[i], ah[i], aw[i]});
+    c->vtaps.push_back({enc_names[i][1], act_b[i], ac[i], ac[i], ah[i], aw[i]});
+    if (i < 3) c->vtaps.push_back({enc_names[i][2], act_p[i], ac[i], ac[i], ah[i + 1], aw[i + 1]});
+  }
+  c->vtaps.push_back({"det_a", det_a, 256, 256, Hc, Wc});
+  c->vtaps.push_back({"det_b", c->lg, c->lgcs, 65, Hc, Wc});
+  if (c->cfg.descriptor_enabled) {
+    c->vtaps.push_back({"desc_a", desc_a, 256, 256, Hc, Wc});
+    c->vtaps.push_back({"desc_b", c->desc_map, 256, 256, Hc, Wc});
+  }
 
   size_t bo = BLOB_HEADER_FLOATS;
   c->ops.clear();
@@ -2554,7 +2592,7 @@ static void launch_wblock(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
   a.xcd_order = c->xcd_order ? 1 : 0;
   {  // range of the input's buffer descriptor: frames 0 .. f0 + n - 1 of the tensor, from `x` (already offset to its first channel)
     const unsigned long long xb = (unsigned long long)(f0 + n) * a.H * a.W * a.csx * sizeof(float);
-    a.x_bytes = xb > 0xfffffff0ull ? 0xfffffff0u : (unsigned)xb;
+    a.x_bytes = xb > W16_REACH ? (unsigned)W16_REACH : (unsigned)xb;
   }
   // persistent (one workgroup per CU walking the tiles) when a workgroup gets enough tiles to
   // amortise; otherwise one workgroup per tile
@@ -2788,7 +2826,7 @@ static int for_each_sub(fpc_ctx* c, int n, F&& body) {
     Sub sb;
     sb.f0 = f0;
     sb.n = cnt;
-    sb.small = n < 2 * c->min_sub;
+    sb.small = n < 2 * c->min_sub && n <= c->small_reach;
     sb.st = p == 0 ? c->stream : c->aux[p - 1];
     sb.side = c->side[p];
     // The runtime multiplexes streams onto a few hardware queues (GPU_MAX_HW_QUEUES) in creation order, and two
@@ -3580,10 +3618,30 @@ int fpc_forward(fpc_ctx* c, const float* frames, int n, float* prob, float* desc
   return FPC_OK;
 }
 
+// ... of the C++ network: the tensors build_vgg_plan listed (no "desc_a" / "desc_b" with the descriptor head disabled)
+static int read_vgg_activation(fpc_ctx* c, const char* name, int frame0, int n, float* out, int* channels, int* height, int* width) {
+  for (const fpc_ctx::VTap& t : c->vtaps) {
+    if (strcmp(t.name, name)) continue;
+    if (!strcmp(name, "det_b") && !c->logits_valid) return FPC_E_INVALID;
+    if (channels) *channels = t.C;
+    if (height) *height = t.H;
+    if (width) *width = t.W;
+    if (!out || n == 0) return FPC_OK;
+    HIPCHECK(hipSetDevice(c->cfg.device));
+    const int HW = t.H * t.W;
+    const size_t tot = (size_t)n * t.C * HW;
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
+                       t.p + (size_t)frame0 * HW * t.cs, t.cs, t.C, HW, n, out, (uint32_t*)nullptr, 0);
+    HIPCHECK(hipGetLastError());
+    return FPC_OK;
+  }
+  return FPC_E_INVALID;
+}
+
 // Tensors the last forward left in the workspace, by the reference module that produced them.
 int fpc_read_activation(fpc_ctx* c, const char* name, int frame0, int n, float* out, int* channels, int* height, int* width) {
   if (!c || !name || frame0 < 0 || n < 0 || frame0 + n > c->B) return FPC_E_INVALID;
-  if (c->vgg) return FPC_E_INVALID;   // the C++ network's layers are read through fpc_forward only
+  if (c->vgg) return read_vgg_activation(c, name, frame0, n, out, channels, height, width);
   const int H4 = c->H / 4, W4 = c->W / 4, Hc = c->Hc, Wc = c->Wc, H16 = c->H / 16, W16 = c->W / 16;
   const bool lowp = c->bf16;          // bf16 tensors (all but the logits)
   struct Tap { const char* name; const void* p; int cs, C, H, W; bool bf; int off; };

@@ -308,11 +308,16 @@ class Engine:
 
     ACTIVATIONS = ("pool", "layer1.0", "layer1.1", "layer2.0", "layer2.1", "det.0", "det.1", "desc_in.0", "desc_in.1",
                    "up", "desc_out.0", "desc_out.1")
+    # arch="vgg" (superpoint::SPModel's modules): "det_b" is the logits, "desc_b" the descriptor map, L2-normalised
+    VGG_ACTIVATIONS = ("conv0_a", "conv0_b", "pool0", "conv1_a", "conv1_b", "pool1", "conv2_a", "conv2_b", "pool2",
+                       "conv3_a", "conv3_b", "det_a", "det_b", "desc_a", "desc_b")
 
     def activation(self, name, frame0=0, n=1):
         """Intermediate tensor of the LAST forward / detect call as a forward hook on the reference module would return
         it: float32 CUDA tensor [n,C,h,w] (fpc_read_activation).  "det.1" (the logits) raises after a `detect` in
-        dtype="bf16" with the fused softmax epilogue -- that call never writes logits; `forward` always does."""
+        dtype="bf16" with the fused softmax epilogue -- that call never writes logits; `forward` always does.  An
+        arch="vgg" engine takes the names of VGG_ACTIVATIONS instead (the desc_* ones raise with the descriptor head
+        disabled)."""
         c, h, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         _lib.check(self._l.fpc_read_activation(self._ctx, name.encode(), frame0, n, None, ctypes.byref(c), ctypes.byref(h),
                                                ctypes.byref(w)), "fpc_read_activation")

@@ -183,7 +183,10 @@ int fpc_default_config(fpc_config* cfg);
  * device workspace for max_batch frames.  FPC_E_INVALID for a geometry the kernels cannot tile (height / width below
  * 16 or not a multiple of the network's stride, width above 3328, 2^30 pixels or more per frame) and for
  * max_batch * height * width >= 2^28 (the kernels address the tensors of a batch with 32-bit byte offsets, up to 16
- * bytes per frame pixel: 64 frames of 1280x960 are 2^26.2; larger jobs run as several calls or contexts). */
+ * bytes per frame pixel: 64 frames of 1280x960 are 2^26.2; larger jobs run as several calls or contexts).
+ * FPC_ARCH_VGG keeps 256 bytes per frame pixel at full resolution: a plan that runs those layers on the generation-2
+ * Winograd kernel in every call (FPC_PLAN_WINOGRAD_GEN2, or a frame of 2^23 pixels or more on the default plan) is
+ * FPC_E_INVALID where max_batch * height * width * 256 exceeds 0xfffffff0 -- fourteen frames of 1280x960. */
 int fpc_create(fpc_ctx** out, const fpc_config* cfg);
 void fpc_destroy(fpc_ctx* ctx);
 
@@ -287,7 +290,13 @@ int fpc_forward(fpc_ctx* ctx, const float* frames_dev, int n, float* prob_map_de
  * The fused kernels never write a block's inner tensor h nor the un-pooled stem output to memory: those have no name
  * here.  "det.1" exists only when the last call produced logits: fpc_forward always does; fpc_detect does except in
  * FPC_BF16 with the fused softmax epilogue (the default there; FPC_PLAN_NO_FUSED_SOFTMAX turns it off), where the
- * name returns FPC_E_INVALID instead of stale memory.  FPC_ARCH_RESNET only.  Asynchronous on the ctx stream. */
+ * name returns FPC_E_INVALID instead of stale memory.
+ * An FPC_ARCH_VGG context takes the names of superpoint::SPModel's modules instead: "conv0_a", "conv0_b", "pool0",
+ * "conv1_a", "conv1_b", "pool1", "conv2_a", "conv2_b", "pool2", "conv3_a", "conv3_b" (the encoder: 64 channels on the
+ * frame's size and at 1/2, 128 at 1/4 and 1/8; "poolN" is the 2 x 2 max-pool behind "convN_b"), "det_a" (256 channels),
+ * "det_b" (= logits, 65), "desc_a" and "desc_b" (256; "desc_b" is the descriptor map as the forward leaves it, already
+ * L2-normalised over its channels).  "desc_a" / "desc_b" return FPC_E_INVALID with the descriptor head disabled.
+ * A name of the other network, or an unknown one, returns FPC_E_INVALID.  Asynchronous on the ctx stream. */
 int fpc_read_activation(fpc_ctx* ctx, const char* name, int frame0, int n, float* out_dev, int* channels, int* height,
                         int* width);
 

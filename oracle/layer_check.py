@@ -1,5 +1,6 @@
 """Layer-isolated float64 parity of the fp32 plans -- TEST INFRASTRUCTURE ONLY (tests/test_layer_oracle.py on the CPU,
-tests/test_gpu_layer_isolated.py on the device).
+tests/test_gpu_layer_isolated.py on the device; the C++ network: tests/test_layer_oracle_vgg.py and
+tests/test_gpu_layer_isolated_vgg.py, through the *_vgg_* twins at the end of this file).
 
 Every layer of the network is fed the input tensor(s) the device itself holds for it (fpc_read_activation) and computed
 once more by oracle.f32_layer / oracle.f32_stem: folded float weights, double accumulation.  The device's output tensor
@@ -108,23 +109,20 @@ def torch_f32_layer(name, inputs, sd):
         return F.relu(y).numpy()
 
 
-def check_layers(engine, frames, sd, tag, launches=None, rows=None):
-    """Call after engine.forward(frames): every tensor of engine.ACTIVATIONS, every frame of the batch, against
-    reference_layer on the device's own input tensor(s).  Prints one line per layer (kernel symbol, max error, max error
-    relative to max |reference|, E_ref of torch_f32_layer on the same input and device error / E_ref), appends the same
-    figures to `rows`, and raises AssertionError with every failing layer's message once all layers were looked at."""
+def _check(engine, frames, sd, tag, launches, rows, names, graph, reference, torch_reference, kernels):
+    """check_layers / check_vgg_layers: `names` in order, `graph` {tensor: its input tensors, "frames" = the frames}."""
     frames = np.ascontiguousarray(frames, np.float32)
     n = frames.shape[0]
-    kernels = layer_kernels(launches or [])
-    graph = dict(oracle.LAYERS)
-    dev ={name: engine.activation(name, 0, n).cpu().numpy() for name in engine.ACTIVATIONS}
+    dev = {name: engine.activation(name, 0, n).cpu().numpy() for name in names}
+    dev["frames"] = frames
     failures = []
-    for name in engine.ACTIVATIONS:
-        inputs = [frames] if name == "pool" else [dev[i] for i in graph[name]]
-        want = reference_layer(name, inputs, sd)
+    for name in names:
+        inputs = [dev[i] for i in graph[name]]
+        want = reference(name, inputs, sd)
         rep = compare_layer(name, dev[name], want)
-        e_ref = float(np.max(np.abs(torch_f32_layer(name, inputs, sd).astype(np.float64) - want)))
-        ratio = rep["max_err"] / e_ref if e_ref > 0 else float("inf")
+        e_ref = float(np.max(np.abs(torch_reference(name, inputs, sd).astype(np.float64) - want)))
+        # (an exact layer -- a max-pool -- has E_ref = 0: ratio 0 where the device is exact too)
+        ratio = rep["max_err"] / e_ref if e_ref > 0 else 0.0 if rep["max_err"] == 0 else float("inf")
         print("layer-isolated | %s | %s | %s | max err %.3e | rel %.3e | E_ref %.3e | device / E_ref %.2f" % (
             tag, name, kernels[name], rep["max_err"], rep["rel"], e_ref, ratio))
         if rows is not None:
@@ -133,3 +131,95 @@ def check_layers(engine, frames, sd, tag, launches=None, rows=None):
         if not rep["ok"]:
             failures.append("%s [%s]: %s" % (tag, kernels[name], rep["message"]))
     assert not failures, "\n".join(failures)
+
+
+def check_layers(engine, frames, sd, tag, launches=None, rows=None):
+    """Call after engine.forward(frames): every tensor of engine.ACTIVATIONS, every frame of the batch, against
+    reference_layer on the device's own input tensor(s).  Prints one line per layer (kernel symbol, max error, max error
+    relative to max |reference|, E_ref of torch_f32_layer on the same input and device error / E_ref), appends the same
+    figures to `rows`, and raises AssertionError with every failing layer's message once all layers were looked at."""
+    graph = dict(oracle.LAYERS)
+    graph["pool"] = ("frames",)
+    _check(engine, frames, sd, tag, launches, rows, engine.ACTIVATIONS, graph, reference_layer, torch_f32_layer,
+           layer_kernels(launches or []))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The C++ network (arch="vgg"): the same comparison over oracle.VGG_LAYERS / oracle.vgg_layer
+# (tests/test_layer_oracle_vgg.py on the CPU, tests/test_gpu_layer_isolated_vgg.py on the device).
+# ---------------------------------------------------------------------------------------------------------------
+def _vgg_op_prefixes(tensor):
+    """The prefixes of the op names (Engine.timings()) that write `tensor`."""
+    if tensor.startswith("pool"):
+        return ("max_pool2d(2,2) after " + oracle._VGG_CONVS["conv%s_b" % tensor[4:]][0],)
+    if tensor == "desc_b":      # the 1 x 1 convolution, then l2norm256_kernel in place
+        return (oracle._VGG_CONVS[tensor][0], "descriptor L2 normalisation")
+    return (oracle._VGG_CONVS[tensor][0],)
+
+
+def vgg_layer_kernels(launches):
+    """layer_kernels for the C++ network: {tensor of Engine.VGG_ACTIVATIONS: "symbol" or "symbol + symbol"}."""
+    out = {}
+    for tensor, _ in oracle.VGG_LAYERS:
+        syms = []
+        for op, sym in launches:
+            if any(op == p or (op.startswith(p) and op[len(p)] in " .+[") for p in _vgg_op_prefixes(tensor)) and sym not in syms:
+                syms.append(sym)
+        out[tensor] = " + ".join(syms) if syms else "?"
+    return out
+
+
+def vgg_layer_ops(launches):
+    """{tensor: [op names that wrote it]} -- the op name of a layer computed in parts says how many and how wide."""
+    return {tensor: [op for op, _ in launches if any(op == p or (op.startswith(p) and op[len(p)] in " .+[")
+                                                      for p in _vgg_op_prefixes(tensor))] for tensor, _ in oracle.VGG_LAYERS}
+
+
+def torch_vgg_layer(name, inputs, sd):
+    """oracle.vgg_layer in plain fp32 on the CPU (torch.nn.functional): E_ref of the tests' tables."""
+    import torch
+    import torch.nn.functional as F
+    with torch.no_grad():
+        x = torch.from_numpy(np.ascontiguousarray(inputs[0], np.float32))
+        if name.startswith("pool"):
+            return F.max_pool2d(x, 2, 2).numpy()
+        p, k, relu = oracle._VGG_CONVS[name]
+        y = F.conv2d(x, torch.from_numpy(sd[p + ".weight"]), torch.from_numpy(sd[p + ".bias"]), padding=k // 2)
+        if relu:
+            y = F.relu(y)
+        if name == "desc_b":
+            y = y / torch.norm(y, 2, 1, keepdim=True)
+        return y.numpy()
+
+
+def check_vgg_layers(engine, frames, sd, tag, launches=None, rows=None, names=None):
+    """check_layers for an arch="vgg" engine: every tensor of `names` (default engine.VGG_ACTIVATIONS; without the
+    desc_* ones where the descriptor head is disabled), every frame, against oracle.vgg_layer on the device's own input."""
+    _check(engine, frames, sd, tag, launches, rows, names or engine.VGG_ACTIVATIONS, dict(oracle.VGG_LAYERS), oracle.vgg_layer,
+           torch_vgg_layer, vgg_layer_kernels(launches or []))
+
+
+def band_rows(a, b, h):
+    """The output rows [lo, hi) of a 3 x 3, padding-1 layer that input rows [a, b) of an h-row frame determine alone:
+    those whose support lies inside the band or on the frame's true top / bottom edge (where the padding is the layer's)."""
+    return (a if a == 0 else a + 1), (b if b == h else b - 1)
+
+
+def compare_band(name, got, want, a, b, h, atol=ATOL):
+    """compare_layer on a band of rows: `got` is rows [a, b) of the device's output tensor, `want` the reference computed
+    from rows [a, b) of the input alone (its zero padding stands in for the rows outside the band, so its first / last
+    row is wrong unless the band touches the frame's edge).  Only band_rows(a, b, h) are compared; worst's y and
+    "rows" are frame rows, the message's y counts from row `lo`."""
+    lo, hi = band_rows(a, b, h)
+    got, want = np.asarray(got), np.asarray(want)
+    assert 0 <= a < lo < hi <= b <= h or 0 == a == lo < hi <= b <= h, (a, b, h)
+    assert want.shape[2] == b - a, (want.shape, a, b)
+    if got.shape != want.shape:
+        return compare_layer(name, got, want, atol)
+    rep = compare_layer(name, got[:, :, lo - a:hi - a], want[:, :, lo - a:hi - a], atol)
+    rep["rows"] = (lo, hi)
+    if rep["worst"] is not None:
+        f, c, y, x = rep["worst"]
+        rep["worst"] = (f, c, y + lo, x)
+    rep["message"] += " [rows %d..%d of the frame's %d, y counted from row %d]" % (lo, hi - 1, h, lo)
+    return rep

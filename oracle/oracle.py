@@ -265,6 +265,40 @@ def f32_layer(name, inputs, sd):
     return _relu(y)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# The C++ network (superpoint::SPModel, cpp/src/model.cc:61-93; vgg_forward below is the whole of it) one layer at a
+# time, by the names of Engine.VGG_ACTIVATIONS / fpc_read_activation: (output tensor, input tensor(s)); "frames" is the
+# gray plane [B,1,H,W].  No BatchNorm: weights and biases as the checkpoint holds them.
+# ---------------------------------------------------------------------------------------------------------------
+VGG_LAYERS = [("conv0_a", ("frames",)), ("conv0_b", ("conv0_a",)), ("pool0", ("conv0_b",)),
+              ("conv1_a", ("pool0",)), ("conv1_b", ("conv1_a",)), ("pool1", ("conv1_b",)),
+              ("conv2_a", ("pool1",)), ("conv2_b", ("conv2_a",)), ("pool2", ("conv2_b",)),
+              ("conv3_a", ("pool2",)), ("conv3_b", ("conv3_a",)),
+              ("det_a", ("conv3_b",)), ("det_b", ("det_a",)), ("desc_a", ("conv3_b",)), ("desc_b", ("desc_a",))]
+_VGG_CONVS = {  # name -> (checkpoint prefix, kernel size, ReLU)
+    "det_a": ("detector_conv_a", 3, True), "det_b": ("detector_conv_b", 1, False),
+    "desc_a": ("descriptor_conv_a", 3, True), "desc_b": ("descriptor_conv_b", 1, False)}
+_VGG_CONVS.update({"conv%d_%s" % (i, ab): ("encoder_conv%d_%s" % (i, ab), 3, True) for i in range(4) for ab in "ab"})
+
+
+def vgg_layer(name, inputs, sd):
+    """ONE layer of the C++ network on its float32 input tensor [B,C,h,w]: a convolution (double accumulation, rounded to
+    float once) + bias (+ ReLU); "poolN": the exact 2 x 2 maximum; "desc_b": the 1 x 1 convolution + bias divided by its
+    norm over the channels, the norm taken in double (model.cc:90-91: no epsilon)."""
+    x = np.ascontiguousarray(inputs[0], np.float32)
+    if name.startswith("pool"):
+        b, c, h, w = x.shape
+        return np.ascontiguousarray(x[:, :, :h // 2 * 2, :w // 2 * 2].reshape(b, c, h // 2, 2, w // 2, 2).max(axis=(3, 5)))
+    p, k, relu = _VGG_CONVS[name]
+    y = _conv2d(x, sd[p + ".weight"], 1, k // 2) + _bias(sd[p + ".bias"])
+    if relu:
+        y = _relu(y)
+    if name == "desc_b":
+        nrm = np.sqrt(np.sum(np.square(y.astype(np.float64)), axis=1, keepdims=True))
+        y = y / nrm.astype(np.float32)
+    return y
+
+
 def forward_bf16_emulated(image, sd, descriptor_enabled=True, with_taps=False):
     """image float32 [B,3,H,W] -> (prob_map, desc, logits[, taps]) as `forward`, with FPC_BF16's roundings."""
     image = np.ascontiguousarray(image, np.float32)
