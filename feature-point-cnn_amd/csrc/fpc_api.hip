@@ -50,6 +50,7 @@
 #include "landmarks.h"
 #include "homography.h"
 #include "weights.h"
+#include "plan_options.h"
 
 namespace fpc {
 
@@ -68,8 +69,28 @@ static thread_local std::string g_hip_err;
   } while (0)
 
 // ------------------------------------------------------------------------------------
-// Kernel instances.  KIND(name, TH,TW, S,EXT, KC, WM,WN, MB,NB)
+// Kernel instances.  Each X-macro list below is the one place an instance is declared: it expands once into its
+// enumerator and once into its table row.  New instances go at the END of a list, and a new Winograd list behind the
+// others: plan_hash mixes the enumerators.
 // ------------------------------------------------------------------------------------
+template <auto Kernel, int Threads, int Lds, typename Args>
+static void launch_as(const Args& a, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL(Kernel, grid, dim3(Threads), Lds, st, a);
+}
+
+// What the host needs to launch one instance, and the head of every table row
+template <typename Args>
+struct Instance {
+  const void* fn;
+  int lds_bytes, threads;
+  void (*launch)(const Args&, dim3, hipStream_t);
+};
+template <auto Kernel, typename Cfg, int Threads, typename Args>
+static Instance<Args> instance_of() {
+  return {(const void*)Kernel, Cfg::LDS_BYTES, Threads, launch_as<Kernel, Threads, Cfg::LDS_BYTES, Args>};
+}
+
+// KIND(name, TH,TW, S,EXT, KC, WM,WN, MB,NB)
 #define FPC_KINDS(X)                                                        \
   X(T816_3x3_K64_N64, 8, 16, 1, 3, 64, 4, 1, 1, 2)                          \
   X(T816_1x1_K64_N64, 8, 16, 1, 1, 64, 4, 1, 1, 2)                          \
@@ -91,59 +112,35 @@ enum Kind {
       K_COUNT
 };
 
-struct KindInfo {
+struct KindInfo : Instance<ConvArgs> {
   const char* name;
   const char* symbol;   // as rocprofv3 prints it
   int TH, TW, S, EXT, KC, WM, WN, MB, NB;
-  int lds_bytes, threads;
-  const void* fn;
-  void (*launch)(const ConvArgs&, dim3, hipStream_t);
 };
 
-#define X(name, TH, TW, S, EXT, KC, WM, WN, MB, NB)                                                    \
-  static void launch_##name(const ConvArgs& a, dim3 grid, hipStream_t st) {                            \
-    using C = ConvCfg<TH, TW, S, EXT, KC, WM, WN, MB, NB>;                                             \
-    hipLaunchKernelGGL((conv_mfma_kernel<TH, TW, S, EXT, KC, WM, WN, MB, NB>), grid, dim3(C::NT),      \
-                       C::LDS_BYTES, st, a);                                                           \
-  }
-FPC_KINDS(X)
-#undef X
-
 static const KindInfo g_kinds[K_COUNT] = {
-#define X(name, TH, TW, S, EXT, KC, WM, WN, MB, NB)                                                    \
-  {#name, "conv_mfma_kernel<" #TH ", " #TW ", " #S ", " #EXT ", " #KC ", " #WM ", " #WN ", " #MB ", " #NB ">", TH, TW, S, EXT, KC, WM, WN, MB, NB, ConvCfg<TH, TW, S, EXT, KC, WM, WN, MB, NB>::LDS_BYTES,   \
-   WM * WN * 64, (const void*)conv_mfma_kernel<TH, TW, S, EXT, KC, WM, WN, MB, NB>, launch_##name},
+#define X(name, TH, TW, S, EXT, KC, WM, WN, MB, NB)                                                                                      \
+  {instance_of<conv_mfma_kernel<TH, TW, S, EXT, KC, WM, WN, MB, NB>, ConvCfg<TH, TW, S, EXT, KC, WM, WN, MB, NB>, WM * WN * 64, ConvArgs>(), \
+   #name, "conv_mfma_kernel<" #TH ", " #TW ", " #S ", " #EXT ", " #KC ", " #WM ", " #WN ", " #MB ", " #NB ">", TH, TW, S, EXT, KC, WM, WN, MB, NB},
     FPC_KINDS(X)
 #undef X
 };
 
-// Round 5: conv2_mfma_kernel (conv_mfma.h: the same convolution with a quarter of the VALU instructions) for the two
+// conv2_mfma_kernel (conv_mfma.h: the same convolution with a quarter of the VALU instructions) for the two
 // instances of the default fp32 plan -- the ConvTranspose phases and descriptor.layer_in.1's 1x1; launches it does not
 // cover (a second K source, workgroups that store only part of their N channels) and every other instance keep
 // conv_mfma_kernel.
 #define FPC_LEAN_KINDS(X)                          \
   X(T320_2x2_K64_N128, 3, 20, 1, 2, 64, 1, 4, 2, 1) \
   X(T320_1x1_K64_N128, 3, 20, 1, 1, 64, 1, 4, 2, 1)
-struct LeanKindInfo {
+struct LeanKindInfo : Instance<ConvArgs> {
   Kind kind;
   const char* symbol;
-  int lds_bytes;
-  const void* fn;
-  void (*launch)(const ConvArgs&, dim3, hipStream_t);
 };
-#define X(name, TH, TW, S, EXT, KC, WM, WN, MB, NB)                                                              \
-  static void launch_lean_##name(const ConvArgs& a, dim3 grid, hipStream_t st) {                                 \
-    using C2 = Conv2Cfg<TH, TW, S, EXT, KC, WM, WN, MB, NB>;                                                    \
-    hipLaunchKernelGGL((conv2_mfma_kernel<TH, TW, S, EXT, KC, WM, WN, MB, NB>), grid, dim3(WM* WN * 64),         \
-                       C2::LDS_BYTES, st, a);                                                                    \
-  }
-FPC_LEAN_KINDS(X)
-#undef X
 static const LeanKindInfo g_lean_kinds[] = {
-#define X(name, TH, TW, S, EXT, KC, WM, WN, MB, NB)                                                                       \
-  {K_##name, "conv2_mfma_kernel<" #TH ", " #TW ", " #S ", " #EXT ", " #KC ", " #WM ", " #WN ", " #MB ", " #NB ">",          \
-   Conv2Cfg<TH, TW, S, EXT, KC, WM, WN, MB, NB>::LDS_BYTES, (const void*)conv2_mfma_kernel<TH, TW, S, EXT, KC, WM, WN, MB, NB>, \
-   launch_lean_##name},
+#define X(name, TH, TW, S, EXT, KC, WM, WN, MB, NB)                                                                                        \
+  {instance_of<conv2_mfma_kernel<TH, TW, S, EXT, KC, WM, WN, MB, NB>, Conv2Cfg<TH, TW, S, EXT, KC, WM, WN, MB, NB>, WM * WN * 64, ConvArgs>(), \
+   K_##name, "conv2_mfma_kernel<" #TH ", " #TW ", " #S ", " #EXT ", " #KC ", " #WM ", " #WN ", " #MB ", " #NB ">"},
     FPC_LEAN_KINDS(X)
 #undef X
 };
@@ -166,8 +163,7 @@ static const LeanKindInfo* lean_kind(Kind k) {
   X(B320_s2_K32_C128, 3, 20, 2, 32, 1, 4, 2, 1, 128)         \
   X(B320_s1_K64_C256, 3, 20, 1, 64, 1, 4, 2, 2, 256)         \
   X(B416_s2_K32_C128, 4, 16, 2, 32, 1, 4, 2, 1, 128)
-// (B416_s2_K32_C128, round 6: B320_s2_K32_C128's fragments on 64 pixels that fill the M = 64 rows -- retile_rows below.
-// New instances go at the END of this list: plan_hash mixes the enumerators of the round-5 choice.)
+// (B416_s2_K32_C128: B320_s2_K32_C128's fragments on 64 pixels that fill the M = 64 rows -- retile_rows below.)
 
 enum BKind {
 #define X(name, ...) BK_##name,
@@ -176,29 +172,16 @@ enum BKind {
       BK_COUNT
 };
 
-struct BKindInfo {
+struct BKindInfo : Instance<BlockArgs> {
   const char* name;
   const char* symbol;
   int TH, TW, S, KC, WM, WN, MB, NB, CMIDP;
-  int lds_bytes;
-  const void* fn;
-  void (*launch)(const BlockArgs&, dim3, hipStream_t);
 };
 
-#define X(name, TH, TW, S, KC, WM, WN, MB, NB, CMIDP)                                                     \
-  static void launchb_##name(const BlockArgs& a, dim3 grid, hipStream_t st) {                             \
-    using BC = BlockCfg<TH, TW, S, KC, WM, WN, MB, NB, CMIDP>;                                            \
-    hipLaunchKernelGGL((block_mfma_kernel<TH, TW, S, KC, WM, WN, MB, NB, CMIDP>), grid, dim3(WM* WN * 64), \
-                       BC::LDS_BYTES, st, a);                                                             \
-  }
-FPC_BLOCK_KINDS(X)
-#undef X
-
 static const BKindInfo g_bkinds[BK_COUNT] = {
-#define X(name, TH, TW, S, KC, WM, WN, MB, NB, CMIDP)                                                      \
-  {#name, "block_mfma_kernel<" #TH ", " #TW ", " #S ", " #KC ", " #WM ", " #WN ", " #MB ", " #NB ", " #CMIDP ">", \
-   TH, TW, S, KC, WM, WN, MB, NB, CMIDP, BlockCfg<TH, TW, S, KC, WM, WN, MB, NB, CMIDP>::LDS_BYTES,         \
-   (const void*)block_mfma_kernel<TH, TW, S, KC, WM, WN, MB, NB, CMIDP>, launchb_##name},
+#define X(name, TH, TW, S, KC, WM, WN, MB, NB, CMIDP)                                                                                            \
+  {instance_of<block_mfma_kernel<TH, TW, S, KC, WM, WN, MB, NB, CMIDP>, BlockCfg<TH, TW, S, KC, WM, WN, MB, NB, CMIDP>, WM * WN * 64, BlockArgs>(), \
+   #name, "block_mfma_kernel<" #TH ", " #TW ", " #S ", " #KC ", " #WM ", " #WN ", " #MB ", " #NB ", " #CMIDP ">", TH, TW, S, KC, WM, WN, MB, NB, CMIDP},
     FPC_BLOCK_KINDS(X)
 #undef X
 };
@@ -256,121 +239,61 @@ enum WKind {
   FPC_W36P_KINDS(X)
   FPC_W36PD_KINDS(X)
   FPC_W36S_KINDS(X)
-  FPC_W36PC_KINDS(X)      // (round 6's lists go behind round 5's: plan_hash mixes the enumerators of the round-5 choice)
+  FPC_W36PC_KINDS(X)
 #undef X
       WK_COUNT
 };
 
-struct WKindInfo {
+struct WKindInfo : Instance<WBlockArgs> {
   const char* name;
   const char* symbol;
   int gen;               // 1: wblock_mfma_kernel, 2: wblock16_kernel, 3: wblock36_kernel
-  int KC, NBT, CMID, lds_bytes;
+  int KC, NBT, CMID;
   int NCG;               // generations 2, 3: channel groups of 16
   int TH;                // tile height in pixels (8; 4 for the latency instance; generation 3: 16 or 8)
   int TW;                // tile width in pixels (16; generation 3: 16 or 32)
-  int threads;           // workgroup size (512; generation 3: 256)
-  const void* fn;
-  void (*launch)(const WBlockArgs&, dim3, hipStream_t);
   bool dust = false;     // generation 3: the 65-channel (64 + dustbin) instance
 };
 
-#define X(name, KC, NBT, CMID)                                                                            \
-  static void launchw_##name(const WBlockArgs& a, dim3 grid, hipStream_t st) {                            \
-    constexpr int lds = WBlockCfg<KC, NBT, CMID>::LDS_BYTES;                                              \
-    hipLaunchKernelGGL((wblock_mfma_kernel<KC, NBT, CMID>), grid, dim3(512), lds, st, a);                 \
-  }
-FPC_WBLOCK_KINDS(X)
-#undef X
-#define X(name, NCG, TH)                                                                                  \
-  static void launchw_##name(const WBlockArgs& a, dim3 grid, hipStream_t st) {                            \
-    constexpr int lds = W16Cfg<NCG, TH>::LDS_BYTES;                                                       \
-    hipLaunchKernelGGL((wblock16_kernel<NCG, TH>), grid, dim3(512), lds, st, a);                          \
-  }
-FPC_W16_KINDS(X)
-#undef X
-#define X(name, NB, TYT, TXT)                                                                             \
-  static void launchw_##name(const WBlockArgs& a, dim3 grid, hipStream_t st) {                            \
-    constexpr int lds = W36Cfg<NB, TYT, TXT>::LDS_BYTES;                                                  \
-    hipLaunchKernelGGL((wblock36_kernel<NB, TYT, TXT>), grid, dim3(256), lds, st, a);                     \
-  }
-FPC_W36_KINDS(X)
-#undef X
-#define X(name, TYT, TXT)                                                                                  \
-  static void launchw_##name(const WBlockArgs& a, dim3 grid, hipStream_t st) {                            \
-    constexpr int lds = W36Cfg<1, TYT, TXT, true>::LDS_BYTES;                                             \
-    hipLaunchKernelGGL((wblock36_dust_kernel<TYT, TXT>), grid, dim3(256), lds, st, a);                    \
-  }
-FPC_W36D_KINDS(X)
-#undef X
-#define X(name, TYT, TXT)                                                                                  \
-  static void launchw_##name(const WBlockArgs& a, dim3 grid, hipStream_t st) {                            \
-    constexpr int lds = W36PCfg<TYT, TXT>::LDS_BYTES;                                                     \
-    hipLaunchKernelGGL((wblock36p_kernel<TYT, TXT>), grid, dim3(512), lds, st, a);                        \
-  }
-FPC_W36P_KINDS(X)
-#undef X
-#define X(name, TYT, TXT)                                                                                  \
-  static void launchw_##name(const WBlockArgs& a, dim3 grid, hipStream_t st) {                            \
-    constexpr int lds = W36PCfg<TYT, TXT, true>::LDS_BYTES;                                               \
-    hipLaunchKernelGGL((wblock36p_dust_kernel<TYT, TXT>), grid, dim3(512), lds, st, a);                   \
-  }
-FPC_W36PD_KINDS(X)
-#undef X
-#define X(name, NB, TYT, TXT)                                                                             \
-  static void launchw_##name(const WBlockArgs& a, dim3 grid, hipStream_t st) {                            \
-    constexpr int lds = W36Cfg<NB, TYT, TXT>::LDS_BYTES;                                                  \
-    hipLaunchKernelGGL((wblock36s_kernel<NB, TYT, TXT>), grid, dim3(256), lds, st, a);                    \
-  }
-FPC_W36S_KINDS(X)
-#undef X
-#define X(name, TYT, TXT)                                                                                  \
-  static void launchw_##name(const WBlockArgs& a, dim3 grid, hipStream_t st) {                            \
-    constexpr int lds = W36PCfg<TYT, TXT, false, true>::LDS_BYTES;                                        \
-    hipLaunchKernelGGL((wconv36p_kernel<TYT, TXT>), grid, dim3(512), lds, st, a);                         \
-  }
-FPC_W36PC_KINDS(X)
-#undef X
-
 static const WKindInfo g_wkinds[WK_COUNT] = {
 #define X(name, KC, NBT, CMID)                                                                            \
-  {#name, "wblock_mfma_kernel<" #KC ", " #NBT ", " #CMID ">", 1, KC, NBT, CMID,                           \
-   WBlockCfg<KC, NBT, CMID>::LDS_BYTES, 0, 8, 16, 512, (const void*)wblock_mfma_kernel<KC, NBT, CMID>, launchw_##name},
+  {instance_of<wblock_mfma_kernel<KC, NBT, CMID>, WBlockCfg<KC, NBT, CMID>, 512, WBlockArgs>(), #name,                         \
+   "wblock_mfma_kernel<" #KC ", " #NBT ", " #CMID ">", 1, KC, NBT, CMID, 0, 8, 16},
     FPC_WBLOCK_KINDS(X)
 #undef X
 #define X(name, NCG, TH)                                                                                  \
-  {#name, "wblock16_kernel<" #NCG ", " #TH ">", 2, 16, NCG / 2, NCG * 16,                                  \
-   W16Cfg<NCG, TH>::LDS_BYTES, NCG, TH, 16, 512, (const void*)wblock16_kernel<NCG, TH>, launchw_##name},
+  {instance_of<wblock16_kernel<NCG, TH>, W16Cfg<NCG, TH>, 512, WBlockArgs>(), #name,                                           \
+   "wblock16_kernel<" #NCG ", " #TH ">", 2, 16, NCG / 2, NCG * 16, NCG, TH, 16},
     FPC_W16_KINDS(X)
 #undef X
 #define X(name, NB, TYT, TXT)                                                                             \
-  {#name, "wblock36_kernel<" #NB ", " #TYT ", " #TXT ">", 3, 16, 2 * NB, 64 * NB,                          \
-   W36Cfg<NB, TYT, TXT>::LDS_BYTES, 4 * NB, 4 * TYT, 4 * TXT, 256, (const void*)wblock36_kernel<NB, TYT, TXT>, launchw_##name},
+  {instance_of<wblock36_kernel<NB, TYT, TXT>, W36Cfg<NB, TYT, TXT>, 256, WBlockArgs>(), #name,                                 \
+   "wblock36_kernel<" #NB ", " #TYT ", " #TXT ">", 3, 16, 2 * NB, 64 * NB, 4 * NB, 4 * TYT, 4 * TXT},
     FPC_W36_KINDS(X)
 #undef X
 #define X(name, TYT, TXT)                                                                                 \
-  {#name, "wblock36_dust_kernel<" #TYT ", " #TXT ">", 3, 16, 2, 64,                                        \
-   W36Cfg<1, TYT, TXT, true>::LDS_BYTES, 4, 4 * TYT, 4 * TXT, 256, (const void*)wblock36_dust_kernel<TYT, TXT>, launchw_##name, true},
+  {instance_of<wblock36_dust_kernel<TYT, TXT>, W36Cfg<1, TYT, TXT, true>, 256, WBlockArgs>(), #name,                           \
+   "wblock36_dust_kernel<" #TYT ", " #TXT ">", 3, 16, 2, 64, 4, 4 * TYT, 4 * TXT, true},
     FPC_W36D_KINDS(X)
 #undef X
 #define X(name, TYT, TXT)                                                                                 \
-  {#name, "wblock36p_kernel<" #TYT ", " #TXT ", 3>", 3, 16, 2, 64,                                            \
-   W36PCfg<TYT, TXT>::LDS_BYTES, 4, 4 * TYT, 4 * TXT, 512, (const void*)wblock36p_kernel<TYT, TXT>, launchw_##name},
+  {instance_of<wblock36p_kernel<TYT, TXT>, W36PCfg<TYT, TXT>, 512, WBlockArgs>(), #name,                                       \
+   "wblock36p_kernel<" #TYT ", " #TXT ", 3>", 3, 16, 2, 64, 4, 4 * TYT, 4 * TXT},
     FPC_W36P_KINDS(X)
 #undef X
 #define X(name, TYT, TXT)                                                                                 \
-  {#name, "wblock36p_dust_kernel<" #TYT ", " #TXT ", 3>", 3, 16, 2, 64,                                    \
-   W36PCfg<TYT, TXT, true>::LDS_BYTES, 4, 4 * TYT, 4 * TXT, 512, (const void*)wblock36p_dust_kernel<TYT, TXT>, launchw_##name, true},
+  {instance_of<wblock36p_dust_kernel<TYT, TXT>, W36PCfg<TYT, TXT, true>, 512, WBlockArgs>(), #name,                            \
+   "wblock36p_dust_kernel<" #TYT ", " #TXT ", 3>", 3, 16, 2, 64, 4, 4 * TYT, 4 * TXT, true},
     FPC_W36PD_KINDS(X)
 #undef X
 #define X(name, NB, TYT, TXT)                                                                             \
-  {#name, "wblock36s_kernel<" #NB ", " #TYT ", " #TXT ">", 3, 16, 2 * NB, 64 * NB,                         \
-   W36Cfg<NB, TYT, TXT>::LDS_BYTES, 4 * NB, 4 * TYT, 4 * TXT, 256, (const void*)wblock36s_kernel<NB, TYT, TXT>, launchw_##name},
+  {instance_of<wblock36s_kernel<NB, TYT, TXT>, W36Cfg<NB, TYT, TXT>, 256, WBlockArgs>(), #name,                                \
+   "wblock36s_kernel<" #NB ", " #TYT ", " #TXT ">", 3, 16, 2 * NB, 64 * NB, 4 * NB, 4 * TYT, 4 * TXT},
     FPC_W36S_KINDS(X)
 #undef X
 #define X(name, TYT, TXT)                                                                                 \
-  {#name, "wconv36p_kernel<" #TYT ", " #TXT ", 3>", 3, 16, 2, 64,                                            \
-   W36PCfg<TYT, TXT, false, true>::LDS_BYTES, 4, 4 * TYT, 4 * TXT, 512, (const void*)wconv36p_kernel<TYT, TXT>, launchw_##name},
+  {instance_of<wconv36p_kernel<TYT, TXT>, W36PCfg<TYT, TXT, false, true>, 512, WBlockArgs>(), #name,                           \
+   "wconv36p_kernel<" #TYT ", " #TXT ", 3>", 3, 16, 2, 64, 4, 4 * TYT, 4 * TXT},
     FPC_W36PC_KINDS(X)
 #undef X
 };
@@ -502,31 +425,40 @@ enum FKind {
       FK_COUNT
 };
 
-struct FKindInfo {
+struct FKindInfo : Instance<BlockBfArgs> {
   const char* name;
   const char* symbol;
   int planes, TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP;
-  int lds_bytes;
-  const void* fn;
-  void (*launch)(const BlockBfArgs&, dim3, hipStream_t);
 };
 
-#define X(name, KERN, CFG, PL, TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP)                                  \
-  static void launchf_##name(const BlockBfArgs& a, dim3 grid, hipStream_t st) {                            \
-    constexpr int lds = CFG<TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP>::LDS_BYTES;                         \
-    hipLaunchKernelGGL((KERN<TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP>), grid, dim3(WM* WN * 64), lds, st, a); \
-  }
-FPC_BF16_KINDS(X)
-#undef X
-
 static const FKindInfo g_fkinds[FK_COUNT] = {
-#define X(name, KERN, CFG, PL, TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP)                                   \
-  {#name, #KERN "<" #TH ", " #TW ", " #S ", " #EXT ", " #KC ", " #WM ", " #WN ", " #MB ", " #NB ", " #CMIDP ">", \
-   PL, TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP, CFG<TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP>::LDS_BYTES,   \
-   (const void*)KERN<TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP>, launchf_##name},
+#define X(name, KERN, CFG, PL, TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP)                                                                  \
+  {instance_of<KERN<TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP>, CFG<TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP>, WM * WN * 64, BlockBfArgs>(), \
+   #name, #KERN "<" #TH ", " #TW ", " #S ", " #EXT ", " #KC ", " #WM ", " #WN ", " #MB ", " #NB ", " #CMIDP ">",                             \
+   PL, TH, TW, S, EXT, KC, WM, WN, MB, NB, CMIDP},
     FPC_BF16_KINDS(X)
 #undef X
 };
+
+// What prepare_kernels does with a table: the dynamic-LDS limit of every instance; under FPC_DIAG, its occupancy
+template <typename Info, size_t N>
+static int allow_dynamic_lds(const Info (&table)[N]) {
+  for (const Info& k : table) HIPCHECK(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes));
+  return FPC_OK;
+}
+#ifdef FPC_DIAG
+template <typename Info, size_t N>
+static void print_occupancy(const Info (&table)[N]) {
+  for (const Info& k : table) {
+    int nb = -1;
+    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, k.threads, k.lds_bytes);
+    hipFuncAttributes fa{};
+    hipFuncGetAttributes(&fa, k.fn);
+    fprintf(stderr, "[diag] %s: lds %d B, regs %d, scratch %zu, static lds %zu, occupancy %d blocks/CU\n", k.name, k.lds_bytes,
+            fa.numRegs, fa.localSizeBytes, fa.sharedSizeBytes, nb);
+  }
+}
+#endif
 
 // ------------------------------------------------------------------------------------
 // Launch plan
@@ -581,6 +513,23 @@ struct Timing {
   double mfma_flops = -1.0;  // ... and what its tiles issued
 };
 
+// One device allocation of a context: carved by a Carver, zeroed, its canary zones (offset, bytes) filled where the
+// context has them.  A context owns five (fpc_ctx::slabs).
+using GuardZones = std::vector<std::pair<size_t, size_t>>;
+struct Carver;
+struct Slab {
+  char* base = nullptr;
+  size_t bytes = 0;
+  GuardZones zones;
+  explicit operator bool() const { return base != nullptr; }
+  int allocate(hipStream_t st, Carver& cv);
+  hipError_t release() {
+    const hipError_t e = base ? hipFree(base) : hipSuccess;
+    *this = Slab{};
+    return e;
+  }
+};
+
 }  // namespace fpc
 
 using namespace fpc;
@@ -599,6 +548,7 @@ struct fpc_ctx {
   int lgcs = 72;                     // channel stride of the logits buffer (80 in bf16 mode)
   int cin = 3;                       // 3: [n,3,H,W] frames (the reference's layout); 1: gray [n,1,H,W]
   int cap = 0, sort_cap = 0;
+  PlanOptions opt;                   // plan_options.h: every launch-plan option, resolved once by fpc_create
   hipStream_t stream = nullptr;
   bool own_stream = false;
   hipStream_t upload = nullptr;       // fpc_upload_stream: the caller's copy stream, on a hardware queue of its own
@@ -610,48 +560,22 @@ struct fpc_ctx {
   std::vector<hipEvent_t> ev_join;
   std::vector<hipStream_t> side;     // per sub-batch: detector head + NMS next to the descriptor head
   std::vector<hipEvent_t> ev_enc, ev_det;
-  bool nms_aside = true;             // FPC_NMS_ASIDE=0: NMS in line on the sub-batch stream
-  bool split_heads = false;          // FPC_SPLIT_HEADS=1: detector head + NMS of a sub-batch on a side stream next to its descriptor head
   hipEvent_t ev_fork = nullptr;
   int small_reach = 1 << 30;         // the C++ network: the largest call the latency plan's generation-2 launches can address (build_vgg_plan)
-  int min_sub = 8;                   // smallest sub-batch worth its own stream (FPC_MIN_SUB); calls below twice this take the latency plan
   int num_cus = 256;
   int fkind_blocks_per_cu[64] = {};   // resident workgroups per CU of every bf16 / split-operand instance (fpc_create)
-  int persist_min_tiles = 1;         // FPC_PERSIST_MIN: tiles per CU from which the Winograd kernel runs persistent (0 = never)
-  bool xcd_order = true;             // FPC_XCD_ORDER=0: plain tile order in the persistent Winograd kernel
-  int nms_passes = 2;
-  bool fuse_softmax = true;        // !FPC_PLAN_NO_FUSED_SOFTMAX (FPC_BF16's detector.layer.1, block_bf16.h)
-  bool convt_fused = true;         // !FPC_PLAN_CONVT_PHASES (FPC_BF16's ConvTranspose as ONE launch, convt_bf16.h)
   bool logits_valid = false;       // the last call wrote the logits ("det.1" of fpc_read_activation): false after a fused-softmax fpc_detect
-  bool nms_one_workgroup = false;  // FPC_PLAN_NMS_ONE_WORKGROUP: round 1's sort (one workgroup per frame) for every frame
-  int nms_g = 0;                     // FPC_NMS_G: workgroups per frame of the NMS rounds kernel (0 = 512 / frames, at most 16)
-  bool fuse_stem_pool = true;        // conv1+bn1+relu+max_pool in one launch (FPC_FUSE_STEM=0: two)
-  bool conv_lean = true;             // OP_CONV launches on conv2_mfma_kernel where it applies (FPC_PLAN_CONV_ROUND1 / FPC_CONV_LEAN=0: conv_mfma_kernel)
-  bool stem_lean = true;             // ... on stem_pool2_kernel where the conv map is whole 16 x 16 tiles (FPC_PLAN_STEM_ROUND3 / FPC_STEM_LEAN=0: stem_pool_kernel)
-  bool stem2 = false;                // decided in fpc_create: stem_lean, fp32 MFMA mode, fused stem + pool, whole tiles
-  bool layer1_t816 = false;          // direct (non-Winograd) layer1 blocks on 8x16 tiles instead of 16x16
 #ifdef FPC_DIAG
   unsigned long long* diag_stamps = nullptr;
   int diag_n = 0;
 #endif
-  bool winograd_in1 = true;          // descriptor.layer_in.1 (256 ch): conv-only Winograd x2 + 1x1 (FPC_WINOGRAD_IN1=0: fused direct block)
-  bool winograd_det = true;          // ... also the detector's 65-channel blocks (FPC_WINOGRAD_DET=0: direct)
-  int w36_cus = 0;                   // FPC_W36_CUS: CUs a generation-3 launch may take (0 = all): A/B knob for contexts that share the GPU
-  bool tiles_round6 = true;          // tiles chosen by the matrix rows they issue: layer2.0 on 4 x 16 (FPC_PLAN_TILES_ROUND5 / FPC_TILES_ROUND6=0: round 5's tilings)
-  bool w36_paired = true;            // the 64-channel F(4x4,3x3) layers on wblock36p_kernel, two waves per SIMD (FPC_PLAN_W36_ONE_WAVE / FPC_W36_PAIRED=0: wblock36_kernel<1, ..>)
-  bool winograd_det_gen3 = true;     // ... on wblock36_dust_kernel in batch calls (FPC_PLAN_DETECTOR_GEN1 / FPC_WINOGRAD_DET_GEN=1: round 1's kernel)
-  bool winograd = true;              // stride-1 blocks with <= 128 channels: Winograd F(2x2,3x3) (FPC_WINOGRAD=0: direct)
-  bool latency_tiles = true;         // calls of a few frames run the 128-channel Winograd blocks on 4 x 16 tiles (FPC_LATENCY_TILES=0: 8 x 16)
-  int winograd_gen = 3;              // 64- and 128-channel Winograd layers on wblock36_kernel (3: F(4x4,3x3)), wblock16_kernel (2) or wblock_mfma_kernel (1; FPC_WINOGRAD_GEN)
-  bool fuse_blocks = true;           // one launch per ResNetBlock (FPC_FUSE=0: conv1 / conv2 launches)
   bool weights_loaded = false;
   bool plan_error = false;           // a layer asked for a kernel instance that does not exist (fpc_create -> FPC_E_INVALID)
 
-  // one slab for all activations / results; carved below
-  char* slab = nullptr;
-  size_t slab_bytes = 0;
-  bool guard_zones = false;                                    // FPC_PLAN_GUARD_ZONES
-  std::vector<std::pair<size_t, size_t>> guards;               // (offset, bytes) of the canary zones in the slab
+  // The five device allocations a context can own: `slab` for all activations / results (build_plan), the others made
+  // by the call that reserves them.  bank_slab, topk_slab and lm_slab go with the bank; fpc_destroy frees what is left.
+  Slab slab, bank_slab, topk_slab, pnp_slab, lm_slab;
+  Slab* const slabs[5] = {&slab, &bank_slab, &topk_slab, &pnp_slab, &lm_slab};
   float *stem_out, *x0, *h4, *x1, *x2, *h8, *x3, *cat, *dh, *dproj, *d0, *lg;
   float *h16, *y16a, *y16b, *lo_h, *lo0, *desc_map, *desc_in_nhwc;
   float* prob;
@@ -678,32 +602,23 @@ struct fpc_ctx {
   int4* mgc_box = nullptr;
   // key-frame bank (fpc_bank_*, fpc_match_bank, fpc_homography_bank): one allocation of its own, made by fpc_bank_create --
   // storage, per-slot norms and fpc_match_bank's workspace, carved with canary zones in a FPC_PLAN_GUARD_ZONES context
-  char* bank_slab = nullptr;
-  size_t bank_bytes = 0;
   BankArgs bank{};
   int bank_format = FPC_BANK_F32;                              // FPC_BANK_BF16: bank.desc is null, the rows are bank16.desc
   BankBf16Args bank16{};                                       // (match_bank_bf16.h)
-  std::vector<std::pair<size_t, size_t>> bank_guards;          // (offset, bytes) of the canary zones in bank_slab
   // top-K candidates of the bank (fpc_bank_topk_reserve, match_bank_topk.h): a third allocation, made by that call and
   // freed with the bank -- the pair tables of max_batch x kmax (frame, candidate) pairs and the RANSAC workspace (pair
   // lists, rows, counts, best keys) of as many problems
-  char* topk_slab = nullptr;
   BankTopkArgs topk{};
   float4* topk_pairs = nullptr;
   int32_t *topk_row = nullptr, *topk_np = nullptr;
   unsigned long long* topk_best = nullptr;
-  std::vector<std::pair<size_t, size_t>> topk_guards;          // (offset, bytes) of the canary zones in topk_slab
   // RANSAC PnP (fpc_pnp_reserve, pnp_ransac.h): an allocation of its own, made by that call and freed by fpc_destroy -- the
   // pair records (with their mask rows), counts and best keys of max_batch problems
-  char* pnp_slab = nullptr;
   float4* pnp_rec = nullptr;
   int32_t* pnp_np = nullptr;
   unsigned long long* pnp_best = nullptr;
-  std::vector<std::pair<size_t, size_t>> pnp_guards;           // (offset, bytes) of the canary zones in pnp_slab
   // landmarks of the bank's rows (fpc_bank_landmarks_reserve): float4 [slots][rows], w = 1 valid / 0; freed with the bank
-  char* lm_slab = nullptr;
   float4* lm_xyzw = nullptr;
-  std::vector<std::pair<size_t, size_t>> lm_guards;            // (offset, bytes) of the canary zones in lm_slab
   int pts_n = 0;                     // frames of the last call that produced keypoints (fpc_detect*, fpc_get_points)
   bool pts_desc = false;             // ... and whether it sampled their descriptors
 
@@ -746,13 +661,15 @@ constexpr uint32_t GUARD_PATTERN = 0xA5C3F00Du;
 struct Carver {
   size_t off = 0;
   size_t guard = 0;
-  std::vector<std::pair<size_t, size_t>>* zones = nullptr;   // (offset, bytes) of every guard zone
+  GuardZones zones;   // (offset, bytes) of every guard zone
+  // a carver for one of `c`'s slabs: zones behind its buffers where the context has them
+  explicit Carver(const fpc_ctx* c) : guard(c->opt.guard_zones ? GUARD_BYTES : 0) {}
   template <typename T>
   size_t take(size_t n) {
     const size_t o = off;
     off = align_up(off + n * sizeof(T), 256);
     if (guard) {
-      zones->push_back({off, guard});
+      zones.push_back({off, guard});
       off += guard;
     }
     return o;
@@ -770,12 +687,11 @@ struct Carver {
   }
   void finish() {
     if (guard) {
-      zones->push_back({off, GUARD_TAIL});
+      zones.push_back({off, GUARD_TAIL});
       off += GUARD_TAIL;
     }
   }
 };
-
 
 __global__ void guard_fill_kernel(uint32_t* p, size_t n, uint32_t v) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
@@ -785,20 +701,19 @@ __global__ void guard_count_kernel(const uint32_t* p, size_t n, uint32_t v, unsi
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) mine += p[i] != v;
   if (mine) atomicAdd(bad, mine);
 }
-using GuardZones = std::vector<std::pair<size_t, size_t>>;
 static unsigned guard_blocks(size_t words) { return (unsigned)std::min<size_t>(4096, (words + 255) / 256); }
 
-// One slab's zones (the context's, the bank's, the top-K workspace's) on c->stream: written, or their damaged words counted.
-static void fill_zones(fpc_ctx* c, char* base, const GuardZones& zones) {
+// One slab's zones on stream `st`: written, or their damaged words counted.
+static void fill_zones(hipStream_t st, char* base, const GuardZones& zones) {
   for (const auto& z : zones) {
     const size_t n = z.second / 4;
-    guard_fill_kernel<<<guard_blocks(n), 256, 0, c->stream>>>(reinterpret_cast<uint32_t*>(base + z.first), n, GUARD_PATTERN);
+    guard_fill_kernel<<<guard_blocks(n), 256, 0, st>>>(reinterpret_cast<uint32_t*>(base + z.first), n, GUARD_PATTERN);
   }
 }
-static void count_zones(fpc_ctx* c, const char* base, const GuardZones& zones, unsigned long long* bad) {
-  for (const auto& z : zones) {
+static void count_zones(hipStream_t st, const Slab& s, unsigned long long* bad) {
+  for (const auto& z : s.zones) {
     const size_t n = z.second / 4;
-    guard_count_kernel<<<guard_blocks(n), 256, 0, c->stream>>>(reinterpret_cast<const uint32_t*>(base + z.first), n, GUARD_PATTERN, bad);
+    guard_count_kernel<<<guard_blocks(n), 256, 0, st>>>(reinterpret_cast<const uint32_t*>(s.base + z.first), n, GUARD_PATTERN, bad);
   }
 }
 
@@ -807,24 +722,27 @@ static int fill_guards(fpc_ctx* c) {
   // returns; c->stream is non-blocking, so nothing orders the two -- the first version lost 2 MB of pattern to it.
   // Waited for in every context: the first call's kernels must not race the zeroing either.)
   HIPCHECK(hipDeviceSynchronize());
-  fill_zones(c, c->slab, c->guards);
-  if (!c->guards.empty()) HIPCHECK(hipStreamSynchronize(c->stream));
+  fill_zones(c->stream, c->slab.base, c->slab.zones);
+  if (!c->slab.zones.empty()) HIPCHECK(hipStreamSynchronize(c->stream));
   return FPC_OK;
 }
 
-// A side slab (the key-frame bank, the top-K workspace) of cv.off bytes: zeroed, then the zones its carver listed filled
-// -- behind a device synchronise, as in fill_guards: the null stream's memset does not order c->stream.  On failure
-// nothing stays allocated.
-static int alloc_side_slab(fpc_ctx* c, const Carver& cv, char** slab) {
+// The cv.off bytes a finished carver asks for: zeroed, then the zones the carver listed filled on `st` -- behind a device
+// synchronise, as in fill_guards: the null stream's memset does not order `st`.  Then every pointer taken with
+// Carver::into is assigned.  On failure nothing stays allocated, and neither the slab nor those pointers are touched.
+int Slab::allocate(hipStream_t st, Carver& cv) {
   char* p = nullptr;
   HIPCHECK(hipMalloc((void**)&p, cv.off));
   hipError_t e = hipMemset(p, 0, cv.off);
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  fill_zones(c, p, *cv.zones);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  fill_zones(st, p, cv.zones);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) hipFree(p);
   HIPCHECK(e);
-  *slab = p;
+  base = p;
+  bytes = cv.off;
+  zones = std::move(cv.zones);
+  cv.bind(p);
   return FPC_OK;
 }
 
@@ -859,14 +777,15 @@ static int carve_results(fpc_ctx* c, Carver& cv) {
   cv.into(&c->mgc_perm_q, whole ? B * cap : 64); cv.into(&c->mgc_perm_t, whole ? B * cap : 64);
   cv.into(&c->mgc_box, whole ? 2 * B * ((cap + 63) / 64) : 64);
   cv.finish();
-  c->slab_bytes = cv.off;
-  if (hipMalloc((void**)&c->slab, c->slab_bytes) != hipSuccess) {
-    g_hip_err = "hipMalloc(workspace " + std::to_string(c->slab_bytes >> 20) + " MiB) failed";
+  c->slab.bytes = cv.off;
+  c->slab.zones = cv.zones;
+  if (hipMalloc((void**)&c->slab.base, c->slab.bytes) != hipSuccess) {
+    g_hip_err = "hipMalloc(workspace " + std::to_string(c->slab.bytes >> 20) + " MiB) failed";
     return FPC_E_HIP;
   }
-  HIPCHECK(hipMemset(c->slab, 0, c->slab_bytes));
+  HIPCHECK(hipMemset(c->slab.base, 0, c->slab.bytes));
   if (int grc = fill_guards(c)) return grc;
-  cv.bind(c->slab);
+  cv.bind(c->slab.base);
   c->bcast_tag = reinterpret_cast<uint32_t*>(c->status + 4);
   return FPC_OK;
 }
@@ -978,7 +897,7 @@ struct ConvSpec {
 static bool conv_is_lean(const fpc_ctx* c, const Op& op) {
   const KindInfo& k = g_kinds[op.kind];
   const ConvArgs& a = op.args;
-  return c->conv_lean && lean_kind(op.kind) && a.nchunk1 == 0 && a.nstore == op.grid_y * (k.WN * k.NB * 32) && a.cso % 4 == 0 &&
+  return c->opt.conv_lean && lean_kind(op.kind) && a.nchunk1 == 0 && a.nstore == op.grid_y * (k.WN * k.NB * 32) && a.cso % 4 == 0 &&
          (!a.res || a.csr % 4 == 0);
 }
 
@@ -1110,7 +1029,7 @@ static void retile_block(fpc_ctx* c, BKind small) {
   tile_block(c->ops.back(), small);
 }
 static void retile_last(fpc_ctx* c, BKind small) {
-  if (!c->latency_tiles || c->ops.empty() || c->ops.back().type != OP_BLOCK) return;
+  if (!c->opt.latency_tiles || c->ops.empty() || c->ops.back().type != OP_BLOCK) return;
   retile_block(c, small);
 }
 // MFMA rows a fused block issues per frame on instance `k`: its tiles x the M of a tile (padding included)
@@ -1123,7 +1042,7 @@ static long block_rows(BKind k, int Ho, int Wo) {
 // A tie keeps the instance it has.  plan_hash keeps mixing the instance it had: the blob is the same.
 // FPC_PLAN_TILES_ROUND5 keeps round 5's tiles.
 static void retile_rows(fpc_ctx* c, BKind fit) {
-  if (!c->tiles_round6 || c->ops.empty() || c->ops.back().type != OP_BLOCK) return;
+  if (!c->opt.tiles_round6 || c->ops.empty() || c->ops.back().type != OP_BLOCK) return;
   Op& o = c->ops.back();
   if (block_rows(fit, o.bargs.Ho, o.bargs.Wo) >= block_rows(o.bkind, o.bargs.Ho, o.bargs.Wo)) return;
   const BKind had = o.bkind;
@@ -1132,7 +1051,7 @@ static void retile_rows(fpc_ctx* c, BKind fit) {
 }
 
 static void retile_last(fpc_ctx* c, Kind small) {
-  if (!c->latency_tiles || c->ops.empty() || c->ops.back().type != OP_CONV) return;
+  if (!c->opt.latency_tiles || c->ops.empty() || c->ops.back().type != OP_CONV) return;
   const KindInfo &k0 = g_kinds[c->ops.back().kind], &k = g_kinds[small];
   if (k.KC != k0.KC || k.WN * k.NB != k0.WN * k0.NB || k.S != k0.S || k.EXT != k0.EXT) { c->plan_error = true; return; }
   Op& o = c->ops.back();
@@ -1212,9 +1131,9 @@ static void add_wblock(fpc_ctx* c, const BlockSpec& s, WKind wk, size_t* blob_of
   // On the same fragments (`half`): generation 2's 128-channel layer on 4 x 16 tiles -- under small_only the caller's
   // large-call op exists already, and only that instance is added.
   WKind own = WK_COUNT;
-  if (c->latency_tiles && k.dust) own = s.cin == 65 ? WK_W816_K24_C72 : WK_W816_K32_C72;
-  else if (c->latency_tiles && k.gen == 3) own = s.cout == 64 ? WK_W16_C64 : WK_W16_C128;
-  const bool half = wk == WK_W16_C128 && (small_only || c->latency_tiles);
+  if (c->opt.latency_tiles && k.dust) own = s.cin == 65 ? WK_W816_K24_C72 : WK_W816_K32_C72;
+  else if (c->opt.latency_tiles && k.gen == 3) own = s.cout == 64 ? WK_W16_C64 : WK_W16_C128;
+  const bool half = wk == WK_W16_C128 && (small_only || c->opt.latency_tiles);
   op.when = small_only ? 1 : (half || own != WK_COUNT) ? 2 : 0;
   if (!(small_only && half)) push_op(c, op, cw);
   if (half) {
@@ -1479,7 +1398,7 @@ static void add_fnet(fpc_ctx* c, const Layer* net, const FKind* kinds, size_t* b
     if (l == L_UP) add_fconvT(c, kinds[l], net[l], bo);
     else add_fblock(c, fblock_spec(c, net[l], kinds[l]), bo);
     if (l != L_DET1) continue;
-    if (c->bf16) c->ops.back().fused_softmax_capable = c->fuse_softmax;
+    if (c->bf16) c->ops.back().fused_softmax_capable = c->opt.fuse_softmax;
     push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
   }
 }
@@ -1501,7 +1420,7 @@ static void build_bf16_ops(fpc_ctx* c, const Layer* net, size_t* bo) {
   kinds[L_DET1] = FK_F816_s1_K80_C80;
   kinds[L_IN0] = FK_F320_s2_K128_C256;
   kinds[L_IN1] = FK_F416_s1_K128_C256;
-  kinds[L_UP] = c->convt_fused ? FK_F816_ctf_K64_C128 : FK_F816_ct_K64_C128;
+  kinds[L_UP] = c->opt.convt_fused ? FK_F816_ctf_K64_C128 : FK_F816_ct_K64_C128;
   kinds[L_OUT0] = FK_F816_s1_K64_C128;
   // (the descriptor map is bf16 as well -- round 3: descriptor16_kernel<8, true> reads it, fpc_forward / the tap convert it)
   kinds[L_OUT1] = FK_F816_s1_K128_C128;
@@ -1555,20 +1474,18 @@ static void add_fconv(fpc_ctx* c, FKind kind, const std::string& prefix, const f
 static int build_vgg_plan(fpc_ctx* c) {
   const int H = c->H, W = c->W, B = c->B, Hc = H / 8, Wc = W / 8;
   const size_t npix8 = (size_t)B * Hc * Wc;
-  if (!c->split && c->winograd) {
+  if (!c->split && c->opt.winograd) {
     // Where generation 2 runs the full-resolution 64-channel layers -- this network's widest tensors, 256 bytes per frame
     // pixel -- every frame it is handed must lie in its reach (w16_frames_in_reach).  A plan that runs it in every call
     // (FPC_PLAN_WINOGRAD_GEN2; generation 3 with a frame too large for W36_MARKER) addresses the whole batch from frame 0:
     // refused here, before anything is allocated, where max_batch frames do not fit.  The default plan runs it only in
     // calls of a few frames, from the call's frame 0: a call of more frames than fit takes the batch plan instead.
     const int reach = w16_frames_in_reach(H, W, 64);
-    const bool every_call = c->winograd_gen == 2 || (c->winograd_gen == 3 && !w36_fits(B, H, W, 64, 64));
+    const bool every_call = c->opt.winograd_gen == 2 || (c->opt.winograd_gen == 3 && !w36_fits(B, H, W, 64, 64));
     if (every_call && B > reach) return FPC_E_INVALID;
-    if (c->winograd_gen == 3 && c->latency_tiles) c->small_reach = reach;
+    if (c->opt.winograd_gen == 3 && c->opt.latency_tiles) c->small_reach = reach;
   }
-  Carver cv;
-  cv.zones = &c->guards;
-  cv.guard = c->guard_zones ? GUARD_BYTES : 0;
+  Carver cv(c);
   // activations: one buffer per tensor (sub-batches of one call run different layers at the same time)
   const int ah[4] = {H, H / 2, H / 4, Hc}, aw[4] = {W, W / 2, W / 4, Wc}, ac[4] = {64, 64, 128, 128};
   float *act_a[4], *act_b[4], *act_p[3], *det_a, *desc_a;
@@ -1609,22 +1526,22 @@ static int build_vgg_plan(fpc_ctx* c) {
       add_fconv(c, fk, prefix, x, cin, cin, cin, Hx, Wx, out, cso, cout, ksize, relu, desc, &bo);
       return;
     }
-    if (ksize == 3 && relu && c->winograd) {  // Winograd F(2x2,3x3), conv-only; 256 outputs = two 128-channel launches
-      const WKind wk2 = c->winograd_gen >= 2 ? (cout == 64 ? WK_W16_C64 : WK_W16_C128) : (cout == 64 ? WK_W816_K32_C64 : WK_W816_K32_C128);
+    if (ksize == 3 && relu && c->opt.winograd) {  // Winograd F(2x2,3x3), conv-only; 256 outputs = two 128-channel launches
+      const WKind wk2 = c->opt.winograd_gen >= 2 ? (cout == 64 ? WK_W16_C64 : WK_W16_C128) : (cout == 64 ? WK_W816_K32_C64 : WK_W816_K32_C128);
       auto add = [&](WKind wk, int when) {
         const size_t i0 = c->ops.size();
         for (int n0 = 0; n0 < cout; n0 += g_wkinds[wk].CMID)
           add_wconv(c, prefix, false, wk, x, cin, cin, Hx, Wx, out, cso, cout, n0, desc, &bo);
         mark_when(c, i0, when);
       };
-      if (c->winograd_gen == 3 && w36_fits(c->B, Hx, Wx, cin, cso) && cin % 32 == 0 && cin >= 64) {
+      if (c->opt.winograd_gen == 3 && w36_fits(c->B, Hx, Wx, cin, cso) && cin % 32 == 0 && cin >= 64) {
         // round 4: F(4x4,3x3) for the C++ network's 3x3 layers too (the conv-only form of wblock36_kernel; 256 outputs in
         // parts), with generation 2 -- fragments of its own -- for calls of a few frames, as the Python network's blocks
         // (priced for a 32-frame call whatever max_batch is: the packed layout must not depend on it -- contexts of
         // different max_batch exchange blobs)
         const int part = w36_conv_part(cout, ((Hx + 15) / 16) * ((Wx + 15) / 16) * 32, 256);
-        add(w36_kind(part, Hx, Wx, c->w36_paired), c->latency_tiles ? 2 : 0);
-        if (c->latency_tiles) add(wk2, 1);
+        add(w36_kind(part, Hx, Wx, c->opt.w36_paired), c->opt.latency_tiles ? 2 : 0);
+        if (c->opt.latency_tiles) add(wk2, 1);
       } else {
         add(wk2, 0);
       }
@@ -1707,25 +1624,25 @@ struct F32Kinds {
 
 // The Winograd instance of a fused stride-1 block (WK_COUNT: none, the direct block runs it)
 static WKind wblock_kind(const fpc_ctx* c, const Layer& L) {
-  if (!c->winograd || L.stride != 1) return WK_COUNT;
+  if (!c->opt.winograd || L.stride != 1) return WK_COUNT;
   const bool fits = w36_fits(c->B, L.H, L.W, L.csx, L.csy);
   // generation 3's projection pass walks x in 16-channel steps, 4 or 8 per pass (wblock36_mfma.h: gemm_over advances
   // by 4): k8_x = cinp / 8 must be a multiple of 8, i.e. cinp of 64 -- true of every layer of both networks; a
   // layer that is not falls back to generation 2 instead of running extra K steps over stale staging rows
-  const int gen = c->winograd_gen == 3 && (!fits || (L.proj && L.cinp % 64 != 0)) ? 2 : c->winograd_gen;
-  if (L.cinp % 32 == 0 && L.cout == 64) return gen == 3 ? w36_kind(64, L.H, L.W, c->w36_paired) : gen == 2 ? WK_W16_C64 : WK_W816_K32_C64;
+  const int gen = c->opt.winograd_gen == 3 && (!fits || (L.proj && L.cinp % 64 != 0)) ? 2 : c->opt.winograd_gen;
+  if (L.cinp % 32 == 0 && L.cout == 64) return gen == 3 ? w36_kind(64, L.H, L.W, c->opt.w36_paired) : gen == 2 ? WK_W16_C64 : WK_W816_K32_C64;
   if (L.cinp % 32 == 0 && L.cout == 128) return gen == 3 ? w36_kind(128, L.H, L.W) : gen == 2 ? WK_W16_C128 : WK_W816_K32_C128;
-  if (!c->winograd_det) return WK_COUNT;
-  if (L.cout == 65 && c->winograd_det_gen3 && c->winograd_gen == 3 && fits &&
+  if (!c->opt.winograd_det) return WK_COUNT;
+  if (L.cout == 65 && c->opt.winograd_det_gen3 && c->opt.winograd_gen == 3 && fits &&
       (L.cin == 65 ? !L.proj : (L.cin == L.cinp && L.cinp % 64 == 0 && L.cinp <= 256)))
-    return w36_kind(65, L.H, L.W, c->w36_paired);
+    return w36_kind(65, L.H, L.W, c->opt.w36_paired);
   if (L.cinp % 32 == 0 && L.coutp == 72) return WK_W816_K32_C72;
   if (L.cinp == 72 && L.coutp == 72) return WK_W816_K24_C72;
   return WK_COUNT;
 }
 
 static void add_f32_block(fpc_ctx* c, const Layer& L, const F32Kinds& k, size_t* bo) {
-  if (c->fuse_blocks) {
+  if (c->opt.fuse_blocks) {
     const WKind wk = wblock_kind(c, L);
     if (wk != WK_COUNT) add_wblock(c, block_spec(L, k.bk), wk, bo);
     else add_block(c, block_spec(L, k.bk), bo);
@@ -1748,8 +1665,8 @@ static void add_f32_in1(fpc_ctx* c, const Layer& L, const F32Kinds& k, size_t* b
   // Generation 3: FOUR parts of 64 channels (the NB = 1 instance, gridDim.y = 4).  A 30 x 40 map is 6 tiles per
   // frame: 192 tiles x 2 halves were 384 one-tile workgroups = 1.5 rounds of the 256 CUs at the 128-channel tile's
   // time; 192 x 4 = 768 half-as-long tiles are 3 full rounds (64 workgroups per part walk 3 tiles each).
-  const bool g3 = c->winograd_gen == 3 && w36_fits(c->B, L.H, L.W, L.csx, L.csy);
-  const WKind wk = g3 ? w36_kind(64, L.H, L.W, c->w36_paired, c->tiles_round6) : c->winograd_gen >= 2 ? WK_W16_C128 : WK_W816_K32_C128;
+  const bool g3 = c->opt.winograd_gen == 3 && w36_fits(c->B, L.H, L.W, L.csx, L.csy);
+  const WKind wk = g3 ? w36_kind(64, L.H, L.W, c->opt.w36_paired, c->opt.tiles_round6) : c->opt.winograd_gen >= 2 ? WK_W16_C128 : WK_W816_K32_C128;
   const int gen = g_wkinds[wk].gen;
   const ConvSpec t = conv2_spec(L, k.k1);
   const size_t ia = c->ops.size();   // [the launch, its shadows, the 1x1]
@@ -1757,14 +1674,14 @@ static void add_f32_in1(fpc_ctx* c, const Layer& L, const F32Kinds& k, size_t* b
   add_conv(c, t, bo);
   retile_last(c, K_T320_1x1_K64_N128);
   if (c->plan_error) return;
-  if (gen == 2 && c->latency_tiles) {
+  if (gen == 2 && c->opt.latency_tiles) {
     // calls of a few frames: the same two-half launch on 4 x 16 tiles (24 tiles x 2 halves per frame instead of
     // 12 x 2), then the same 1x1 -- 0.10 ms for one frame against 0.16 ms for the fused direct block on 20 tiles
     c->ops[ia].when = 2;
     c->ops.insert(c->ops.begin() + ia + 1, half_tile_copy(c->ops[ia]));
     c->ops[ia + 1].when = 1;
     c->convw.insert(c->convw.begin() + ia + 1, fpc_ctx::ConvW(c->convw[ia]));
-  } else if (gen == 3 && c->latency_tiles) {
+  } else if (gen == 3 && c->opt.latency_tiles) {
     // generation 3's fragments have 36 positions: the small-call variant (generation 2 on 4 x 16 tiles, then the same
     // 1x1) gets fragments of its own
     mark_when(c, ia, 2);
@@ -1775,7 +1692,7 @@ static void add_f32_in1(fpc_ctx* c, const Layer& L, const F32Kinds& k, size_t* b
     if (c->plan_error) return;
     c->ops[ib] = half_tile_copy(c->ops[ib]);
     mark_when(c, ib, 1);
-  } else if (c->latency_tiles || c->winograd_gen == 1) {
+  } else if (c->opt.latency_tiles || c->opt.winograd_gen == 1) {
     mark_when(c, ia, 2);
     // a call of a few frames has 12 tiles per frame here: three dependent launches cost more latency than they save
     // work, so small calls take the fused direct block instead (its weights sit in the blob next to the others)
@@ -1785,7 +1702,7 @@ static void add_f32_in1(fpc_ctx* c, const Layer& L, const F32Kinds& k, size_t* b
 }
 
 static void build_f32_ops(fpc_ctx* c, const Layer* net, size_t* bo) {
-  const BKind l1kind = c->layer1_t816 ? BK_B816_s1_K64_C64 : BK_B1616_s1_K32_C64;
+  const BKind l1kind = c->opt.layer1_t816 ? BK_B816_s1_K64_C64 : BK_B1616_s1_K32_C64;
   F32Kinds kinds[L_COUNT];
   kinds[L_ENC10] = kinds[L_ENC11] = {K_T816_3x3_K64_N64, K_T816_1x1_K64_N64, l1kind};
   kinds[L_ENC20] = {K_T620_3x3s2_K32_N128, K_T620_1x1_K64_N128, BK_B620_s2_K32_C128};
@@ -1801,22 +1718,22 @@ static void build_f32_ops(fpc_ctx* c, const Layer* net, size_t* bo) {
     if (l == L_UP) {
       add_conv(c, upsample_spec(L, k.k3), bo);
       retile_last(c, K_T320_2x2_K64_N128);
-    } else if (l == L_DET0 && !c->fuse_blocks) {
+    } else if (l == L_DET0 && !c->opt.fuse_blocks) {
       // detector.layer.0: the projection shortcut has K = 128 while conv2 has K = 72 (65 padded):
       // run the shortcut as its own 1x1 and add it as the residual of conv2
       add_conv(c, conv1_spec(L, k.k3), bo);
       add_conv(c, shortcut_spec(L, K_T620_1x1_K64_N96, c->dproj), bo);
       add_conv(c, conv2_spec(L, k.k1, c->dproj), bo);
-    } else if (l == L_IN1 && c->fuse_blocks && c->winograd && c->winograd_in1) {
+    } else if (l == L_IN1 && c->opt.fuse_blocks && c->opt.winograd && c->opt.winograd_in1) {
       add_f32_in1(c, L, k, bo);
     } else {
       add_f32_block(c, L, k, bo);
     }
-    if (l == L_ENC20 && c->fuse_blocks) {
+    if (l == L_ENC20 && c->opt.fuse_blocks) {
       retile_last(c, BK_B320_s2_K32_C128);
       retile_rows(c, BK_B416_s2_K32_C128);
     }
-    if (l == L_IN0 && c->fuse_blocks) retile_last(c, BK_B310_s2_K32_C256);
+    if (l == L_IN0 && c->opt.fuse_blocks) retile_last(c, BK_B310_s2_K32_C256);
     if (l == L_DET1) push_op(c, OP_SOFTMAX, "exp-softmax+depth_to_space+threshold");
   }
 }
@@ -1826,9 +1743,7 @@ static int build_plan(fpc_ctx* c) {
   const int H = c->H, W = c->W, B = c->B;
   const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, Hc = H / 8, Wc = W / 8, H16 = H / 16, W16 = W / 16;
   // ---- carve the slab: this network's activations, then what both networks share
-  Carver cv;
-  cv.zones = &c->guards;
-  cv.guard = c->guard_zones ? GUARD_BYTES : 0;
+  Carver cv(c);
   const size_t npix4 = (size_t)B * H4 * W4, npix8 = (size_t)B * Hc * Wc, npix16 = (size_t)B * H16 * W16;
   cv.into(&c->stem_out, (size_t)B * H2 * W2 * 64);
   cv.into(&c->x0, npix4 * 64); cv.into(&c->h4, npix4 * 64); cv.into(&c->x1, npix4 * 64); cv.into(&c->x2, npix4 * 64);
@@ -1875,7 +1790,7 @@ static int build_plan(fpc_ctx* c) {
   c->stem.tiles_y = (H2 + STEM_T - 1) / STEM_T;
   // round 5: the fp32 stem + pool on stem_pool2_kernel where the conv map's width is whole tiles (VGA, HD, QVGA).  The fragments carry the bias as a K step in EVERY geometry (pack layout revision 4; stem_pool_kernel and
   // stem_kernel skip that step), so the choice is a launch-time one and blobs stay exchangeable between geometries
-  c->stem2 = c->stem_lean && !c->bf16 && !c->split && !c->vgg && (c->fuse_stem_pool || c->cin == 1) && H2 % 2 == 0 && W2 % STEM_T == 0;
+  c->opt.stem2 = c->opt.stem_lean && !c->bf16 && !c->split && !c->vgg && (c->opt.fuse_stem_pool || c->cin == 1) && H2 % 2 == 0 && W2 % STEM_T == 0;
   return FPC_OK;
 }
 
@@ -2501,11 +2416,11 @@ static void diag_stamp(fpc_ctx* c, const Op& op, Args& a, int tiles) {
 // The stem's kernel: chosen HERE, for the launch and for the name fpc_get_timings reports alike
 enum StemKind { STEM_PLAIN, STEM_POOL, STEM_POOL2, STEM_X3, STEM_X3_F16, STEM_BF16 };
 static StemKind stem_kind(const fpc_ctx* c) {
-  if (!(c->fuse_stem_pool || c->cin == 1 || c->bf16)) return STEM_PLAIN;   // conv1 alone: OP_POOL follows
+  if (!(c->opt.fuse_stem_pool || c->cin == 1 || c->bf16)) return STEM_PLAIN;   // conv1 alone: OP_POOL follows
   if (c->split_f16) return STEM_X3_F16;
   if (c->bf16) return STEM_BF16;   // bf16 operands like every other layer of the mode, bf16 out, no atomics
   if (c->split) return STEM_X3;
-  return c->stem2 ? STEM_POOL2 : STEM_POOL;
+  return c->opt.stem2 ? STEM_POOL2 : STEM_POOL;
 }
 
 // Launches the stem for `sb`'s frames -- unless `sb` is null: the name alone -- and returns its symbol
@@ -2589,14 +2504,14 @@ static void launch_wblock(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
   a.frame0 = f0;
   diag_stamp(c, op, a, a.tiles_x * a.tiles_y * n);
   a.total = a.tiles_x * a.tiles_y * n;
-  a.xcd_order = c->xcd_order ? 1 : 0;
+  a.xcd_order = c->opt.xcd_order ? 1 : 0;
   {  // range of the input's buffer descriptor: frames 0 .. f0 + n - 1 of the tensor, from `x` (already offset to its first channel)
     const unsigned long long xb = (unsigned long long)(f0 + n) * a.H * a.W * a.csx * sizeof(float);
     a.x_bytes = xb > W16_REACH ? (unsigned)W16_REACH : (unsigned)xb;
   }
   // persistent (one workgroup per CU walking the tiles) when a workgroup gets enough tiles to
   // amortise; otherwise one workgroup per tile
-  int grid = (c->persist_min_tiles > 0 && a.total >= c->persist_min_tiles * c->num_cus) ? c->num_cus : a.total;
+  int grid = (c->opt.persist_min_tiles > 0 && a.total >= c->opt.persist_min_tiles * c->num_cus) ? c->num_cus : a.total;
   if (g_wkinds[op.wkind].gen == 3) {
     // Pointers to the launch's first frame, as many frames per launch as stay below W36_MARKER bytes (all of them,
     // except at the C++ network's full-resolution layers: 78.6 MB per VGA frame and tensor).
@@ -2604,7 +2519,7 @@ static void launch_wblock(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
     const float* x0 = a.x;
     float* o0 = a.out;
     const int Hf = a.H, tx_f = a.tiles_x, ty_f = a.tiles_y;
-    const WKind sk = c->tiles_round6 ? w36_stacked_kind(op.wkind) : WK_COUNT;
+    const WKind sk = c->opt.tiles_round6 ? w36_stacked_kind(op.wkind) : WK_COUNT;
     double mf = 0.0;
     for (int g0 = 0; g0 < n; g0 += fpl) {
       const int gn = std::min(fpl, n - g0);
@@ -2627,7 +2542,7 @@ static void launch_wblock(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
       // leave the other CUs to the launches of the other sub-batch's stream -- 640 tiles: 216 workgroups x 3 rounds
       // instead of 256 of which 128 idle through the third; 320 tiles: 160 x 2.
       // (a launch of gridDim.y parts shares the CUs between them: each part's tile walk gets CUs / parts)
-      const int cus_cap = c->w36_cus > 0 ? std::min(c->num_cus, c->w36_cus) : c->num_cus;
+      const int cus_cap = c->opt.w36_cus > 0 ? std::min(c->num_cus, c->opt.w36_cus) : c->num_cus;
       const int cus8 = std::max(1, cus_cap / 8 / std::max(1, op.grid_y)), per_xcd = (a.total + 7) / 8;
       const int rounds = (per_xcd + cus8 - 1) / cus8;
       const int grid3 = 8 * std::min(cus8, (per_xcd + rounds - 1) / rounds);
@@ -2759,7 +2674,7 @@ static void run_nms(fpc_ctx* c, const Sub& sb) {
   a.nmsmap = c->nmsmap + f0 * HW; a.cand = c->cand + f0 * HW; a.ncand = c->ncand + f0;
   a.sort_scratch = c->sort_scratch + (size_t)f0 * c->sort_cap;
   a.sort_cap = c->sort_cap;
-  const bool chunked = !c->nms_one_workgroup;
+  const bool chunked = !c->opt.nms_one_workgroup;
   a.aux = chunked ? c->nms_aux + (size_t)f0 * NMS_AUX_INTS : nullptr;
   a.H = c->H; a.W = c->W; a.r = c->cfg.nms_dist; a.border = c->cfg.border_remove; a.cap = c->cap;
   a.count = c->count + f0; a.xy = c->xy + (size_t)f0 * c->cap * 2; a.conf = c->conf + (size_t)f0 * c->cap;
@@ -2767,8 +2682,8 @@ static void run_nms(fpc_ctx* c, const Sub& sb) {
   a.max_rounds = c->H * c->W;
   // enough workgroups that a typical frame (a few thousand candidates) has about one candidate
   // per thread; the second launch normally finds nothing left to do
-  const int G = c->nms_g > 0 ? c->nms_g : std::max(1, std::min(16, 512 / n));
-  for (int pass = 0; pass < c->nms_passes; ++pass) {
+  const int G = c->opt.nms_g > 0 ? c->opt.nms_g : std::max(1, std::min(16, 512 / n));
+  for (int pass = 0; pass < c->opt.nms_passes; ++pass) {
     if (c->cfg.nms_dist == 4)
       hipLaunchKernelGGL(nms_rounds_kernel<4>, dim3(G, n), dim3(NMS_ROUNDS_THREADS), 0, sb.st, a);
     else
@@ -2818,7 +2733,7 @@ static int for_each_sub(fpc_ctx* c, int n, F&& body) {
   // fpc_set_timing(n > 1): every n-th pass over a batch carries the events -- decided HERE, for every entry point alike
   // (fpc_detect, fpc_forward, fpc_detect_u8*, each network pass of fpc_homography_adaptation)
   if (c->timing_every > 1) c->timing = c->timing_calls++ % c->timing_every == 0;
-  int parts = std::min<int>((int)c->aux.size() + 1, std::max(1, n / c->min_sub));
+  int parts = std::min<int>((int)c->aux.size() + 1, std::max(1, n / c->opt.min_sub));
   if (parts > 1) HIPCHECK(hipEventRecord(c->ev_fork, c->stream));
   int f0 = 0;
   for (int p = 0; p < parts; ++p) {
@@ -2826,7 +2741,7 @@ static int for_each_sub(fpc_ctx* c, int n, F&& body) {
     Sub sb;
     sb.f0 = f0;
     sb.n = cnt;
-    sb.small = n < 2 * c->min_sub && n <= c->small_reach;
+    sb.small = n < 2 * c->opt.min_sub && n <= c->small_reach;
     sb.st = p == 0 ? c->stream : c->aux[p - 1];
     sb.side = c->side[p];
     // The runtime multiplexes streams onto a few hardware queues (GPU_MAX_HW_QUEUES) in creation order, and two
@@ -2859,7 +2774,7 @@ static void run_path(fpc_ctx* c, const float* frames, const Sub& sb0, bool de, i
   c->logits_valid = !sb.fuse_softmax;
   hipMemsetAsync(c->range + (size_t)sb.f0 * FPC_RANGE_WORDS, 0, sizeof(uint32_t) * FPC_RANGE_WORDS * sb.n, sb.st);
   run_network(c, frames, sb, 0, sb.st);
-  if (de && upto && c->nms_aside && !sb.small && sb.side) {
+  if (de && upto && c->opt.nms_aside && !sb.small && sb.side) {
     // detector head and softmax in line; the (latency-bound, few-CU) NMS on the side stream next to the descriptor head
     run_network(c, frames, sb, 1, sb.st);
     if (!sb.fuse_softmax) run_softmax(c, sb, !upto);
@@ -2872,7 +2787,7 @@ static void run_path(fpc_ctx* c, const float* frames, const Sub& sb0, bool de, i
     run_desc(c, sb, c->desc_map);
     return;
   }
-  if (!de || !(c->split_heads || sb.small) || !sb.side) {
+  if (!de || !(c->opt.split_heads || sb.small) || !sb.side) {
     run_network(c, frames, sb, 1, sb.st);
     if (!sb.fuse_softmax) run_softmax(c, sb, !upto);
     if (upto) run_nms(c, sb);
@@ -2962,24 +2877,16 @@ enum { SLOT_MAIN = 0, SLOT_AUX = 1, SLOT_SIDE = 100, SLOT_UPLOAD = 200 };
 
 // Dynamic-LDS limits of every kernel instance and the occupancy table of the bf16 / split-operand instances.
 static int prepare_kernels(fpc_ctx* c, const fpc_config* cfg) {
-  for (int k = 0; k < K_COUNT; ++k)
-    HIPCHECK(hipFuncSetAttribute(g_kinds[k].fn, hipFuncAttributeMaxDynamicSharedMemorySize, g_kinds[k].lds_bytes));
-  for (const LeanKindInfo& l : g_lean_kinds) HIPCHECK(hipFuncSetAttribute(l.fn, hipFuncAttributeMaxDynamicSharedMemorySize, l.lds_bytes));
-  for (int k = 0; k < WK_COUNT; ++k)
-    HIPCHECK(hipFuncSetAttribute(g_wkinds[k].fn, hipFuncAttributeMaxDynamicSharedMemorySize, g_wkinds[k].lds_bytes));
-  for (int k = 0; k < BK_COUNT; ++k)
-    HIPCHECK(hipFuncSetAttribute(g_bkinds[k].fn, hipFuncAttributeMaxDynamicSharedMemorySize, g_bkinds[k].lds_bytes));
+  if (int rc = allow_dynamic_lds(g_kinds)) return rc;
+  if (int rc = allow_dynamic_lds(g_lean_kinds)) return rc;
+  if (int rc = allow_dynamic_lds(g_wkinds)) return rc;
+  if (int rc = allow_dynamic_lds(g_bkinds)) return rc;
+  if (int rc = allow_dynamic_lds(g_fkinds)) return rc;
   static_assert(FK_COUNT <= 64, "fpc_ctx::fkind_blocks_per_cu");
   for (int k = 0; k < FK_COUNT; ++k) {
-    HIPCHECK(hipFuncSetAttribute(g_fkinds[k].fn, hipFuncAttributeMaxDynamicSharedMemorySize, g_fkinds[k].lds_bytes));
     int nb = 0;
-    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, g_fkinds[k].fn, g_fkinds[k].WM * g_fkinds[k].WN * 64, g_fkinds[k].lds_bytes));
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, g_fkinds[k].fn, g_fkinds[k].threads, g_fkinds[k].lds_bytes));
     c->fkind_blocks_per_cu[k] = std::max(1, nb);
-#ifdef FPC_DIAG
-    hipFuncAttributes fa{};
-    hipFuncGetAttributes(&fa, g_fkinds[k].fn);
-    fprintf(stderr, "[diag] %s: lds %d B, regs %d, scratch %zu, occupancy %d blocks/CU\n", g_fkinds[k].name, g_fkinds[k].lds_bytes, fa.numRegs, fa.localSizeBytes, nb);
-#endif
   }
   HIPCHECK(hipFuncSetAttribute((const void*)softmax_d2s_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                12 * cfg->width * (int)sizeof(float)));
@@ -2990,18 +2897,9 @@ static int prepare_kernels(fpc_ctx* c, const fpc_config* cfg) {
   HIPCHECK(hipFuncSetAttribute((const void*)nms_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                NMS_LDS_KEYS * (int)sizeof(unsigned long long)));
 #ifdef FPC_DIAG
-  for (int k = 0; k < BK_COUNT; ++k) {
-    int nb = -1;
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, g_bkinds[k].fn, g_bkinds[k].WM * g_bkinds[k].WN * 64, g_bkinds[k].lds_bytes);
-    hipFuncAttributes fa{};
-    hipFuncGetAttributes(&fa, g_bkinds[k].fn);
-    fprintf(stderr, "[diag] %s: lds %d B, regs %d, static lds %zu, occupancy %d blocks/CU\n", g_bkinds[k].name, g_bkinds[k].lds_bytes, fa.numRegs, fa.sharedSizeBytes, nb);
-  }
-  for (int k = 0; k < K_COUNT; ++k) {
-    int nb = -1;
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, g_kinds[k].fn, g_kinds[k].threads, g_kinds[k].lds_bytes);
-    fprintf(stderr, "[diag] %s: lds %d B, occupancy %d blocks/CU\n", g_kinds[k].name, g_kinds[k].lds_bytes, nb);
-  }
+  print_occupancy(g_fkinds);
+  print_occupancy(g_bkinds);
+  print_occupancy(g_kinds);
 #endif
   return FPC_OK;
 }
@@ -3040,6 +2938,8 @@ int fpc_create(fpc_ctx** out, const fpc_config* cfg) {
     c->num_cus = std::max(1, prop.multiProcessorCount);
   }
   c->cfg = *cfg;
+  // launch-plan options: plan_flags and the config's fields first, then the FPC_* variables over them (plan_options.h)
+  c->opt = resolve_plan_options(*cfg, [](const char* name) -> const char* { return getenv(name); });
   c->H = cfg->height;
   c->W = cfg->width;
   c->B = cfg->max_batch;
@@ -3076,61 +2976,7 @@ int fpc_create(fpc_ctx** out, const fpc_config* cfg) {
   if (!c->stream) { qmap::release_owner(c.get()); g_hip_err = "hipStreamCreateWithFlags"; return FPC_E_HIP; }
   c->own_stream = true;
   {
-    // Launch-plan knobs: fpc_config fields (include/fpc.h, FPC_PLAN_*) first, then the FPC_* environment variables as
-    // overrides for A/B runs of an unmodified caller.
-    int nsub = cfg->num_streams > 0 ? std::min(8, cfg->num_streams) : (c->split ? 3 : 2);   // measured: 2 sub-batches for the fp32-MFMA kernels, 3 for the (shorter) split-operand ones
-    const unsigned pf = cfg->plan_flags;
-    c->fuse_blocks = !(pf & FPC_PLAN_NO_FUSED_BLOCKS);
-    c->guard_zones = (pf & FPC_PLAN_GUARD_ZONES) != 0;
-    if (const char* e = getenv("FPC_GUARD_ZONES")) c->guard_zones = atoi(e) != 0;      // (a whole test run under the canary zones)
-    c->winograd_det_gen3 = !(pf & FPC_PLAN_DETECTOR_GEN1);
-    c->w36_paired = !(pf & FPC_PLAN_W36_ONE_WAVE);
-    if (const char* e = getenv("FPC_W36_PAIRED")) c->w36_paired = atoi(e) != 0;
-    c->tiles_round6 = !(pf & FPC_PLAN_TILES_ROUND5);
-    if (const char* e = getenv("FPC_TILES_ROUND6")) c->tiles_round6 = atoi(e) != 0;
-    if (const char* e = getenv("FPC_W36_CUS")) c->w36_cus = std::max(0, atoi(e));
-    if (const char* e = getenv("FPC_WINOGRAD_DET_GEN")) c->winograd_det_gen3 = atoi(e) >= 3;
-    c->winograd = !(pf & FPC_PLAN_NO_WINOGRAD);
-    c->winograd_det = !(pf & FPC_PLAN_NO_WINOGRAD_DETECTOR);
-    c->winograd_in1 = !(pf & FPC_PLAN_NO_WINOGRAD_LAYER_IN1);
-    c->xcd_order = !(pf & FPC_PLAN_NO_XCD_ORDER);
-    c->fuse_stem_pool = !(pf & FPC_PLAN_NO_FUSED_STEM_POOL);
-    c->stem_lean = !(pf & FPC_PLAN_STEM_ROUND3);
-    c->conv_lean = !(pf & FPC_PLAN_CONV_ROUND1);
-    if (const char* e = getenv("FPC_CONV_LEAN")) c->conv_lean = atoi(e) != 0;
-    if (const char* e = getenv("FPC_STEM_LEAN")) c->stem_lean = atoi(e) != 0;
-    // Round 4, with the streams on hardware queues of their own: one context, two sub-batches, Python network, fp32 MFMA:
-    // 10 740 -> 10 845 frames/s (steady 10 790 -> 10 930; two runs each); the C++ network loses 2 %, bf16 HD and the QVGA
-    // detector do not move, one-sub-batch contexts (the bench's two in turn) +0.1 %: the default where it was measured to pay.
-    c->split_heads = (pf & FPC_PLAN_SPLIT_HEADS) != 0;   // (and by default where it pays: below, once nsub is final)
-    if (pf & FPC_PLAN_NO_PERSISTENT_GRID) c->persist_min_tiles = 0;
-    c->layer1_t816 = (pf & FPC_PLAN_LAYER1_TILE_8x16) != 0;
-    c->winograd_gen = (pf & FPC_PLAN_WINOGRAD_GEN1) ? 1 : (pf & FPC_PLAN_WINOGRAD_GEN2) ? 2 : 3;
-    if (const char* e = getenv("FPC_WINOGRAD_GEN")) c->winograd_gen = std::min(3, std::max(1, atoi(e)));
-    c->latency_tiles = !(pf & FPC_PLAN_NO_LATENCY_TILES);
-    if (const char* e = getenv("FPC_LATENCY_TILES")) c->latency_tiles = atoi(e) != 0;
-    c->fuse_softmax = !(pf & FPC_PLAN_NO_FUSED_SOFTMAX);
-    c->convt_fused = !(pf & FPC_PLAN_CONVT_PHASES);
-    if (const char* e = getenv("FPC_CONVT_FUSED")) c->convt_fused = atoi(e) != 0;
-    if (const char* e = getenv("FPC_FUSE_SOFTMAX")) c->fuse_softmax = atoi(e) != 0;
-    c->nms_one_workgroup = (pf & FPC_PLAN_NMS_ONE_WORKGROUP) != 0;
-    if (const char* e = getenv("FPC_NMS_CHUNKED")) c->nms_one_workgroup = atoi(e) == 0;
-    if (cfg->min_sub_batch > 0) c->min_sub = cfg->min_sub_batch;
-    if (cfg->nms_round_launches > 0) c->nms_passes = std::min(64, cfg->nms_round_launches);
-    else if (cfg->nms_round_launches < 0) c->nms_passes = 0;
-    if (const char* e = getenv("FPC_STREAMS")) nsub = std::max(1, std::min(8, atoi(e)));
-    if (!(pf & FPC_PLAN_HEADS_IN_LINE) && nsub >= 2 && !c->vgg && !c->bf16 && !c->split) c->split_heads = true;
-    if (const char* e = getenv("FPC_FUSE")) c->fuse_blocks = atoi(e) != 0;
-    if (const char* e = getenv("FPC_WINOGRAD")) c->winograd = atoi(e) != 0;
-    if (const char* e = getenv("FPC_XCD_ORDER")) c->xcd_order = atoi(e) != 0;
-    if (const char* e = getenv("FPC_MIN_SUB")) c->min_sub = std::max(1, atoi(e));
-    if (const char* e = getenv("FPC_PERSIST_MIN")) c->persist_min_tiles = atoi(e);
-    if (const char* e = getenv("FPC_WINOGRAD_DET")) c->winograd_det = atoi(e) != 0;
-    if (const char* e = getenv("FPC_WINOGRAD_IN1")) c->winograd_in1 = atoi(e) != 0;
-    if (const char* e = getenv("FPC_FUSE_STEM")) c->fuse_stem_pool = atoi(e) != 0;
-    if (const char* e = getenv("FPC_NMS_PASSES")) c->nms_passes = std::max(0, std::min(64, atoi(e)));
-    if (const char* e = getenv("FPC_NMS_G")) c->nms_g = std::max(0, std::min(64, atoi(e)));
-    if (getenv("FPC_L1_T816")) c->layer1_t816 = true;
+    const int nsub = c->opt.nsub, nside = c->opt.nside;
     // (from here to the end of the stream block: a failure leaves through `fail`, which drops the lock first)
     auto fail = [&](const char* what) {
       g_hip_err = what;
@@ -3147,16 +2993,6 @@ int fpc_create(fpc_ctx** out, const fpc_config* cfg) {
       if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail("hipEventCreateWithFlags");
       c->ev_join.push_back(ev);
     }
-    // FPC_SPLIT_HEADS (detector head + NMS of a sub-batch on a side stream next to its descriptor head): the default of
-    // the Python network in FPC_F32 with two or more sub-batches since round 4 (above: +1 % with the streams on queues of
-    // their own; the C++ network loses 2 % with it); the variable overrides either way.
-    if (const char* e = getenv("FPC_SPLIT_HEADS")) c->split_heads = atoi(e) != 0;
-    c->nms_aside = !c->split;  // measured: +1.5 % with two sub-batches (fp32-MFMA kernels), nothing with three (split modes)
-    if (pf & FPC_PLAN_NMS_IN_LINE) c->nms_aside = false;
-    if (const char* e = getenv("FPC_NMS_ASIDE")) c->nms_aside = atoi(e) != 0;
-    if (c->split_heads) c->nms_aside = false;
-    // one side stream per sub-batch only while main + aux + side <= 4 streams, otherwise just the first
-    const int nside = 2 * nsub <= 4 ? nsub : 1;
     for (int i = 0; i < nsub; ++i) {
       hipStream_t st = nullptr;
       hipEvent_t e1, e2;
@@ -3219,11 +3055,7 @@ void fpc_destroy(fpc_ctx* c) {
     if (c->own_stream) give_back(c->stream, SLOT_MAIN);
     qmap::release_owner(c);
   }
-  if (c->slab) hipFree(c->slab);
-  if (c->bank_slab) hipFree(c->bank_slab);
-  if (c->topk_slab) hipFree(c->topk_slab);
-  if (c->pnp_slab) hipFree(c->pnp_slab);
-  if (c->lm_slab) hipFree(c->lm_slab);
+  for (Slab* s : c->slabs) s->release();
   if (c->blob) hipFree(c->blob);
   if (c->u8stage) hipFree(c->u8stage);
   if (c->ha_ws) hipFree(c->ha_ws);
@@ -3334,7 +3166,7 @@ int fpc_tile_choice(int what, int H, int W, int frames, unsigned plan_flags) {
 int fpc_check_guards(fpc_ctx* c, long long* bad_words) {
   if (!c || !bad_words) return FPC_E_INVALID;
   *bad_words = 0;
-  if (!c->guard_zones || c->guards.empty()) return FPC_E_INVALID;      // the context was not created with FPC_PLAN_GUARD_ZONES
+  if (!c->opt.guard_zones || c->slab.zones.empty()) return FPC_E_INVALID;      // the context was not created with FPC_PLAN_GUARD_ZONES
   HIPCHECK(hipSetDevice(c->cfg.device));
   HIPCHECK(hipDeviceSynchronize());
   unsigned long long* d = nullptr;
@@ -3344,11 +3176,7 @@ int fpc_check_guards(fpc_ctx* c, long long* bad_words) {
     if (e0 != hipSuccess) hipFree(d);
     HIPCHECK(e0);
   }
-  count_zones(c, c->slab, c->guards, d);
-  count_zones(c, c->bank_slab, c->bank_guards, d);      // (fpc_bank_create; none without a bank)
-  count_zones(c, c->topk_slab, c->topk_guards, d);      // (fpc_bank_topk_reserve)
-  count_zones(c, c->pnp_slab, c->pnp_guards, d);        // (fpc_pnp_reserve)
-  count_zones(c, c->lm_slab, c->lm_guards, d);          // (fpc_bank_landmarks_reserve)
+  for (const Slab* s : c->slabs) count_zones(c->stream, *s, d);      // (a slab that was never reserved has no zones)
   unsigned long long h = 0;
   const hipError_t e1 = hipStreamSynchronize(c->stream);
   const hipError_t e2 = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
@@ -3443,8 +3271,8 @@ int fpc_broadcast_weights(fpc_ctx* c, void* nccl_comm, int root) {
       scratch = nullptr;
       if (root_bytes <= c->blob_floats * sizeof(float)) {
         c->weights_loaded = false;
-      } else if (root_bytes <= c->slab_bytes) {
-        dst = c->slab;
+      } else if (root_bytes <= c->slab.bytes) {
+        dst = c->slab.base;
         slab_used = true;
       } else {
         g_hip_err = "no memory to take part in the weight broadcast (" + std::to_string(root_bytes) + " bytes: no scratch, and neither this "
@@ -3457,9 +3285,9 @@ int fpc_broadcast_weights(fpc_ctx* c, void* nccl_comm, int root) {
   he = hipStreamSynchronize(c->stream);
   if (scratch) hipFree(scratch);
   if (slab_used) {      // foreign bytes in the workspace: back to the state fpc_create left (zeros, canary zones)
-    hipMemsetAsync(c->slab, 0, std::min(c->slab_bytes, align_up(root_bytes, 256)), c->stream);
+    hipMemsetAsync(c->slab.base, 0, std::min(c->slab.bytes, align_up(root_bytes, 256)), c->stream);
     hipStreamSynchronize(c->stream);
-    if (c->guard_zones) fill_guards(c);
+    if (c->opt.guard_zones) fill_guards(c);
   }
   if (nrc != 0 || he != hipSuccess) {
     if (match) c->weights_loaded = false;      // the blob may hold part of the new bytes
@@ -4090,36 +3918,18 @@ int fpc_bank_create_ex(fpc_ctx* c, int slots, int rows, int format) {
   const size_t B = c->B, cap = c->cap, D = c->D;
   const size_t per_slot = B * (cap * 16 + (size_t)rows * 8);
   const int chunk = (int)std::min<size_t>(slots, std::max<size_t>(1, BANK_WS_BUDGET / per_slot));
-  Carver cv;
-  std::vector<std::pair<size_t, size_t>> zones;
-  cv.zones = &zones;
-  cv.guard = c->guard_zones ? GUARD_BYTES : 0;
-  const size_t o_desc = half ? cv.take<bf16_t>((size_t)slots * rows * D) : cv.take<float>((size_t)slots * rows * D);
-  const size_t o_xy = cv.take<int32_t>((size_t)slots * rows * 2);
-  const size_t o_cnt = cv.take<int32_t>(slots), o_nrm = cv.take<float>((size_t)slots * rows);
-  const size_t o_top = cv.take<unsigned long long>(B * chunk * cap * 2), o_col = cv.take<unsigned long long>(B * chunk * rows);
-  const size_t o_sc = cv.take<int32_t>(B * slots), o_best = cv.take<int32_t>(B);
-  const size_t o_q = half ? cv.take<bf16_t>(B * cap * D) : 0;
-  char* p = nullptr;
-  if (int rc = alloc_side_slab(c, cv, &p)) return rc;           // (zeroed: every slot starts empty)
-  c->bank_slab = p;
-  c->bank_bytes = cv.off;
-  c->bank_guards = zones;
+  // (without a bank, c->bank and c->bank16 hold nulls: the format that is not carved keeps them)
   BankArgs& b = c->bank;
-  b.desc = half ? nullptr : reinterpret_cast<float*>(p + o_desc);
+  Carver cv(c);
+  if (half) cv.into(&c->bank16.desc, (size_t)slots * rows * D);
+  else cv.into(&b.desc, (size_t)slots * rows * D);
+  cv.into(&b.xy, (size_t)slots * rows * 2);
+  cv.into(&b.count, slots); cv.into(&b.norms, (size_t)slots * rows);
+  cv.into(&b.top2, B * chunk * cap * 2); cv.into(&b.colbest, B * chunk * rows);
+  cv.into(&b.score, B * slots); cv.into(&b.best, B);
+  if (half) cv.into(&c->bank16.q, B * cap * D);
+  if (int rc = c->bank_slab.allocate(c->stream, cv)) return rc;           // (zeroed: every slot starts empty)
   c->bank_format = format;
-  c->bank16 = BankBf16Args{};
-  if (half) {
-    c->bank16.desc = reinterpret_cast<bf16_t*>(p + o_desc);
-    c->bank16.q = reinterpret_cast<bf16_t*>(p + o_q);
-  }
-  b.xy = reinterpret_cast<int32_t*>(p + o_xy);
-  b.count = reinterpret_cast<int32_t*>(p + o_cnt);
-  b.norms = reinterpret_cast<float*>(p + o_nrm);
-  b.top2 = reinterpret_cast<unsigned long long*>(p + o_top);
-  b.colbest = reinterpret_cast<unsigned long long*>(p + o_col);
-  b.score = reinterpret_cast<int32_t*>(p + o_sc);
-  b.best = reinterpret_cast<int32_t*>(p + o_best);
   b.slots = slots; b.rows = rows; b.D = c->D; b.chunk = chunk;
   return FPC_OK;
 }
@@ -4137,22 +3947,12 @@ int fpc_bank_destroy(fpc_ctx* c) {
   if (!c || !c->bank_slab) return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
   HIPCHECK(hipStreamSynchronize(c->stream));                    // calls that still read the bank
-  HIPCHECK(hipFree(c->bank_slab));
-  c->bank_slab = nullptr;
-  c->bank_bytes = 0;
-  c->bank_guards.clear();
-  if (c->topk_slab) {                                           // the top-K workspace is sized by the bank: it goes with it
-    HIPCHECK(hipFree(c->topk_slab));
-    c->topk_slab = nullptr;
-    c->topk_guards.clear();
-    c->topk = BankTopkArgs{};
-  }
-  if (c->lm_slab) {                                             // ... and so do the landmarks of its rows
-    HIPCHECK(hipFree(c->lm_slab));
-    c->lm_slab = nullptr;
-    c->lm_xyzw = nullptr;
-    c->lm_guards.clear();
-  }
+  // the top-K workspace and the landmarks are sized by the bank: they go with it
+  HIPCHECK(c->bank_slab.release());
+  HIPCHECK(c->topk_slab.release());
+  c->topk = BankTopkArgs{};
+  HIPCHECK(c->lm_slab.release());
+  c->lm_xyzw = nullptr;
   c->bank = BankArgs{};
   c->bank_format = FPC_BANK_F32;
   c->bank16 = BankBf16Args{};
@@ -4168,7 +3968,7 @@ int fpc_bank_get(fpc_ctx* c, fpc_bank_view* out) {
   out->rows = c->bank.rows;
   out->desc_dim = c->bank.D;
   out->chunk = c->bank.chunk;
-  out->bytes = c->bank_bytes;
+  out->bytes = c->bank_slab.bytes;
   return FPC_OK;
 }
 
@@ -4380,37 +4180,21 @@ static bool pnp_params_ok(const fpc_pnp_params* p) {
 int fpc_pnp_reserve(fpc_ctx* c, size_t* bytes) {
   if (!c || c->pnp_slab) return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
-  Carver cv;
-  std::vector<std::pair<size_t, size_t>> zones;
-  cv.zones = &zones;
-  cv.guard = c->guard_zones ? GUARD_BYTES : 0;
+  Carver cv(c);
   const size_t B = c->B, cap = c->cap;
-  const size_t o_rec = cv.take<float4>(B * cap * 2), o_np = cv.take<int32_t>(B), o_best = cv.take<unsigned long long>(B);
-  char* p = nullptr;
-  if (int rc = alloc_side_slab(c, cv, &p)) return rc;
-  c->pnp_slab = p;
-  c->pnp_guards = zones;
-  c->pnp_rec = reinterpret_cast<float4*>(p + o_rec);
-  c->pnp_np = reinterpret_cast<int32_t*>(p + o_np);
-  c->pnp_best = reinterpret_cast<unsigned long long*>(p + o_best);
-  if (bytes) *bytes = cv.off;
+  cv.into(&c->pnp_rec, B * cap * 2); cv.into(&c->pnp_np, B); cv.into(&c->pnp_best, B);
+  if (int rc = c->pnp_slab.allocate(c->stream, cv)) return rc;
+  if (bytes) *bytes = c->pnp_slab.bytes;
   return FPC_OK;
 }
 
 int fpc_bank_landmarks_reserve(fpc_ctx* c, size_t* bytes) {
   if (!c || !c->bank_slab || c->lm_slab) return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
-  Carver cv;
-  std::vector<std::pair<size_t, size_t>> zones;
-  cv.zones = &zones;
-  cv.guard = c->guard_zones ? GUARD_BYTES : 0;
-  const size_t o_lm = cv.take<float4>((size_t)c->bank.slots * c->bank.rows);
-  char* p = nullptr;
-  if (int rc = alloc_side_slab(c, cv, &p)) return rc;           // (zeroed: no row is valid)
-  c->lm_slab = p;
-  c->lm_guards = zones;
-  c->lm_xyzw = reinterpret_cast<float4*>(p + o_lm);
-  if (bytes) *bytes = cv.off;
+  Carver cv(c);
+  cv.into(&c->lm_xyzw, (size_t)c->bank.slots * c->bank.rows);
+  if (int rc = c->lm_slab.allocate(c->stream, cv)) return rc;           // (zeroed: no row is valid)
+  if (bytes) *bytes = c->lm_slab.bytes;
   return FPC_OK;
 }
 
@@ -4570,28 +4354,14 @@ int fpc_bank_topk_reserve(fpc_ctx* c, int kmax, size_t* bytes) {
     return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
   const size_t pairs = (size_t)c->B * kmax, cap = c->cap, rows = c->bank.rows;
-  Carver cv;
-  std::vector<std::pair<size_t, size_t>> zones;
-  cv.zones = &zones;
-  cv.guard = c->guard_zones ? GUARD_BYTES : 0;
-  const size_t o_top = cv.take<unsigned long long>(pairs * cap * 2), o_col = cv.take<unsigned long long>(pairs * rows);
-  const size_t o_slot = cv.take<int32_t>(pairs), o_sc = cv.take<int32_t>(pairs);
-  const size_t o_pairs = cv.take<float4>(pairs * cap), o_row = cv.take<int32_t>(pairs * cap);
-  const size_t o_np = cv.take<int32_t>(pairs), o_best = cv.take<unsigned long long>(pairs);
-  char* p = nullptr;
-  if (int rc = alloc_side_slab(c, cv, &p)) return rc;
-  c->topk_slab = p;
-  c->topk_guards = zones;
-  c->topk.top2 = reinterpret_cast<unsigned long long*>(p + o_top);
-  c->topk.colbest = reinterpret_cast<unsigned long long*>(p + o_col);
-  c->topk.cand_slot = reinterpret_cast<int32_t*>(p + o_slot);
-  c->topk.cand_score = reinterpret_cast<int32_t*>(p + o_sc);
+  Carver cv(c);
+  cv.into(&c->topk.top2, pairs * cap * 2); cv.into(&c->topk.colbest, pairs * rows);
+  cv.into(&c->topk.cand_slot, pairs); cv.into(&c->topk.cand_score, pairs);
+  cv.into(&c->topk_pairs, pairs * cap); cv.into(&c->topk_row, pairs * cap);
+  cv.into(&c->topk_np, pairs); cv.into(&c->topk_best, pairs);
+  if (int rc = c->topk_slab.allocate(c->stream, cv)) return rc;
   c->topk.kmax = kmax;
-  c->topk_pairs = reinterpret_cast<float4*>(p + o_pairs);
-  c->topk_row = reinterpret_cast<int32_t*>(p + o_row);
-  c->topk_np = reinterpret_cast<int32_t*>(p + o_np);
-  c->topk_best = reinterpret_cast<unsigned long long*>(p + o_best);
-  if (bytes) *bytes = cv.off;
+  if (bytes) *bytes = c->topk_slab.bytes;
   return FPC_OK;
 }
 
@@ -5029,7 +4799,7 @@ int fpc_get_timings(fpc_ctx* c, int cap, const char** names, const char** kernel
           case OP_WBLOCK: k = g_wkinds[t.wkind >= 0 ? t.wkind : op->wkind].symbol; break;
           case OP_BF16: k = g_fkinds[op->fkind].symbol; break;
           case OP_SOFTMAX: k = "softmax_d2s_kernel"; break;
-          case OP_NMS: k = c->nms_one_workgroup ? "nms_rounds_kernel+nms_sort_kernel" : "nms_rounds_kernel+nms_finish_kernel+nms_chunk_sort_kernel+nms_merge_kernel"; break;
+          case OP_NMS: k = c->opt.nms_one_workgroup ? "nms_rounds_kernel+nms_sort_kernel" : "nms_rounds_kernel+nms_finish_kernel+nms_chunk_sort_kernel+nms_merge_kernel"; break;
           case OP_DESC: k = "descriptor16_kernel"; break;
           case OP_VCONV0: k = "vgg_conv0_kernel"; break;
           case OP_POOL2: k = "maxpool2_kernel"; break;

@@ -88,14 +88,24 @@ def _shared(key, make, *args, **kw):
     return _cache[key]
 
 
-def record(arch, dtype, flags, h, w, kw):
-    """What the fixture holds for one case, from the library the package loads."""
+def record(arch, dtype, flags, h, w, kw, env=None):
+    """What the fixture holds for one case, from the library the package loads.  `env`: variables set while the context
+    is created (fpc_create reads them) and restored behind it."""
     from fpc_amd.engine import Engine
 
     vgg = arch == "vgg"
     kw = dict(kw)
     cin = kw.pop("in_channels", 1 if vgg else 3)
-    eng = Engine(h, w, max_batch=MAX_BATCH, in_channels=cin, dtype=dtype, arch=arch, plan_flags=list(flags), **kw)
+    old = {k: os.environ.get(k) for k in env or {}}
+    os.environ.update(env or {})
+    try:
+        eng = Engine(h, w, max_batch=MAX_BATCH, in_channels=cin, dtype=dtype, arch=arch, plan_flags=list(flags), **kw)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     try:
         eng.load_state_dict(_shared(("sd", arch), synth.make_vgg_state_dict if vgg else synth.make_state_dict, seed=0))
         frames = _shared(("frames", cin == 1, h, w), synth.make_batch, 11, MAX_BATCH, h, w, gray=cin == 1)[:, :cin].copy()
@@ -119,3 +129,36 @@ def test_plan_pins(case):
     for key in want:
         assert got[key] == want[key], "%s: %s differs from tests/golden/plan_pins.json" % (case[0], key)
     assert sorted(got) == sorted(want)
+
+
+# An FPC_* variable set instead of its plan flag gives the flag's plan: (variables, the flags whose record it must equal,
+# whether that record is a large-call one, dtype).  No fixture data of their own.
+SUB2 = {"min_sub_batch": 2}
+VARIABLE_FOR_FLAG = (
+    ({"FPC_WINOGRAD_GEN": "1"}, ("winograd_gen1",), {}, "f32"),
+    ({"FPC_WINOGRAD_GEN": "2"}, ("winograd_gen2",), {}, "f32"),
+    ({"FPC_FUSE": "0"}, ("no_fused_blocks",), {}, "f32"),
+    ({"FPC_TILES_ROUND6": "0"}, ("tiles_round5",), {}, "f32"),
+    ({"FPC_LATENCY_TILES": "0"}, ("no_latency_tiles",), SUB2, "f32"),
+    ({"FPC_WINOGRAD": "0"}, ("no_winograd",), SUB2, "f32"),
+    ({"FPC_WINOGRAD": "0", "FPC_L1_T816": "0"}, ("no_winograd", "layer1_tile_8x16"), SUB2, "f32"),   # (set at all: on)
+    ({"FPC_WINOGRAD_DET": "0"}, ("no_winograd_detector",), SUB2, "f32"),
+    ({"FPC_WINOGRAD_IN1": "0"}, ("no_winograd_layer_in1",), SUB2, "f32"),
+    ({"FPC_WINOGRAD_DET_GEN": "1"}, ("detector_gen1",), SUB2, "f32"),
+    ({"FPC_W36_PAIRED": "0"}, ("w36_one_wave",), SUB2, "f32"),
+    ({"FPC_CONV_LEAN": "0"}, ("conv_round1",), SUB2, "f32"),
+    ({"FPC_STEM_LEAN": "0"}, ("stem_round3",), SUB2, "f32"),
+    ({"FPC_CONVT_FUSED": "0"}, ("convt_phases",), SUB2, "bf16"),
+    ({"FPC_FUSE_SOFTMAX": "0"}, ("no_fused_softmax",), SUB2, "bf16"),
+    ({"FPC_MIN_SUB": "2"}, (), SUB2, "f32"),                                                         # (no min_sub_batch)
+)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env,flags,kw,dtype", VARIABLE_FOR_FLAG, ids=["+".join("%s=%s" % i for i in v[0].items()) for v in VARIABLE_FOR_FLAG])
+def test_variable_gives_its_flags_plan(env, flags, kw, dtype):
+    h, w = GEOMETRIES[0]
+    cid = "-".join(["resnet", dtype] + (["sub2"] if kw else []) + list(flags) + ["%dx%d" % (h, w)])
+    want = _shared("pins", load_pins)[cid]
+    got = record("resnet", dtype, (), h, w, {} if "FPC_MIN_SUB" in env else kw, env=env)
+    assert got == want, "%s does not give the plan of %s" % (env, cid)
