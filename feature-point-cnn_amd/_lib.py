@@ -39,6 +39,7 @@ SYMBOLS = [
     "fpc_match_frames_guided_epipolar", "fpc_match_bank_guided_epipolar",
     "fpc_match_frames_guided_epipolar_cells", "fpc_match_bank_guided_epipolar_cells",
     "fpc_default_pose_params", "fpc_pose_fundamental", "fpc_pose_frames", "fpc_pose_bank",
+    "fpc_default_pose_homography_params", "fpc_pose_homography", "fpc_pose_homography_frames", "fpc_pose_homography_bank",
     "fpc_default_pnp_params", "fpc_pnp_reserve", "fpc_bank_landmarks_reserve", "fpc_bank_store_landmarks",
     "fpc_bank_landmarks_get", "fpc_ransac_pnp", "fpc_pnp_frames", "fpc_pnp_bank",
     "fpc_match_frames_guided_pose", "fpc_match_bank_guided_pose",
@@ -99,6 +100,14 @@ class FpcPoseParams(ctypes.Structure):
     _fields_ = [("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
                 ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
                 ("reproj_threshold", ctypes.c_float), ("min_front", ctypes.c_int)]
+
+
+class FpcPoseHomographyParams(ctypes.Structure):
+    """fpc_pose_homography_params (include/fpc.h)."""
+    _fields_ = [("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
+                ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
+                ("reproj_threshold", ctypes.c_float), ("min_front", ctypes.c_int), ("min_baseline", ctypes.c_float),
+                ("which", ctypes.c_int)]
 
 
 class FpcPnpParams(ctypes.Structure):
@@ -226,6 +235,12 @@ def load():
     l.fpc_pose_fundamental.argtypes = [vp, ci, vp, vp, vp, ci, vp, pp, vp, vp, vp, vp, vp]
     l.fpc_pose_frames.argtypes = [vp, ci, ci, vp, vp, vp, vp, pp, vp, vp, vp, vp, vp]
     l.fpc_pose_bank.argtypes = [vp, ci, vp, vp, vp, pp, vp, vp, vp, vp, vp]
+    hp = ctypes.POINTER(FpcPoseHomographyParams)
+    l.fpc_default_pose_homography_params.argtypes = [hp]
+    # the homography twins' arguments with (H_dev, params) where their params stand and eight outputs for their three
+    l.fpc_pose_homography.argtypes = [vp, ci, vp, vp, vp, ci, vp, hp] + [vp] * 8
+    l.fpc_pose_homography_frames.argtypes = [vp, ci, ci, vp, vp, vp, vp, hp] + [vp] * 8
+    l.fpc_pose_homography_bank.argtypes = [vp, ci, vp, vp, vp, hp] + [vp] * 8
     np_ = ctypes.POINTER(FpcPnpParams)
     l.fpc_default_pnp_params.argtypes = [np_]
     l.fpc_pnp_reserve.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]

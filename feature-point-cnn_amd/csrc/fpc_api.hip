@@ -44,6 +44,7 @@
 #include "ransac_homography.h"
 #include "ransac_fundamental.h"
 #include "pose_epipolar.h"
+#include "pose_homography.h"
 #include "match_bank_topk.h"
 #include "pnp_ransac.h"
 #include "sim3_ransac.h"
@@ -4154,6 +4155,72 @@ int fpc_pose_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, 
   const HfArgs a = hf_args(c, n, p->reproj_threshold);
   if (int rc = pairs_bank(c, a, n, slot, match, nullptr)) return rc;
   return pose_launch(c, a, p, F, R, t, nfront, xyz, front, c->cap);
+}
+
+// ---- relative pose from a homography (include/fpc.h; kernel in pose_homography.h) ------------------------------------------
+// The homography calls' pack / gather kernels with a NULL mask, their pair records and workspace, as the pose calls above.
+int fpc_default_pose_homography_params(fpc_pose_homography_params* p) {
+  if (!p) return FPC_E_INVALID;
+  p->q_fx = p->q_fy = p->t_fx = p->t_fy = 500.0f;
+  p->q_cx = p->t_cx = 320.0f;
+  p->q_cy = p->t_cy = 240.0f;
+  p->reproj_threshold = 3.0f;
+  p->min_front = 8;
+  p->min_baseline = 0.01f;
+  p->which = 0;
+  return FPC_OK;
+}
+
+static bool pose_homography_params_ok(const fpc_pose_homography_params* p) {
+  return p && camera_ok(p->q_fx, p->q_fy, p->q_cx, p->q_cy) && camera_ok(p->t_fx, p->t_fy, p->t_cx, p->t_cy) &&
+         threshold_ok(p->reproj_threshold) && p->min_front >= 1 && std::isfinite(p->min_baseline) && p->min_baseline >= 0.f &&
+         (p->which == 0 || p->which == 1);
+}
+
+// what the three calls share: the outputs that must exist
+struct PoseHOut {
+  int32_t* kind; float *R, *t, *plane; int32_t *nfront, *nplane; float* xyz; uint8_t* front;
+  bool ok() const { return kind && R && t && nfront; }
+};
+
+// the solver step behind the pair list (a: hf_args with the parameters' threshold, nothing of RANSAC's)
+static int pose_homography_launch(fpc_ctx* c, const HfArgs& a, const fpc_pose_homography_params* p, const float* H,
+                                  const PoseHOut& o, int ostride) {
+  const PoseHArgs pa{p->q_fx, p->q_fy, p->q_cx, p->q_cy, p->t_fx, p->t_fy, p->t_cx, p->t_cy, p->min_front, p->min_baseline,
+                     p->which};
+  hipLaunchKernelGGL(pose_homography_kernel, dim3(a.n), dim3(256), 0, c->stream, a, pa, H, o.kind, o.R, o.t, o.plane, o.nfront,
+                     o.nplane, o.xyz, o.front, ostride);
+  return launched();
+}
+
+int fpc_pose_homography(fpc_ctx* c, int n, const float* src_xy, const float* dst_xy, const int32_t* npairs, int stride,
+                        const float* H, const fpc_pose_homography_params* p, int32_t* kind, float* R, float* t, float* plane,
+                        int32_t* nfront, int32_t* nplane, float* xyz, uint8_t* front) {
+  const PoseHOut o{kind, R, t, plane, nfront, nplane, xyz, front};
+  if (!c || !H || !o.ok() || !pose_homography_params_ok(p)) return FPC_E_INVALID;
+  const HfArgs a = hf_args(c, n, p->reproj_threshold);
+  if (int rc = pairs_explicit(c, a, src_xy, dst_xy, npairs, stride, nullptr)) return rc;
+  return pose_homography_launch(c, a, p, H, o, stride);
+}
+
+int fpc_pose_homography_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy, const int32_t* nkey, const int32_t* match,
+                               const float* H, const fpc_pose_homography_params* p, int32_t* kind, float* R, float* t,
+                               float* plane, int32_t* nfront, int32_t* nplane, float* xyz, uint8_t* front) {
+  const PoseHOut o{kind, R, t, plane, nfront, nplane, xyz, front};
+  if (!c || !H || !o.ok() || !pose_homography_params_ok(p)) return FPC_E_INVALID;
+  const HfArgs a = hf_args(c, n, p->reproj_threshold);
+  if (int rc = pairs_frames(c, a, pairing, key_xy, nkey, match, nullptr)) return rc;
+  return pose_homography_launch(c, a, p, H, o, c->cap);
+}
+
+int fpc_pose_homography_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const float* H,
+                             const fpc_pose_homography_params* p, int32_t* kind, float* R, float* t, float* plane,
+                             int32_t* nfront, int32_t* nplane, float* xyz, uint8_t* front) {
+  const PoseHOut o{kind, R, t, plane, nfront, nplane, xyz, front};
+  if (!c || !H || !o.ok() || !pose_homography_params_ok(p)) return FPC_E_INVALID;
+  const HfArgs a = hf_args(c, n, p->reproj_threshold);
+  if (int rc = pairs_bank(c, a, n, slot, match, nullptr)) return rc;
+  return pose_homography_launch(c, a, p, H, o, c->cap);
 }
 
 // ---- absolute pose from bank landmarks: RANSAC PnP (include/fpc.h; kernels in pnp_ransac.h) ------------------------------------

@@ -840,6 +840,68 @@ class Engine:
         """pose_bank_async, then host arrays (R [n,3,3], t [n,3], nfront [n], xyz [n,cap,3], front bool [n,cap])."""
         return self._host(self.pose_bank_async(n, slot, match, F, K_query, K_train, points, **params))
 
+    # -- relative pose from the homographies: planar scenes and pure rotations (fpc_pose_homography / _frames / _bank) ---------
+    POSE_H_KINDS = {"failed": 0, "unique": 1, "twofold": 2, "rotation": 3}       # include/fpc.h FPC_POSE_H_*
+
+    def _pose_h_params(self, K_query, K_train, params):
+        return self._two_camera_params(_lib.FpcPoseHomographyParams, "fpc_default_pose_homography_params",
+                                       ("reproj_threshold", "min_front", "min_baseline", "which"), "homography pose",
+                                       K_query, K_train, params)
+
+    def _pose_h_out(self, n, stride, points):
+        """Empty outputs (kind int32 [n], R float32 [n,2,3,3], t float32 [n,2,3], plane float32 [n,2,4], nfront int32 [n,2],
+        nplane int32 [n,2], xyz float32 [n,stride,3], front uint8 [n,stride]); the last two None without `points`."""
+        dev = self.torch_device
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        xyz = f32(n, stride, 3) if points else None
+        front = torch.empty((n, stride), dtype=torch.uint8, device=dev) if points else None
+        return i32(n), f32(n, 2, 3, 3), f32(n, 2, 3), f32(n, 2, 4), i32(n, 2), i32(n, 2), xyz, front
+
+    def _pose_h(self, name, n, pairs, H, p, stride, points):
+        """fpc_<name> behind its pair source: H [n,3,3] goes in front of the parameters."""
+        return self._solve(name, n, pairs, p, self._pose_h_out(n, stride, points), self._guided_h(n, H, "H"))
+
+    def pose_homography_async(self, src, dst, npairs, H, K_query=None, K_train=None, points=True, **params):
+        """fpc_pose_homography: ransac_homography_async's pairs and the H it returned (device [n,3,3] as it is, or a host
+        array) -> device tensors (kind int32 [n], see POSE_H_KINDS; R float32 [n,2,3,3] and t float32 [n,2,3] of solutions 0
+        and 1 with X_train = R X_query + t, |t| = 1; plane float32 [n,2,4], (N, d) with N.X = d in the query camera's
+        frame; nfront int32 [n,2], the support; nplane int32 [n,2], the plane pairs in front; xyz float32 [n,stride,3]
+        and front bool [n,stride], the points of solution `which`); xyz and front are None with points=False.  K_query /
+        K_train: 3 x 3 camera matrices or (fx, fy, cx, cy).  Parameters: reproj_threshold, min_front, min_baseline,
+        which.  A solution that does not exist is all zeros; a pure rotation has solution 0's R and nothing else.  Does
+        not synchronise."""
+        p = self._pose_h_params(K_query, K_train, params)
+        n, pairs = self._explicit_pairs(src, dst, npairs)
+        return self._pose_h("fpc_pose_homography", n, pairs, H, p, pairs[3], points)
+
+    def pose_homography(self, src, dst, npairs, H, K_query=None, K_train=None, points=True, **params):
+        """pose_homography_async, then host arrays."""
+        return self._host(self.pose_homography_async(src, dst, npairs, H, K_query, K_train, points, **params))
+
+    def pose_homography_frames_async(self, n, match, H, key_xy=None, pairing="key", K_query=None, K_train=None, points=True,
+                                     **params):
+        """fpc_pose_homography_frames: homography_frames_async's arguments, pairs and output H -> pose_homography_async's
+        tensors with xyz [n,cap,3] and front bool [n,cap] by query row.  Does not synchronise."""
+        p, pairs = self._frames_pairs(n, pairing, key_xy, match, self._pose_h_params, K_query, K_train, params)
+        return self._pose_h("fpc_pose_homography_frames", n, pairs, H, p, self.capacity, points)
+
+    def pose_homography_frames(self, n, match, H, key_xy=None, pairing="key", K_query=None, K_train=None, points=True,
+                               **params):
+        """pose_homography_frames_async, then host arrays."""
+        return self._host(self.pose_homography_frames_async(n, match, H, key_xy, pairing, K_query, K_train, points, **params))
+
+    def pose_homography_bank_async(self, n, slot, match, H, K_query=None, K_train=None, points=True, **params):
+        """fpc_pose_homography_bank: pose_homography_frames_async with frame f's key coordinates taken from bank slot
+        slot[f], as homography_bank_async, and H that call's output; a frame with slot -1 fails (zeros).  xyz[f] and
+        front[f] go into bank_store_landmarks as they are.  Does not synchronise."""
+        p, pairs = self._bank_pairs(n, slot, match, self._pose_h_params, K_query, K_train, params)
+        return self._pose_h("fpc_pose_homography_bank", n, pairs, H, p, self.capacity, points)
+
+    def pose_homography_bank(self, n, slot, match, H, K_query=None, K_train=None, points=True, **params):
+        """pose_homography_bank_async, then host arrays."""
+        return self._host(self.pose_homography_bank_async(n, slot, match, H, K_query, K_train, points, **params))
+
     # -- absolute pose from landmarks: RANSAC PnP (fpc_pnp_reserve / fpc_bank_*landmarks* / fpc_ransac_pnp / _frames / _bank) ----
     def pnp_reserve(self):
         """fpc_pnp_reserve: the PnP workspace (pair records, counts and best keys of max_batch problems); the only PnP call

@@ -924,6 +924,106 @@ int fpc_pose_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* m
                   const fpc_pose_params* params, float* R_dev, float* t_dev, int32_t* nfront_dev, float* xyz_dev,
                   uint8_t* front_dev);
 
+/* --- relative pose from a homography: planar scenes and pure rotations -------------------------------------------------------
+ * The caveat of the fundamental section is this section's case: a wall, a floor, a desk, a poster, or a camera that turns on
+ * the spot has no unique F, and the homography calls end in an H and a mask.  fpc_pose_homography,
+ * fpc_pose_homography_frames and fpc_pose_homography_bank turn one H per frame -- what fpc_ransac_homography /
+ * fpc_homography_frames / fpc_homography_bank wrote, passed on unchanged -- into rotations, translation directions, the
+ * plane and one 3-D point per pair, on the device.  They mirror those three calls argument for argument: the same pair
+ * definition, strides, clamping of counts, pairing, key and slot rules, workspace and execution rules, with H_dev float32
+ * [n][9] as an INPUT and fpc_pose_homography_params in the place of fpc_ransac_params.
+ * Outputs (S is `stride` for fpc_pose_homography and the capacity for the other two; a row of xyz / front is a pair
+ * (fpc_pose_homography) or a query row (frames, bank), as for fpc_pose_*):
+ *    kind_dev    int32   [n]        FPC_POSE_H_FAILED, FPC_POSE_H_UNIQUE, FPC_POSE_H_TWOFOLD or FPC_POSE_H_ROTATION
+ *    R_dev       float32 [n][2][9]  row-major; X_train = R X_query + t, det R = +1
+ *    t_dev       float32 [n][2][3]  |t| = 1
+ *    plane_dev   float32 [n][2][4]  may be NULL; (N, d): the plane N.X = d in the query camera's frame, |N| = 1, d > 0, at
+ *                                   the scale where |t| = 1
+ *    nfront_dev  int32   [n][2]     the support count defined below
+ *    nplane_dev  int32   [n][2]     may be NULL; a candidate's H inliers in front
+ *    xyz_dev     float32 [n][S][3]  may be NULL; the points of solution `which`, in fpc_pose_*'s format
+ *    front_dev   uint8   [n][S]     may be NULL; likewise
+ * xyz[f] and front[f] go into fpc_bank_store_landmarks as they are.  Solution 0 is the better one; a solution that does not
+ * exist is all zeros.  Everything is evaluated in fp64 from the fp32 H; only R, t, the plane and xyz are rounded to fp32.
+ *  - Normalisation: with K = [fx 0 cx; 0 fy cy; 0 0 1] of either side, H^ = K_t^-1 H K_q, written out for that K (H K_q
+ *    column by column, then rows 0 and 1 less cx, cy times row 2 and divided by fx, fy), scaled to max |h^| = 1.  A zero H
+ *    (a failed frame of the homography calls), a non-finite H, a frame with no pairs, or a bank slot outside [0, slots)
+ *    fails the frame.
+ *  - Eigen-decomposition: S = H^T H^ is diagonalised by the cyclic Jacobi of the fundamental section at N = 3 (10 sweeps,
+ *    the same rotation rule).  lambda1 >= lambda2 >= lambda3 are the diagonal entries in descending order, ties to the
+ *    lowest index, as the pose call picks its two; v1, v2 are their columns and v3 = v1 x v2.  The frame fails unless
+ *    lambda3 > 1e-12 lambda1.  Then H^ <- H^ / sqrt(lambda2) and lambda_i <- lambda_i / lambda2; if det H^ < 0, H^ <- -H^,
+ *    which puts both cameras on one side of the plane.
+ *  - Baseline: b = sqrt(lambda1) - sqrt(lambda3); for H = R + T N^T / d this is |T| / d, the baseline over the plane's
+ *    distance.  b <= min_baseline makes the frame a pure rotation: kind = FPC_POSE_H_ROTATION, solution 0's R =
+ *    w1 v1^T + w2 v2^T + w3 v3^T with w1 = H^ v1 / |H^ v1|, w2 = H^ v2 with its w1 component removed, then normalised, and
+ *    w3 = w1 x w2; everything else of the frame is zero (a non-finite R fails the frame).
+ *  - Candidates (the four-solution form of Ma, Soatto, Kosecka and Sastry, An Invitation to 3-D Vision, section 5.3): with
+ *    a = sqrt(max(0, 1 - lambda3)), c = sqrt(max(0, lambda1 - 1)) and e = sqrt(lambda1 - lambda3),
+ *        u+- = (a v1 +- c v3) / e,
+ *    and for each sign U = [v2, u, v2 x u], W = [H^ v2, H^ u, H^ v2 x H^ u] (columns),
+ *        R = W U^T,      N = v2 x u,      T = (H^ - R) N.
+ *    The four candidates are c = 0 .. 3 = (R+, T+, N+), (R+, -T+, -N+), (R-, T-, N-), (R-, -T-, -N-), with t = T / |T| and
+ *    d = 1 / |T|.  A candidate with a non-finite value is dropped.
+ *  - Counting, per candidate, over ALL pairs of the list: triangulation and the IN FRONT test are those of fpc_pose_*,
+ *    unchanged.  nplane_c counts the pairs that are inliers of H by the homography section's "Inliers" rule at this
+ *    struct's reproj_threshold and are in front.  nfront_c, the support, counts the pairs that are in front and pass the
+ *    Sampson rule of the fundamental section at the same threshold under
+ *        F_c = K_t^-T [t]x R K_q^-1
+ *    (E = [t]x R; its columns divided by q_fx, q_fy and the third less q_cx, q_cy times those; then its rows likewise with
+ *    the train camera).  Plane pairs satisfy that rule by construction (H.p lies on p's epipolar line); pairs off the
+ *    plane satisfy it only under the true motion.
+ *  - Selection: candidates with nplane_c < min_front are dropped; the rest are ranked by the integer key
+ *    (nfront_c << 32) | ~c, and solutions 0 and 1 are the two largest.  kind is UNIQUE when one candidate remains, TWOFOLD
+ *    when two or more remain, FAILED when none does.  front[row] = 1 for solution `which`'s support pairs, xyz[row] is
+ *    their midpoint (the formula of fpc_pose_*), zeros everywhere else; the call writes every row of its frames' front /
+ *    xyz.
+ *  - The twofold ambiguity is a property of planes, not of this code.  Cheirality removes the two -T candidates; the other
+ *    two both keep every plane point in front unless some point violates N.x > 0 for one of them.  In a float64 check of
+ *    this rule on 300 planted VGA scenes (K = (500, 500, 320, 240), planes at depth 4 - 8 tilted up to 50 degrees,
+ *    rotations of 3 - 20 degrees, baselines of 0.1 - 0.5 plane distances, integer pixels, 3 px) the two survivors tied on
+ *    support in 56 % of the scenes when every pair lay on the plane, and the pick between them was wrong in about a third
+ *    of all scenes.  With 5 % of the pairs off the plane the tie rate fell to 1.7 % and the wrong picks to 0.7 %; with 15 %
+ *    there were 0 wrong picks in 297 scenes.  So the call always returns both survivors and their counts, and what
+ *    nfront[1] against nfront[0] means is the caller's decision; a third view through fpc_pnp_* against either solution's
+ *    points also settles it.
+ *  - Which candidate gets which index c: v1, v2 are determined up to their signs (and, where two lambdas meet, up to a
+ *    rotation).  Negating v1 swaps c = 0 <-> 1 and 2 <-> 3; negating v2 swaps 0 <-> 3 and 1 <-> 2.  The SET of four
+ *    candidates is invariant; the index c of a candidate, and so the outcome of an exact tie between two candidates, is
+ *    not -- as for fpc_pose_*.
+ *  - Workspace, execution and determinism are fpc_pose_*'s: the calls run the homography calls' pack / gather kernels
+ *    (without a mask: nothing of the caller's is zeroed) into the same pair-list workspace; nothing new is carved or
+ *    allocated, the plan hash and the guard zones are what they were; asynchronous on the ctx stream, no host
+ *    synchronisation, no device-to-host copy, every count and slot read on the device, so fpc_match_bank,
+ *    fpc_homography_bank, fpc_pose_homography_bank, fpc_bank_store + fpc_bank_store_landmarks needs no host call in
+ *    between; bit-identical outputs on repeated calls; the three entry points give bit-identical outputs on equal pair
+ *    lists, and fpc_pose_homography_bank is bit-identical to fpc_pose_homography_frames with that slot as key.
+ * FPC_E_INVALID (nothing is written): everything the homography twin refuses for the arguments they share; a NULL H_dev /
+ * params / kind_dev / R_dev / t_dev / nfront_dev; fx or fy not > 0 or any non-finite intrinsic; reproj_threshold not > 0
+ * (or not below 1e18); min_front < 1; min_baseline negative or not finite; which outside 0 .. 1. */
+enum { FPC_POSE_H_FAILED = 0, FPC_POSE_H_UNIQUE = 1, FPC_POSE_H_TWOFOLD = 2, FPC_POSE_H_ROTATION = 3 };
+typedef struct fpc_pose_homography_params {
+  float q_fx, q_fy, q_cx, q_cy;   /* intrinsics of the query camera (pixels), fx, fy > 0                                  */
+  float t_fx, t_fy, t_cx, t_cy;   /* intrinsics of the train camera                                                       */
+  float reproj_threshold;         /* px, > 0: which pairs count (plane pairs: the homography rule; support: Sampson)      */
+  int   min_front;                /* >= 1; a candidate with fewer plane pairs in front is dropped                         */
+  float min_baseline;             /* >= 0; baseline over plane distance at or below which the frame is a pure rotation    */
+  int   which;                    /* 0 or 1: the solution whose points go to xyz / front                                  */
+} fpc_pose_homography_params;
+/* fpc_default_pose_params' cameras and reproj_threshold, min_front 8, min_baseline 0.01, which 0 */
+int fpc_default_pose_homography_params(fpc_pose_homography_params* params);
+int fpc_pose_homography(fpc_ctx* ctx, int n, const float* src_xy_dev, const float* dst_xy_dev, const int32_t* npairs_dev,
+                        int stride, const float* H_dev, const fpc_pose_homography_params* params, int32_t* kind_dev,
+                        float* R_dev, float* t_dev, float* plane_dev, int32_t* nfront_dev, int32_t* nplane_dev,
+                        float* xyz_dev, uint8_t* front_dev);
+int fpc_pose_homography_frames(fpc_ctx* ctx, int n, int pairing, const int32_t* key_xy_dev, const int32_t* nkey_dev,
+                               const int32_t* match_dev, const float* H_dev, const fpc_pose_homography_params* params,
+                               int32_t* kind_dev, float* R_dev, float* t_dev, float* plane_dev, int32_t* nfront_dev,
+                               int32_t* nplane_dev, float* xyz_dev, uint8_t* front_dev);
+int fpc_pose_homography_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const float* H_dev,
+                             const fpc_pose_homography_params* params, int32_t* kind_dev, float* R_dev, float* t_dev,
+                             float* plane_dev, int32_t* nfront_dev, int32_t* nplane_dev, float* xyz_dev, uint8_t* front_dev);
+
 /* --- absolute pose from bank landmarks: RANSAC perspective-n-point on the device ------------------------------------------
  * fpc_pose_* ends in a translation DIRECTION: two views cannot give its scale, so every relocalisation comes back at a scale
  * of its own.  The triangulated points it writes remove that limit.  They are indexed by the query row, which is the row
