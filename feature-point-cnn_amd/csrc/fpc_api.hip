@@ -3693,11 +3693,13 @@ int fpc_match(fpc_ctx* c, const float* q, int nq, const float* t, int nt, int cr
     return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
   if (nq == 0) return FPC_OK;
-  if (nt == 0) {
-    HIPCHECK(hipMemsetAsync(match, 0xff, sizeof(int32_t) * nq, c->stream));  // -1
+  HIPCHECK(hipMemsetAsync(c->rowbest, 0xff, sizeof(unsigned long long) * nq, c->stream));
+  if (nt == 0) {  // no train rows: the finalize kernel on an untouched rowbest writes -1 / +inf (it reads no colbest then)
+    hipLaunchKernelGGL(match_finalize_kernel, dim3((nq + 255) / 256), dim3(256), 0, c->stream, c->rowbest, c->colbest, nq,
+                       cross_check, max_dist, match, dist);
+    HIPCHECK(hipGetLastError());
     return FPC_OK;
   }
-  HIPCHECK(hipMemsetAsync(c->rowbest, 0xff, sizeof(unsigned long long) * nq, c->stream));
   HIPCHECK(hipMemsetAsync(c->colbest, 0xff, sizeof(unsigned long long) * nt, c->stream));
   MatchArgs a{};
   a.q = q; a.t = t; a.nq = nq; a.nt = nt; a.D = c->D; a.rowbest = c->rowbest; a.colbest = c->colbest; a.first = nullptr; a.tol2 = -1.f;

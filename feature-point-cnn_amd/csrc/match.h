@@ -26,6 +26,17 @@ struct MatchArgs {
   float tol2;                   // tol^2; < 0: arg-min mode
 };
 
+// The epilogue of every 64 x 64 distance tile (here, match_frames.h, match_guided.h, match_guided_epipolar.h,
+// match_bank_bf16.h): d^2 = |q|^2 + |t|^2 - 2 q.t in fp32, rounding negatives and -0 up to +0 -- so no -0.0 bit pattern
+// reaches a (d^2 bits, index) key -- and letting a NaN through.  Every scan of a tile compares with a strict < against
+// a best that starts at +inf, so a pair whose d^2 is NaN or +inf is never a minimum, never a second best and never
+// within a tolerance (include/fpc.h, "Non-finite descriptor rows").  `d2 > 0 ? d2 : 0` would turn a NaN into an exact
+// hit, and so would fmaxf.
+__device__ __forceinline__ float match_d2(float qn, float tn, float acc) {
+  const float d2 = qn + tn - 2.f * acc;
+  return !(d2 <= 0.f) ? d2 : 0.f;
+}
+
 __global__ __launch_bounds__(256) void match_gemm_kernel(const MatchArgs a) {
   // per-workgroup arg-min tables: the four waves of a 128 x 128 tile reduce into LDS first, then ONE global 64-bit
   // atomicMin per row and per column of the tile
@@ -104,10 +115,8 @@ __global__ __launch_bounds__(256) void match_gemm_kernel(const MatchArgs a) {
       const int rowl = (r & 3) + 8 * (r >> 2) + 4 * half;
       const float qnr = __shfl(qn[mi], rowl);                         // |q|^2 of that row lives in lane `rowl`
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        float d2 = qnr + tn[ni] - 2.f * acc[mi][ni][r];
-        tile[(mi * 32 + rowl) * 68 + ni * 32 + l31] = d2 > 0.f ? d2 : 0.f;
-      }
+      for (int ni = 0; ni < 2; ++ni)
+        tile[(mi * 32 + rowl) * 68 + ni * 32 + l31] = match_d2(qnr, tn[ni], acc[mi][ni][r]);
     }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the tile is private to this wave: no workgroup barrier needed
   {  // lane = row of the tile: arg-min (lowest column index on ties) and first-within over its 64 columns
@@ -172,8 +181,8 @@ __global__ __launch_bounds__(256) void match_finalize_kernel(const unsigned long
   if (i >= nq) return;
   const unsigned long long rb = rowbest[i];
   const int j = (int)(rb & 0xffffffffu);
-  const float d = sqrtf(__uint_as_float((unsigned)(rb >> 32)));
-  bool ok = rb != ~0ull;
+  bool ok = rb != ~0ull;   // untouched: no train row at a finite distance (nt = 0 included) -> -1 / +inf
+  const float d = ok ? sqrtf(__uint_as_float((unsigned)(rb >> 32))) : INFINITY;
   if (ok && cross_check) ok = (int)(colbest[j] & 0xffffffffu) == i;
   if (ok && max_dist > 0.f) ok = d < max_dist;
   match[i] = ok ? j : -1;

@@ -249,8 +249,7 @@ __device__ __forceinline__ void mf_strip_bf16(const MatchFramesArgs& a, const Mb
         const float qnr = s_qn[mi * 32 + rowl];
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
-          float d2 = qnr + tn[ni] - 2.f * acc[mi][ni][r];
-          d2 = d2 > 0.f ? d2 : 0.f;
+          float d2 = match_d2(qnr, tn[ni], acc[mi][ni][r]);
           if constexpr (GATED) d2 = (pass >> ((mi * 16 + r) * 2 + ni)) & 1ull ? d2 : INFINITY;
           tile[(mi * 32 + rowl) * MF_PITCH + ni * 32 + l31] = d2;
         }

@@ -193,10 +193,8 @@ __device__ __forceinline__ void mf_strip(const MatchFramesArgs& a, const MfSets&
         const int rowl = (r & 3) + 8 * (r >> 2) + 4 * half;
         const float qnr = s_qn[mi * 32 + rowl];
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          float d2 = qnr + tn[ni] - 2.f * acc[mi][ni][r];
-          tile[(mi * 32 + rowl) * MF_PITCH + ni * 32 + l31] = d2 > 0.f ? d2 : 0.f;
-        }
+        for (int ni = 0; ni < 2; ++ni)
+          tile[(mi * 32 + rowl) * MF_PITCH + ni * 32 + l31] = match_d2(qnr, tn[ni], acc[mi][ni][r]);
       }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the tile is private to this wave
     {
@@ -278,6 +276,10 @@ __global__ __launch_bounds__(256) void match_frames_kernel(const MatchFramesArgs
 // ratio test, ANDed; d = the distance to the nearest train row.  Shared with the bank's score pass (match_bank.h).
 __device__ __forceinline__ bool mf_row_ok(unsigned long long k1, unsigned long long k2, int i,
                                           const unsigned long long* colbest, float max_dist, float ratio, float& d) {
+  if (k1 == ~0ull) {       // no train row at a finite distance: no index to look up in colbest
+    d = INFINITY;
+    return false;
+  }
   const int j = (int)(k1 & 0xffffffffu);
   d = sqrtf(__uint_as_float((unsigned)(k1 >> 32)));
   bool ok = true;

@@ -178,8 +178,7 @@ __device__ __forceinline__ void mg_tile(const float* const (&qrow)[2], const flo
       const float qnr = s_qn[mi * 32 + rowl];
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
-        float d2 = qnr + tn[ni] - 2.f * acc[mi][ni][r];
-        d2 = d2 > 0.f ? d2 : 0.f;
+        const float d2 = match_d2(qnr, tn[ni], acc[mi][ni][r]);
         tile[(mi * 32 + rowl) * MF_PITCH + ni * 32 + l31] = (pass >> ((mi * 16 + r) * 2 + ni)) & 1ull ? d2 : INFINITY;
       }
     }

@@ -366,12 +366,22 @@ int fpc_sample_descriptors(fpc_ctx* ctx, const float* desc_nchw_dev, const doubl
  * cross_check != 0 only mutual nearest neighbours survive; with max_dist > 0 only matches closer
  * than max_dist.  q [nq][128], t [nt][128], match [nq] (train index or -1), dist [nq] (L2
  * distance to the nearest train descriptor; may be NULL) -- all device pointers; nq, nt <=
- * the ctx's keypoint capacity.  Asynchronous on the ctx stream. */
+ * the ctx's keypoint capacity.  Asynchronous on the ctx stream.
+ *
+ * Non-finite descriptor rows.  Every matcher of this header evaluates d^2 = |q|^2 + |t|^2 - 2 q.t in fp32 (the bf16 bank:
+ * on its rounded rows), and the rule is stated for that fp32 d^2: a pair whose d^2 is NaN or +inf -- a row that holds a
+ * NaN or an Inf (an all-zero sample of fpc_sample_descriptors, caller memory), or finite rows whose fp32 norms overflow --
+ * is never a row minimum, never a column minimum (it takes no part in the cross check), never a second best (it takes no
+ * part in the ratio test) and never within a tolerance or below max_dist.  A query row with no train row at a finite
+ * distance gets match -1 and dist +inf, as a query row with no train rows at all (nt = 0) does.  The other rows are
+ * matched as if the non-finite rows were absent.  This is what cv2.BFMatcher and cpp/src/main.cc:18-29 do: a non-finite
+ * distance is never a minimum and never below a tolerance. */
 int fpc_match(fpc_ctx* ctx, const float* q_dev, int nq, const float* t_dev, int nt, int cross_check,
               float max_dist, int32_t* match_dev, float* dist_dev);
 /* ~ SearchKeyFrameCorrespondence (cpp/src/main.cc:18-29,79-83): for every key-frame descriptor the
  * index of the FIRST current-frame descriptor (in the order given, i.e. descending confidence)
- * whose L2 distance is below `tolerance` (cpp/src/main.cc:54: 0.8), or -1. */
+ * whose L2 distance is below `tolerance` (cpp/src/main.cc:54: 0.8), or -1.  A non-finite d^2 (fpc_match) is below no
+ * tolerance: a non-finite key row gets -1, a non-finite current-frame row is nobody's first. */
 int fpc_first_within(fpc_ctx* ctx, const float* key_dev, int nk, const float* cur_dev, int nc,
                      float tolerance, int32_t* first_dev);
 
@@ -397,7 +407,9 @@ int fpc_first_within(fpc_ctx* ctx, const float* key_dev, int nk, const float* cu
  * than `tolerance`, or -1.  first_dev [n][cap]; rows j >= nkey get -1.  key_dev / nkey_dev required; tolerance >= 0.
  *
  * Both: asynchronous on the ctx stream (no host synchronisation, no device-to-host copy; may be enqueued right after
- * fpc_detect and before the next one), deterministic (bit-identical outputs on repeated calls). */
+ * fpc_detect and before the next one), deterministic (bit-identical outputs on repeated calls).  Non-finite descriptor
+ * rows, in a frame or in the key set: fpc_match's rule on the fp32 d^2 -- such a pair is no row minimum, no column minimum,
+ * no second best and within no tolerance; a row with no train row at a finite distance: match -1, dist +inf. */
 enum { FPC_PAIR_KEY = 0, FPC_PAIR_PREVIOUS = 1 };
 int fpc_match_frames(fpc_ctx* ctx, int n, int pairing, const float* key_dev, const int32_t* nkey_dev,
                      int cross_check, float max_dist, float ratio, int32_t* match_dev, float* dist_dev);
@@ -499,6 +511,8 @@ int fpc_homography_frames(fpc_ctx* ctx, int n, int pairing, const int32_t* key_x
  *    slot best[f] -- bit-identical to what that call returns with desc[best[f]], count[best[f]] as its key (it IS that
  *    call's kernels, with the key chosen per frame on the device).  A frame with best[f] = -1: -1 / +inf.
  *  - score_dev or best_dev may be NULL, not both.
+ *  - Non-finite descriptor rows, in a frame or in a slot: fpc_match's rule on the fp32 d^2 -- such a pair counts in no score
+ *    and is no minimum of the table; a slot of non-finite rows scores 0.
  *  - WARNING: a bare cross check (max_dist = 0, ratio = 0) does not discriminate between slots.  Two UNRELATED descriptor
  *    sets have many mutual nearest neighbours (on random unit-norm sets a large share of the smaller set), so an
  *    unrelated slot can outscore the right one.  Give max_dist (the reference's threshold is 0.7, settings.py:6) or a
@@ -627,6 +641,8 @@ int fpc_fundamental_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int
  *  - Execution as above: asynchronous on the ctx stream, no allocation after create, no host synchronisation, counts and
  *    slots read on the device.  Deterministic: selection is integer and order-free, the matrix instruction's internal
  *    accumulation order is fixed by the hardware; repeated calls give bit-identical outputs.
+ *  - Non-finite descriptor rows: fpc_match's rule, on the fp32 d^2 of the ROUNDED rows (a NaN is stored as 0x7FC0, an
+ *    overflow as +-inf): such a pair counts in no score and is no minimum of a table.
  *  - When to use it: to rank slots under max_dist or a ratio (tests/test_match_bank_bf16.py: on planted data the scores and
  *    best equal the fp32 rule's).  The WARNING above about a bare cross check applies, and there the two formats differ. */
 #define FPC_BANK_F32  0
@@ -664,6 +680,8 @@ int fpc_bank_format(fpc_ctx* ctx, int* format, const void** desc);
  *    workspace is fpc_match_frames', carved at fpc_create); every count and slot is read on the device; deterministic
  *    (bit-identical outputs on repeated calls).  fpc_detect, fpc_match_frames, fpc_homography_frames,
  *    fpc_match_frames_guided, fpc_homography_frames needs no host call in between.
+ * Non-finite descriptor rows: fpc_match's rule on the fp32 d^2 -- such a pair is no candidate's minimum, no column minimum,
+ * no second best, and a row with no candidate at a finite distance is -1 / +inf.
  * FPC_E_INVALID (nothing is written): everything fpc_match_frames refuses; a NULL H_dev; radius not finite or not > 0;
  * FPC_PAIR_KEY without key_xy_dev; key_dev without key_xy_dev; no bank or a NULL slot_dev (bank variant). */
 int fpc_match_frames_guided(fpc_ctx* ctx, int n, int pairing, const float* key_dev, const int32_t* nkey_dev,
@@ -702,6 +720,8 @@ int fpc_match_bank_guided(fpc_ctx* ctx, int n, const int32_t* slot_dev, const fl
  *    every count and slot read on the device.  fpc_match_frames, fpc_homography_frames, fpc_match_frames_guided_cells,
  *    fpc_homography_frames needs no host call in between.  Per call: the order of the query sets (frames 0 .. n-1) and of
  *    the train sets (the key once; under FPC_PAIR_PREVIOUS frame f-1's query order is reused; the slot of every frame).
+ * Non-finite descriptor rows: fpc_match's rule on the fp32 d^2 -- such a pair is no candidate's minimum, no column minimum,
+ * no second best, and a row with no candidate at a finite distance is -1 / +inf.
  * FPC_E_INVALID (nothing is written, stats_dev included): everything fpc_match_frames_guided / fpc_match_bank_guided
  * refuse; the bank variant on a FPC_BANK_BF16 bank (that format's ordered strip is the follow-up). */
 int fpc_cell_order(fpc_ctx* ctx, const int32_t* xy_dev, const int32_t* n_dev, int sets, int stride, int32_t* perm_dev);
@@ -746,6 +766,8 @@ int fpc_match_bank_guided_cells(fpc_ctx* ctx, int n, const int32_t* slot_dev, co
  *    fpc_detect, fpc_match_frames, fpc_fundamental_frames, fpc_match_frames_guided_epipolar, fpc_fundamental_frames needs no
  *    host call in between; the same holds through the bank with fpc_match_bank, fpc_fundamental_bank,
  *    fpc_match_bank_guided_epipolar, fpc_fundamental_bank.
+ * Non-finite descriptor rows: fpc_match's rule on the fp32 d^2 -- such a pair is no candidate's minimum, no column minimum,
+ * no second best, and a row with no candidate at a finite distance is -1 / +inf.
  * FPC_E_INVALID (nothing is written): everything fpc_match_frames_guided / fpc_match_bank_guided refuse, with F_dev for
  * H_dev; the bank variant on a FPC_BANK_BF16 bank (that format's epipolar gate is the follow-up). */
 int fpc_match_frames_guided_epipolar(fpc_ctx* ctx, int n, int pairing, const float* key_dev, const int32_t* nkey_dev,
@@ -789,6 +811,8 @@ int fpc_match_bank_guided_epipolar(fpc_ctx* ctx, int n, const int32_t* slot_dev,
  *    fpc_match_frames, fpc_fundamental_frames, fpc_match_frames_guided_epipolar_cells, fpc_fundamental_frames needs no host
  *    call in between; the same holds through the bank with fpc_match_bank, fpc_fundamental_bank,
  *    fpc_match_bank_guided_epipolar_cells, fpc_fundamental_bank.
+ * Non-finite descriptor rows: fpc_match's rule on the fp32 d^2 -- such a pair is no candidate's minimum, no column minimum,
+ * no second best, and a row with no candidate at a finite distance is -1 / +inf.
  * FPC_E_INVALID (nothing is written, stats_dev included): everything fpc_match_frames_guided_epipolar /
  * fpc_match_bank_guided_epipolar refuse; the bank variant on a FPC_BANK_BF16 bank (that format's strip is the follow-up). */
 int fpc_match_frames_guided_epipolar_cells(fpc_ctx* ctx, int n, int pairing, const float* key_dev, const int32_t* nkey_dev,
@@ -838,6 +862,7 @@ int fpc_match_bank_guided_epipolar_cells(fpc_ctx* ctx, int n, const int32_t* slo
  * a call does not depend on n or k (the score pass loops over the bank's slot chunks, as in fpc_match_bank).  fpc_detect,
  * fpc_match_bank_topk, fpc_homography_bank_topk, fpc_match_bank_guided(best), fpc_homography_bank(best) needs no host call
  * in between.
+ * Non-finite descriptor rows: fpc_match's rule on the fp32 d^2, in the scores and in every candidate's table.
  * FPC_E_INVALID (nothing is written): everything fpc_match_bank (but a NULL score_dev) / fpc_homography_bank refuses; no
  * reservation; k outside [1, kmax]; a NULL cand_slot_dev; a NULL match_dev / H_dev / ninliers_dev (homography call). */
 #define FPC_BANK_TOPK_MAX 16
@@ -1167,6 +1192,8 @@ int fpc_pnp_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* ma
  *    slot is read on the device; deterministic (bit-identical outputs on repeated calls).  fpc_detect, fpc_match_bank,
  *    fpc_pnp_bank, fpc_match_bank_guided_pose, fpc_pnp_bank needs no host call in between; the same holds with a key
  *    through fpc_match_frames, fpc_pnp_frames, fpc_match_frames_guided_pose, fpc_pnp_frames.
+ * Non-finite descriptor rows: fpc_match's rule on the fp32 d^2 -- such a pair is no candidate's minimum, no column minimum,
+ * no second best, and a row with no candidate at a finite distance is -1 / +inf.
  * FPC_E_INVALID (nothing is written): everything fpc_match_frames refuses; NULL R_dev, t_dev or match_dev; radius not finite
  * or not > 0; fx or fy not > 0 or a non-finite intrinsic; frames variant: NULL key_dev, nkey_dev or key_xyz_dev; bank
  * variant: no bank, NULL slot_dev, or a FPC_BANK_BF16 bank (that format's pose gate is a follow-up, as its epipolar one).

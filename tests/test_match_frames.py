@@ -13,31 +13,39 @@ FPC_E_INVALID = -1
 PAIR_KEY, PAIR_PREVIOUS = 0, 1
 
 
-def pair_rule(q, t, cross_check=True, max_dist=0.0, ratio=0.0):
+def pair_rule(q, t, cross_check=True, max_dist=0.0, ratio=0.0, gram=None):
     """One pair in float64 -> (match int32[nq], d1 float64[nq], d2 float64[nq]).  Nearest / second-nearest train row in
     (distance, index) order; a row with no train rows: -1, +inf; fewer than two train rows: d2 = +inf and the ratio test
-    fails."""
+    fails.  Non-finite descriptor rows (include/fpc.h): a pair whose distance is NaN or +inf is no minimum of its row or
+    column and no second best -- it is masked to +inf here, and +inf never wins; a row without a finite distance is
+    -1 / +inf.  (The library decides "finite" on its fp32 d^2; rows that hold a NaN or an Inf are non-finite in both.)
+    gram: the float64 products q t^T by another routine than the matrix product -- tests/test_match_edges.py passes an
+    einsum, whose dot products all run through one loop, so that bit-equal rows give bit-equal distances (a blocked GEMM
+    need not)."""
     nq, nt = len(q), len(t)
     m = np.full(nq, -1, np.int32)
     d1, d2 = np.full(nq, np.inf), np.full(nq, np.inf)
     if nq == 0 or nt == 0:
         return m, d1, d2
     q64, t64 = np.asarray(q, np.float64), np.asarray(t, np.float64)
-    dd = (q64 * q64).sum(1)[:, None] + (t64 * t64).sum(1)[None, :] - 2.0 * q64 @ t64.T
-    dd = np.sqrt(np.maximum(dd, 0.0))
+    with np.errstate(invalid="ignore", over="ignore"):
+        qt = q64 @ t64.T if gram is None else gram(q64, t64)
+        dd = (q64 * q64).sum(1)[:, None] + (t64 * t64).sum(1)[None, :] - 2.0 * qt
+        dd = np.sqrt(np.maximum(dd, 0.0))
+    dd[~np.isfinite(dd)] = np.inf
     order = np.argsort(dd, axis=1, kind="stable")            # equal distances keep the lower index first
     rows = np.arange(nq)
     best = order[:, 0]
     d1 = dd[rows, best]
     if nt >= 2:
         d2 = dd[rows, order[:, 1]]
-    ok = np.ones(nq, bool)
+    ok = np.isfinite(d1)
     if cross_check:
         ok &= np.argmin(dd, axis=0)[best] == rows              # argmin: the first (lowest) row on ties
     if max_dist > 0:
         ok &= d1 < max_dist
     if ratio > 0:
-        ok &= (nt >= 2) & (d1 < ratio * d2)
+        ok &= np.isfinite(d2) & (d1 < ratio * d2)              # (fewer than two finite distances: d2 = +inf)
     m[ok] = best[ok]
     return m, d1, d2
 
