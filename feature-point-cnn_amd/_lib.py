@@ -45,6 +45,7 @@ SYMBOLS = [
     "fpc_match_frames_guided_pose", "fpc_match_bank_guided_pose",
     "fpc_default_landmark_params", "fpc_landmarks_pairs", "fpc_landmarks_frames", "fpc_landmarks_bank",
     "fpc_default_sim3_params", "fpc_ransac_sim3", "fpc_sim3_frames", "fpc_sim3_bank",
+    "fpc_default_refine_params", "fpc_refine_pose", "fpc_refine_pose_frames", "fpc_refine_pose_bank",
 ]
 
 ABI_VERSION = 4
@@ -122,6 +123,14 @@ class FpcLandmarkParams(ctypes.Structure):
     _fields_ = [("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
                 ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
                 ("reproj_threshold", ctypes.c_float), ("min_parallax_deg", ctypes.c_float)]
+
+
+class FpcRefineParams(ctypes.Structure):
+    """fpc_refine_params (include/fpc.h)."""
+    _fields_ = [("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
+                ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
+                ("reproj_threshold", ctypes.c_float), ("min_parallax_deg", ctypes.c_float), ("iterations", ctypes.c_int),
+                ("lambda0", ctypes.c_float), ("min_front", ctypes.c_int)]
 
 
 class FpcSim3Params(ctypes.Structure):
@@ -276,6 +285,12 @@ def load():
     l.fpc_ransac_sim3.argtypes = [vp, ci, vp, vp, vp, ci, sp, vp, vp, vp, vp, vp]
     l.fpc_sim3_frames.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, sp, vp, vp, vp, vp, vp]
     l.fpc_sim3_bank.argtypes = [vp, ci, vp, vp, vp, vp, sp, vp, vp, vp, vp, vp]
+    fp = ctypes.POINTER(FpcRefineParams)
+    l.fpc_default_refine_params.argtypes = [fp]
+    # the pose twins' arguments with (R_in_dev, t_in_dev) where their F_dev stands and six outputs for their five
+    l.fpc_refine_pose.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, fp] + [vp] * 6
+    l.fpc_refine_pose_frames.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, fp] + [vp] * 6
+    l.fpc_refine_pose_bank.argtypes = [vp, ci, vp, vp, vp, vp, fp] + [vp] * 6
     l.fpc_bank_topk_reserve.argtypes =[vp, ci, ctypes.POINTER(ctypes.c_size_t)]
     l.fpc_match_bank_topk.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp, vp]
     l.fpc_homography_bank_topk.argtypes = [vp, ci, ci, vp, vp, rp, vp, vp, vp, vp, vp]

@@ -49,6 +49,7 @@
 #include "pnp_ransac.h"
 #include "sim3_ransac.h"
 #include "landmarks.h"
+#include "refine_pose.h"
 #include "homography.h"
 #include "weights.h"
 #include "plan_options.h"
@@ -4763,6 +4764,72 @@ int fpc_landmarks_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* ma
   src.bank_lm = c->lm_xyzw;                                      // (null without a landmark reservation: triangulation only)
   src.rows = c->bank.rows; src.slots = c->bank.slots;
   return landmarks_launch(c, n, src, R, t, p, xyz, kind, counts, c->cap);
+}
+
+// ---- two-view bundle adjustment of a pose call's R, t and points (include/fpc.h; kernel in refine_pose.h) --------------------
+// The pose calls' pair sources with a NULL mask, their pair records and workspace: a refine call leaves the pair list its pose
+// twin built, built again.
+int fpc_default_refine_params(fpc_refine_params* p) {
+  if (!p) return FPC_E_INVALID;
+  p->q_fx = p->q_fy = p->t_fx = p->t_fy = 500.0f;
+  p->q_cx = p->t_cx = 320.0f;
+  p->q_cy = p->t_cy = 240.0f;
+  p->reproj_threshold = 3.0f;
+  p->min_parallax_deg = 1.0f;
+  p->iterations = 8;
+  p->lambda0 = 1e-3f;
+  p->min_front = 8;
+  return FPC_OK;
+}
+
+static bool refine_params_ok(const fpc_refine_params* p) {
+  return p && camera_ok(p->q_fx, p->q_fy, p->q_cx, p->q_cy) && camera_ok(p->t_fx, p->t_fy, p->t_cx, p->t_cy) &&
+         threshold_ok(p->reproj_threshold) && p->min_parallax_deg >= 0.f && p->min_parallax_deg < 90.f &&   // (a NaN fails)
+         p->iterations >= 1 && p->iterations <= 16 && std::isfinite(p->lambda0) && p->lambda0 > 0.f && p->min_front >= 1;
+}
+
+// what the three calls refuse before their pair source is looked at
+static bool refine_ok(const fpc_ctx* c, const float* R_in, const float* t_in, const fpc_refine_params* p, const float* R,
+                      const float* t, const int32_t* nfront, const float* xyz) {
+  return c && R_in && t_in && R && t && nfront && xyz && refine_params_ok(p);
+}
+
+// the solver step behind the pair list (a: hf_args with the parameters' threshold, nothing of RANSAC's)
+static int refine_launch(fpc_ctx* c, const HfArgs& a, const fpc_refine_params* p, const float* R_in, const float* t_in, float* R,
+                         float* t, int32_t* nfront, float* xyz, uint8_t* front, float* stats, int ostride) {
+  const double s = std::sin((double)p->min_parallax_deg * (3.14159265358979323846 / 180.0));
+  const RefineArgs ra{p->q_fx, p->q_fy, p->q_cx, p->q_cy, p->t_fx, p->t_fy, p->t_cx, p->t_cy,
+                      p->min_parallax_deg > 0.f ? s * s : POSE_PARALLEL, p->iterations, p->lambda0, p->min_front};
+  hipLaunchKernelGGL(refine_pose_kernel, dim3(a.n), dim3(256), 0, c->stream, a, ra, R_in, t_in, R, t, nfront, xyz, front, stats,
+                     ostride);
+  return launched();
+}
+
+int fpc_refine_pose(fpc_ctx* c, int n, const float* src_xy, const float* dst_xy, const int32_t* npairs, int stride,
+                    const float* R_in, const float* t_in, const fpc_refine_params* p, float* R, float* t, int32_t* nfront,
+                    float* xyz, uint8_t* front, float* stats) {
+  if (!refine_ok(c, R_in, t_in, p, R, t, nfront, xyz)) return FPC_E_INVALID;
+  const HfArgs a = hf_args(c, n, p->reproj_threshold);
+  if (int rc = pairs_explicit(c, a, src_xy, dst_xy, npairs, stride, nullptr)) return rc;
+  return refine_launch(c, a, p, R_in, t_in, R, t, nfront, xyz, front, stats, stride);
+}
+
+int fpc_refine_pose_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy, const int32_t* nkey, const int32_t* match,
+                           const float* R_in, const float* t_in, const fpc_refine_params* p, float* R, float* t,
+                           int32_t* nfront, float* xyz, uint8_t* front, float* stats) {
+  if (!refine_ok(c, R_in, t_in, p, R, t, nfront, xyz)) return FPC_E_INVALID;
+  const HfArgs a = hf_args(c, n, p->reproj_threshold);
+  if (int rc = pairs_frames(c, a, pairing, key_xy, nkey, match, nullptr)) return rc;
+  return refine_launch(c, a, p, R_in, t_in, R, t, nfront, xyz, front, stats, c->cap);
+}
+
+int fpc_refine_pose_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const float* R_in, const float* t_in,
+                         const fpc_refine_params* p, float* R, float* t, int32_t* nfront, float* xyz, uint8_t* front,
+                         float* stats) {
+  if (!refine_ok(c, R_in, t_in, p, R, t, nfront, xyz)) return FPC_E_INVALID;
+  const HfArgs a = hf_args(c, n, p->reproj_threshold);
+  if (int rc = pairs_bank(c, a, n, slot, match, nullptr)) return rc;
+  return refine_launch(c, a, p, R_in, t_in, R, t, nfront, xyz, front, stats, c->cap);
 }
 
 int fpc_results(fpc_ctx* c, fpc_device_results* out) {

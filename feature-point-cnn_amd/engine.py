@@ -583,10 +583,11 @@ class Engine:
         slot = self._dev_int32("slot", slot, "[n]", n)
         return p, (slot, self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity))
 
-    def _solve(self, name, n, pairs, p, out, *more):
-        """fpc_<name>(ctx, n, *pairs, *more, params, *out) -> out, its last tensor (a uint8 mask, or None) as bool."""
-        self._call(name, n, *pairs, *more, ctypes.byref(p), *out, inputs=(*pairs, *more))
-        return (*out[:-1], None if out[-1] is None else out[-1].view(torch.bool))
+    def _solve(self, name, n, pairs, p, out, *more, tail=()):
+        """fpc_<name>(ctx, n, *pairs, *more, params, *out, *tail) -> out, its last tensor (a uint8 mask, or None) as bool,
+        then the tensors of `tail` as they are."""
+        self._call(name, n, *pairs, *more, ctypes.byref(p), *out, *tail, inputs=(*pairs, *more))
+        return (*out[:-1], None if out[-1] is None else out[-1].view(torch.bool), *tail)
 
     def _key_xy(self, key_xy):
         """key_xy -> (xy int32 [k,2], device count) or (None, None).  An (xy, count) pair of device tensors is used as it
@@ -901,6 +902,70 @@ class Engine:
     def pose_homography_bank(self, n, slot, match, H, K_query=None, K_train=None, points=True, **params):
         """pose_homography_bank_async, then host arrays."""
         return self._host(self.pose_homography_bank_async(n, slot, match, H, K_query, K_train, points, **params))
+
+    # -- two-view bundle adjustment of a pose call's R, t and points (fpc_refine_pose / _frames / _bank) -------------------------
+    def _refine_params(self, K_query, K_train, params):
+        return self._two_camera_params(_lib.FpcRefineParams, "fpc_default_refine_params",
+                                       ("reproj_threshold", "min_parallax_deg", "iterations", "lambda0", "min_front"),
+                                       "refine", K_query, K_train, params)
+
+    def _refine_in(self, n, R, t, which):
+        """The input pose as contiguous device tensors (R float32 [n,9] or [n,3,3], t float32 [n,3]): a pose call's output
+        as it is, or solution `which` of a homography pose call's [n,2,3,3] / [n,2,3], copied on the device."""
+        rm = torch.as_tensor(R).to(self.torch_device, torch.float32)
+        tv = torch.as_tensor(t).to(self.torch_device, torch.float32)
+        if rm.dim() == 4 or which is not None:
+            if which not in (0, 1) or tuple(rm.shape) != (n, 2, 3, 3) or tuple(tv.shape) != (n, 2, 3):
+                raise ValueError("which=0 or 1 selects a solution of R [n,2,3,3] and t [n,2,3]")
+            rm, tv = rm[:, which], tv[:, which]
+        rm, tv = self._guided_h(n, rm, "R"), tv.contiguous()
+        if tuple(tv.shape) != (n, 3):
+            raise ValueError("t must be [n,3]")
+        return rm, tv
+
+    def _refine(self, name, n, pairs, R, t, which, p, stride):
+        """fpc_<name> behind its pair source: (R_in, t_in) go in front of the parameters, stats behind the pose outputs."""
+        rm, tv = self._refine_in(n, R, t, which)
+        stats = torch.empty((n, 4), dtype=torch.float32, device=self.torch_device)
+        return self._solve(name, n, pairs, p, self._pose_out(n, stride, True), rm, tv, tail=(stats,))
+
+    def refine_pose_async(self, src, dst, npairs, R, t, K_query=None, K_train=None, which=None, **params):
+        """fpc_refine_pose: pose_fundamental_async's pairs and the R, t it returned (device tensors as they are, or host
+        arrays; with which=0 / 1 that solution of pose_homography_async's [n,2,3,3] / [n,2,3]) -> device tensors (R float32
+        [n,3,3] and t float32 [n,3], refined by a two-view bundle adjustment; nfront int32 [n]; xyz float32 [n,stride,3], the
+        refined points; front bool [n,stride]; stats float32 [n,4]: rms reprojection error before and after, attempts made,
+        attempts accepted).  Parameters: reproj_threshold, min_parallax_deg, iterations, lambda0, min_front.  A failed frame
+        is all zeros.  Does not synchronise."""
+        p = self._refine_params(K_query, K_train, params)
+        n, pairs = self._explicit_pairs(src, dst, npairs)
+        return self._refine("fpc_refine_pose", n, pairs, R, t, which, p, pairs[3])
+
+    def refine_pose(self, src, dst, npairs, R, t, K_query=None, K_train=None, which=None, **params):
+        """refine_pose_async, then host arrays (R [n,3,3], t [n,3], nfront [n], xyz [n,stride,3], front bool [n,stride],
+        stats [n,4])."""
+        return self._host(self.refine_pose_async(src, dst, npairs, R, t, K_query, K_train, which, **params))
+
+    def refine_pose_frames_async(self, n, match, R, t, key_xy=None, pairing="key", K_query=None, K_train=None, which=None,
+                                 **params):
+        """fpc_refine_pose_frames: pose_frames_async's arguments and pairs with its output R, t -> refine_pose_async's
+        tensors with xyz [n,cap,3] and front bool [n,cap] by query row.  Does not synchronise."""
+        p, pairs = self._frames_pairs(n, pairing, key_xy, match, self._refine_params, K_query, K_train, params)
+        return self._refine("fpc_refine_pose_frames", n, pairs, R, t, which, p, self.capacity)
+
+    def refine_pose_frames(self, n, match, R, t, key_xy=None, pairing="key", K_query=None, K_train=None, which=None, **params):
+        """refine_pose_frames_async, then host arrays."""
+        return self._host(self.refine_pose_frames_async(n, match, R, t, key_xy, pairing, K_query, K_train, which, **params))
+
+    def refine_pose_bank_async(self, n, slot, match, R, t, K_query=None, K_train=None, which=None, **params):
+        """fpc_refine_pose_bank: refine_pose_frames_async with frame f's key coordinates taken from bank slot slot[f], as
+        pose_bank_async, whose R, t go in as they are; a frame with slot -1 fails (zeros).  xyz[f] and front[f] go into
+        bank_store_landmarks as they are.  Does not synchronise."""
+        p, pairs = self._bank_pairs(n, slot, match, self._refine_params, K_query, K_train, params)
+        return self._refine("fpc_refine_pose_bank", n, pairs, R, t, which, p, self.capacity)
+
+    def refine_pose_bank(self, n, slot, match, R, t, K_query=None, K_train=None, which=None, **params):
+        """refine_pose_bank_async, then host arrays."""
+        return self._host(self.refine_pose_bank_async(n, slot, match, R, t, K_query, K_train, which, **params))
 
     # -- absolute pose from landmarks: RANSAC PnP (fpc_pnp_reserve / fpc_bank_*landmarks* / fpc_ransac_pnp / _frames / _bank) ----
     def pnp_reserve(self):

@@ -1261,7 +1261,8 @@ int fpc_match_bank_guided_pose(fpc_ctx* ctx, int n, const int32_t* slot_dev,
  *    device.  Deterministic: bit-identical outputs on repeated calls; the three entry points give bit-identical outputs on
  *    equal lists, and fpc_landmarks_bank is bit-identical to fpc_landmarks_frames with that slot's own storage as the key.
  *    It works on a FPC_BANK_BF16 bank: it reads only xy, counts and landmarks.
- *  - Not here: fusing repeated observations of one landmark, bundle adjustment, a cell-ordered variant.
+ *  - Not here: fusing repeated observations of one landmark, bundle adjustment over more than two views, a cell-ordered
+ *    variant.
  * FPC_E_INVALID (nothing is written): everything the PnP twins refuse for the arguments they share (n, stride, a NULL pair
  * array, npairs_dev, match_dev); NULL params, R_dev, t_dev, xyz_dev or kind_dev; fx or fy not > 0 or a non-finite intrinsic on
  * either side; reproj_threshold not > 0 (or not below 1e18); min_parallax_deg not in [0, 90); fpc_landmarks_frames: a NULL
@@ -1284,6 +1285,96 @@ int fpc_landmarks_frames(fpc_ctx* ctx, int n, const int32_t* key_xy_dev, const i
 int fpc_landmarks_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const float* R_dev,
                        const float* t_dev, const fpc_landmark_params* params, float* xyz_dev, uint8_t* kind_dev,
                        int32_t* counts_dev);
+
+/* --- two-view bundle adjustment: refine R, t and the points of a pose call --------------------------------------------------
+ * fpc_pose_* and fpc_pose_homography_* are linear: R and t come from decomposing an F or an H that RANSAC fitted
+ * algebraically, and every point is the midpoint of two rays.  fpc_refine_pose, fpc_refine_pose_frames and
+ * fpc_refine_pose_bank minimise what a mapper cares about -- the reprojection error in both images -- over R, the direction
+ * of t and one point per pair, by damped Gauss-Newton steps (Levenberg-Marquardt) on the device.  They mirror
+ * fpc_pose_fundamental / fpc_pose_frames / fpc_pose_bank argument for argument: the same pair definition, strides, clamping
+ * of counts, pairing, key and slot rules and pair-list workspace, with the input pose R_in_dev float32 [n][9] row-major and
+ * t_in_dev float32 [n][3] in the place of F_dev and fpc_refine_params in the place of fpc_pose_params.  What fpc_pose_* wrote
+ * goes in unchanged; one solution of fpc_pose_homography_* goes in once its [n][2] slice has been made contiguous.
+ * Outputs: R_dev, t_dev, nfront_dev and front_dev (may be NULL) as for fpc_pose_*; xyz_dev float32 [n][S][3] is REQUIRED: it
+ * is the state of the iteration; stats_dev float32 [n][4] (may be NULL): the rms reprojection error over the members before,
+ * the same after, attempts made, attempts accepted.  R_dev / t_dev may alias R_in_dev / t_in_dev.  Everything below is fp64
+ * unless said otherwise.
+ *  - Convention: X_train = R X_query + t, |t| = 1, the points in the query camera's frame at that scale: the pose calls'.
+ *  - Input: a frame fails if R_in is all zero (a failed frame of the pose calls), if R_in or t_in holds a non-finite entry, or
+ *    if |t_in| is not > 0.  Otherwise R = R_in and t = t_in / |t_in| rounded to fp32.  R is used as given; it is not
+ *    orthonormalised.
+ *  - Members: every pair of the list is triangulated under (R, t) exactly as in the pose section (a = R p^, b = q^, det, lam,
+ *    mu); X = (lam p^ + R^T (mu q^ - t)) / 2 is the midpoint.  A pair is a MEMBER iff
+ *        det > sin^2(min_parallax_deg) (a.a)(b.b)   (sin^2 formed by the host in double; at 0 degrees, and wherever sin^2 is
+ *                                                     below it, the floor of the pose calls: det > 1e-12 (a.a)(b.b)),
+ *        lam > 0 and mu > 0,
+ *        X passes the reprojection test of the landmark section against the query pixel and the query camera,
+ *        R X + t passes it against the train pixel and the train camera,
+ *    and X rounded to fp32, the start point, has a third coordinate > 0.  The membership is fixed for the whole call.
+ *  - Cost: C = sum over the members of |pi_q(X) - p|^2 + |pi_t(R X + t) - q|^2 with pi(Y) = (fx Y0 / Y2 + cx, fy Y1 / Y2 + cy),
+ *    p the query pixel and q the train pixel, evaluated from the fp32 state (R, t, X).  A state with a member whose depth
+ *    (X2, or the third coordinate of R X + t) is not > 0 has C = +inf.
+ *  - Unknowns and gauge: dX (three) per member; for the train camera the left perturbation of the PnP refit,
+ *    X_c <- X_c + omega x X_c + upsilon with X_c = R X + t; the query camera is the origin.  The scale is fixed by
+ *    upsilon = B eta, B = [b1 b2] orthogonal to t: with k the index of the smallest |t_k| (ties to the lowest index),
+ *    b1 = (t x e_k) / |t x e_k| and b2 = (t x b1) / |t x b1|.  That leaves 5 pose unknowns delta = (omega, eta).
+ *  - Per member, with J_p(Y) = [fx / Y2, 0, -fx Y0 / Y2^2; 0, fy / Y2, -fy Y1 / Y2^2] and the residuals r_q = pi_q(X) - p,
+ *    r_t = pi_t(X_c) - q:
+ *        J_q = J_p(X) (query camera),   J_t = J_p(X_c) R,   J_c = [-J_p(X_c) [X_c]x , J_p(X_c) B]   (2 x 5),
+ *        U = J_q^T J_q + J_t^T J_t,     W = J_c^T J_t   (5 x 3),     g_X = J_q^T r_q + J_t^T r_t.
+ *  - Damping (Marquardt): U* = U + lambda diag(U); its inverse is the adjugate over the determinant, and a determinant that
+ *    is not > 0 or not finite (at any member) rejects the attempt.  With A = sum J_c^T J_c and g_c = sum J_c^T r_t:
+ *        S = A + lambda diag(A) - sum W U*^-1 W^T,        b = g_c - sum W U*^-1 g_X:
+ *    15 + 5 + 5 sums (S without its damping, diag A, b), accumulated per thread over a fixed stride and summed in a fixed
+ *    order (no floating-point atomics).
+ *  - Step: S delta = -b by Gaussian elimination with partial pivoting; a pivot not above 1e-14 of the largest diagonal entry
+ *    of S makes it singular and rejects the attempt.  R' = E(omega) R with E as in the PnP refit; t' = E t + B eta;
+ *    s = 1 / |t'| and t' <- s t' (|t'| not > 1e-12 rejects the attempt); dX = -U*^-1 (g_X + W^T delta) and X' = s (X + dX).
+ *    R', t' and X' are rounded to fp32 and C' is evaluated from them.
+ *  - Accept and reject: the step is accepted iff C' < C; then lambda <- max(lambda / 10, 1e-10).  Otherwise the state is kept
+ *    and lambda <- min(10 lambda, 1e6).  Either way it counts as one attempt.  lambda starts at lambda0.  The call ends after
+ *    `iterations` attempts, or after an accepted step with C - C' <= 1e-6 C.
+ *  - Result: front[row] = 1 for the members that, at the final state, have a depth > 0 in both cameras and pass both
+ *    reprojection tests; xyz[row] holds their points; every other row of the frame is zero; nfront is their count.  The rms
+ *    of stats is sqrt(C / (2 m)) over the m members -- the root mean square of the 2 m reprojection distances -- at the start
+ *    and at the final state.  The outputs never have a higher cost than the input state: a frame on which no attempt was
+ *    accepted returns the input pose (t normalised) with its midpoints.  The call writes every row of its frames' front /
+ *    xyz: nothing needs to be cleared beforehand.
+ *  - Failure: a failed input, no pairs, or nfront < min_front: nine zeros, three zeros, nfront = 0, an all-zero front and
+ *    xyz, four zero stats.  A bank slot outside [0, slots) leaves the frame without pairs and fails the same way.
+ *  - Determinism and execution: as for the pose calls.  Bit-identical outputs on repeated calls; the three entry points give
+ *    bit-identical outputs on equal pair lists, and fpc_refine_pose_bank is bit-identical to fpc_refine_pose_frames with that
+ *    slot as key.  Asynchronous on the ctx stream, no host synchronisation, no device-to-host copy, no allocation; the point
+ *    state lives in the caller's xyz.  Nothing is carved; the plan hash and the guard zones are what they were.
+ *    fpc_match_bank, fpc_fundamental_bank, fpc_pose_bank, fpc_refine_pose_bank, fpc_bank_store, fpc_bank_store_landmarks needs
+ *    no host call in between.  It works on a FPC_BANK_BF16 bank: it reads only xy and counts.
+ *  - Not here: more than two views, robust kernels, refining the intrinsics, a cell-ordered variant.
+ * FPC_E_INVALID (nothing is written): everything the pose twins refuse for the arguments they share; a NULL R_in_dev /
+ * t_in_dev / params / R_dev / t_dev / nfront_dev / xyz_dev; fx or fy not > 0 or any non-finite intrinsic; reproj_threshold
+ * not > 0 (or not below 1e18); min_parallax_deg not in [0, 90); iterations outside 1 .. 16; lambda0 not > 0 or not finite;
+ * min_front < 1. */
+typedef struct fpc_refine_params {
+  float q_fx, q_fy, q_cx, q_cy;   /* intrinsics of the query camera (pixels), fx, fy > 0                                  */
+  float t_fx, t_fy, t_cx, t_cy;   /* intrinsics of the train camera                                                       */
+  float reproj_threshold;         /* px, > 0, below 1e18: membership and the final front test                             */
+  float min_parallax_deg;         /* >= 0, < 90: as fpc_landmark_params                                                   */
+  int   iterations;               /* 1 .. 16 attempts                                                                     */
+  float lambda0;                  /* > 0, finite: the first damping                                                       */
+  int   min_front;                /* >= 1; fewer points in front at the final state -> the frame fails                    */
+} fpc_refine_params;
+/* fx = fy = 500, centre (320, 240) on both sides, reproj_threshold 3.0, min_parallax_deg 1.0, iterations 8, lambda0 1e-3,
+ * min_front 8 */
+int fpc_default_refine_params(fpc_refine_params* params);
+int fpc_refine_pose(fpc_ctx* ctx, int n, const float* src_xy_dev, const float* dst_xy_dev, const int32_t* npairs_dev,
+                    int stride, const float* R_in_dev, const float* t_in_dev, const fpc_refine_params* params, float* R_dev,
+                    float* t_dev, int32_t* nfront_dev, float* xyz_dev, uint8_t* front_dev, float* stats_dev);
+int fpc_refine_pose_frames(fpc_ctx* ctx, int n, int pairing, const int32_t* key_xy_dev, const int32_t* nkey_dev,
+                           const int32_t* match_dev, const float* R_in_dev, const float* t_in_dev,
+                           const fpc_refine_params* params, float* R_dev, float* t_dev, int32_t* nfront_dev, float* xyz_dev,
+                           uint8_t* front_dev, float* stats_dev);
+int fpc_refine_pose_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const float* R_in_dev,
+                         const float* t_in_dev, const fpc_refine_params* params, float* R_dev, float* t_dev,
+                         int32_t* nfront_dev, float* xyz_dev, uint8_t* front_dev, float* stats_dev);
 
 /* --- Sim(3) alignment: RANSAC similarity between two frames' landmarks ----------------------------------------------------
  * Every key frame carries landmarks in its own camera frame, at the scale it inherited from the key frame it was localised
