@@ -42,6 +42,7 @@ SYMBOLS = [
     "fpc_default_pose_homography_params", "fpc_pose_homography", "fpc_pose_homography_frames", "fpc_pose_homography_bank",
     "fpc_default_pnp_params", "fpc_pnp_reserve", "fpc_bank_landmarks_reserve", "fpc_bank_store_landmarks",
     "fpc_bank_landmarks_get", "fpc_ransac_pnp", "fpc_pnp_frames", "fpc_pnp_bank",
+    "fpc_ransac_p3p", "fpc_p3p_frames", "fpc_p3p_bank",
     "fpc_match_frames_guided_pose", "fpc_match_bank_guided_pose",
     "fpc_default_landmark_params", "fpc_landmarks_pairs", "fpc_landmarks_frames", "fpc_landmarks_bank",
     "fpc_default_sim3_params", "fpc_ransac_sim3", "fpc_sim3_frames", "fpc_sim3_bank",
@@ -259,6 +260,9 @@ def load():
     l.fpc_ransac_pnp.argtypes = [vp, ci, vp, vp, vp, ci, np_, vp, vp, vp, vp]
     l.fpc_pnp_frames.argtypes = [vp, ci, vp, vp, vp, vp, np_, vp, vp, vp, vp]
     l.fpc_pnp_bank.argtypes = [vp, ci, vp, vp, np_, vp, vp, vp, vp]
+    l.fpc_ransac_p3p.argtypes = l.fpc_ransac_pnp.argtypes
+    l.fpc_p3p_frames.argtypes = l.fpc_pnp_frames.argtypes
+    l.fpc_p3p_bank.argtypes = l.fpc_pnp_bank.argtypes
     l.fpc_match_frames_guided.argtypes = [vp, ci, ci, vp, vp, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float,
                                           vp, vp]
     l.fpc_match_bank_guided.argtypes = [vp, ci, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float, vp, vp]

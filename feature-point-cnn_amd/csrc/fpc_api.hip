@@ -48,6 +48,7 @@
 #include "match_bank_topk.h"
 #include "pnp_ransac.h"
 #include "sim3_ransac.h"
+#include "p3p_ransac.h"
 #include "landmarks.h"
 #include "refine_pose.h"
 #include "homography.h"
@@ -4240,9 +4241,16 @@ int fpc_default_pnp_params(fpc_pnp_params* p) {
   return FPC_OK;
 }
 
-static bool pnp_params_ok(const fpc_pnp_params* p) {
+// the absolute-pose models share fpc_pnp_params; a model's sample size is its floor on min_inliers
+enum PoseModel { POSE_DLT, POSE_P3P };
+static bool pose_fields_ok(const fpc_pnp_params* p, int sample) {
   return p && camera_ok(p->fx, p->fy, p->cx, p->cy) &&
-         ransac_fields_ok(p->iterations, p->reproj_threshold, p->refits, p->min_inliers, PNP_SAMPLE);
+         ransac_fields_ok(p->iterations, p->reproj_threshold, p->refits, p->min_inliers, sample);
+}
+static bool pnp_params_ok(const fpc_pnp_params* p) { return pose_fields_ok(p, PNP_SAMPLE); }
+static bool p3p_params_ok(const fpc_pnp_params* p) { return pose_fields_ok(p, P3P_SAMPLE); }
+static bool pose_params_ok(const fpc_pnp_params* p, PoseModel model) {
+  return model == POSE_P3P ? p3p_params_ok(p) : pnp_params_ok(p);
 }
 
 // The only PnP call that allocates or synchronises: pair records, counts and best keys of max_batch problems, an allocation
@@ -4293,46 +4301,86 @@ static PnpArgs pnp_args(fpc_ctx* c, int n, const fpc_pnp_params* p) {
   return a;
 }
 
-// the solver step behind the pair list
-static int pnp_launch(fpc_ctx* c, const PnpArgs& a, float* R, float* t, int32_t* ninliers, uint8_t* inlier, int mstride) {
-  hipLaunchKernelGGL(pnp_score_kernel, dim3((a.T + PNP_THREADS - 1) / PNP_THREADS, a.n), dim3(PNP_THREADS), 0, c->stream, a);
-  hipLaunchKernelGGL(pnp_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, R, t, ninliers, inlier, mstride);
+// the solver step behind the pair list: the model's score kernel and its refit kernel
+static int pnp_launch(fpc_ctx* c, PoseModel model, const PnpArgs& a, float* R, float* t, int32_t* ninliers, uint8_t* inlier,
+                      int mstride) {
+  if (model == POSE_P3P) {
+    hipLaunchKernelGGL(p3p_score_kernel, dim3((a.T + P3P_THREADS - 1) / P3P_THREADS, a.n), dim3(P3P_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(p3p_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, R, t, ninliers, inlier, mstride);
+  } else {
+    hipLaunchKernelGGL(pnp_score_kernel, dim3((a.T + PNP_THREADS - 1) / PNP_THREADS, a.n), dim3(PNP_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(pnp_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, R, t, ninliers, inlier, mstride);
+  }
   return launched();
 }
 
-// fpc_pnp_frames / fpc_pnp_bank: the gather kernel over either train set, then the solver
-static int pnp_gather(fpc_ctx* c, int n, const PnpTrain& tr, const int32_t* match, const fpc_pnp_params* p, float* R, float* t,
-                      int32_t* ninliers, uint8_t* inlier) {
+// fpc_pnp_frames / fpc_pnp_bank and their P3P twins: the gather kernel over either train set, then the model's solver
+static int pnp_gather(fpc_ctx* c, PoseModel model, int n, const PnpTrain& tr, const int32_t* match, const fpc_pnp_params* p,
+                      float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
   HIPCHECK(hipSetDevice(c->cfg.device));
   const PnpArgs a = pnp_args(c, n, p);
   hipLaunchKernelGGL(pnp_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, match, inlier, tr);
-  return pnp_launch(c, a, R, t, ninliers, inlier, c->cap);
+  return pnp_launch(c, model, a, R, t, ninliers, inlier, c->cap);
 }
 
-int fpc_ransac_pnp(fpc_ctx* c, int n, const float* xy, const float* xyz, const int32_t* npairs, int stride,
-                   const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !c->pnp_slab || !xy || !xyz || !npairs || !R || !t || !ninliers || !pnp_params_ok(p) || !explicit_ok(c, n, stride))
+// The three pair sources, each written once for both models: the checks, the pair list, the solver.
+static int pose_explicit(fpc_ctx* c, PoseModel model, int n, const float* xy, const float* xyz, const int32_t* npairs, int stride,
+                         const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->pnp_slab || !xy || !xyz || !npairs || !R || !t || !ninliers || !pose_params_ok(p, model) ||
+      !explicit_ok(c, n, stride))
     return FPC_E_INVALID;
   HIPCHECK(hipSetDevice(c->cfg.device));
   const PnpArgs a = pnp_args(c, n, p);
   hipLaunchKernelGGL(pnp_pack_kernel, dim3((stride + 255) / 256, n), dim3(256), 0, c->stream, a, xy, xyz, npairs, stride, inlier);
-  return pnp_launch(c, a, R, t, ninliers, inlier, stride);
+  return pnp_launch(c, model, a, R, t, ninliers, inlier, stride);
+}
+
+static int pose_frames(fpc_ctx* c, PoseModel model, int n, const float* key_xyz, const uint8_t* key_valid, const int32_t* nkey,
+                       const int32_t* match, const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->pnp_slab || !key_xyz || !nkey || !match || !R || !t || !ninliers || !pose_params_ok(p, model) || !frames_ok(c, n))
+    return FPC_E_INVALID;
+  return pnp_gather(c, model, n, PnpTrain{key_xyz, key_valid, nkey, nullptr, nullptr, nullptr, 0, 0}, match, p, R, t, ninliers,
+                    inlier);
+}
+
+static int pose_bank(fpc_ctx* c, PoseModel model, int n, const int32_t* slot, const int32_t* match, const fpc_pnp_params* p,
+                     float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  if (!c || !c->pnp_slab || !R || !t || !ninliers || !pose_params_ok(p, model) || !bank_ok(c, n, slot, match))
+    return FPC_E_INVALID;
+  // (without landmark storage lm is null: no frame has pairs)
+  return pnp_gather(c, model, n, PnpTrain{nullptr, nullptr, nullptr, slot, c->lm_xyzw, c->bank.count, c->bank.rows, c->bank.slots},
+                    match, p, R, t, ninliers, inlier);
+}
+
+int fpc_ransac_pnp(fpc_ctx* c, int n, const float* xy, const float* xyz, const int32_t* npairs, int stride,
+                   const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  return pose_explicit(c, POSE_DLT, n, xy, xyz, npairs, stride, p, R, t, ninliers, inlier);
 }
 
 int fpc_pnp_frames(fpc_ctx* c, int n, const float* key_xyz, const uint8_t* key_valid, const int32_t* nkey, const int32_t* match,
                    const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !c->pnp_slab || !key_xyz || !nkey || !match || !R || !t || !ninliers || !pnp_params_ok(p) || !frames_ok(c, n))
-    return FPC_E_INVALID;
-  return pnp_gather(c, n, PnpTrain{key_xyz, key_valid, nkey, nullptr, nullptr, nullptr, 0, 0}, match, p, R, t, ninliers, inlier);
+  return pose_frames(c, POSE_DLT, n, key_xyz, key_valid, nkey, match, p, R, t, ninliers, inlier);
 }
 
 int fpc_pnp_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const fpc_pnp_params* p, float* R, float* t,
                  int32_t* ninliers, uint8_t* inlier) {
-  if (!c || !c->pnp_slab || !R || !t || !ninliers || !pnp_params_ok(p) || !bank_ok(c, n, slot, match))
-    return FPC_E_INVALID;
-  // (without landmark storage lm is null: no frame has pairs)
-  return pnp_gather(c, n, PnpTrain{nullptr, nullptr, nullptr, slot, c->lm_xyzw, c->bank.count, c->bank.rows, c->bank.slots},
-                    match, p, R, t, ninliers, inlier);
+  return pose_bank(c, POSE_DLT, n, slot, match, p, R, t, ninliers, inlier);
+}
+
+// ---- absolute pose from a minimal sample: P3P + 1 (include/fpc.h; kernels in p3p_ransac.h) -----------------------------------
+int fpc_ransac_p3p(fpc_ctx* c, int n, const float* xy, const float* xyz, const int32_t* npairs, int stride,
+                   const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  return pose_explicit(c, POSE_P3P, n, xy, xyz, npairs, stride, p, R, t, ninliers, inlier);
+}
+
+int fpc_p3p_frames(fpc_ctx* c, int n, const float* key_xyz, const uint8_t* key_valid, const int32_t* nkey, const int32_t* match,
+                   const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+  return pose_frames(c, POSE_P3P, n, key_xyz, key_valid, nkey, match, p, R, t, ninliers, inlier);
+}
+
+int fpc_p3p_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const fpc_pnp_params* p, float* R, float* t,
+                 int32_t* ninliers, uint8_t* inlier) {
+  return pose_bank(c, POSE_P3P, n, slot, match, p, R, t, ninliers, inlier);
 }
 
 // ---- Sim(3) alignment between two frames' landmarks (include/fpc.h; kernels in sim3_ransac.h) ----------------------------------

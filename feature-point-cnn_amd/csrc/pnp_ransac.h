@@ -19,7 +19,8 @@
 //                     function and takes its polar step (fm_jacobi at N = 3; refit_head); then `refits` times one pass over
 //                     the pairs (the 21 + 6 sums of J^T J and J^T r, and the count, in fp64 through hf_block_sum) and one
 //                     lane's 6 x 6 solve_lds; through refit_tail it writes R, t, the inlier count and the mask of the pose
-//                     it returns.
+//                     it returns.  Its body is pnp_refit_body<Minimal>, which p3p_ransac.h instantiates with its own derive
+//                     step; this kernel's is PnpDlt.
 //   pnp_landmarks_store_kernel / pnp_landmarks_invalidate_kernel   element-wise, over one slot's rows (or every slot's).
 #pragma once
 #include "ransac_fundamental.h"
@@ -352,23 +353,32 @@ __device__ __forceinline__ bool pnp_inlier(const double (&R)[9], const double (&
   return c > 0.0 && ex * ex + ey * ey < thr2 * c * c;
 }
 
-__global__ __launch_bounds__(256) void pnp_refit_kernel(PnpArgs a, float* __restrict__ Rout, float* __restrict__ tout,
-                                                        int32_t* __restrict__ ninl, uint8_t* mask, int mstride) {
-  __shared__ double red[4 * PNP_NSUM];
-  __shared__ double sys[PNP_ROWS * PNP_COLS];
-  __shared__ double jm[9], jv[9], jw[9];
-  __shared__ double s28[PNP_NSUM];
-  __shared__ double sm[6][7];
-  __shared__ double pw[12], pose[12];
-  __shared__ int solved;
-  const int f = blockIdx.x, tid = threadIdx.x;
-  const int M = hf_clamp(a.np[f], a.cap);
-  const unsigned long long key = a.best[f];
-  const float4* __restrict__ rec = a.rec + (size_t)f * a.cap * 2;
-  const double thr2 = (double)a.thr * (double)a.thr;
-  const double fx = a.fx, fy = a.fy, cx = a.cx, cy = a.cy;
-  double R[9], t[3];
-  bool ok = refit_head(M >= PNP_SAMPLE && key != 0ull, &solved, [&]() {
+// The refit kernels' LDS, at namespace scope with internal linkage so that pnp_refit_body and the derive steps name the
+// arrays directly: a kernel holds those its own code reaches and no others, and the optimiser treats them as it treats a
+// kernel's own (an array handed over by pointer stays whole; tests/test_static_isa.py pins pnp_refit_kernel's size).
+// hf_block_sum's partial sums, the sums for the solving lane, the Gauss-Newton system, the pose (12 fp32 values as doubles:
+// R row-major, then t), the derive step's verdict ...
+static __shared__ double pnp_refit_red[4 * PNP_NSUM];
+static __shared__ double pnp_refit_s28[PNP_NSUM];
+static __shared__ double pnp_refit_sm[6][7];
+static __shared__ double pnp_refit_pose[12];
+static __shared__ int pnp_refit_solved;
+// ... and the DLT derive's own: the 11 x 12 system, the Jacobi's matrices, P
+static __shared__ double pnp_refit_sys[PNP_ROWS * PNP_COLS];
+static __shared__ double pnp_refit_jm[9], pnp_refit_jv[9], pnp_refit_jw[9];
+static __shared__ double pnp_refit_pw[12];
+
+// pnp_refit_body's Minimal of the DLT: the best sample's P by the score kernel's device function, then its polar step
+struct PnpDlt {
+  static constexpr int SAMPLE = PNP_SAMPLE;
+  static __device__ __forceinline__ bool derive(const PnpArgs& a, const float4* __restrict__ rec, int f, unsigned long long key,
+                                                int M) {
+    double* const sys = pnp_refit_sys;
+    double* const jm = pnp_refit_jm;
+    double* const jv = pnp_refit_jv;
+    double* const jw = pnp_refit_jw;
+    double* const pw = pnp_refit_pw;
+    double* const pose = pnp_refit_pose;
     uint32_t idx[PNP_SAMPLE];
     double P[12];
     PnpPair first;
@@ -378,7 +388,28 @@ __global__ __launch_bounds__(256) void pnp_refit_kernel(PnpArgs a, float* __rest
 #pragma unroll
     for (int i = 0; i < 12; ++i) pw[i] = P[i];
     return pnp_polar(pw, jm, jv, jw, pose);
-  });
+  }
+};
+
+// A refit kernel of the absolute-pose models (workgroup of 256, one per problem).
+//   Minimal::SAMPLE          the sample's size: the fewest pairs of a frame and the fewest inliers of a refit
+//   Minimal::derive(a, rec, f, key, M)   one lane: the best sample's pose into pnp_refit_pose; false: the frame fails
+template <class Minimal>
+__device__ __forceinline__ void pnp_refit_body(const PnpArgs& a, float* __restrict__ Rout, float* __restrict__ tout,
+                                               int32_t* __restrict__ ninl, uint8_t* mask, int mstride) {
+  double* const red = pnp_refit_red;
+  double* const s28 = pnp_refit_s28;
+  double (*const sm)[7] = pnp_refit_sm;
+  double* const pose = pnp_refit_pose;
+  int& solved = pnp_refit_solved;
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const int M = hf_clamp(a.np[f], a.cap);
+  const unsigned long long key = a.best[f];
+  const float4* __restrict__ rec = a.rec + (size_t)f * a.cap * 2;
+  const double thr2 = (double)a.thr * (double)a.thr;
+  const double fx = a.fx, fy = a.fy, cx = a.cx, cy = a.cy;
+  double R[9], t[3];
+  bool ok = refit_head(M >= Minimal::SAMPLE && key != 0ull, &solved, [&]() { return Minimal::derive(a, rec, f, key, M); });
   if (ok) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = pose[i];
@@ -408,7 +439,7 @@ __global__ __launch_bounds__(256) void pnp_refit_kernel(PnpArgs a, float* __rest
         }
       }
       hf_block_sum<PNP_NSUM>(s, red);
-      if (s[27] < 6.0) break;
+      if (s[27] < (double)Minimal::SAMPLE) break;
       if (tid == 0) {
 #pragma unroll
         for (int i = 0; i < PNP_NSUM; ++i) s28[i] = s[i];                   // (through LDS: s[dynamic] would be scratch)
@@ -472,6 +503,11 @@ __global__ __launch_bounds__(256) void pnp_refit_kernel(PnpArgs a, float* __rest
   __syncthreads();
   if (tid < 9) Rout[f * 9 + tid] = (float)pose[tid];
   if (tid < 3) tout[f * 3 + tid] = (float)pose[9 + tid];
+}
+
+__global__ __launch_bounds__(256) void pnp_refit_kernel(PnpArgs a, float* __restrict__ Rout, float* __restrict__ tout,
+                                                        int32_t* __restrict__ ninl, uint8_t* mask, int mstride) {
+  pnp_refit_body<PnpDlt>(a, Rout, tout, ninl, mask, mstride);
 }
 
 // ---- landmarks of the key-frame bank ----------------------------------------------------------------------------------

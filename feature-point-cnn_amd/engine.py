@@ -1043,9 +1043,23 @@ class Engine:
         tensors or host arrays) -> device tensors (R float32 [n,3,3] and t float32 [n,3] with X_cam = R X + t, ninliers
         int32 [n], inlier bool [n,stride]); a failed frame is all zeros.  K: the camera as a 3 x 3 matrix or (fx, fy, cx,
         cy).  Parameters: the other fields of fpc_pnp_params.  Needs pnp_reserve().  Does not synchronise."""
+        return self._pose_explicit("fpc_ransac_pnp", xy, xyz, npairs, K, params)
+
+    # the three pair sources of the absolute-pose calls, for either model (`name`: the DLT's call or its P3P twin)
+    def _pose_explicit(self, name, xy, xyz, npairs, K, params):
         p = self._pnp_params(K, params)
         n, pairs = self._explicit_pairs(xy, xyz, npairs, 3, "xy must be [n,stride,2], xyz [n,stride,3] and npairs [n]")
-        return self._solve("fpc_ransac_pnp", n, pairs, p, self._pnp_out(n, pairs[3]))
+        return self._solve(name, n, pairs, p, self._pnp_out(n, pairs[3]))
+
+    def _pose_frames(self, name, n, match, key_xyz, key_valid, K, params):
+        p = self._pnp_params(K, params)
+        kx, kv, kc = self._key_landmarks(key_xyz, key_valid)
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        return self._solve(name, n, (kx, kv, kc, match), p, self._pnp_out(n))
+
+    def _pose_bank(self, name, n, slot, match, K, params):
+        p, pairs = self._bank_pairs(n, slot, match, self._pnp_params, K, params)
+        return self._solve(name, n, pairs, p, self._pnp_out(n))
 
     def ransac_pnp(self, xy, xyz, npairs, K=None, **params):
         """ransac_pnp_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,stride])."""
@@ -1056,10 +1070,7 @@ class Engine:
         match_frames_async's table against the key frame whose rows' 3-D points are key_xyz (float32 [k,3], or a device
         pair (xyz, count)) and key_valid (bool / uint8 [k], None: every row) -> device tensors (R [n,3,3], t [n,3],
         ninliers [n], inlier bool [n,cap] by query row).  Does not synchronise."""
-        p = self._pnp_params(K, params)
-        kx, kv, kc = self._key_landmarks(key_xyz, key_valid)
-        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
-        return self._solve("fpc_pnp_frames", n, (kx, kv, kc, match), p, self._pnp_out(n))
+        return self._pose_frames("fpc_pnp_frames", n, match, key_xyz, key_valid, K, params)
 
     def pnp_frames(self, n, match, key_xyz, key_valid=None, K=None, **params):
         """pnp_frames_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""
@@ -1069,12 +1080,38 @@ class Engine:
         """fpc_pnp_bank: pnp_frames_async with frame f's landmarks taken from bank slot slot[f] (int32 [n], device; normally
         match_bank_async's `best`) and `match` that call's table; a frame with slot -1, or a bank without landmarks, fails
         (zeros).  Does not synchronise."""
-        p, pairs = self._bank_pairs(n, slot, match, self._pnp_params, K, params)
-        return self._solve("fpc_pnp_bank", n, pairs, p, self._pnp_out(n))
+        return self._pose_bank("fpc_pnp_bank", n, slot, match, K, params)
 
     def pnp_bank(self, n, slot, match, K=None, **params):
         """pnp_bank_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""
         return self._host(self.pnp_bank_async(n, slot, match, K, **params))
+
+    # -- absolute pose from a minimal sample: P3P + 1 (fpc_ransac_p3p / _frames / _bank) --------------------------------------
+    # The twins of the six calls above: the same arguments, parameters (min_inliers may go down to 4) and returns, with a
+    # sample of four pairs that coplanar landmarks -- those of a pose_homography_* call -- do not defeat.
+    def ransac_p3p_async(self, xy, xyz, npairs, K=None, **params):
+        """fpc_ransac_p3p: ransac_pnp_async with the minimal-sample model.  Needs pnp_reserve().  Does not synchronise."""
+        return self._pose_explicit("fpc_ransac_p3p", xy, xyz, npairs, K, params)
+
+    def ransac_p3p(self, xy, xyz, npairs, K=None, **params):
+        """ransac_p3p_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,stride])."""
+        return self._host(self.ransac_p3p_async(xy, xyz, npairs, K, **params))
+
+    def p3p_frames_async(self, n, match, key_xyz, key_valid=None, K=None, **params):
+        """fpc_p3p_frames: pnp_frames_async with the minimal-sample model.  Does not synchronise."""
+        return self._pose_frames("fpc_p3p_frames", n, match, key_xyz, key_valid, K, params)
+
+    def p3p_frames(self, n, match, key_xyz, key_valid=None, K=None, **params):
+        """p3p_frames_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""
+        return self._host(self.p3p_frames_async(n, match, key_xyz, key_valid, K, **params))
+
+    def p3p_bank_async(self, n, slot, match, K=None, **params):
+        """fpc_p3p_bank: pnp_bank_async with the minimal-sample model.  Does not synchronise."""
+        return self._pose_bank("fpc_p3p_bank", n, slot, match, K, params)
+
+    def p3p_bank(self, n, slot, match, K=None, **params):
+        """p3p_bank_async, then host arrays (R [n,3,3], t [n,3], ninliers [n], inlier bool [n,cap])."""
+        return self._host(self.p3p_bank_async(n, slot, match, K, **params))
 
     # -- map growth: landmarks for a new key frame from its PnP pose (fpc_landmarks_pairs / _frames / _bank) -----------------
     def _landmark_params(self, K_query, K_train, params):

@@ -1120,7 +1120,9 @@ int fpc_pose_homography_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const
  *  - Failure: a frame with fewer than 6 pairs, with no non-degenerate sample, with a failed rank test, or with fewer than
  *    min_inliers inliers after the last refit gets nine zeros, three zeros, ninliers = 0 and an all-zero mask.
  *  - Caveat: coplanar landmarks leave the DLT at rank < 11.  A slot whose valid landmarks all lie on one plane fails, just
- *    as an exact-homography scene fails the fundamental calls.
+ *    as an exact-homography scene fails the fundamental calls.  For such slots -- the landmarks of a fpc_pose_homography_*
+ *    call are coplanar by construction -- use fpc_ransac_p3p / fpc_p3p_frames / fpc_p3p_bank (next section): the same
+ *    arguments, a minimal sample that a plane does not defeat.
  *  - Determinism, execution: as for the fundamental calls.  The three entry points give bit-identical outputs on equal pair
  *    lists, and fpc_pnp_bank is bit-identical to fpc_pnp_frames with that slot's landmarks at the SAME frame index.
  *    Everything but the two reserve calls is asynchronous on the ctx stream: no host synchronisation, no device-to-host
@@ -1151,6 +1153,72 @@ int fpc_pnp_frames(fpc_ctx* ctx, int n, const float* key_xyz_dev, const uint8_t*
                    const int32_t* match_dev, const fpc_pnp_params* params, float* R_dev, float* t_dev,
                    int32_t* ninliers_dev, uint8_t* inlier_dev);
 int fpc_pnp_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const fpc_pnp_params* params,
+                 float* R_dev, float* t_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
+
+/* --- absolute pose from a minimal sample: P3P + 1, where the landmarks may be coplanar -----------------------------------
+ * A second absolute-pose model beside the 6-point DLT above, for what the DLT cannot solve: landmarks on one plane (the
+ * xyz / front of a fpc_pose_homography_* call are, by construction) and pair lists too short or too contaminated for samples
+ * of six.  A sample is FOUR pairs: three give up to four poses in closed form, the fourth picks one.  fpc_ransac_p3p,
+ * fpc_p3p_frames and fpc_p3p_bank take the argument lists of fpc_ransac_pnp, fpc_pnp_frames and fpc_pnp_bank, and
+ * everything the section above says of workspace (the fpc_pnp_reserve reservation; nothing else is allocated), landmarks,
+ * pairs, the mask's indexing, the convention X_cam = R X + t, the inlier rule of the returned pose, the failure outputs,
+ * determinism and execution (asynchronous on the ctx stream, no host call needed between fpc_match_bank and fpc_p3p_bank)
+ * holds word for word.  Their R, t go into fpc_match_*_guided_pose, fpc_landmarks_* and fpc_sim3_* as the DLT's do.  What
+ * differs, in the order of that section (tests/test_p3p_ransac.py restates it in float64):
+ *  - Sampling: the same mix(), key and budget of 32 draws; the first 4 distinct indices are the sample, in that order (they
+ *    are the first four of the six the DLT would take).  A frame with fewer than 4 pairs fails.
+ *  - Minimal solve, in fp64 without contraction, from the sample's pairs 0, 1, 2 with landmarks X_i and unit bearings
+ *    f_i = (x^, y^, 1) / sqrt((x^^2 + y^^2) + 1), x^ = (x - cx) / fx, y^ = (y - cy) / fy.  Every three-term sum below is
+ *    (first + second) + third.  With a^2 = |X1 - X2|^2, b^2 = |X0 - X2|^2, c^2 = |X0 - X1|^2 (one of them not > 0: a
+ *    coincident pair, degenerate), cos alpha = f1 . f2, cos beta = f0 . f2, cos gamma = f0 . f1, q = (a^2 - c^2) / b^2 and
+ *    r = (a^2 + c^2) / b^2, Grunert's quartic in v = s2 / s0 (s_i the depth of point i along f_i) has the coefficients
+ *        A4 = (q - 1)^2 - 4 (c^2 / b^2) cos^2 alpha
+ *        A3 = 4 [q (1 - q) cos beta - (1 - r) cos alpha cos gamma + 2 (c^2 / b^2) cos^2 alpha cos beta]
+ *        A2 = 2 [q^2 - 1 + 2 q^2 cos^2 beta + 2 ((b^2 - c^2) / b^2) cos^2 alpha - 4 r cos alpha cos beta cos gamma
+ *                + 2 ((b^2 - a^2) / b^2) cos^2 gamma]
+ *        A1 = 4 [-q (1 + q) cos beta + 2 (a^2 / b^2) cos^2 gamma cos beta - (1 - r) cos alpha cos gamma]
+ *        A0 = (1 + q)^2 - 4 (a^2 / b^2) cos^2 gamma.
+ *    The sample is degenerate unless |A4| > 1e-12 max |A_i| (and that maximum is below 1e300).
+ *  - Root finder (Ferrari, no iteration but a fixed number of Newton steps).  b_k = A_k / A4; with v = y - b3 / 4 the quartic
+ *    is y^4 + p y^2 + g y + h, p = b2 - 3 b3^2 / 8, g = b1 - b3 b2 / 2 + b3^3 / 8, h = b0 - b3 b1 / 4 + b3^2 b2 / 16
+ *    - 3 b3^4 / 256.  Its resolvent cubic is m^3 + c2 m^2 + c1 m + c0 with c2 = p, c1 = p^2 / 4 - h, c0 = -g^2 / 8.  With
+ *    P = c1 - c2^2 / 3, Q = 2 c2^3 / 27 - c2 c1 / 3 + c0 and D = Q^2 / 4 + P^3 / 27, its largest real root is m = z - c2 / 3,
+ *    z = cbrt(-Q / 2 + sqrt D) + cbrt(-Q / 2 - sqrt D) where D > 0, else z = 2 rho cos(acos(clamp(-Q / (2 rho^3), -1, 1)) / 3)
+ *    with rho = sqrt(max(-P / 3, 0)) (z = 0 where rho = 0); m then takes TWO Newton steps on the cubic (a step whose result
+ *    is not finite is not taken).  The sample is degenerate unless m > 0.  With s = sqrt(2 m), e = p / 2 + m and
+ *    k = g / (2 s) the quartic factors into y^2 - s y + (e + k) and y^2 + s y + (e - k), with the discriminants
+ *    dA = 2 m - 4 (e + k) and dB = 2 m - 4 (e - k).  The four CANDIDATES, in this order, are
+ *        y0 = (s + sqrt dA) / 2,   y1 = (s - sqrt dA) / 2,   y2 = (-s + sqrt dB) / 2,   y3 = (-s - sqrt dB) / 2;
+ *    a candidate whose discriminant is negative does not exist.  v = y - b3 / 4 takes TWO Newton steps on the monic quartic
+ *    (Horner form; same rule for a non-finite step).  All four are always walked.
+ *  - Candidate -> pose.  v > 0 is required; u = ((q - 1) v^2 - 2 q cos beta v + 1 + q) / (2 (cos gamma - v cos alpha)) must be
+ *    > 0 and finite (a vanishing denominator fails here); w = 1 + v^2 - 2 v cos beta > 0; s0 = sqrt(b^2 / w), s1 = u s0,
+ *    s2 = v s0; C_i = s_i f_i.  The candidate is kept only if ||C0 - C1|^2 - c^2| <= 2e-6 c^2 and ||C1 - C2|^2 - a^2|
+ *    <= 2e-6 a^2 (1e-6 on the lengths; |C0 - C2| = b holds by the choice of s0).  The triad of three points p0, p1, p2 is
+ *    x = (p1 - p0) / |p1 - p0|, z = c / |c| with c = (p1 - p0) x (p2 - p0), y = z x x -- the Sim(3) section's, with its test:
+ *    degenerate unless |c|^2 > 1e-12 |p1 - p0|^2 |p2 - p0|^2 (collinear points).  R = T_C T_X^T from the triads of
+ *    (C0, C1, C2) and (X0, X1, X2), R_ij = x_C,i x_X,j + y_C,i y_X,j + z_C,i z_X,j; t = C0 - R X0.
+ *  - Disambiguation by the sample's fourth pair: with (a, b, c) = R X3 + t the candidate is eligible when c > 0 (the first
+ *    three points have the depths s_i f_i,z > 0 by u, v > 0) and its error e = (fx (a / c) - (x3 - cx))^2
+ *    + (fy (b / c) - (y3 - cy))^2 is finite.  The eligible candidate of smallest e wins; ties go to the lower candidate
+ *    index.  A sample without an eligible candidate, or with a non-finite R or t, is degenerate.
+ *  - Scoring: P = [R | t] takes the place of the DLT's P: K P scaled to max |p| = 1, oriented at the sample's first pair,
+ *    rounded to fp32; the same fp32 count, the same selection (largest count, ties to the lower t).
+ *  - Best sample -> pose: the best sample's R, t are derived once more by the same procedure and rounded to fp32 (a
+ *    non-finite value fails the frame).  There is no polar step: R is a rotation by construction.
+ *  - Refit: the DLT rule's Gauss-Newton step, word for word, except that it stops below 4 inliers, not 6.
+ *  - Failure: as above with 4 in the place of 6 and no rank test.
+ *  - Caveat: three collinear landmarks, or landmarks that coincide, have no unique pose: such samples are degenerate, and
+ *    a slot that holds nothing else fails.  A planar slot is fine.
+ *  - Bit-identity: the three entry points give bit-identical outputs on equal pair lists, and fpc_p3p_bank is bit-identical
+ *    to fpc_p3p_frames with that slot's landmarks at the SAME frame index.
+ * FPC_E_INVALID (nothing is written): everything the PnP twins refuse, except that min_inliers >= 4 is accepted. */
+int fpc_ransac_p3p(fpc_ctx* ctx, int n, const float* xy_dev, const float* xyz_dev, const int32_t* npairs_dev, int stride,
+                   const fpc_pnp_params* params, float* R_dev, float* t_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
+int fpc_p3p_frames(fpc_ctx* ctx, int n, const float* key_xyz_dev, const uint8_t* key_valid_dev, const int32_t* nkey_dev,
+                   const int32_t* match_dev, const fpc_pnp_params* params, float* R_dev, float* t_dev,
+                   int32_t* ninliers_dev, uint8_t* inlier_dev);
+int fpc_p3p_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const fpc_pnp_params* params,
                  float* R_dev, float* t_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
 
 /* --- pose-guided matching: the match once more, under the estimated absolute poses as the gate ----------------------------
