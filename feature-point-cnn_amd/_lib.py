@@ -43,6 +43,7 @@ SYMBOLS = [
     "fpc_default_pnp_params", "fpc_pnp_reserve", "fpc_bank_landmarks_reserve", "fpc_bank_store_landmarks",
     "fpc_bank_landmarks_get", "fpc_ransac_pnp", "fpc_pnp_frames", "fpc_pnp_bank",
     "fpc_ransac_p3p", "fpc_p3p_frames", "fpc_p3p_bank",
+    "fpc_default_essential_params", "fpc_ransac_essential", "fpc_essential_frames", "fpc_essential_bank",
     "fpc_match_frames_guided_pose", "fpc_match_bank_guided_pose",
     "fpc_default_landmark_params", "fpc_landmarks_pairs", "fpc_landmarks_frames", "fpc_landmarks_bank",
     "fpc_default_sim3_params", "fpc_ransac_sim3", "fpc_sim3_frames", "fpc_sim3_bank",
@@ -95,6 +96,13 @@ class FpcRansacParams(ctypes.Structure):
     """fpc_ransac_params (include/fpc.h)."""
     _fields_ = [("iterations", ctypes.c_int), ("reproj_threshold", ctypes.c_float), ("seed", ctypes.c_uint32),
                 ("refits", ctypes.c_int), ("min_inliers", ctypes.c_int)]
+
+
+class FpcEssentialParams(ctypes.Structure):
+    """fpc_essential_params (include/fpc.h): the fields of fpc_ransac_params, then the two cameras."""
+    _fields_ = FpcRansacParams._fields_ + [
+        ("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
+        ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float)]
 
 
 class FpcPoseParams(ctypes.Structure):
@@ -263,6 +271,12 @@ def load():
     l.fpc_ransac_p3p.argtypes = l.fpc_ransac_pnp.argtypes
     l.fpc_p3p_frames.argtypes = l.fpc_pnp_frames.argtypes
     l.fpc_p3p_bank.argtypes = l.fpc_pnp_bank.argtypes
+    ep = ctypes.POINTER(FpcEssentialParams)
+    l.fpc_default_essential_params.argtypes = [ep]
+    # the fundamental twins' arguments with fpc_essential_params and E_dev behind F_dev
+    l.fpc_ransac_essential.argtypes = [vp, ci, vp, vp, vp, ci, ep, vp, vp, vp, vp]
+    l.fpc_essential_frames.argtypes = [vp, ci, ci, vp, vp, vp, ep, vp, vp, vp, vp]
+    l.fpc_essential_bank.argtypes = [vp, ci, vp, vp, ep, vp, vp, vp, vp]
     l.fpc_match_frames_guided.argtypes = [vp, ci, ci, vp, vp, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float,
                                           vp, vp]
     l.fpc_match_bank_guided.argtypes = [vp, ci, vp, vp, ctypes.c_float, ci, ctypes.c_float, ctypes.c_float, vp, vp]

@@ -49,6 +49,7 @@
 #include "pnp_ransac.h"
 #include "sim3_ransac.h"
 #include "p3p_ransac.h"
+#include "essential_ransac.h"
 #include "landmarks.h"
 #include "refine_pose.h"
 #include "homography.h"
@@ -4159,6 +4160,65 @@ int fpc_pose_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, 
   const HfArgs a = hf_args(c, n, p->reproj_threshold);
   if (int rc = pairs_bank(c, a, n, slot, match, nullptr)) return rc;
   return pose_launch(c, a, p, F, R, t, nfront, xyz, front, c->cap);
+}
+
+// ---- relative pose from minimal samples: the 5-point essential matrix + 1 (include/fpc.h; kernels in essential_ransac.h) -----
+// The fundamental calls' pack / gather kernels, pair records and workspace; the parameters are theirs and the pose calls'
+// cameras, checked once for the three entry points.
+int fpc_default_essential_params(fpc_essential_params* p) {
+  if (!p) return FPC_E_INVALID;
+  p->iterations = 1024;
+  p->reproj_threshold = 3.0f;
+  p->seed = 0;
+  p->refits = 2;
+  p->min_inliers = 8;
+  p->q_fx = p->q_fy = p->t_fx = p->t_fy = 500.0f;
+  p->q_cx = p->t_cx = 320.0f;
+  p->q_cy = p->t_cy = 240.0f;
+  return FPC_OK;
+}
+
+// the three calls' own checks (the pair source's follow in its helper), and their arguments on the pair-list workspace
+static bool essential_ok(const fpc_ctx* c, const fpc_essential_params* p, const float* F, const int32_t* ninliers) {
+  return c && F && ninliers && p && ransac_fields_ok(p->iterations, p->reproj_threshold, p->refits, p->min_inliers, ES_SAMPLE) &&
+         camera_ok(p->q_fx, p->q_fy, p->q_cx, p->q_cy) && camera_ok(p->t_fx, p->t_fy, p->t_cx, p->t_cy);
+}
+static EsArgs essential_args(const fpc_ctx* c, int n, const fpc_essential_params* p) {
+  EsArgs a{};
+  static_cast<HfArgs&>(a) = hf_args(c, n, p->reproj_threshold);
+  a.T = p->iterations; a.refits = p->refits; a.min_inliers = p->min_inliers; a.seed = p->seed;
+  a.q_fx = p->q_fx; a.q_fy = p->q_fy; a.q_cx = p->q_cx; a.q_cy = p->q_cy;
+  a.t_fx = p->t_fx; a.t_fy = p->t_fy; a.t_cx = p->t_cx; a.t_cy = p->t_cy;
+  return a;
+}
+static int essential_launch(fpc_ctx* c, const EsArgs& a, float* F, float* E, int32_t* ninliers, uint8_t* inlier, int mstride) {
+  hipLaunchKernelGGL(essential_score_kernel, dim3((a.T + ES_THREADS - 1) / ES_THREADS, a.n), dim3(ES_THREADS), 0, c->stream, a);
+  hipLaunchKernelGGL(essential_refit_kernel, dim3(a.n), dim3(256), 0, c->stream, a, F, E, ninliers, inlier, mstride);
+  return launched();
+}
+
+int fpc_ransac_essential(fpc_ctx* c, int n, const float* src_xy, const float* dst_xy, const int32_t* npairs, int stride,
+                         const fpc_essential_params* p, float* F, float* E, int32_t* ninliers, uint8_t* inlier) {
+  if (!essential_ok(c, p, F, ninliers)) return FPC_E_INVALID;
+  const EsArgs a = essential_args(c, n, p);
+  if (int rc = pairs_explicit(c, a, src_xy, dst_xy, npairs, stride, inlier)) return rc;
+  return essential_launch(c, a, F, E, ninliers, inlier, stride);
+}
+
+int fpc_essential_frames(fpc_ctx* c, int n, int pairing, const int32_t* key_xy, const int32_t* nkey, const int32_t* match,
+                         const fpc_essential_params* p, float* F, float* E, int32_t* ninliers, uint8_t* inlier) {
+  if (!essential_ok(c, p, F, ninliers)) return FPC_E_INVALID;
+  const EsArgs a = essential_args(c, n, p);
+  if (int rc = pairs_frames(c, a, pairing, key_xy, nkey, match, inlier)) return rc;
+  return essential_launch(c, a, F, E, ninliers, inlier, c->cap);
+}
+
+int fpc_essential_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* match, const fpc_essential_params* p, float* F,
+                       float* E, int32_t* ninliers, uint8_t* inlier) {
+  if (!essential_ok(c, p, F, ninliers)) return FPC_E_INVALID;
+  const EsArgs a = essential_args(c, n, p);
+  if (int rc = pairs_bank(c, a, n, slot, match, inlier)) return rc;
+  return essential_launch(c, a, F, E, ninliers, inlier, c->cap);
 }
 
 // ---- relative pose from a homography (include/fpc.h; kernel in pose_homography.h) ------------------------------------------

@@ -763,6 +763,52 @@ class Engine:
         """fundamental_bank_async, then host arrays (F [n,3,3], ninliers [n], inlier bool [n,cap])."""
         return self._host(self.fundamental_bank_async(n, slot, match, **params))
 
+    # -- minimal-sample relative pose: RANSAC essential matrices, 5 + 1 pairs (fpc_ransac_essential / _frames / _bank) ------
+    def _essential_params(self, K_query, K_train, params):
+        return self._two_camera_params(_lib.FpcEssentialParams, "fpc_default_essential_params", self._RANSAC_FIELDS,
+                                       "essential", K_query, K_train, params)
+
+    def _essential_out(self, n, stride=None):
+        """Empty outputs (F float32 [n,3,3], E float32 [n,3,3], ninliers int32 [n], mask uint8 [n,stride or cap])."""
+        f, ninl, mask = self._ransac_out(n, stride=stride)
+        return f, torch.empty_like(f), ninl, mask
+
+    def ransac_essential_async(self, src, dst, npairs, K_query=None, K_train=None, **params):
+        """fpc_ransac_essential: ransac_fundamental_async's pairs and the two cameras (3 x 3 matrices or (fx, fy, cx, cy))
+        -> device tensors (F float32 [n,3,3] in ransac_fundamental_async's form, which pose_*, refine_pose_* and the
+        epipolar guided matchers take as it is; E float32 [n,3,3], the same matrix in normalised coordinates, norm 1;
+        ninliers int32 [n]; inlier bool [n,stride]).  A sample is 5 + 1 pairs, so planar scenes are solved and far fewer
+        iterations are needed than by the 8-point; an exactly planar scene has two valid answers, one is returned.  A failed
+        frame is all zeros.  min_inliers must be >= 6.  Does not synchronise."""
+        p = self._essential_params(K_query, K_train, params)
+        n, pairs = self._explicit_pairs(src, dst, npairs)
+        return self._solve("fpc_ransac_essential", n, pairs, p, self._essential_out(n, stride=pairs[3]))
+
+    def ransac_essential(self, src, dst, npairs, K_query=None, K_train=None, **params):
+        """ransac_essential_async, then host arrays (F [n,3,3], E [n,3,3], ninliers [n], inlier bool [n,stride])."""
+        return self._host(self.ransac_essential_async(src, dst, npairs, K_query, K_train, **params))
+
+    def essential_frames_async(self, n, match, key_xy=None, pairing="key", K_query=None, K_train=None, **params):
+        """fpc_essential_frames: fundamental_frames_async's arguments and pairs -> device tensors (F [n,3,3], E [n,3,3],
+        ninliers [n], inlier bool [n,cap] by query row).  Does not synchronise."""
+        p, pairs = self._frames_pairs(n, pairing, key_xy, match, self._essential_params, K_query, K_train, params)
+        return self._solve("fpc_essential_frames", n, pairs, p, self._essential_out(n))
+
+    def essential_frames(self, n, match, key_xy=None, pairing="key", K_query=None, K_train=None, **params):
+        """essential_frames_async, then host arrays (F [n,3,3], E [n,3,3], ninliers [n], inlier bool [n,cap])."""
+        return self._host(self.essential_frames_async(n, match, key_xy, pairing, K_query, K_train, **params))
+
+    def essential_bank_async(self, n, slot, match, K_query=None, K_train=None, **params):
+        """fpc_essential_bank: essential_frames_async with frame f's key coordinates taken from bank slot slot[f], as
+        fundamental_bank_async -> device tensors (F [n,3,3], E [n,3,3], ninliers [n], inlier bool [n,cap]); a frame with
+        slot -1 fails (zeros).  Does not synchronise."""
+        p, pairs = self._bank_pairs(n, slot, match, self._essential_params, K_query, K_train, params)
+        return self._solve("fpc_essential_bank", n, pairs, p, self._essential_out(n))
+
+    def essential_bank(self, n, slot, match, K_query=None, K_train=None, **params):
+        """essential_bank_async, then host arrays (F [n,3,3], E [n,3,3], ninliers [n], inlier bool [n,cap])."""
+        return self._host(self.essential_bank_async(n, slot, match, K_query, K_train, **params))
+
     # -- relative pose from the fundamental matrices: R, t and triangulated points (fpc_pose_fundamental / _frames / _bank) ---
     @staticmethod
     def _intrinsics(k, name):

@@ -1221,6 +1221,112 @@ int fpc_p3p_frames(fpc_ctx* ctx, int n, const float* key_xyz_dev, const uint8_t*
 int fpc_p3p_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const fpc_pnp_params* params,
                  float* R_dev, float* t_dev, int32_t* ninliers_dev, uint8_t* inlier_dev);
 
+/* --- relative pose from a minimal sample: the 5-point essential matrix + 1 -----------------------------------------------
+ * The calibrated twin of the fundamental calls.  fpc_ransac_fundamental samples eight pairs and solves a linear system that
+ * knows nothing of the cameras: on pairs that follow a homography it is degenerate (its caveat above), and its samples of
+ * eight ask for 0.4^8 = 6.6e-4 all-inlier draws at 60 % outliers.  Whoever calls fpc_pose_* holds both cameras' intrinsics;
+ * with them the relative pose has five degrees of freedom, five pairs determine it (0.4^5 = 1.0e-2; 4.1e-3 with the sixth
+ * pair counted), and the five-point problem is NOT degenerate on a plane.  fpc_ransac_essential, fpc_essential_frames and
+ * fpc_essential_bank mirror fpc_ransac_fundamental, fpc_fundamental_frames and fpc_fundamental_bank argument for argument
+ * -- the same pair definition, mask indexing, strides, pairing, slot rules, workspace (the ctx's pair lists: nothing is
+ * allocated), execution rules and determinism -- with fpc_essential_params (the fields of fpc_ransac_params, then the two
+ * cameras as in fpc_pose_params) and one more output.  tests/test_essential_ransac.py restates the rule in float64.
+ *  - Outputs: F_dev float32 [n][9] IN THE FUNDAMENTAL CALLS' FORM: (u, v, 1) F (x, y, 1)^T = 0 in pixels, Frobenius norm 1,
+ *    the element of largest magnitude (of the fp32 values; ties: the lowest index) positive; F = K_t^-T E K_q^-1.  It goes
+ *    into fpc_pose_*, fpc_refine_pose_* and the epipolar guided matchers unchanged.  E_dev float32 [n][9], may be NULL: the
+ *    same matrix in normalised coordinates, K_t^T F K_q formed in fp64 from the returned fp32 F, norm 1, rounded to fp32,
+ *    the same sign rule (so E_dev may be -K_t^T F K_q).  ninliers and inlier are those of the returned fp32 F under the
+ *    fundamental section's Sampson test in pixels, in fp64: a later fpc_pose_* call with the same threshold uses exactly
+ *    the pairs of this mask.
+ *  - Failure: a frame with fewer than 6 pairs, with no non-degenerate sample, or with fewer than min_inliers inliers after
+ *    the last refit gets zeros in F_dev and E_dev, ninliers = 0 and an all-zero mask.
+ *  - Sampling: the fundamental section's draws (mix(), the key (f * 4096 + t) * 32 + k, 32 draws); the first 6 distinct
+ *    indices are the sample, in that order (the first six of the eight the 8-point would take).  Pairs 0 .. 4 are solved,
+ *    pair 5 picks the root.
+ *  - Minimal solve, in fp64 without contraction (a * b + c is two roundings everywhere).  Bearings p^ = ((x - q_cx) / q_fx,
+ *    (y - q_cy) / q_fy, 1), q^ = ((u - t_cx) / t_fx, (v - t_cy) / t_fy, 1).  The 5 x 9 system of the rows q^ (x) p^ =
+ *    [ux uy u vx vy v x y 1] is reduced by the 8-point's elimination with FULL pivoting (the same pivot order and tie rule;
+ *    a last pivot below 1e-10 of the first: degenerate).  Its free unknowns are those of the columns 5 .. 8 after the
+ *    pivoting; setting one of them to 1 and the other three to 0, in that order, and back-substituting (y_i = -(sum_{j > i}
+ *    a_ij y_j + a_i,free) / a_ii, the sum in ascending j from 0.0) gives the null vectors X, Y, Z, W, and E = x X + y Y +
+ *    z Z + W.
+ *  - The ten cubic constraints: det E = 0 and the nine entries, row-major, of (E E^T - tr(E E^T) / 2 I) E = 0, as a 10 x 20
+ *    matrix (row 0: det E) over the monomials
+ *        x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1.
+ *    Every entry of E is a linear polynomial with the coefficients (X, Y, Z, W) over (x, y, z, 1); a product accumulates
+ *    into its result from 0.0, one rounded product at a time: linear x linear in the order i, j of the factors'
+ *    coefficients, quadratic x linear in the order of the quadratic's monomials (xx xy xz x yy yz y zz z 1), then the
+ *    linear factor's; a difference subtracts its second product term by term into the first.  det E = (E11 E22 - E12 E21)
+ *    E00 - (E10 E22 - E12 E20) E01 + (E10 E21 - E11 E20) E02, accumulated in that order; (E E^T)_ij = E_i0 E_j0 + E_i1 E_j1
+ *    + E_i2 E_j2; tr = ((E E^T)_00 + (E E^T)_11) + (E E^T)_22; row (i, j) = L_i0 E_0j + L_i1 E_1j + L_i2 E_2j with
+ *    L = E E^T - tr / 2 I.
+ *  - Gauss-Jordan on the left 10 x 10 block with row pivoting: the pivot of column c is the entry of largest magnitude at
+ *    or below the diagonal (ties: the lowest row); a pivot not above 1e-12 of the first column's makes the sample
+ *    degenerate; the pivot row is divided by the pivot, then a_ic times it is subtracted from every other row i.
+ *  - With R the right block, the rows <x^2z> - z <x^2>, <y^2z> - z <y^2>, <xyz> - z <xy> (rows 4 - z 5, 6 - z 7, 8 - z 9)
+ *    give B(z) (x, y, 1)^T = 0 with, for the row pair (a, b) and ascending powers of z,
+ *        B_x = [Ra2, Ra1 - Rb2, Ra0 - Rb1, -Rb0],  B_y = [Ra5, Ra4 - Rb5, Ra3 - Rb4, -Rb3],
+ *        B_1 = [Ra9, Ra8 - Rb9, Ra7 - Rb8, Ra6 - Rb7, -Rb6].
+ *    p(z) = det B = B00 (B11 B22 - B12 B21) - B01 (B10 B22 - B12 B20) + B02 (B10 B21 - B11 B20), of degree 10, its products
+ *    accumulated as above in the order i, j of the factors' coefficients.
+ *  - Real roots, by derivative interlacing with fixed trips.  bound is the first power of two B = 1, 2, 4, .. with
+ *    c(B) = |p_10| B^10 - sum_(i < 10) |p_i| B^i > 0 (Cauchy's polynomial by Horner's rule; 64 trips of "B <- 2 B unless
+ *    c(B) > 0", then c(B) > 0 or the sample is degenerate): every root lies inside, and it is within a factor 2 of the
+ *    best bound of its kind (1 + max |p_i / p_10| is up to 1e14 times wider here).  For d = 1 .. 10, P_d = p^(10 - d) has the coefficients p_(i + 10 - d)
+ *    (i + 10 - d)! / i! and the d + 1 break points -bound, the d - 1 values level d - 1 handed on, bound.  Each of its d
+ *    intervals [lo, hi], in ascending order, is walked: `change` is (P_d(lo) > 0) != (P_d(hi) > 0); 40 bisections (mid =
+ *    (lo + hi) / 2 replaces the end whose sign (P_d > 0) it shares, lo's on a tie of signs); r = (lo + hi) / 2 then takes 3
+ *    Newton steps r - P_d(r) / P_d'(r), each kept only where it lies in [lo, hi]; all polynomials by Horner's rule from
+ *    the leading coefficient.  The interval hands on r where `change` holds, else its upper end (not a root).  The roots of
+ *    p are the values with `change` of level 10, in ascending order.
+ *  - Every root z: (x, y, 1) is the null vector of B(z), n = B_row0(z) x B_row1(z), x = n0 / n2, y = n1 / n2 (a non-finite
+ *    x or y: no candidate); E = ((x X + y Y) + z Z) + W; F = K_t^-T E K_q^-1.  Choice: the candidate with the smallest
+ *    e^2 / g of the sample's sixth pair (e, g the Sampson terms of the fundamental section, in pixels through F, in fp64);
+ *    ties go to the lower root.  A sample without a candidate is degenerate, scores 0 and is never chosen.
+ *  - Scoring and selection: the candidate's F is scaled to max |f| = 1 and rounded to fp32; the fundamental model's fp32
+ *    count and selection (largest count, ties to the lower t).
+ *  - The best sample's F, derived once more by the same procedure, brought to norm 1, rounded to fp32 and given the sign.
+ *  - Refit, `refits` times, on the essential manifold (the linear 8-point refit would leave it, and has rank 6 on a plane).
+ *    The current fp32 F is split by the pose section's decomposition, candidate 0: (R, t^), E = [t^]x R (the twisted pair
+ *    gives -E: no cheirality test is needed).  One Gauss-Newton step over the current inliers' Sampson residuals
+ *    r = e / sqrt(g) in pixels (e, g through K_t^-T [t^]x R K_q^-1) in the 5 unknowns (omega, eta): R' = Q R with Q the
+ *    rotation of the unit quaternion (1, omega / 2) / |(1, omega / 2)| (no trigonometric function is evaluated),
+ *    t' = (Q t^ + B eta) / |Q t^ + B eta| with B the refine section's tangent basis of t^.  The Jacobian holds g FIXED:
+ *    with a = R p^, dr/d omega = ((t^ x a) x q^) / sqrt(g), dr/d eta_k = (b_k . (a x q^)) / sqrt(g).  The 15 + 5 sums of
+ *    J^T J and J^T r are accumulated in fp64 in a fixed order (no floating-point atomics); (J^T J) delta = -J^T r is solved
+ *    by elimination with partial pivoting, a pivot not above 1e-14 of the largest diagonal entry failing.  F' = K_t^-T
+ *    [t']x R' K_q^-1, norm 1, fp32, sign.  The step is ACCEPTED only if F' has at least as many inliers as F; otherwise,
+ *    and with fewer than 6 inliers, a failed decomposition, a singular system, |Q t^ + B eta| <= 1e-12 or a non-finite
+ *    result, the previous F stays and the refits end.
+ *  - Determinism: as for the fundamental calls; the three entry points give bit-identical outputs on equal pair lists, and
+ *    fpc_essential_bank is bit-identical to fpc_essential_frames with that slot as key at the SAME frame index.
+ *  - Caveats: a pair list that lies EXACTLY on a plane is explained by two essential matrices (the twofold ambiguity
+ *    fpc_pose_homography_* reports as two solutions); no sixth coplanar pair and no count of inliers tells them apart.  The
+ *    call returns ONE of them and either is correct output.  Under a pure rotation every [t]x R fits: the call succeeds and t
+ *    is meaningless; min_baseline of the homography pose calls is the test for that.
+ * FPC_E_INVALID (nothing is written): everything the fundamental twin refuses for the shared fields and fpc_pose_* for the
+ * cameras (a focal length not > 0, a non-finite intrinsic), and min_inliers < 6. */
+typedef struct fpc_essential_params {
+  int      iterations;        /* T hypotheses per frame, 1 .. 4096                                   */
+  float    reproj_threshold;  /* pixels (Sampson), > 0                                               */
+  uint32_t seed;              /* same seed + same inputs -> bit-identical outputs                    */
+  int      refits;            /* 0 .. 4 guarded Gauss-Newton steps after the best sample             */
+  int      min_inliers;       /* >= 6; fewer inliers after the last refit -> the frame fails         */
+  float    q_fx, q_fy, q_cx, q_cy;   /* the query / src camera                                       */
+  float    t_fx, t_fy, t_cx, t_cy;   /* the train / dst camera                                       */
+} fpc_essential_params;
+/* 1024 iterations, 3.0 px, seed 0, 2 refits, 8 inliers; both cameras (500, 500, 320, 240). */
+int fpc_default_essential_params(fpc_essential_params* params);
+int fpc_ransac_essential(fpc_ctx* ctx, int n, const float* src_xy_dev, const float* dst_xy_dev, const int32_t* npairs_dev,
+                         int stride, const fpc_essential_params* params, float* F_dev, float* E_dev, int32_t* ninliers_dev,
+                         uint8_t* inlier_dev);
+int fpc_essential_frames(fpc_ctx* ctx, int n, int pairing, const int32_t* key_xy_dev, const int32_t* nkey_dev,
+                         const int32_t* match_dev, const fpc_essential_params* params, float* F_dev, float* E_dev,
+                         int32_t* ninliers_dev, uint8_t* inlier_dev);
+int fpc_essential_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev,
+                       const fpc_essential_params* params, float* F_dev, float* E_dev, int32_t* ninliers_dev,
+                       uint8_t* inlier_dev);
+
 /* --- pose-guided matching: the match once more, under the estimated absolute poses as the gate ----------------------------
  * The third model's second pass, "search by projection": with one (R, t) per frame -- what fpc_pnp_frames / fpc_pnp_bank
  * wrote, passed on unchanged, or the previous frame's pose as a motion prior -- the train set's landmarks are projected into
