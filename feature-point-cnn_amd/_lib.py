@@ -48,6 +48,8 @@ SYMBOLS = [
     "fpc_default_landmark_params", "fpc_landmarks_pairs", "fpc_landmarks_frames", "fpc_landmarks_bank",
     "fpc_default_sim3_params", "fpc_ransac_sim3", "fpc_sim3_frames", "fpc_sim3_bank",
     "fpc_default_refine_params", "fpc_refine_pose", "fpc_refine_pose_frames", "fpc_refine_pose_bank",
+    "fpc_pnp_topk_reserve", "fpc_pnp_bank_topk", "fpc_p3p_bank_topk", "fpc_fundamental_bank_topk",
+    "fpc_essential_bank_topk",
 ]
 
 ABI_VERSION = 4
@@ -312,6 +314,12 @@ def load():
     l.fpc_bank_topk_reserve.argtypes =[vp, ci, ctypes.POINTER(ctypes.c_size_t)]
     l.fpc_match_bank_topk.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp, vp]
     l.fpc_homography_bank_topk.argtypes = [vp, ci, ci, vp, vp, rp, vp, vp, vp, vp, vp]
+    # the homography call's arguments with the model's parameters and outputs, and the picked model(s) behind best_dev
+    l.fpc_pnp_topk_reserve.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
+    l.fpc_pnp_bank_topk.argtypes = [vp, ci, ci, vp, vp, np_] + [vp] * 8
+    l.fpc_p3p_bank_topk.argtypes = l.fpc_pnp_bank_topk.argtypes
+    l.fpc_fundamental_bank_topk.argtypes = [vp, ci, ci, vp, vp, rp] + [vp] * 6
+    l.fpc_essential_bank_topk.argtypes = [vp, ci, ci, vp, vp, ep] + [vp] * 7
     l.fpc_sample_descriptors.argtypes = [vp, vp, vp, ci, vp]
     l.fpc_read_activation.argtypes = [vp, ctypes.c_char_p, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
     l.fpc_plan_hash.argtypes = [vp]

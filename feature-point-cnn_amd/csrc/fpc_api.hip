@@ -518,7 +518,7 @@ struct Timing {
 };
 
 // One device allocation of a context: carved by a Carver, zeroed, its canary zones (offset, bytes) filled where the
-// context has them.  A context owns five (fpc_ctx::slabs).
+// context has them.  A context owns six (fpc_ctx::slabs).
 using GuardZones = std::vector<std::pair<size_t, size_t>>;
 struct Carver;
 struct Slab {
@@ -576,10 +576,11 @@ struct fpc_ctx {
   bool weights_loaded = false;
   bool plan_error = false;           // a layer asked for a kernel instance that does not exist (fpc_create -> FPC_E_INVALID)
 
-  // The five device allocations a context can own: `slab` for all activations / results (build_plan), the others made
-  // by the call that reserves them.  bank_slab, topk_slab and lm_slab go with the bank; fpc_destroy frees what is left.
-  Slab slab, bank_slab, topk_slab, pnp_slab, lm_slab;
-  Slab* const slabs[5] = {&slab, &bank_slab, &topk_slab, &pnp_slab, &lm_slab};
+  // The six device allocations a context can own: `slab` for all activations / results (build_plan), the others made
+  // by the call that reserves them.  bank_slab, topk_slab, pnp_topk_slab and lm_slab go with the bank; fpc_destroy frees
+  // what is left.
+  Slab slab, bank_slab, topk_slab, pnp_slab, lm_slab, pnp_topk_slab;
+  Slab* const slabs[6] = {&slab, &bank_slab, &topk_slab, &pnp_slab, &lm_slab, &pnp_topk_slab};
   float *stem_out, *x0, *h4, *x1, *x2, *h8, *x3, *cat, *dh, *dproj, *d0, *lg;
   float *h16, *y16a, *y16b, *lo_h, *lo0, *desc_map, *desc_in_nhwc;
   float* prob;
@@ -621,6 +622,11 @@ struct fpc_ctx {
   float4* pnp_rec = nullptr;
   int32_t* pnp_np = nullptr;
   unsigned long long* pnp_best = nullptr;
+  // absolute pose per top-K candidate (fpc_pnp_topk_reserve): the same three buffers for max_batch x kmax problems, an
+  // allocation of its own, made by that call and freed with the bank
+  float4* pnp_topk_rec = nullptr;
+  int32_t* pnp_topk_np = nullptr;
+  unsigned long long* pnp_topk_best = nullptr;
   // landmarks of the bank's rows (fpc_bank_landmarks_reserve): float4 [slots][rows], w = 1 valid / 0; freed with the bank
   float4* lm_xyzw = nullptr;
   int pts_n = 0;                     // frames of the last call that produced keypoints (fpc_detect*, fpc_get_points)
@@ -3957,6 +3963,8 @@ int fpc_bank_destroy(fpc_ctx* c) {
   HIPCHECK(c->bank_slab.release());
   HIPCHECK(c->topk_slab.release());
   c->topk = BankTopkArgs{};
+  HIPCHECK(c->pnp_topk_slab.release());
+  c->pnp_topk_rec = nullptr; c->pnp_topk_np = nullptr; c->pnp_topk_best = nullptr;
   HIPCHECK(c->lm_slab.release());
   c->lm_xyzw = nullptr;
   c->bank = BankArgs{};
@@ -4183,9 +4191,9 @@ static bool essential_ok(const fpc_ctx* c, const fpc_essential_params* p, const 
   return c && F && ninliers && p && ransac_fields_ok(p->iterations, p->reproj_threshold, p->refits, p->min_inliers, ES_SAMPLE) &&
          camera_ok(p->q_fx, p->q_fy, p->q_cx, p->q_cy) && camera_ok(p->t_fx, p->t_fy, p->t_cx, p->t_cy);
 }
-static EsArgs essential_args(const fpc_ctx* c, int n, const fpc_essential_params* p) {
+static EsArgs essential_args(const fpc_ctx* c, int n, const fpc_essential_params* p, int per_frame = 0) {
   EsArgs a{};
-  static_cast<HfArgs&>(a) = hf_args(c, n, p->reproj_threshold);
+  static_cast<HfArgs&>(a) = hf_args(c, n, p->reproj_threshold, per_frame);
   a.T = p->iterations; a.refits = p->refits; a.min_inliers = p->min_inliers; a.seed = p->seed;
   a.q_fx = p->q_fx; a.q_fy = p->q_fy; a.q_cx = p->q_cx; a.q_cy = p->q_cy;
   a.t_fx = p->t_fx; a.t_fy = p->t_fy; a.t_cx = p->t_cx; a.t_cy = p->t_cy;
@@ -4351,10 +4359,13 @@ int fpc_bank_landmarks_get(fpc_ctx* c, const float** xyzw) {
   return FPC_OK;
 }
 
-static PnpArgs pnp_args(fpc_ctx* c, int n, const fpc_pnp_params* p) {
+// A PnpArgs on the PnP reservation, one problem per frame; with per_frame = k on fpc_pnp_topk_reserve's, whose n problems are
+// k per frame.
+static PnpArgs pnp_args(fpc_ctx* c, int n, const fpc_pnp_params* p, int per_frame = 0) {
   PnpArgs a{};
-  a.rec = c->pnp_rec; a.np = c->pnp_np; a.best = c->pnp_best;
-  a.cap = c->cap; a.n = n;
+  a.rec = per_frame ? c->pnp_topk_rec : c->pnp_rec; a.np = per_frame ? c->pnp_topk_np : c->pnp_np;
+  a.best = per_frame ? c->pnp_topk_best : c->pnp_best;
+  a.cap = c->cap; a.n = n; a.per_frame = per_frame;
   a.T = p->iterations; a.refits = p->refits; a.min_inliers = p->min_inliers;
   a.thr = p->reproj_threshold; a.seed = p->seed;
   a.fx = p->fx; a.fy = p->fy; a.cx = p->cx; a.cy = p->cy;
@@ -4375,11 +4386,12 @@ static int pnp_launch(fpc_ctx* c, PoseModel model, const PnpArgs& a, float* R, f
 }
 
 // fpc_pnp_frames / fpc_pnp_bank and their P3P twins: the gather kernel over either train set, then the model's solver
-static int pnp_gather(fpc_ctx* c, PoseModel model, int n, const PnpTrain& tr, const int32_t* match, const fpc_pnp_params* p,
-                      float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
+// (a: pnp_args; its a.n problems are the frames, or per_frame of them each -- the top-K calls, whose tr.slot and match hold
+// an entry per problem)
+static int pnp_gather(fpc_ctx* c, PoseModel model, const PnpArgs& a, const PnpTrain& tr, const int32_t* match, float* R, float* t,
+                      int32_t* ninliers, uint8_t* inlier) {
   HIPCHECK(hipSetDevice(c->cfg.device));
-  const PnpArgs a = pnp_args(c, n, p);
-  hipLaunchKernelGGL(pnp_gather_kernel, dim3(n), dim3(256), 0, c->stream, a, c->xy, c->count, match, inlier, tr);
+  hipLaunchKernelGGL(pnp_gather_kernel, dim3(a.n), dim3(256), 0, c->stream, a, c->xy, c->count, match, inlier, tr);
   return pnp_launch(c, model, a, R, t, ninliers, inlier, c->cap);
 }
 
@@ -4399,8 +4411,8 @@ static int pose_frames(fpc_ctx* c, PoseModel model, int n, const float* key_xyz,
                        const int32_t* match, const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier) {
   if (!c || !c->pnp_slab || !key_xyz || !nkey || !match || !R || !t || !ninliers || !pose_params_ok(p, model) || !frames_ok(c, n))
     return FPC_E_INVALID;
-  return pnp_gather(c, model, n, PnpTrain{key_xyz, key_valid, nkey, nullptr, nullptr, nullptr, 0, 0}, match, p, R, t, ninliers,
-                    inlier);
+  return pnp_gather(c, model, pnp_args(c, n, p), PnpTrain{key_xyz, key_valid, nkey, nullptr, nullptr, nullptr, 0, 0}, match, R, t,
+                    ninliers, inlier);
 }
 
 static int pose_bank(fpc_ctx* c, PoseModel model, int n, const int32_t* slot, const int32_t* match, const fpc_pnp_params* p,
@@ -4408,8 +4420,9 @@ static int pose_bank(fpc_ctx* c, PoseModel model, int n, const int32_t* slot, co
   if (!c || !c->pnp_slab || !R || !t || !ninliers || !pose_params_ok(p, model) || !bank_ok(c, n, slot, match))
     return FPC_E_INVALID;
   // (without landmark storage lm is null: no frame has pairs)
-  return pnp_gather(c, model, n, PnpTrain{nullptr, nullptr, nullptr, slot, c->lm_xyzw, c->bank.count, c->bank.rows, c->bank.slots},
-                    match, p, R, t, ninliers, inlier);
+  return pnp_gather(c, model, pnp_args(c, n, p),
+                    PnpTrain{nullptr, nullptr, nullptr, slot, c->lm_xyzw, c->bank.count, c->bank.rows, c->bank.slots}, match, R, t,
+                    ninliers, inlier);
 }
 
 int fpc_ransac_pnp(fpc_ctx* c, int n, const float* xy, const float* xyz, const int32_t* npairs, int stride,
@@ -4586,6 +4599,78 @@ int fpc_homography_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot,
   if (pick || best)
     hipLaunchKernelGGL(bank_pick_kernel, dim3(n), dim3(64), 0, c->stream, ninliers, cand_slot, k, pick, best);
   return launched();
+}
+
+// ---- top-K candidates under the pose and epipolar models (include/fpc.h): the single-slot bank calls' kernels over n k
+// ---- problems (per_frame = k), then the pick and the picked candidate's model -------------------------------------------------
+// what the four calls refuse beside their single-slot twins' checks
+static bool topk_ok(const fpc_ctx* c, int n, int k, const int32_t* cand_slot, const int32_t* match) {
+  return c->topk_slab && k >= 1 && k <= c->topk.kmax && bank_ok(c, n, cand_slot, match);
+}
+// their tail: m0 [n][k][w0] (R or F) and m1 [n][k][w1] (t, or null) -> best0 [n][w0], best1 [n][w1]
+static int topk_pick(fpc_ctx* c, int n, int k, const int32_t* ninliers, const int32_t* cand_slot, int32_t* pick, int32_t* best,
+                     const float* m0, int w0, float* best0, const float* m1, int w1, float* best1) {
+  if (pick || best || best0 || best1)
+    hipLaunchKernelGGL(bank_pick_model_kernel, dim3(n), dim3(64), 0, c->stream, ninliers, cand_slot, k, pick, best, m0, w0, best0,
+                       m1, w1, best1);
+  return launched();
+}
+
+// The only call of the pose top-K calls that allocates or synchronises: the PnP reservation's three buffers for max_batch x
+// kmax problems, an allocation of its own (the bank's bytes, the top-K reservation and the PnP reservation are what they were).
+int fpc_pnp_topk_reserve(fpc_ctx* c, size_t* bytes) {
+  if (!c || !c->bank_slab || !c->topk_slab || c->pnp_topk_slab) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const size_t problems = (size_t)c->B * c->topk.kmax, cap = c->cap;
+  Carver cv(c);
+  cv.into(&c->pnp_topk_rec, problems * cap * 2); cv.into(&c->pnp_topk_np, problems); cv.into(&c->pnp_topk_best, problems);
+  if (int rc = c->pnp_topk_slab.allocate(c->stream, cv)) return rc;
+  if (bytes) *bytes = c->pnp_topk_slab.bytes;
+  return FPC_OK;
+}
+
+static int pose_bank_topk(fpc_ctx* c, PoseModel model, int n, int k, const int32_t* cand_slot, const int32_t* match,
+                          const fpc_pnp_params* p, float* R, float* t, int32_t* ninliers, uint8_t* inlier, int32_t* pick,
+                          int32_t* best, float* best_R, float* best_t) {
+  if (!c || !c->pnp_topk_slab || !R || !t || !ninliers || !pose_params_ok(p, model) || !topk_ok(c, n, k, cand_slot, match))
+    return FPC_E_INVALID;
+  // n k problems on the reserved records: problem f k + j is frame f against the landmarks of slot cand_slot[f][j] with
+  // match[f][j] (without landmark storage lm is null: no problem has pairs)
+  if (int rc = pnp_gather(c, model, pnp_args(c, n * k, p, k),
+                          PnpTrain{nullptr, nullptr, nullptr, cand_slot, c->lm_xyzw, c->bank.count, c->bank.rows, c->bank.slots},
+                          match, R, t, ninliers, inlier))
+    return rc;
+  return topk_pick(c, n, k, ninliers, cand_slot, pick, best, R, 9, best_R, t, 3, best_t);
+}
+
+int fpc_pnp_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot, const int32_t* match, const fpc_pnp_params* p, float* R,
+                      float* t, int32_t* ninliers, uint8_t* inlier, int32_t* pick, int32_t* best, float* best_R, float* best_t) {
+  return pose_bank_topk(c, POSE_DLT, n, k, cand_slot, match, p, R, t, ninliers, inlier, pick, best, best_R, best_t);
+}
+
+int fpc_p3p_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot, const int32_t* match, const fpc_pnp_params* p, float* R,
+                      float* t, int32_t* ninliers, uint8_t* inlier, int32_t* pick, int32_t* best, float* best_R, float* best_t) {
+  return pose_bank_topk(c, POSE_P3P, n, k, cand_slot, match, p, R, t, ninliers, inlier, pick, best, best_R, best_t);
+}
+
+int fpc_fundamental_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot, const int32_t* match,
+                              const fpc_ransac_params* p, float* F, int32_t* ninliers, uint8_t* inlier, int32_t* pick,
+                              int32_t* best, float* best_F) {
+  if (!c || !F || !ninliers || !ransac_params_ok(p, FM_SAMPLE) || !topk_ok(c, n, k, cand_slot, match)) return FPC_E_INVALID;
+  const HfArgs a = ransac_args(c, n * k, p, k);
+  if (int rc = pairs_bank(c, a, n, cand_slot, match, inlier)) return rc;
+  if (int rc = fundamental_launch(c, a, F, ninliers, inlier, c->cap)) return rc;
+  return topk_pick(c, n, k, ninliers, cand_slot, pick, best, F, 9, best_F, nullptr, 0, nullptr);
+}
+
+int fpc_essential_bank_topk(fpc_ctx* c, int n, int k, const int32_t* cand_slot, const int32_t* match,
+                            const fpc_essential_params* p, float* F, float* E, int32_t* ninliers, uint8_t* inlier, int32_t* pick,
+                            int32_t* best, float* best_F) {
+  if (!essential_ok(c, p, F, ninliers) || !topk_ok(c, n, k, cand_slot, match)) return FPC_E_INVALID;
+  const EsArgs a = essential_args(c, n * k, p, k);
+  if (int rc = pairs_bank(c, a, n, cand_slot, match, inlier)) return rc;
+  if (int rc = essential_launch(c, a, F, E, ninliers, inlier, c->cap)) return rc;
+  return topk_pick(c, n, k, ninliers, cand_slot, pick, best, F, 9, best_F, nullptr, 0, nullptr);
 }
 
 // ---- guided matching: plain, cell-ordered, epipolar and under a pose (include/fpc.h; two strip skeletons and three gates in

@@ -1,5 +1,6 @@
 // match_bank_topk.h -- verified relocalisation: the k best slots of the key-frame bank per frame, a match table against each,
-// and one RANSAC problem per (frame, candidate) (fpc_bank_topk_reserve / fpc_match_bank_topk / fpc_homography_bank_topk,
+// and one RANSAC problem per (frame, candidate) (fpc_bank_topk_reserve / fpc_match_bank_topk / fpc_homography_bank_topk and
+// the pose and epipolar models' fpc_pnp_bank_topk / fpc_p3p_bank_topk / fpc_fundamental_bank_topk / fpc_essential_bank_topk,
 // include/fpc.h).
 //
 // fpc_match_bank ranks the slots by appearance and keeps one; a look-alike slot that outscores the right one loses the
@@ -17,8 +18,11 @@
 //                               the guided pass run, so a pair's d^2 has their bits.  A candidate of -1 is an empty train set.
 //   bank_topk_finalize_kernel   grid (ceil(cap / 256), n, k): mf_row_ok on every row of every pair -> match / dist [n][k][cap].
 //   bank_pick_kernel            grid n: arg-max of ninliers[f][.] on the integer key (ninliers << 32) | ~j.
+//   bank_pick_model_kernel      bank_pick_kernel, and the picked candidate's model (R and t, or F) beside it.
 // The RANSAC problems run on ransac_homography.h's kernels with HfArgs::per_frame = k: problem p = f k + j has its own pair
-// list, mask row and slot, and frame f's pixels and sampler -- what fpc_homography_bank computes at frame index f.
+// list, mask row and slot, and frame f's pixels and sampler -- what fpc_homography_bank computes at frame index f.  The
+// fundamental and essential kernels take the same HfArgs; the absolute-pose kernels (pnp_ransac.h, p3p_ransac.h) carry
+// PnpArgs::per_frame with the same meaning, on records that fpc_pnp_topk_reserve allocates.
 #pragma once
 #include "match_bank_bf16.h"
 #include "ransac_homography.h"
@@ -134,12 +138,11 @@ __global__ __launch_bounds__(256) void bank_topk_finalize_kernel(const MatchFram
   if (dist) dist[o] = d;
 }
 
-// grid n, 64 threads, k <= 64: pick[f] = the j with the most inliers (ties to the lower j), -1 when there are none;
-// best[f] = cand_slot[f][pick[f]] or -1.  pick / best may be null.
-__global__ __launch_bounds__(64) void bank_pick_kernel(const int32_t* __restrict__ ninliers, const int32_t* __restrict__ cand_slot,
-                                                       int k, int32_t* pick, int32_t* best) {
-  const int f = blockIdx.x, j = threadIdx.x;
-  unsigned long long key = 0ull;                                    // (ninliers << 32) | ~j
+// (one wave, lane j < 64, k <= 64) the j with the most inliers among ninliers[f][.] (ties to the lower j), -1 when there are
+// none; the same in every lane.  The integer key (ninliers << 32) | ~j.
+__device__ __forceinline__ int bank_pick(const int32_t* __restrict__ ninliers, int f, int k) {
+  const int j = threadIdx.x;
+  unsigned long long key = 0ull;
   if (j < k) {
     const int ni = ninliers[(size_t)f * k + j];
     if (ni > 0) key = ((unsigned long long)(unsigned)ni << 32) | (unsigned)~j;
@@ -149,11 +152,36 @@ __global__ __launch_bounds__(64) void bank_pick_kernel(const int32_t* __restrict
     const unsigned long long other = __shfl_xor(key, o);
     key = other > key ? other : key;
   }
-  if (j == 0) {
-    const int p = key ? (int)~(unsigned)(key & 0xffffffffu) : -1;
+  return key ? (int)~(unsigned)(key & 0xffffffffu) : -1;
+}
+
+// grid n, 64 threads, k <= 64: pick[f] = bank_pick; best[f] = cand_slot[f][pick[f]] or -1.  pick / best may be null.
+__global__ __launch_bounds__(64) void bank_pick_kernel(const int32_t* __restrict__ ninliers, const int32_t* __restrict__ cand_slot,
+                                                       int k, int32_t* pick, int32_t* best) {
+  const int f = blockIdx.x;
+  const int p = bank_pick(ninliers, f, k);
+  if (threadIdx.x == 0) {
     if (pick) pick[f] = p;
     if (best) best[f] = p >= 0 ? cand_slot[(size_t)f * k + p] : -1;
   }
+}
+
+// The pose and epipolar top-K calls' tail (fpc_pnp_bank_topk / fpc_p3p_bank_topk / fpc_fundamental_bank_topk /
+// fpc_essential_bank_topk): bank_pick_kernel, and the picked candidate's model beside it -- best0[f][.] = m0[f][pick[f]][.]
+// (w0 <= 64 floats: R or F) and best1[f][.] = m1[f][pick[f]][.] (w1 <= 64 floats: t), zeros where pick[f] is -1.  Every
+// output may be null (m1 with best1).  The models were written by the refit kernel launched in front of this one.
+__global__ __launch_bounds__(64) void bank_pick_model_kernel(const int32_t* __restrict__ ninliers,
+                                                             const int32_t* __restrict__ cand_slot, int k, int32_t* pick,
+                                                             int32_t* best, const float* __restrict__ m0, int w0, float* best0,
+                                                             const float* __restrict__ m1, int w1, float* best1) {
+  const int f = blockIdx.x, j = threadIdx.x;
+  const int p = bank_pick(ninliers, f, k);
+  if (j == 0) {
+    if (pick) pick[f] = p;
+    if (best) best[f] = p >= 0 ? cand_slot[(size_t)f * k + p] : -1;
+  }
+  if (best0 && j < w0) best0[(size_t)f * w0 + j] = p >= 0 ? m0[((size_t)f * k + p) * w0 + j] : 0.f;
+  if (best1 && j < w1) best1[(size_t)f * w1 + j] = p >= 0 ? m1[((size_t)f * k + p) * w1 + j] : 0.f;
 }
 
 }  // namespace fpc

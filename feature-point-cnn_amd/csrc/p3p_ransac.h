@@ -194,7 +194,7 @@ struct P3pMinimal {
     uint32_t idx[P3P_SAMPLE];
     double R[9], t[3];
     PnpPair first;
-    if (!(hf_sample_distinct<P3P_SAMPLE, P3P_DRAWS>(a.seed, (uint32_t)f, ~(uint32_t)key, (uint32_t)M, idx) &&
+    if (!(hf_sample_distinct<P3P_SAMPLE, P3P_DRAWS>(a.seed, (uint32_t)hf_frame(a.per_frame, f), ~(uint32_t)key, (uint32_t)M, idx) &&
           p3p_solve(rec, idx, a, R, t, first)))
       return false;
     bool finite = true;

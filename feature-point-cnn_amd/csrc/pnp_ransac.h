@@ -44,6 +44,10 @@ struct PnpArgs {
   float thr;
   uint32_t seed;
   float fx, fy, cx, cy;
+  // fpc_pnp_bank_topk / fpc_p3p_bank_topk (match_bank_topk.h): HfArgs::per_frame's meaning -- the grid's index is a PROBLEM
+  // p = f per_frame + j with its own records, count, best key, mask row and slot, while the frame f = p / per_frame selects
+  // the query pixels and feeds the sampler.  0 (every other entry point): one problem per frame, p = f.
+  int per_frame;
 };
 
 struct PnpPair { float x, y, X, Y, Z; int row; };
@@ -225,11 +229,13 @@ struct PnpTrain {
   int rows, slots;
 };
 
-// one workgroup per frame; rows i < count[f] with 0 <= match < the train count and a valid landmark, in ascending i
+// one workgroup per frame (per problem: PnpArgs::per_frame, with tr.slot and match holding an entry per problem); rows
+// i < count[f] with 0 <= match < the train count and a valid landmark, in ascending i
 __global__ __launch_bounds__(256) void pnp_gather_kernel(PnpArgs a, const int32_t* __restrict__ xy, const int32_t* __restrict__ count,
                                                          const int32_t* __restrict__ match, uint8_t* mask, const PnpTrain tr) {
   const int f = blockIdx.x, cap = a.cap;
-  const int cnt = hf_clamp(count[f], cap);
+  const int fq = hf_frame(a.per_frame, f);     // the frame whose keypoints are the query side
+  const int cnt = hf_clamp(count[fq], cap);
   const float4* lm = nullptr;
   int nt = 0;
   if (tr.slot) {
@@ -266,7 +272,7 @@ __global__ __launch_bounds__(256) void pnp_gather_kernel(PnpArgs a, const int32_
       out[0] = make_float4((float)qxy[2 * i], (float)qxy[2 * i + 1], X, Y);
       out[1] = make_float4(Z, __int_as_float(i), 0.f, 0.f);
     }
-  } src{a, tr, xy + (size_t)f * cap * 2, lm, f, nt, 0.f, 0.f, 0.f};
+  } src{a, tr, xy + (size_t)fq * cap * 2, lm, f, nt, 0.f, 0.f, 0.f};
   gather_body(src, f, cnt, cap, match, mask, a.np, a.best);
 }
 
@@ -279,7 +285,7 @@ struct PnpModel {
   float thr;
   __device__ __forceinline__ explicit PnpModel(const PnpArgs& a) : thr(a.thr) {}
   static __device__ __forceinline__ const float4* records(const PnpArgs& a, int f) { return a.rec + (size_t)f * a.cap * 2; }
-  static __device__ __forceinline__ int frame(const PnpArgs&, int f) { return f; }
+  static __device__ __forceinline__ int frame(const PnpArgs& a, int f) { return hf_frame(a.per_frame, f); }
   __device__ __forceinline__ bool solve(const PnpArgs& a, const float4* __restrict__ rec, const uint32_t (&idx)[PNP_SAMPLE],
                                         double* sys) {
     double P[12];
@@ -382,7 +388,7 @@ struct PnpDlt {
     uint32_t idx[PNP_SAMPLE];
     double P[12];
     PnpPair first;
-    if (!(hf_sample_distinct<PNP_SAMPLE, PNP_DRAWS>(a.seed, (uint32_t)f, ~(uint32_t)key, (uint32_t)M, idx) &&
+    if (!(hf_sample_distinct<PNP_SAMPLE, PNP_DRAWS>(a.seed, (uint32_t)hf_frame(a.per_frame, f), ~(uint32_t)key, (uint32_t)M, idx) &&
           pnp_solve6<1>(sys, rec, idx, a, P, first)))
       return false;
 #pragma unroll
@@ -394,6 +400,7 @@ struct PnpDlt {
 // A refit kernel of the absolute-pose models (workgroup of 256, one per problem).
 //   Minimal::SAMPLE          the sample's size: the fewest pairs of a frame and the fewest inliers of a refit
 //   Minimal::derive(a, rec, f, key, M)   one lane: the best sample's pose into pnp_refit_pose; false: the frame fails
+//                            (f: the problem; the sampler's frame is hf_frame(a.per_frame, f))
 template <class Minimal>
 __device__ __forceinline__ void pnp_refit_body(const PnpArgs& a, float* __restrict__ Rout, float* __restrict__ tout,
                                                int32_t* __restrict__ ninl, uint8_t* mask, int mstride) {

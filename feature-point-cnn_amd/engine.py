@@ -1366,6 +1366,118 @@ class Engine:
         hm, ni, _, _, best = self.homography_bank_topk_async(n, cs, m, **params)
         return self._host((best, hm, ni, cs, csc))
 
+    # -- verified relocalisation by pose: every candidate under PnP, P3P, F or E (fpc_pnp_topk_reserve / fpc_*_bank_topk) ----
+    def pnp_topk_reserve(self):
+        """fpc_pnp_topk_reserve: the absolute-pose workspace of max_batch x kmax (frame, candidate) problems, kmax being
+        bank_topk_reserve's; the only call of pnp_bank_topk / p3p_bank_topk that allocates (no pnp_reserve is needed).
+        Freed with the bank.  Returns the bytes it allocated (bank_info()["bytes"] is unchanged)."""
+        self._bank_info()
+        nbytes = ctypes.c_size_t(0)
+        _lib.check(self._l.fpc_pnp_topk_reserve(self._ctx, ctypes.byref(nbytes)), "fpc_pnp_topk_reserve")
+        return int(nbytes.value)
+
+    def _topk_pairs(self, n, cand_slot, match, fill, *args):
+        """The top-K pair source -> (fill(*args), k, cand_slot int32 [n,k], match int32 [n,k,cap]), behind the check that a
+        bank exists."""
+        self._bank_info()
+        p = fill(*args)
+        cand_slot = self._dev_int32("cand_slot", cand_slot, "[n,k]", n, None)
+        k = int(cand_slot.shape[1])
+        return p, k, cand_slot, self._dev_int32("match", match, "[n,k,%d]" % self.capacity, n, k, self.capacity)
+
+    def _pose_bank_topk(self, name, n, cand_slot, match, K, params):
+        p, k, cand_slot, match = self._topk_pairs(n, cand_slot, match, self._pnp_params, K, params)
+        rm, ni, mask = self._ransac_out(n, k)
+        tv = torch.empty((n, k, 3), dtype=torch.float32, device=self.torch_device)
+        pick, best = self._int32(n), self._int32(n)
+        best_r = torch.empty((n, 3, 3), dtype=torch.float32, device=self.torch_device)
+        best_t = torch.empty((n, 3), dtype=torch.float32, device=self.torch_device)
+        self._call(name, n, k, cand_slot, match, ctypes.byref(p), rm, tv, ni, mask, pick, best, best_r, best_t,
+                   inputs=(cand_slot, match))
+        return rm, tv, ni, mask.view(torch.bool), pick, best, best_r, best_t
+
+    def pnp_bank_topk_async(self, n, cand_slot, match, K=None, **params):
+        """fpc_pnp_bank_topk: pnp_bank_async for every candidate -- cand_slot int32 [n,k] and match int32 [n,k,cap] are
+        match_bank_topk_async's -> device tensors (R [n,k,3,3], t [n,k,3], ninliers [n,k], inlier bool [n,k,cap], pick
+        int32 [n]: the candidate with the most inliers, ties to the lower j, -1: none; best int32 [n]: its slot, or -1;
+        best_R [n,3,3] and best_t [n,3]: its pose, zeros where pick is -1).  Column j is bit-identical to
+        pnp_bank_async(n, cand_slot[:, j], match[:, j]).  K and the parameters as in pnp_bank_async.  Needs
+        pnp_topk_reserve().  Does not synchronise."""
+        return self._pose_bank_topk("fpc_pnp_bank_topk", n, cand_slot, match, K, params)
+
+    def pnp_bank_topk(self, n, cand_slot, match, K=None, **params):
+        """pnp_bank_topk_async, then host arrays (R [n,k,3,3], t [n,k,3], ninliers [n,k], inlier bool [n,k,cap], pick [n],
+        best [n], best_R [n,3,3], best_t [n,3])."""
+        return self._host(self.pnp_bank_topk_async(n, cand_slot, match, K, **params))
+
+    def p3p_bank_topk_async(self, n, cand_slot, match, K=None, **params):
+        """fpc_p3p_bank_topk: pnp_bank_topk_async with the minimal-sample model (p3p_bank_async for every candidate).  Does
+        not synchronise."""
+        return self._pose_bank_topk("fpc_p3p_bank_topk", n, cand_slot, match, K, params)
+
+    def p3p_bank_topk(self, n, cand_slot, match, K=None, **params):
+        """p3p_bank_topk_async, then host arrays (R [n,k,3,3], t [n,k,3], ninliers [n,k], inlier bool [n,k,cap], pick [n],
+        best [n], best_R [n,3,3], best_t [n,3])."""
+        return self._host(self.p3p_bank_topk_async(n, cand_slot, match, K, **params))
+
+    def fundamental_bank_topk_async(self, n, cand_slot, match, **params):
+        """fpc_fundamental_bank_topk: fundamental_bank_async for every candidate, arguments as homography_bank_topk_async
+        -> device tensors (F [n,k,3,3], ninliers [n,k], inlier bool [n,k,cap], pick int32 [n], best int32 [n], best_F
+        [n,3,3]: the picked candidate's F, zeros where pick is -1 -- what match_bank_guided_epipolar_async(best, best_F)
+        and pose_bank_async take).  A wrong candidate still collects chance inliers under an epipolar model: min_inliers
+        is the caller's floor.  Needs bank_topk_reserve() only.  Does not synchronise."""
+        p, k, cand_slot, match = self._topk_pairs(n, cand_slot, match, self._ransac_params, params)
+        fm, ni, mask = self._ransac_out(n, k)
+        pick, best = self._int32(n), self._int32(n)
+        best_f = torch.empty((n, 3, 3), dtype=torch.float32, device=self.torch_device)
+        self._call("fpc_fundamental_bank_topk", n, k, cand_slot, match, ctypes.byref(p), fm, ni, mask, pick, best, best_f,
+                   inputs=(cand_slot, match))
+        return fm, ni, mask.view(torch.bool), pick, best, best_f
+
+    def fundamental_bank_topk(self, n, cand_slot, match, **params):
+        """fundamental_bank_topk_async, then host arrays (F [n,k,3,3], ninliers [n,k], inlier bool [n,k,cap], pick [n],
+        best [n], best_F [n,3,3])."""
+        return self._host(self.fundamental_bank_topk_async(n, cand_slot, match, **params))
+
+    def essential_bank_topk_async(self, n, cand_slot, match, K_query=None, K_train=None, **params):
+        """fpc_essential_bank_topk: essential_bank_async for every candidate -> device tensors (F [n,k,3,3], E [n,k,3,3],
+        ninliers [n,k], inlier bool [n,k,cap], pick int32 [n], best int32 [n], best_F [n,3,3]), as
+        fundamental_bank_topk_async; the cameras and parameters as in essential_bank_async.  Does not synchronise."""
+        p, k, cand_slot, match = self._topk_pairs(n, cand_slot, match, self._essential_params, K_query, K_train, params)
+        fm, ni, mask = self._ransac_out(n, k)
+        em = torch.empty_like(fm)
+        pick, best = self._int32(n), self._int32(n)
+        best_f = torch.empty((n, 3, 3), dtype=torch.float32, device=self.torch_device)
+        self._call("fpc_essential_bank_topk", n, k, cand_slot, match, ctypes.byref(p), fm, em, ni, mask, pick, best, best_f,
+                   inputs=(cand_slot, match))
+        return fm, em, ni, mask.view(torch.bool), pick, best, best_f
+
+    def essential_bank_topk(self, n, cand_slot, match, K_query=None, K_train=None, **params):
+        """essential_bank_topk_async, then host arrays (F [n,k,3,3], E [n,k,3,3], ninliers [n,k], inlier bool [n,k,cap],
+        pick [n], best [n], best_F [n,3,3])."""
+        return self._host(self.essential_bank_topk_async(n, cand_slot, match, K_query, K_train, **params))
+
+    def relocalise_pose(self, n, k, K=None, model="p3p", radius=8.0, cross_check=True, max_dist=0.7, ratio=0.0, min_score=0,
+                        **params):
+        """The pose of every frame against the map, over the k best slots: match_bank_topk_async, then p3p_bank_topk_async
+        (model "p3p") or pnp_bank_topk_async ("pnp") on every candidate, then match_bank_guided_pose_async(best, best_R,
+        best_t, radius) -- the picked slot once more, by projection -- and pnp_bank_async(best) on that table; one
+        synchronisation, no host call in between -> host arrays (best [n]: the picked slot, -1: none verified; R [n,3,3], t
+        [n,3], ninliers [n], inlier bool [n,cap]: the final pose, zeros where best is -1; then every candidate's: cand_R
+        [n,k,3,3], cand_t [n,k,3], cand_ninliers [n,k], pick [n], cand_slot [n,k], cand_score [n,k]).  K and the
+        parameters go to both pose calls (min_inliers >= 6 for the second).  Needs an "f32" bank with landmarks,
+        bank_topk_reserve(kmax >= k), pnp_topk_reserve() and pnp_reserve()."""
+        if model not in ("pnp", "p3p"):
+            raise ValueError("model must be 'pnp' or 'p3p', got %r" % (model,))
+        if self.bank_info()["format"] != "f32":           # before anything is launched: the chain's third call would refuse it
+            raise ValueError("relocalise_pose needs an 'f32' bank: match_bank_guided_pose has no 'bf16' gate")
+        pose_topk = self.p3p_bank_topk_async if model == "p3p" else self.pnp_bank_topk_async
+        _, cs, csc, m, _ = self.match_bank_topk_async(n, k, cross_check, max_dist, ratio, min_score)
+        rk, tk, nk, _, pick, best, best_r, best_t = pose_topk(n, cs, m, K, **params)
+        m2, _ = self.match_bank_guided_pose_async(n, best, best_r, best_t, radius, K, cross_check, max_dist, ratio)
+        rm, tv, ni, mask = self.pnp_bank_async(n, best, m2, K, **params)
+        return self._host((best, rm, tv, ni, mask, rk, tk, nk, pick, cs, csc))
+
     # -- guided matching: the match once more under the estimated homographies (fpc_match_*_guided), and its cell-ordered
     # -- form (fpc_cell_order / fpc_match_*_guided_cells): the same tables, fewer tiles ------------------------------------
     def _guided_h(self, n, hm, what="H"):

@@ -1383,6 +1383,66 @@ int fpc_match_bank_guided_pose(fpc_ctx* ctx, int n, const int32_t* slot_dev,
                                float radius, int cross_check, float max_dist, float ratio,
                                int32_t* match_dev, float* dist_dev);
 
+/* --- verified relocalisation by pose: the K best slots of the bank per frame, each checked by PnP, P3P, F or E ------------
+ * fpc_homography_bank_topk verifies the shortlist of fpc_match_bank_topk with a homography: in a scene with depth that is a
+ * pick but not a pose, and the inlier share of a homography on such a scene is arbitrary.  The calls below run the absolute-
+ * pose models (fpc_pnp_bank, fpc_p3p_bank) and the epipolar models (fpc_fundamental_bank, fpc_essential_bank) against EVERY
+ * candidate, pick the candidate with the most inliers and hand its model on -- without a host loop over the candidates.
+ *
+ * fpc_pnp_topk_reserve: needs a bank and a fpc_bank_topk_reserve reservation, whose kmax it takes.  The ONLY call of this
+ * section that allocates or synchronises: the pair records [max_batch kmax][cap][2] float4, pair counts and best keys of
+ * max_batch x kmax absolute-pose problems, in an allocation of its own.  *bytes (may be NULL) receives its size;
+ * fpc_bank_get().bytes, the top-K reservation, the PnP reservation and fpc_create's workspace are what they were.  No
+ * fpc_pnp_reserve is needed.  FPC_E_INVALID without a bank, without a top-K reservation or when it already exists;
+ * fpc_bank_destroy and fpc_destroy free it.  In a FPC_PLAN_GUARD_ZONES context every buffer of it is followed by a canary
+ * zone of its own, and fpc_check_guards counts those too.  The epipolar calls run on fpc_bank_topk_reserve's workspace, as
+ * fpc_homography_bank_topk does, and need no reservation of this kind.
+ *
+ * fpc_pnp_bank_topk / fpc_p3p_bank_topk: one absolute-pose problem per (frame, candidate).  1 <= k <= kmax; cand_slot_dev
+ * [n][k] and match_dev [n][k][cap] are fpc_match_bank_topk's; R_dev float32 [n][k][9], t_dev float32 [n][k][3], ninliers_dev
+ * int32 [n][k], inlier_dev uint8 [n][k][cap] (may be NULL).
+ *  - Problem (f, j) is bit-identical to fpc_pnp_bank / fpc_p3p_bank(n, slot = cand_slot[.][j], match = match[.][j], params)
+ *    at frame index f -- R, t, ninliers and the mask, failures included: a candidate of -1, a slot outside the bank, a slot
+ *    without valid landmarks, a bank without landmark storage and fewer pairs than the sample (6 / 4) each give zeros, 0 and
+ *    an all-zero mask.  The sampler and the refit's re-derivation hash f, not f k + j.
+ *  - pick_dev int32 [n] (may be NULL): the j with the largest ninliers[f][j], ties to the LOWER j; -1 when every
+ *    ninliers[f][.] is 0.  best_dev int32 [n] (may be NULL): cand_slot[f][pick[f]], or -1.  The integer key
+ *    (ninliers << 32) | ~j of fpc_homography_bank_topk: independent of the execution order.
+ *  - best_R_dev float32 [n][9], best_t_dev float32 [n][3] (both may be NULL): R[f][pick[f]] and t[f][pick[f]], zeros where
+ *    pick[f] is -1 -- written on the device, ready for fpc_match_bank_guided_pose(best, best_R, best_t), which leaves a
+ *    frame with R = t = 0 without matches, and fpc_pnp_bank(best) behind it.
+ *  - A candidate whose landmarks do not belong to the frame's scene collects NO inliers to speak of under an absolute-pose
+ *    model (0 of about 640 pairs on the scene of tests/test_pose_bank_topk.py), so min_inliers alone already rejects it.
+ * fpc_fundamental_bank_topk / fpc_essential_bank_topk: the same shape on the epipolar models.  F_dev float32 [n][k][9] (and
+ * E_dev float32 [n][k][9] of the essential call, may be NULL), ninliers_dev, inlier_dev, pick_dev and best_dev as above;
+ * best_F_dev float32 [n][9] (may be NULL): F[f][pick[f]], zeros where pick[f] is -1, ready for
+ * fpc_match_bank_guided_epipolar(best, best_F) and fpc_pose_bank.
+ *  - Problem (f, j) is bit-identical to fpc_fundamental_bank / fpc_essential_bank with column j, at frame index f.
+ *  - Needs keypoints only; nothing is allocated (fpc_bank_topk_reserve's pair lists, rows, counts and best keys).
+ *  - WARNING: an epipolar model constrains a pair to a line, not to a point, so a scrambled candidate still collects CHANCE
+ *    inliers: 15 - 36 of about 640 pairs at 3 px on the scene above, where the true slot keeps 606 - 613.  min_inliers is
+ *    therefore the CALLER's floor against chance, and pick is by maximum, not by the first candidate that passes.
+ * Execution: the four calls are asynchronous on the ctx stream, with no host synchronisation, no device-to-host copy and no
+ * allocation; counts and slots are read on the device; repeated calls give bit-identical outputs.  The number of launches of
+ * a call (gather, score, refit, pick) does not depend on n or k.  fpc_detect, fpc_match_bank_topk, fpc_p3p_bank_topk,
+ * fpc_match_bank_guided_pose(best, best_R, best_t), fpc_pnp_bank(best) needs no host call in between.
+ * FPC_E_INVALID (nothing is written): everything the single-slot call (fpc_pnp_bank but its fpc_pnp_reserve, fpc_p3p_bank,
+ * fpc_fundamental_bank, fpc_essential_bank) refuses; no fpc_bank_topk_reserve; no fpc_pnp_topk_reserve (absolute-pose
+ * calls); k outside [1, kmax]; a NULL cand_slot_dev, match_dev, R_dev / t_dev or F_dev, or ninliers_dev. */
+int fpc_pnp_topk_reserve(fpc_ctx* ctx, size_t* bytes);
+int fpc_pnp_bank_topk(fpc_ctx* ctx, int n, int k, const int32_t* cand_slot_dev, const int32_t* match_dev,
+                      const fpc_pnp_params* params, float* R_dev, float* t_dev, int32_t* ninliers_dev, uint8_t* inlier_dev,
+                      int32_t* pick_dev, int32_t* best_dev, float* best_R_dev, float* best_t_dev);
+int fpc_p3p_bank_topk(fpc_ctx* ctx, int n, int k, const int32_t* cand_slot_dev, const int32_t* match_dev,
+                      const fpc_pnp_params* params, float* R_dev, float* t_dev, int32_t* ninliers_dev, uint8_t* inlier_dev,
+                      int32_t* pick_dev, int32_t* best_dev, float* best_R_dev, float* best_t_dev);
+int fpc_fundamental_bank_topk(fpc_ctx* ctx, int n, int k, const int32_t* cand_slot_dev, const int32_t* match_dev,
+                              const fpc_ransac_params* params, float* F_dev, int32_t* ninliers_dev, uint8_t* inlier_dev,
+                              int32_t* pick_dev, int32_t* best_dev, float* best_F_dev);
+int fpc_essential_bank_topk(fpc_ctx* ctx, int n, int k, const int32_t* cand_slot_dev, const int32_t* match_dev,
+                            const fpc_essential_params* params, float* F_dev, float* E_dev, int32_t* ninliers_dev,
+                            uint8_t* inlier_dev, int32_t* pick_dev, int32_t* best_dev, float* best_F_dev);
+
 /* --- map growth: landmarks for a new key frame from its PnP pose ----------------------------------------------------------
  * fpc_pose_* is the only call above that creates 3-D points, from two views and at the scale |t| = 1 of that pair.  A frame
  * that fpc_pnp_frames / fpc_pnp_bank has localised has an R, t at the MAP's scale; the calls below give that frame its own
