@@ -2478,7 +2478,7 @@ static const char* launch_stem(fpc_ctx* c, const Op& op, int i, const float* fra
       x.tiles_x = (x.Wp + SB2_PW - 1) / SB2_PW;   // stem_bf16.h: 8 x 7 pooled pixels per tile
       x.tiles_y = (x.Hp + SB2_PH - 1) / SB2_PH;
       const int T = x.tiles_x * x.tiles_y * n;
-      const dim3 pg(std::min((T + 7) / 8 * 8, std::max(8, 2 * c->num_cus / 8 * 8)));  // two workgroups per CU, a multiple of 8
+      const dim3 pg(bf16_persistent_grid(T, 2 * c->num_cus, 1, c->opt.bf16_grid));  // two workgroups per CU, a multiple of 8
       if (gray) hipLaunchKernelGGL(stem_bf16_kernel<1>, pg, dim3(SB2_THREADS), StemB2Cfg<1>::LDS_BYTES, sb->st, x);
       else hipLaunchKernelGGL(stem_bf16_kernel<3>, pg, dim3(SB2_THREADS), StemB2Cfg<3>::LDS_BYTES, sb->st, x);
     } else {
@@ -2595,7 +2595,7 @@ static void launch_fblock(fpc_ctx* c, const Op& op, int i, const Sub& sb) {
     a.ncand = c->ncand + f0;
   }
   // (op.grid_y parts -- convt_bf16_kernel's output-channel halves -- share the CUs)
-  const int g = std::min((a.total_tiles + 7) / 8 * 8, std::max(8, c->fkind_blocks_per_cu[op.fkind] * c->num_cus / op.grid_y / 8 * 8));
+  const int g = bf16_persistent_grid(a.total_tiles, c->fkind_blocks_per_cu[op.fkind] * c->num_cus, op.grid_y, c->opt.bf16_grid);
   g_fkinds[op.fkind].launch(a, dim3(g, op.grid_y), sb.st);
 }
 

@@ -35,6 +35,7 @@ struct PlanOptions {
   int persist_min_tiles = 1;         // FPC_PERSIST_MIN: tiles per CU from which the Winograd kernel runs persistent (0 = never)
   bool xcd_order = true;             // FPC_XCD_ORDER=0: plain tile order in the persistent Winograd kernel
   int w36_cus = 0;                   // FPC_W36_CUS: CUs a generation-3 launch may take (0 = all): A/B knob for contexts that share the GPU
+  int bf16_grid = 0;                 // FPC_BF16_GRID: workgroups a persistent FPC_BF16 launch may take (0 = blocks per CU x CUs): A/B and test knob, w36_cus' twin
   // ---- NMS
   bool nms_one_workgroup = false;    // one workgroup per frame sorts its survivors (FPC_NMS_CHUNKED=0); default: in slices
   int nms_passes = 2;                // parallel NMS launches before the per-frame finish (FPC_NMS_PASSES)
@@ -93,6 +94,7 @@ static const OptionRow g_plan_options[] = {
     FPC_OPT_INT(persist_min_tiles, FPC_PLAN_NO_PERSISTENT_GRID, 0, "FPC_PERSIST_MIN", INT_MIN, INT_MAX),
     FPC_OPT_BOOL(xcd_order, FPC_PLAN_NO_XCD_ORDER, 0, "FPC_XCD_ORDER", READ_NONZERO),
     FPC_OPT_INT(w36_cus, 0, 0, "FPC_W36_CUS", 0, INT_MAX),
+    FPC_OPT_INT(bf16_grid, 0, 0, "FPC_BF16_GRID", 0, INT_MAX),
     FPC_OPT_BOOL(nms_one_workgroup, FPC_PLAN_NMS_ONE_WORKGROUP, 1, "FPC_NMS_CHUNKED", READ_ZERO),
     FPC_OPT_INT(nms_passes, 0, 0, "FPC_NMS_PASSES", 0, 64),
     FPC_OPT_INT(nms_g, 0, 0, "FPC_NMS_G", 0, 64),
@@ -101,6 +103,13 @@ static const OptionRow g_plan_options[] = {
 };
 #undef FPC_OPT_BOOL
 #undef FPC_OPT_INT
+
+// The persistent grid of an FPC_BF16 launch of `tiles` tiles in `parts` gridDim.y parts: a multiple of 8 (the tile walk
+// is per XCD), at most `resident` workgroups (blocks per CU x CUs) shared by the parts -- or at most `cap` (bf16_grid)
+// where that is set.
+inline int bf16_persistent_grid(int tiles, int resident, int parts, int cap) {
+  return std::min((tiles + 7) / 8 * 8, std::max(8, (cap > 0 ? cap : resident) / parts / 8 * 8));
+}
 
 inline int read_option(const char* e, const OptionRow& r) {
   switch (r.read) {

@@ -108,7 +108,10 @@ typedef struct fpc_config {
                           /* (cpp/src/model.cc, settings.h:19-25): gray input                */
                           /* (in_channels = 1), 256-D descriptors, fp32 or split mode        */
   /* Launch-plan knobs (zeros = the default plan).  The FPC_* environment variables of the
-   * same names still override them, for A/B runs of an unmodified caller. */
+   * same names still override them, for A/B runs of an unmodified caller.  Variables with no field or flag here
+   * (csrc/plan_options.h has the whole table): FPC_W36_CUS (CUs a persistent F(4x4,3x3) launch may take, 0 = all),
+   * FPC_BF16_GRID (workgroups a persistent FPC_BF16 launch may take, 0 = blocks per CU x CUs), FPC_PERSIST_MIN,
+   * FPC_NMS_G, FPC_MIN_SUB, FPC_STREAMS. */
   int num_streams;        /* sub-batches of one call on separate HIP streams; 0 = default (2; 3 in split modes)  */
   unsigned plan_flags;    /* FPC_PLAN_* bits                                                                   */
   int nms_round_launches; /* parallel NMS launches before the per-frame finish: 0 = default (2), -1 = none     */

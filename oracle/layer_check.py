@@ -1,5 +1,5 @@
 """Layer-isolated float64 parity of the fp32 plans -- TEST INFRASTRUCTURE ONLY (tests/test_layer_oracle.py on the CPU,
-tests/test_gpu_layer_isolated.py on the device; the C++ network: tests/test_layer_oracle_vgg.py and
+tests/test_gpu_layer_isolated.py on the device; the bf16 mode: compare_bf16_layer / check_bf16_layers below; the C++ network: tests/test_layer_oracle_vgg.py and
 tests/test_gpu_layer_isolated_vgg.py, through the *_vgg_* twins at the end of this file).
 
 Every layer of the network is fed the input tensor(s) the device itself holds for it (fpc_read_activation) and computed
@@ -142,6 +142,212 @@ def check_layers(engine, frames, sd, tag, launches=None, rows=None):
     graph["pool"] = ("frames",)
     _check(engine, frames, sd, tag, launches, rows, engine.ACTIVATIONS, graph, reference_layer, torch_f32_layer,
            layer_kernels(launches or []))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The bf16 mode (dtype="bf16"): the same layer-isolated comparison, per element, with no allowance for a share of elements
+# (tests/test_layer_oracle_bf16.py on the CPU, tests/test_gpu_layer_isolated_bf16.py on the device).
+#
+# The emulation (oracle.bf16_layer_parts) puts the mode's roundings where the kernels put them and accumulates in double;
+# the device accumulates in fp32, in another order.  The two can differ at an element only where that moved a value
+# across a bf16 rounding boundary: at the output, or at an h = round_bf16(relu(conv1 + bias)) feeding it -- and conv2 of a
+# block is 1 x 1, so the h's that feed an output element are the one pixel's channels.  With EPS_h / EPS_y the most an fp32
+# accumulation of conv1 / of y may lie from the double one,
+#     U     = max(rb(relu(v + EPS_h)) - h, h - rb(relu(v - EPS_h)))       the most a device h differs from the emulation's
+#     delta = EPS_y + conv1x1(U, |w2|)                                    ("up" and the stem have no h: delta = EPS_y)
+# a bf16-stored output is accepted iff rb(relu(y - delta)) <= got <= rb(relu(y + delta)) (the stem: both bounds max-pooled,
+# the pool being monotone), the fp32 logits iff |got - relu(y)| <= delta.  EPS is BF16_EPS_MARGIN x E_ref, E_ref the
+# largest error against the double value of the SAME computation in plain fp32 on the CPU (torch_bf16_parts: same bf16
+# operands, same input, the emulation's h): DESIGN.md's table has the fp32-accumulating direct kernels at up to 4.56 x
+# E_ref, and 8 is under twice that.  Each EPS must itself be <= ATOL.  So that wide intervals cannot make the check
+# vacuous, at most BF16_MAX_AMBIGUOUS of a bf16 layer's elements may have an interval of more than one bf16 value, and
+# the median delta of the logits must be <= ATOL.
+# ---------------------------------------------------------------------------------------------------------------
+BF16_EPS_MARGIN = 8.0
+BF16_MAX_AMBIGUOUS = 0.10
+
+
+def _t(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, np.float32))
+
+
+def _conv_in_quarters(F, x, w, quarters, **kw):
+    """conv2d / conv_transpose2d `F` with the input channels accumulated in `quarters` chunks, the partial sums added in
+    float in order: another fp32 accumulation order of the same sum."""
+    cin = x.shape[1]
+    if quarters <= 1 or cin % quarters:
+        return F(x, w, **kw)
+    q = cin // quarters
+    transposed = w.shape[0] == cin and F.__name__ == "conv_transpose2d"
+    acc = None
+    for k in range(quarters):
+        wk = w[k * q:(k + 1) * q] if transposed else w[:, k * q:(k + 1) * q]
+        part = F(x[:, k * q:(k + 1) * q], wk, **kw)
+        acc = part if acc is None else acc + part
+    return acc
+
+
+def torch_bf16_parts(name, inputs, sd, h=None, quarters=1):
+    """oracle.bf16_layer_parts in plain fp32 on the CPU (torch.nn.functional), same bf16-rounded operands -> dict with y
+    and, for a block, v and h.  `h`: the h that conv2 reads (the emulation's, for E_ref of y alone); None: its own,
+    round_bf16(relu(v)), as a device computes it.  `quarters` > 1: conv1 (the transposed convolution for "up") accumulated
+    in that many chunks of input channels -- a second fp32 accumulation order."""
+    import torch
+    import torch.nn.functional as F
+    with torch.no_grad():
+        x = _t(oracle.round_bf16(np.concatenate(inputs, 1) if len(inputs) > 1 else inputs[0]))
+        if name == "pool":
+            w, b = oracle.bf16_folded_weights("pool", sd, gray=x.shape[1] == 1)
+            return {"y": F.conv2d(x, _t(w), _t(b), stride=2, padding=3).numpy()}
+        if name == "up":
+            wt, bt = oracle.bf16_folded_weights("up", sd)
+            y = _conv_in_quarters(F.conv_transpose2d, x, _t(wt), quarters, stride=2, padding=1, output_padding=1)
+            return {"y": (y + _t(bt)[None, :, None, None]).numpy()}
+        (w1, b1, w2, wp, b2), stride = oracle.bf16_folded_weights(name, sd)
+        v = (_conv_in_quarters(F.conv2d, x, _t(w1), quarters, stride=stride, padding=1) + _t(b1)[None, :, None, None]).numpy()
+        own = oracle.round_bf16(np.maximum(v, np.float32(0)))
+        y = F.conv2d(_t(own if h is None else h), _t(w2))
+        bias = _t(b2)[None, :, None, None]
+        y = y + F.conv2d(x, _t(wp), stride=stride) + bias if wp is not None else y + bias + x
+        return {"v": v, "h": own, "y": y.numpy()}
+
+
+def bf16_output_of(name, parts, out_f32):
+    """The tensor a device that computed `parts` (y before ReLU and rounding) stores: what the stand-in devices of
+    tests/test_layer_oracle_bf16.py hand to the check."""
+    y = np.maximum(np.asarray(parts["y"], np.float32), np.float32(0))
+    if name == "pool":
+        y = oracle.maxpool3s2(y)
+    return y if out_f32 else oracle.round_bf16(y)
+
+
+def bf16_eps(name, inputs, sd, parts):
+    """(EPS_h, EPS_y, E_ref of conv1, E_ref of y) of one layer on these inputs; EPS_h is 0 where there is no h."""
+    ref = torch_bf16_parts(name, inputs, sd, h=parts.get("h"))
+    e_y = float(np.max(np.abs(ref["y"].astype(np.float64) - parts["y"])))
+    e_h = float(np.max(np.abs(ref["v"].astype(np.float64) - parts["v"]))) if "v" in parts else 0.0
+    return BF16_EPS_MARGIN * e_h, BF16_EPS_MARGIN * e_y, e_h, e_y
+
+
+def _rb_relu_outward(v, eps, up):
+    """round_bf16(relu(v +- eps)), the float sum nudged outward so that its own rounding cannot narrow the interval."""
+    f = (v.astype(np.float64) + (eps if up else -eps)).astype(np.float32)
+    f = np.nextafter(f, np.float32(np.inf if up else -np.inf))
+    return oracle.round_bf16(np.maximum(f, np.float32(0)))
+
+
+def bf16_delta(parts, eps_h, eps_y):
+    """delta [n,C,h,w] (float64) of the rule above."""
+    y = parts["y"]
+    if "h" not in parts:
+        return np.full(y.shape, eps_y, np.float64)
+    h = parts["h"].astype(np.float64)
+    u = np.maximum(_rb_relu_outward(parts["v"], eps_h, True) - h, h - _rb_relu_outward(parts["v"], eps_h, False))
+    w2 = np.abs(parts["w2"].astype(np.float64))[:, :, 0, 0]
+    return eps_y + np.einsum("oc,nchw->nohw", w2, u, optimize=True)
+
+
+def compare_bf16_layer(name, got, parts, eps_h, eps_y, tile=None):
+    """One tensor of the bf16 mode, the device's `got` [n,C,h,w] against oracle.bf16_layer_parts of its own input(s) ->
+    a report like compare_layer's: ok, layer, message, n_over, frames_over, worst = (frame, channel, y, x), max_want,
+    max_err (against the emulation's stored value), plus flips (share of elements != that value), ambiguous (share of
+    elements whose accepted interval holds more than one bf16 value; None for the fp32 logits), median_delta, eps_h,
+    eps_y.  Not ok: an element outside its interval or not finite, an EPS over ATOL, a layer over BF16_MAX_AMBIGUOUS
+    (the logits: median delta over ATOL), a reference outside MAX_MAGNITUDE, a wrong shape.  `tile` = (TH, TW) of the
+    kernel's output tile adds the position in that tile to a failure's message."""
+    got = np.asarray(got)
+    out_f32 = bool(parts["out_f32"])
+    pool = name == "pool"
+    want = bf16_output_of(name, parts, out_f32)
+    rep = {"ok": False, "layer": name, "n_over": -1, "frames_over": [], "worst": None, "max_err": float("nan"),
+           "max_want": float("nan"), "flips": float("nan"), "ambiguous": None, "median_delta": float("nan"),
+           "eps_h": eps_h, "eps_y": eps_y}
+    if got.shape != want.shape:
+        rep["message"] = "%s: shape %s on the device, %s in the reference" % (name, got.shape, want.shape)
+        return rep
+    n, _, h, w = want.shape
+    max_want = float(np.max(np.abs(want)))
+    rep["max_want"] = max_want
+    if not max_want <= MAX_MAGNITUDE:
+        rep["message"] = "%s: max |reference| = %g is outside the range (%g) the absolute %g bar is stated for" % (
+            name, max_want, MAX_MAGNITUDE, ATOL)
+        return rep
+    if not (eps_h <= ATOL and eps_y <= ATOL):
+        rep["message"] = "%s: EPS_h %.3g / EPS_y %.3g over the %g ceiling" % (name, eps_h, eps_y, ATOL)
+        return rep
+    delta = bf16_delta(parts, eps_h, eps_y)
+    rep["median_delta"] = float(np.median(delta))
+    y = parts["y"]
+    if out_f32:
+        lo, hi = want.astype(np.float64) - delta, want.astype(np.float64) + delta
+    else:
+        lo, hi = _rb_relu_outward(y, delta, False), _rb_relu_outward(y, delta, True)
+        if pool:
+            lo, hi = oracle.maxpool3s2(lo), oracle.maxpool3s2(hi)
+        rep["ambiguous"] = float(np.mean(lo != hi))
+    g = got.astype(np.float64)
+    dist = np.maximum(lo - g, g - hi)               # > 0: outside the interval by that much
+    dist = np.where(np.isfinite(g), dist, np.inf)
+    over = dist > 0
+    err = np.abs(g - want)
+    rep["max_err"] = float(np.where(np.isfinite(err), err, np.inf).max())
+    rep["flips"] = float(np.mean(got != want))
+    rep["n_over"] = int(over.sum())
+    i, c, yy, x = (int(v) for v in np.unravel_index(int(np.argmax(dist)), dist.shape))
+    rep["worst"] = (i, c, yy, x)
+    rep["frames_over"] = [k for k in range(n) if over[k].any()]
+    vacuous = (rep["median_delta"] > ATOL) if out_f32 else (rep["ambiguous"] > BF16_MAX_AMBIGUOUS)
+    rep["ok"] = rep["n_over"] == 0 and not vacuous
+    share = ("median delta %.3g" % rep["median_delta"]) if out_f32 else ("%.2f %% ambiguous" % (100 * rep["ambiguous"]))
+    if rep["n_over"]:
+        where = ""
+        if tile:
+            th, tw = tile
+            where = ", row %d col %d of %d x %d tile (%d, %d)" % (yy % th, x % tw, th, tw, yy // th, x // tw)
+        y_at = ("max-pooled from y around (%d, %d)" % (2 * yy, 2 * x)) if pool else ("y %r, delta %.3g" % (float(y[i, c, yy, x]), float(delta[i, c, yy, x])))
+        rep["message"] = ("%s: %d of %d elements outside their interval in frame(s) %s; worst: device %r, accepted [%r, %r], "
+                          "emulation %r (%s) at frame %d channel %d (chunk of 64: %d, lane %d) y %d x %d -- y mod 16 = %d, "
+                          "x mod 16 = %d%s, row %d of the stacked image (%d rows per frame), map %d x %d; %s" % (
+                              name, rep["n_over"], dist.size, rep["frames_over"], float(got[i, c, yy, x]), float(lo[i, c, yy, x]),
+                              float(hi[i, c, yy, x]), float(want[i, c, yy, x]), y_at, i, c, c // 64, c % 64, yy, x, yy % 16, x % 16,
+                              where, i * h + yy, h, h, w, share))
+    elif vacuous:
+        rep["message"] = "%s: the check is too wide to mean anything here: %s (EPS_h %.3g, EPS_y %.3g)" % (name, share, eps_h, eps_y)
+    else:
+        rep["message"] = "%s: every element inside its interval; %.3f %% differ from the emulation, max %.3g; %s" % (
+            name, 100 * rep["flips"], rep["max_err"], share)
+    return rep
+
+
+def check_bf16_layers(engine, frames, sd, tag, launches=None, rows=None, tiles=None):
+    """check_layers for a dtype="bf16" engine, after engine.forward(frames): every tensor of engine.ACTIVATIONS (without
+    the descriptor head's where it is disabled), every frame, each from the device's own input tensor(s), by
+    compare_bf16_layer with the EPS of bf16_eps on those inputs.  Prints one line per layer, appends the figures to `rows`,
+    raises AssertionError with every failing layer's message.  `tiles`: {tensor: (TH, TW)} for the messages."""
+    frames = np.ascontiguousarray(frames, np.float32)
+    n = frames.shape[0]
+    with_desc = getattr(engine, "descriptor_enabled", True)
+    names = [t for t in engine.ACTIVATIONS if with_desc or not (t.startswith("desc") or t == "up")]
+    dev = {name: engine.activation(name, 0, n).cpu().numpy() for name in names}
+    dev["frames"] = frames
+    graph = dict(oracle.BF16_LAYERS)
+    graph["pool"] = ("frames",)
+    kernels = layer_kernels(launches or [])
+    failures = []
+    for name in names:
+        inputs = [dev[i] for i in graph[name]]
+        parts = oracle.bf16_layer_parts(name, inputs, sd)
+        eps_h, eps_y, e_h, e_y = bf16_eps(name, inputs, sd, parts)
+        rep = compare_bf16_layer(name, dev[name], parts, eps_h, eps_y, tile=(tiles or {}).get(name))
+        amb = "median delta %.3e" % rep["median_delta"] if rep["ambiguous"] is None else "ambiguous %.3f %%" % (100 * rep["ambiguous"])
+        print("layer-isolated bf16 | %s | %s | %s | flips %.4f %% | %s | max err %.3e | E_ref h %.3e y %.3e | EPS h %.3e y %.3e" % (
+            tag, name, kernels[name], 100 * rep["flips"], amb, rep["max_err"], e_h, e_y, eps_h, eps_y))
+        if rows is not None:
+            rows.append(dict(rep, tag=tag, kernel=kernels[name], e_ref_h=e_h, e_ref_y=e_y))
+        if not rep["ok"]:
+            failures.append("%s [%s]: %s" % (tag, kernels[name], rep["message"]))
+    assert not failures, "\n".join(failures)
 
 
 # ---------------------------------------------------------------------------------------------------------------

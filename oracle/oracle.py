@@ -157,43 +157,83 @@ def _bias(t):
     return t.astype(np.float32)[None, :, None, None]
 
 
+def maxpool3s2(a):
+    """[B,C,h,w] float32 -> the 3 x 3, stride-2, padding-1 maximum [B,C,h/2,w/2] (exact)."""
+    a = np.ascontiguousarray(a, np.float32)
+    b, c, h, w = a.shape
+    out = np.empty((b, c, h // 2, w // 2), np.float32)
+    lib().oracle_maxpool3s2(_p(a), _p(out), b, c, h, w)
+    return out
+
+
+def bf16_folded_weights(name, sd, gray=False):
+    """The BatchNorm-folded bf16 weights and float biases of one layer of the FPC_BF16 plan, as the product packs them.
+    "pool": the stem's (w [64,3,7,7] -- [64,1,7,7], the three filters summed in double, for gray frames -- and bias [64]);
+    "up": (wt [256,128,3,3], bias [128]); a block: (w1, b1, w2, wp or None, b2 (+ the projection's)), stride."""
+    if name == "pool":
+        s, t = _fold(sd, "encoder.bn1")
+        w = sd["encoder.conv1.weight"]
+        if gray:
+            w = w.astype(np.float64)
+            w = w[:, 0:1] + w[:, 1:2] + w[:, 2:3]
+        return _wq(w, s), t.astype(np.float32)
+    if name == "up":     # ConvTranspose2d(256, 128, 3, 2, 1, 1) + bias, bn, relu (superpoint.py:45-47,55-57)
+        s, t = _fold(sd, "descriptor.bn")
+        wt = round_bf16((sd["descriptor.up_sample.weight"].astype(np.float64) * s[None, :, None, None]).astype(np.float32))
+        return wt, (sd["descriptor.up_sample.bias"].astype(np.float64) * s + t).astype(np.float32)
+    p, stride, proj, _ = _BF16_BLOCKS[name]
+    s1, t1 = _fold(sd, p + ".bn1")
+    s2, t2 = _fold(sd, p + ".bn2")
+    wp = None
+    if proj:
+        sp, tp = _fold(sd, p + ".identity_downsample.1")
+        wp, t2 = _wq(sd[p + ".identity_downsample.0.weight"], sp), t2 + tp
+    return (_wq(sd[p + ".conv1.weight"], s1), t1.astype(np.float32), _wq(sd[p + ".conv2.weight"], s2), wp,
+            t2.astype(np.float32)), stride
+
+
+def bf16_layer_parts(name, inputs, sd):
+    """The pieces of ONE tensor of the FPC_BF16 plan on given input tensor(s) (oracle/layer_check.py::compare_bf16_layer
+    bounds the device's tensor from them) -> dict:
+      y        the output before ReLU and rounding (float, from double accumulation).  "pool": the stem's convolution + bias
+               at half resolution, before ReLU and the max-pool; "up": the transposed convolution + bias;
+      out_f32  whether the mode stores relu(y) as it is (det.1) or rounded to bf16;
+      v, h, w2 (blocks only) conv1 + bias before ReLU, h = round_bf16(relu(v)), the folded bf16 weight [cout,cmid,1,1] of conv2.
+    "pool" takes the frames ([B,3,H,W], or [B,1,H,W] gray); every other input is rounded to bf16 where the kernel reads it."""
+    x = round_bf16(np.ascontiguousarray(np.concatenate(inputs, 1) if len(inputs) > 1 else inputs[0], np.float32))
+    if name == "pool":
+        w, t = bf16_folded_weights("pool", sd, gray=x.shape[1] == 1)
+        return {"y": _conv2d(x, w, 2, 3) + t[None, :, None, None], "out_f32": False}
+    if name == "up":
+        wt, bt = bf16_folded_weights("up", sd)
+        b, _, h, w = x.shape
+        up = np.empty((b, 128, 2 * h, 2 * w), np.float32)
+        lib().oracle_conv_transpose2d(_p(x), _p(np.ascontiguousarray(wt)), _p(bt), _p(up), b, 256, h, w, 128)
+        return {"y": up, "out_f32": False}
+    (w1, b1, w2, wp, b2), stride = bf16_folded_weights(name, sd)
+    v = _conv2d(x, w1, stride, 1) + b1[None, :, None, None]
+    h = round_bf16(_relu(v))
+    y = _conv2d(h, w2, 1, 0)
+    if wp is not None:
+        # one fp32 accumulator over [h | x] on the device; here two double-accumulated halves added in float
+        y = y + _conv2d(x, wp, stride, 0) + b2[None, :, None, None]
+    else:
+        y = y + b2[None, :, None, None] + x
+    return {"v": v, "h": h, "y": y, "w2": w2, "out_f32": _BF16_BLOCKS[name][3]}
+
+
 def bf16_emulated_stem(image, sd):
     """frames -> the pooled stem output ("pool") before it is stored (the device stores it as bf16: round_bf16 of
     this): bf16 frame and weights, fp32 accumulation / bias / ReLU / max-pool."""
-    image = np.ascontiguousarray(image, np.float32)
-    b, _, hh, ww = image.shape
-    s, t = _fold(sd, "encoder.bn1")
-    st = _relu(_conv2d(round_bf16(image), _wq(sd["encoder.conv1.weight"], s), 2, 3) + _bias(t))
-    x0 = np.empty((b, 64, hh // 4, ww // 4), np.float32)
-    lib().oracle_maxpool3s2(_p(np.ascontiguousarray(st)), _p(x0), b, 64, hh // 2, ww // 2)
-    return x0
+    return maxpool3s2(_relu(bf16_layer_parts("pool", [image], sd)["y"]))
 
 
 def bf16_emulated_layer(name, inputs, sd):
     """ONE layer of the FPC_BF16 plan on given input tensor(s) [B,C,h,w] (float32 arrays; values the mode keeps in bf16
     are rounded here where the kernel rounds them, so feeding the device's own tensors back in is exact)."""
-    x = round_bf16(np.ascontiguousarray(np.concatenate(inputs, 1) if len(inputs) > 1 else inputs[0], np.float32))
-    if name == "up":     # ConvTranspose2d(256, 128, 3, 2, 1, 1) + bias, bn, relu (superpoint.py:45-47,55-57)
-        s, t = _fold(sd, "descriptor.bn")
-        wt = round_bf16((sd["descriptor.up_sample.weight"].astype(np.float64) * s[None, :, None, None]).astype(np.float32))
-        bt = (sd["descriptor.up_sample.bias"].astype(np.float64) * s + t).astype(np.float32)
-        b, _, h, w = x.shape
-        up = np.empty((b, 128, 2 * h, 2 * w), np.float32)
-        lib().oracle_conv_transpose2d(_p(x), _p(np.ascontiguousarray(wt)), _p(bt), _p(up), b, 256, h, w, 128)
-        return round_bf16(_relu(up))
-    p, stride, proj, out_f32 = _BF16_BLOCKS[name]
-    s1, t1 = _fold(sd, p + ".bn1")
-    s2, t2 = _fold(sd, p + ".bn2")
-    h = round_bf16(_relu(_conv2d(x, _wq(sd[p + ".conv1.weight"], s1), stride, 1) + _bias(t1)))
-    y = _conv2d(h, _wq(sd[p + ".conv2.weight"], s2), 1, 0)
-    if proj:
-        sp, tp = _fold(sd, p + ".identity_downsample.1")
-        # one fp32 accumulator over [h | x] on the device; here two double-accumulated halves added in float
-        y = y + _conv2d(x, _wq(sd[p + ".identity_downsample.0.weight"], sp), stride, 0) + _bias(t2 + tp)
-    else:
-        y = y + _bias(t2) + x
-    y = _relu(y)
-    return y if out_f32 else round_bf16(y)
+    parts = bf16_layer_parts(name, inputs, sd)
+    y = _relu(parts["y"])
+    return y if parts["out_f32"] else round_bf16(y)
 
 
 # ---------------------------------------------------------------------------------------------------------------

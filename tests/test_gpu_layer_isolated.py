@@ -14,6 +14,7 @@ plain fp32 on the CPU (E_ref); nothing is asserted from that ratio -- DESIGN.md 
 
 Weights: seed 3, dustbin_bias 4.0; frames: synth.make_batch(11, n, h, w); fp32, arch "resnet".
 """
+import os
 import re
 
 import pytest
@@ -67,7 +68,9 @@ def ran(kernels, want):
 L1 = ("layer1.0", "layer1.1")
 C128 = ("layer2.1", "desc_out.0", "desc_out.1")
 DET = ("det.0", "det.1")
-# id -> (h, w, frames, Engine keywords, {kernel the case is there for: the tensors it must have written}, kernels that must NOT run)
+# id -> (h, w, frames, Engine keywords, {kernel the case is there for: the tensors it must have written}, kernels that must NOT run
+#        [, environment of the Engine's creation])
+W36_8, W36_16 = {"FPC_W36_CUS": "8"}, {"FPC_W36_CUS": "16"}
 CASES = {
     "stacked_walk": (160, 192, 5, dict(plan_flags=[NLT]), {STACKED: C128, "wblock36p_dust_kernel<2, 8, 3>": DET}, []),
     "stacked_walk_other_seams": (224, 192, 4, dict(plan_flags=[NLT]), {STACKED: C128, "wblock36p_dust_kernel<4, 4, 3>": DET}, []),
@@ -99,19 +102,62 @@ CASES = {
     "detector_gen1": (176, 208, 2, dict(plan_flags=[flag_of("DETECTOR_GEN1"), NLT]), {"wblock_mfma_kernel<*, 3, 72>": DET, PAIRED64: L1}, ["wblock36p_dust*", "wblock36_dust*"]),
     "stem_round3": (160, 192, 1, dict(plan_flags=[flag_of("STEM_ROUND3")]), {"stem_pool_kernel": ("pool",)}, ["stem_pool2_kernel"]),
     "conv_round1": (176, 208, 2, dict(plan_flags=[flag_of("CONV_ROUND1")]), {"conv_mfma_kernel<3, 20, 1, 1, *": ("desc_in.1",), "conv_mfma_kernel<3, 20, 1, 2, *": ("up",)}, ["conv2_mfma*"]),
+    # the F(4x4,3x3) kernels' XCD-chunked tile walk: FPC_W36_CUS caps a launch at 8 (16) workgroups, one (two) per XCD, and
+    # every launch named here has more tiles than that (run_case asserts it from the geometry), so its workgroups walk
+    # several.  (wconv36p_kernel<8, 2, 3> and the 1/16-resolution maps have one or two tiles at these sizes: not named.)
+    "stacked_walk_w36_8": (160, 192, 5, dict(plan_flags=[NLT]), {STACKED: C128, "wblock36p_dust_kernel<2, 8, 3>": DET}, [], W36_8),
+    "frame_by_frame_128_w36_8": (224, 192, 3, dict(plan_flags=[NLT]), {"wblock36_kernel<2, 4, 4>": C128}, [STACKED], W36_8),
+    "paired_64_w36_8": (224, 160, 1, dict(plan_flags=[NLT]), {PAIRED64: L1}, [CONV82], W36_8),
+    "conv_8x2_tiles_w36_8": (288, 128, 1, dict(plan_flags=[NLT]), {"wblock36p_kernel<2, 8, 3>": L1}, [], W36_8),
+    "w36_one_wave_w36_8": (176, 208, 3, dict(plan_flags=[flag_of("W36_ONE_WAVE"), NLT]), {"wblock36_kernel<1, 4, 4>": L1, "wblock36_dust_kernel<2, 8>": DET}, [], W36_8),
+    "stacked_walk_w36_16": (160, 192, 8, dict(plan_flags=[NLT]), {STACKED: C128, "wblock36p_dust_kernel<2, 8, 3>": DET}, [], W36_16),
+    # wblock16_kernel's persistent walk (persist_min_tiles: from one tile per CU on) on layer 1 of the latency plan
+    "latency_persistent_layer1": (176, 208, 11, dict(), {"wblock16_kernel<4, *": L1}, []),
 }
+MAP_DIVISOR = {t: 4 for t in L1}
+MAP_DIVISOR.update({t: 8 for t in C128 + DET})
+
+
+def tiles_of(sym, tensor, h, w, n):
+    """Tiles of the launch of `sym` that writes `tensor` for n frames of h x w: a generation-3 workgroup takes 16 Winograd
+    tiles of 4 x 4 pixels arranged TYT x TXT (wblock36s_kernel: of the n frames stacked into one image); wblock16_kernel<NCG,
+    TH> takes TH x 16 pixels."""
+    mh, mw = h // MAP_DIVISOR[tensor], w // MAP_DIVISOR[tensor]
+    nums = [int(v) for v in re.findall(r"\d+", sym.partition("<")[2])]
+    if sym.startswith("wblock16_kernel"):
+        return -(-mh // nums[1]) * -(-mw // 16) * n
+    tyt, txt = nums[1:3] if sym.startswith(("wblock36_kernel", "wblock36s_kernel")) else nums[0:2]
+    if sym.startswith("wblock36s_kernel"):
+        return -(-n * mh // (4 * tyt)) * -(-mw // (4 * txt))
+    return -(-mh // (4 * tyt)) * -(-mw // (4 * txt)) * n
+
+
+def engine_of(cid):
+    """The Engine of case `cid`, created under the case's environment (read at creation), weights loaded."""
+    from fpc_amd.engine import Engine
+    h, w, n, kw = CASES[cid][:4]
+    env = CASES[cid][6] if len(CASES[cid]) > 6 else {}
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        e = Engine(h, w, max_batch=n, **kw)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    e.load_state_dict(SD)
+    return e
 _launches = {}     # case id -> [(op name, kernel symbol)] of its forward
 
 
 def launches_of_case(cid, engine=None):
     """The launches of case `cid`: as recorded when it ran, or (the case deselected) from a forward of its own."""
     if cid not in _launches:
-        from fpc_amd.engine import Engine
-        h, w, n, kw = CASES[cid][:4]
-        e = engine or Engine(h, w, max_batch=n, **kw)
+        h, w, n = CASES[cid][:3]
+        e = engine or engine_of(cid)
         try:
-            if engine is None:
-                e.load_state_dict(SD)
             _launches[cid] = launches_of(e, frames_of(h, w, n))
         finally:
             if engine is None:
@@ -119,13 +165,12 @@ def launches_of_case(cid, engine=None):
     return _launches[cid]
 
 
-def run_case(cid):
-    from fpc_amd.engine import Engine
-    h, w, n, kw, there_for, absent = CASES[cid]
+def run_case(cid, more_tiles_than=0):
+    """`more_tiles_than`: every launch the case is there for must have more tiles than that, by tiles_of."""
+    h, w, n, kw, there_for, absent = CASES[cid][:6]
     frames = frames_of(h, w, n)
-    e = Engine(h, w, max_batch=n, **kw)
+    e = engine_of(cid)
     try:
-        e.load_state_dict(SD)
         launches = launches_of_case(cid, e)
         kernels = [s for _, s in launches]
         wrote = layer_check.layer_kernels(launches)
@@ -133,6 +178,9 @@ def run_case(cid):
             assert ran(kernels, k), (cid, k, sorted(set(kernels)))
             for t in tensors:
                 assert ran(wrote[t].split(" + "), k), (cid, k, t, wrote[t])
+                if more_tiles_than:
+                    sym = next(x for x in wrote[t].split(" + ") if ran([x], k))
+                    assert tiles_of(sym, t, h, w, n) > more_tiles_than, (cid, sym, t, tiles_of(sym, t, h, w, n))
         for k in absent:
             assert not ran(kernels, k), (cid, k)
         e.forward(frames)
@@ -189,6 +237,27 @@ def test_latency_plan(cid):
     (ConvTranspose, layer_in.1's 1 x 1) and the stem: stem_pool2_kernel where the stem's 80 x 96 map is whole 16 x 16 tiles,
     stem_pool_kernel where it is not (88 x 104)."""
     run_case(cid)
+
+
+# ---------------------------------------------------------------- the persistent tile walks: workgroups that take several tiles
+@pytest.mark.parametrize("cid", ["stacked_walk_w36_8", "frame_by_frame_128_w36_8", "paired_64_w36_8", "conv_8x2_tiles_w36_8",
+                                 "w36_one_wave_w36_8", "stacked_walk_w36_16"])
+def test_w36_tile_walk(cid):
+    """Cases above once more with FPC_W36_CUS = 8 (one of them 16): a generation-3 launch then has 8 (16) workgroups, XCD k's
+    walking the tiles [k ceil(T / 8), (k + 1) ceil(T / 8)) -- several each, the last XCDs fewer or none -- where every other
+    case of this file gives each workgroup one tile.  w36_one_wave runs three frames here: the detector's 8 x 32 tiles are 3
+    per frame on a 22 x 26 map."""
+    cap = int(CASES[cid][6]["FPC_W36_CUS"])
+    run_case(cid, more_tiles_than=cap)
+
+
+def test_latency_plan_persistent_layer1():
+    """176 x 208, eleven frames on the default (latency) plan: wblock16_kernel<4, 8> on layer 1 has 6 x 4 tiles of 8 x 16 per
+    44 x 52 map, 264 in the launch -- at least one per CU, from where the launch is persistent (persist_min_tiles = 1): one
+    workgroup per CU, the first ones walking a second tile."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    run_case("latency_persistent_layer1", more_tiles_than=cus - 1)
 
 
 # ---------------------------------------------------------------- kernels still shipped behind a flag

@@ -34,6 +34,7 @@ VARIABLES = (
     "FPC_STEM_LEAN", "FPC_WINOGRAD_GEN", "FPC_LATENCY_TILES", "FPC_CONVT_FUSED", "FPC_FUSE_SOFTMAX", "FPC_NMS_CHUNKED",
     "FPC_STREAMS", "FPC_FUSE", "FPC_WINOGRAD", "FPC_XCD_ORDER", "FPC_MIN_SUB", "FPC_PERSIST_MIN", "FPC_WINOGRAD_DET",
     "FPC_WINOGRAD_IN1", "FPC_FUSE_STEM", "FPC_NMS_PASSES", "FPC_NMS_G", "FPC_L1_T816", "FPC_SPLIT_HEADS", "FPC_NMS_ASIDE",
+    "FPC_BF16_GRID",
 )
 # each flag with the variable that sets the same option, and the value of it that means the OTHER way
 FLAG_AGAINST_VARIABLE = (
@@ -64,7 +65,7 @@ def restated(dtype=F32, arch=RESNET, num_streams=0, pf=0, nms_round_launches=0, 
     o = dict(nms_aside=1, split_heads=0, min_sub=8, persist_min_tiles=1, xcd_order=1, nms_passes=2, fuse_softmax=1,
              convt_fused=1, nms_one_workgroup=0, nms_g=0, fuse_stem_pool=1, conv_lean=1, stem_lean=1, stem2=0, layer1_t816=0,
              winograd_in1=1, winograd_det=1, w36_cus=0, tiles_round6=1, w36_paired=1, winograd_det_gen3=1, winograd=1,
-             latency_tiles=1, winograd_gen=3, fuse_blocks=1, guard_zones=0)
+             latency_tiles=1, winograd_gen=3, fuse_blocks=1, guard_zones=0, bf16_grid=0)
     nsub = min(8, num_streams) if num_streams > 0 else (3 if split else 2)
     o["fuse_blocks"] = not on("NO_FUSED_BLOCKS")
     o["guard_zones"] = on("GUARD_ZONES")
@@ -75,6 +76,7 @@ def restated(dtype=F32, arch=RESNET, num_streams=0, pf=0, nms_round_launches=0, 
     o["tiles_round6"] = not on("TILES_ROUND5")
     if get("FPC_TILES_ROUND6") is not None: o["tiles_round6"] = atoi(get("FPC_TILES_ROUND6")) != 0
     if get("FPC_W36_CUS") is not None: o["w36_cus"] = max(0, atoi(get("FPC_W36_CUS")))
+    if get("FPC_BF16_GRID") is not None: o["bf16_grid"] = max(0, atoi(get("FPC_BF16_GRID")))      # (added with the option)
     if get("FPC_WINOGRAD_DET_GEN") is not None: o["winograd_det_gen3"] = atoi(get("FPC_WINOGRAD_DET_GEN")) >= 3
     o["winograd"] = not on("NO_WINOGRAD")
     o["winograd_det"] = not on("NO_WINOGRAD_DETECTOR")
@@ -152,7 +154,7 @@ def test_defaults(driver):
     got = check(driver)
     assert got["nsub"] == 2 and got["nside"] == 2 and got["split_heads"] == 1 and got["nms_aside"] == 0
     assert got["min_sub"] == 8 and got["nms_passes"] == 2 and got["winograd_gen"] == 3 and got["persist_min_tiles"] == 1
-    assert len(got) == 28
+    assert len(got) == 29 and got["bf16_grid"] == 0
 
 
 @pytest.mark.parametrize("flag", sorted(FLAGS))
@@ -213,6 +215,9 @@ def test_quirks(driver):
     # FPC_W36_CUS at least 0
     for v, want in (("-8", 0), ("0", 0), ("96", 96)):
         assert check(driver, env={"FPC_W36_CUS": v})["w36_cus"] == want
+    # FPC_BF16_GRID at least 0
+    for v, want in (("-8", 0), ("0", 0), ("8", 8), ("16", 16), ("1000000", 1000000)):
+        assert check(driver, dtype=BF16, env={"FPC_BF16_GRID": v})["bf16_grid"] == want
     # FPC_STREAMS clamped to 1..8, over num_streams
     for v, want in (("0", 1), ("-1", 1), ("1", 1), ("4", 4), ("8", 8), ("9", 8)):
         assert check(driver, num_streams=3, env={"FPC_STREAMS": v})["nsub"] == want
@@ -240,3 +245,22 @@ def test_stream_options(driver, arch, dtype):
         for num_streams in (0, 1, 3):
             got = check(driver, dtype=dtype, arch=arch, num_streams=num_streams, env=env)
             assert not (got["split_heads"] and got["nms_aside"])
+
+
+def test_bf16_persistent_grid(driver):
+    """bf16_persistent_grid(tiles, resident, parts, cap): cap 0 is the rule as it stood -- min(ceil8(T), max(8, resident /
+    parts / 8 * 8)) -- and a cap stands in for `resident`, never below 8 per part, always a multiple of 8."""
+    def grid(tiles, resident, parts, cap):
+        out = subprocess.run([driver, "grid"] + [str(v) for v in (tiles, resident, parts, cap)], check=True, capture_output=True,
+                             text=True).stdout
+        return int(out)
+
+    for tiles in (1, 7, 8, 9, 50, 175, 512, 513, 5000):
+        for resident in (256, 512, 768):
+            for parts in (1, 2):
+                old = min((tiles + 7) // 8 * 8, max(8, resident // parts // 8 * 8))
+                assert grid(tiles, resident, parts, 0) == old
+                for cap in (1, 8, 15, 16, 17, 24, 100000):
+                    want = min((tiles + 7) // 8 * 8, max(8, cap // parts // 8 * 8))
+                    assert grid(tiles, resident, parts, cap) == want and want % 8 == 0 and want >= 8
+    assert grid(175, 512, 1, 8) == 8 and grid(175, 512, 1, 16) == 16 and grid(10, 512, 2, 8) == 8 and grid(10, 512, 2, 16) == 8
