@@ -50,6 +50,8 @@ SYMBOLS = [
     "fpc_default_refine_params", "fpc_refine_pose", "fpc_refine_pose_frames", "fpc_refine_pose_bank",
     "fpc_pnp_topk_reserve", "fpc_pnp_bank_topk", "fpc_p3p_bank_topk", "fpc_fundamental_bank_topk",
     "fpc_essential_bank_topk",
+    "fpc_default_window_params", "fpc_window_reserve", "fpc_refine_window", "fpc_refine_window_frames",
+    "fpc_refine_window_bank",
 ]
 
 ABI_VERSION = 4
@@ -142,6 +144,17 @@ class FpcRefineParams(ctypes.Structure):
                 ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
                 ("reproj_threshold", ctypes.c_float), ("min_parallax_deg", ctypes.c_float), ("iterations", ctypes.c_int),
                 ("lambda0", ctypes.c_float), ("min_front", ctypes.c_int)]
+
+
+class FpcWindowParams(ctypes.Structure):
+    """fpc_window_params (include/fpc.h)."""
+    _fields_ = [("q_fx", ctypes.c_float), ("q_fy", ctypes.c_float), ("q_cx", ctypes.c_float), ("q_cy", ctypes.c_float),
+                ("t_fx", ctypes.c_float), ("t_fy", ctypes.c_float), ("t_cx", ctypes.c_float), ("t_cy", ctypes.c_float),
+                ("reproj_threshold", ctypes.c_float), ("iterations", ctypes.c_int), ("lambda0", ctypes.c_float),
+                ("min_obs", ctypes.c_int)]
+
+
+WINDOW_MAX_FRAMES = 16        # include/fpc.h FPC_WINDOW_MAX_FRAMES
 
 
 class FpcSim3Params(ctypes.Structure):
@@ -311,6 +324,13 @@ def load():
     l.fpc_refine_pose.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, fp] + [vp] * 6
     l.fpc_refine_pose_frames.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, fp] + [vp] * 6
     l.fpc_refine_pose_bank.argtypes = [vp, ci, vp, vp, vp, vp, fp] + [vp] * 6
+    wp = ctypes.POINTER(FpcWindowParams)
+    l.fpc_default_window_params.argtypes = [wp]
+    l.fpc_window_reserve.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
+    # an observation source and the key, then (R_in_dev, t_in_dev, params) and the seven outputs
+    l.fpc_refine_window.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, wp] + [vp] * 7
+    l.fpc_refine_window_frames.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, wp] + [vp] * 7
+    l.fpc_refine_window_bank.argtypes = [vp, ci, vp, vp, vp, vp, vp, wp] + [vp] * 7
     l.fpc_bank_topk_reserve.argtypes =[vp, ci, ctypes.POINTER(ctypes.c_size_t)]
     l.fpc_match_bank_topk.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp, vp]
     l.fpc_homography_bank_topk.argtypes = [vp, ci, ci, vp, vp, rp, vp, vp, vp, vp, vp]

@@ -52,6 +52,7 @@
 #include "essential_ransac.h"
 #include "landmarks.h"
 #include "refine_pose.h"
+#include "refine_window.h"
 #include "homography.h"
 #include "weights.h"
 #include "plan_options.h"
@@ -518,7 +519,7 @@ struct Timing {
 };
 
 // One device allocation of a context: carved by a Carver, zeroed, its canary zones (offset, bytes) filled where the
-// context has them.  A context owns six (fpc_ctx::slabs).
+// context has them.  A context owns seven (fpc_ctx::slabs).
 using GuardZones = std::vector<std::pair<size_t, size_t>>;
 struct Carver;
 struct Slab {
@@ -576,11 +577,11 @@ struct fpc_ctx {
   bool weights_loaded = false;
   bool plan_error = false;           // a layer asked for a kernel instance that does not exist (fpc_create -> FPC_E_INVALID)
 
-  // The six device allocations a context can own: `slab` for all activations / results (build_plan), the others made
+  // The seven device allocations a context can own: `slab` for all activations / results (build_plan), the others made
   // by the call that reserves them.  bank_slab, topk_slab, pnp_topk_slab and lm_slab go with the bank; fpc_destroy frees
   // what is left.
-  Slab slab, bank_slab, topk_slab, pnp_slab, lm_slab, pnp_topk_slab;
-  Slab* const slabs[6] = {&slab, &bank_slab, &topk_slab, &pnp_slab, &lm_slab, &pnp_topk_slab};
+  Slab slab, bank_slab, topk_slab, pnp_slab, lm_slab, pnp_topk_slab, window_slab;
+  Slab* const slabs[7] = {&slab, &bank_slab, &topk_slab, &pnp_slab, &lm_slab, &pnp_topk_slab, &window_slab};
   float *stem_out, *x0, *h4, *x1, *x2, *h8, *x3, *cat, *dh, *dproj, *d0, *lg;
   float *h16, *y16a, *y16b, *lo_h, *lo0, *desc_map, *desc_in_nhwc;
   float* prob;
@@ -629,6 +630,10 @@ struct fpc_ctx {
   unsigned long long* pnp_topk_best = nullptr;
   // landmarks of the bank's rows (fpc_bank_landmarks_reserve): float4 [slots][rows], w = 1 valid / 0; freed with the bank
   float4* lm_xyzw = nullptr;
+  // local bundle adjustment (fpc_window_reserve, refine_window.h): an allocation of its own, freed by fpc_destroy -- the
+  // observation table and pixels [16][cap], the key pixels, flags and stepped points [cap], the chunks' partial sums and
+  // the pose state
+  RwArgs rw{};
   int pts_n = 0;                     // frames of the last call that produced keypoints (fpc_detect*, fpc_get_points)
   bool pts_desc = false;             // ... and whether it sampled their descriptors
 
@@ -5023,6 +5028,105 @@ int fpc_refine_pose_bank(fpc_ctx* c, int n, const int32_t* slot, const int32_t* 
   const HfArgs a = hf_args(c, n, p->reproj_threshold);
   if (int rc = pairs_bank(c, a, n, slot, match, nullptr)) return rc;
   return refine_launch(c, a, p, R_in, t_in, R, t, nfront, xyz, front, stats, c->cap);
+}
+
+// ---- local bundle adjustment of a key frame's landmarks over up to 16 frames (include/fpc.h; kernels in refine_window.h) -----
+int fpc_default_window_params(fpc_window_params* p) {
+  if (!p) return FPC_E_INVALID;
+  p->q_fx = p->q_fy = p->t_fx = p->t_fy = 500.0f;
+  p->q_cx = p->t_cx = 320.0f;
+  p->q_cy = p->t_cy = 240.0f;
+  p->reproj_threshold = 3.0f;
+  p->iterations = 8;
+  p->lambda0 = 1e-3f;
+  p->min_obs = 6;
+  return FPC_OK;
+}
+
+// The only call of the section that allocates or synchronises: an allocation of its own (nothing is carved: the plan hash,
+// the packed size and the bank's bytes are what they were).
+int fpc_window_reserve(fpc_ctx* c, size_t* bytes) {
+  if (!c || c->window_slab) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const size_t cap = c->cap, chunks = (cap + RW_CHUNK - 1) / RW_CHUNK;
+  Carver cv(c);
+  RwArgs& w = c->rw;
+  cv.into(&w.st, 1); cv.into(&w.tab, RW_FRAMES * cap); cv.into(&w.pix, RW_FRAMES * cap); cv.into(&w.kpix, cap);
+  cv.into(&w.lmk, cap); cv.into(&w.xd, cap * 3); cv.into(&w.xnew, cap * 3); cv.into(&w.part, chunks * RW_PART);
+  cv.into(&w.cpart, chunks); cv.into(&w.bad, chunks);
+  if (int rc = c->window_slab.allocate(c->stream, cv)) return rc;
+  if (bytes) *bytes = c->window_slab.bytes;
+  return FPC_OK;
+}
+
+static bool window_params_ok(const fpc_window_params* p) {
+  return p && camera_ok(p->q_fx, p->q_fy, p->q_cx, p->q_cy) && camera_ok(p->t_fx, p->t_fy, p->t_cx, p->t_cy) &&
+         threshold_ok(p->reproj_threshold) && p->iterations >= 1 && p->iterations <= 16 && std::isfinite(p->lambda0) &&
+         p->lambda0 > 0.f && p->min_obs >= 3;                    // (a NaN fails its comparison)
+}
+
+// what the three calls share behind their source's own checks: the arguments every source has, then the launches -- the
+// membership passes, C of the start, `iterations` times the attempt's five kernels (no-ops once the call has stopped on the
+// device), the result.  S rows of obs per frame.
+extern "C++" template <class Source>    // (this block is extern "C")
+static int window_launch(fpc_ctx* c, int n, const Source& src, const float* R_in, const float* t_in, const fpc_window_params* p,
+                         float* R, float* t, int32_t* nobs, float* xyz, uint8_t* kind, uint8_t* obs, float* stats, int S) {
+  if (!c->window_slab || n > FPC_WINDOW_MAX_FRAMES || !R_in || !t_in || !R || !t || !nobs || !xyz || !kind || !window_params_ok(p))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  RwArgs a = c->rw;
+  a.q_fx = p->q_fx; a.q_fy = p->q_fy; a.q_cx = p->q_cx; a.q_cy = p->q_cy;
+  a.t_fx = p->t_fx; a.t_fy = p->t_fy; a.t_cx = p->t_cx; a.t_cy = p->t_cy;
+  a.thr = p->reproj_threshold; a.iterations = p->iterations; a.lambda0 = p->lambda0; a.min_obs = p->min_obs;
+  a.n = n; a.cap = c->cap; a.S = S; a.xyz = xyz;
+  const int rows = (c->cap + 255) / 256, chunks = (c->cap + RW_CHUNK - 1) / RW_CHUNK;
+  hipStream_t st = c->stream;
+  HIPCHECK(hipMemsetAsync(a.tab, 0x7f, sizeof(int32_t) * RW_FRAMES * c->cap, st));
+  HIPCHECK(hipMemsetAsync(nobs, 0, sizeof(int32_t) * n, st));
+  if (obs) HIPCHECK(hipMemsetAsync(obs, 0, (size_t)n * S, st));
+  hipLaunchKernelGGL(rw_init_kernel<Source>, dim3(rows), dim3(256), 0, st, src, a, R_in, t_in);
+  hipLaunchKernelGGL(rw_members_kernel<Source>, dim3((S + 255) / 256, n), dim3(256), 0, st, src, a);
+  hipLaunchKernelGGL(rw_resolve_kernel<Source>, dim3(rows, n), dim3(256), 0, st, src, a);
+  hipLaunchKernelGGL(rw_finish_kernel, dim3(1), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(rw_cost_kernel, dim3(chunks), dim3(RW_CHUNK), 0, st, a, 0);
+  hipLaunchKernelGGL(rw_decide_kernel, dim3(1), dim3(256), 0, st, a, 1);
+  for (int it = 0; it < p->iterations; ++it) {
+    hipLaunchKernelGGL(rw_build_kernel, dim3(chunks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(rw_solve_kernel, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(rw_step_kernel, dim3(chunks), dim3(RW_CHUNK), 0, st, a);
+    hipLaunchKernelGGL(rw_cost_kernel, dim3(chunks), dim3(RW_CHUNK), 0, st, a, 1);
+    hipLaunchKernelGGL(rw_decide_kernel, dim3(1), dim3(256), 0, st, a, 0);
+  }
+  hipLaunchKernelGGL(rw_final_kernel, dim3(rows), dim3(256), 0, st, a, R, t, nobs, kind, obs, stats);
+  return launched();
+}
+
+int fpc_refine_window(fpc_ctx* c, int n, const float* xy, const int32_t* idx, const int32_t* nobs_in, int stride,
+                      const float* key_xy, const float* key_xyz, const uint8_t* key_valid, const int32_t* nkey,
+                      const float* R_in, const float* t_in, const fpc_window_params* p, float* R, float* t, int32_t* nobs,
+                      float* xyz, uint8_t* kind, uint8_t* obs, float* stats) {
+  if (!c || !xy || !idx || !nobs_in || !key_xy || !key_xyz || !nkey || !explicit_ok(c, n, stride)) return FPC_E_INVALID;
+  const RwExplicit src{xy, idx, nobs_in, stride, key_xy, key_xyz, key_valid, nkey, c->cap};
+  return window_launch(c, n, src, R_in, t_in, p, R, t, nobs, xyz, kind, obs, stats, stride);
+}
+
+int fpc_refine_window_frames(fpc_ctx* c, int n, const int32_t* key_xy, const int32_t* nkey, const float* key_xyz,
+                             const uint8_t* key_valid, const int32_t* match, const float* R_in, const float* t_in,
+                             const fpc_window_params* p, float* R, float* t, int32_t* nobs, float* xyz, uint8_t* kind,
+                             uint8_t* obs, float* stats) {
+  if (!c || !key_xy || !nkey || !key_xyz || !match || !frames_ok(c, n)) return FPC_E_INVALID;
+  const RwKey src{RwFrames{c->xy, c->count, match, c->cap}, key_xy, key_xyz, key_valid, nkey};
+  return window_launch(c, n, src, R_in, t_in, p, R, t, nobs, xyz, kind, obs, stats, c->cap);
+}
+
+int fpc_refine_window_bank(fpc_ctx* c, int n, const int32_t* key_slot, const int32_t* slot, const int32_t* match,
+                           const float* R_in, const float* t_in, const fpc_window_params* p, float* R, float* t, int32_t* nobs,
+                           float* xyz, uint8_t* kind, uint8_t* obs, float* stats) {
+  if (!c || !c->bank_slab || !key_slot || !match || !frames_ok(c, n)) return FPC_E_INVALID;
+  // (without landmark storage bank_lm is null: the key has no rows, and the call fails on the device)
+  const RwBank src{RwFrames{c->xy, c->count, match, c->cap}, key_slot, slot, c->bank.xy, c->bank.count, c->lm_xyzw, c->bank.rows,
+                   c->bank.slots};
+  return window_launch(c, n, src, R_in, t_in, p, R, t, nobs, xyz, kind, obs, stats, c->cap);
 }
 
 int fpc_results(fpc_ctx* c, fpc_device_results* out) {

@@ -1013,6 +1013,102 @@ class Engine:
         """refine_pose_bank_async, then host arrays."""
         return self._host(self.refine_pose_bank_async(n, slot, match, R, t, K_query, K_train, which, **params))
 
+    # -- local bundle adjustment of a key frame's landmarks over up to 16 frames (fpc_window_reserve / fpc_refine_window*) -------
+    def window_reserve(self):
+        """fpc_window_reserve: the window calls' observation table, partial sums and pose state; the only call of the family
+        that allocates.  Freed with the engine.  Returns the bytes it allocated."""
+        nbytes = ctypes.c_size_t(0)
+        _lib.check(self._l.fpc_window_reserve(self._ctx, ctypes.byref(nbytes)), "fpc_window_reserve")
+        return int(nbytes.value)
+
+    def _window_params(self, K_query, K_train, params):
+        return self._two_camera_params(_lib.FpcWindowParams, "fpc_default_window_params",
+                                       ("reproj_threshold", "iterations", "lambda0", "min_obs"), "window", K_query, K_train,
+                                       params)
+
+    def _window(self, name, n, source, R, t, p, stride, alias=False):
+        """fpc_<name>(ctx, n, *source, R_in, t_in, params, R, t, nobs, xyz, kind, obs, stats) -> (R float32 [n,3,3], t float32
+        [n,3], nobs int32 [n], xyz float32 [cap,3], kind uint8 [cap], obs bool [n,stride], stats float32 [4]) on the device.
+        alias: R and t are written over the input tensors."""
+        rm, tv = self._refine_in(n, R, t, None)
+        dev = self.torch_device
+        ro = rm.view(n, 3, 3) if alias else torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
+        to = tv if alias else torch.empty((n, 3), dtype=torch.float32, device=dev)
+        nobs = self._int32(n)
+        xyz = torch.empty((self.capacity, 3), dtype=torch.float32, device=dev)
+        kind = torch.empty((self.capacity,), dtype=torch.uint8, device=dev)
+        obs = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+        stats = torch.empty((4,), dtype=torch.float32, device=dev)
+        self._call(name, n, *source, rm, tv, ctypes.byref(p), ro, to, nobs, xyz, kind, obs, stats, inputs=(*source, rm, tv))
+        return ro, to, nobs, xyz, kind, obs.view(torch.bool), stats
+
+    def refine_window_async(self, xy, idx, nobs, key_xy, key_xyz, R, t, key_valid=None, K_query=None, K_train=None,
+                            alias=False, **params):
+        """fpc_refine_window: per frame the observed pixels xy (float32 [n,stride,2]) of the key's landmarks idx (int32
+        [n,stride]) with nobs int32 [n]; the key's pixels key_xy (float32 [k,2]), its landmarks key_xyz (float32 [k,3], or a
+        device pair (xyz, count)) and their flags key_valid (None: every finite row); the poses R, t of fpc_pnp_* -- device
+        tensors or host arrays -> device tensors (R [n,3,3], t [n,3], nobs [n], xyz [cap,3], kind uint8 [cap]: 1 refined, 2
+        copied unchanged, 0 none; obs bool [n,stride] by pair; stats [4]: rms before, rms after, attempts, accepted).
+        Parameters: reproj_threshold, iterations, lambda0, min_obs.  Needs window_reserve.  Does not synchronise."""
+        p = self._window_params(K_query, K_train, params)
+        xy = torch.as_tensor(xy).to(self.torch_device, torch.float32).contiguous()
+        idx = torch.as_tensor(idx).to(self.torch_device, torch.int32).contiguous()
+        nobs = torch.as_tensor(nobs).to(self.torch_device, torch.int32).contiguous()
+        if xy.dim() != 3 or xy.shape[2] != 2 or idx.shape != xy.shape[:2] or nobs.shape != (xy.shape[0],):
+            raise ValueError("xy must be [n,stride,2], idx [n,stride] and nobs [n]")
+        n, stride = int(xy.shape[0]), int(xy.shape[1])
+        lm, vl, kc = self._key_landmarks(key_xyz, key_valid)
+        kx = torch.as_tensor(key_xy).to(self.torch_device, torch.float32).contiguous()
+        if kx.dim() != 2 or kx.shape[1] != 2 or kx.shape[0] < lm.shape[0]:
+            raise ValueError("key_xy must be [k,2] with a row for each row of key_xyz")
+        return self._window("fpc_refine_window", n, (xy, idx, nobs, stride, kx, lm, vl, kc), R, t, p, stride, alias)
+
+    def refine_window(self, xy, idx, nobs, key_xy, key_xyz, R, t, key_valid=None, K_query=None, K_train=None, alias=False,
+                      **params):
+        """refine_window_async, then host arrays."""
+        return self._host(self.refine_window_async(xy, idx, nobs, key_xy, key_xyz, R, t, key_valid, K_query, K_train, alias,
+                                                   **params))
+
+    def refine_window_frames_async(self, n, match, R, t, key_xy, key_xyz, key_valid=None, K_query=None, K_train=None,
+                                   alias=False, **params):
+        """fpc_refine_window_frames: the frames of the last detect with their match table against the key frame whose pixels
+        are key_xy and whose landmarks are key_xyz / key_valid (as landmarks_frames_async), under pnp_frames_async's R, t ->
+        refine_window_async's outputs, obs bool [n,cap] by query row.  Does not synchronise."""
+        p = self._window_params(K_query, K_train, params)
+        kx, kc = self._key_xy(key_xy)
+        if kx is None:
+            raise ValueError("refine_window_frames needs key_xy")
+        lm, vl, _ = self._key_landmarks(key_xyz, key_valid)
+        if lm.shape[0] < kx.shape[0]:
+            raise ValueError("key_xyz needs a row for each row of key_xy")
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        return self._window("fpc_refine_window_frames", n, (kx, kc, lm, vl, match), R, t, p, self.capacity, alias)
+
+    def refine_window_frames(self, n, match, R, t, key_xy, key_xyz, key_valid=None, K_query=None, K_train=None, alias=False,
+                             **params):
+        """refine_window_frames_async, then host arrays."""
+        return self._host(self.refine_window_frames_async(n, match, R, t, key_xy, key_xyz, key_valid, K_query, K_train, alias,
+                                                          **params))
+
+    def refine_window_bank_async(self, n, key_slot, match, R, t, slot=None, K_query=None, K_train=None, alias=False, **params):
+        """fpc_refine_window_bank: refine_window_frames_async with the key's pixels and landmarks taken from bank slot
+        key_slot (an int, or a device tensor int32 [1], read on the device); slot (device int32 [n], match_bank_async's best,
+        or None): frame f takes part iff slot[f] is the key slot.  `xyz`, `kind` go into bank_store_landmarks(key_slot, xyz,
+        kind) as they are.  Does not synchronise."""
+        self._bank_info()
+        p = self._window_params(K_query, K_train, params)
+        if not isinstance(key_slot, torch.Tensor):
+            key_slot = torch.tensor([int(key_slot)], dtype=torch.int32, device=self.torch_device)
+        key_slot = self._dev_int32("key_slot", key_slot, "[1]", 1)
+        if slot is not None:
+            slot = self._dev_int32("slot", slot, "[n]", n)
+        match = self._dev_int32("match", match, "[n,%d]" % self.capacity, n, self.capacity)
+        return self._window("fpc_refine_window_bank", n, (key_slot, slot, match), R, t, p, self.capacity, alias)
+
+    def refine_window_bank(self, n, key_slot, match, R, t, slot=None, K_query=None, K_train=None, alias=False, **params):
+        """refine_window_bank_async, then host arrays."""
+        return self._host(self.refine_window_bank_async(n, key_slot, match, R, t, slot, K_query, K_train, alias, **params))
+
     # -- absolute pose from landmarks: RANSAC PnP (fpc_pnp_reserve / fpc_bank_*landmarks* / fpc_ransac_pnp / _frames / _bank) ----
     def pnp_reserve(self):
         """fpc_pnp_reserve: the PnP workspace (pair records, counts and best keys of max_batch problems); the only PnP call

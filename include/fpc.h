@@ -1585,7 +1585,8 @@ int fpc_landmarks_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32
  *    state lives in the caller's xyz.  Nothing is carved; the plan hash and the guard zones are what they were.
  *    fpc_match_bank, fpc_fundamental_bank, fpc_pose_bank, fpc_refine_pose_bank, fpc_bank_store, fpc_bank_store_landmarks needs
  *    no host call in between.  It works on a FPC_BANK_BF16 bank: it reads only xy and counts.
- *  - Not here: more than two views, robust kernels, refining the intrinsics, a cell-ordered variant.
+ *  - Not here: more than two views (fpc_refine_window_* below), robust kernels, refining the intrinsics, a cell-ordered
+ *    variant.
  * FPC_E_INVALID (nothing is written): everything the pose twins refuse for the arguments they share; a NULL R_in_dev /
  * t_in_dev / params / R_dev / t_dev / nfront_dev / xyz_dev; fx or fy not > 0 or any non-finite intrinsic; reproj_threshold
  * not > 0 (or not below 1e18); min_parallax_deg not in [0, 90); iterations outside 1 .. 16; lambda0 not > 0 or not finite;
@@ -1612,6 +1613,115 @@ int fpc_refine_pose_frames(fpc_ctx* ctx, int n, int pairing, const int32_t* key_
 int fpc_refine_pose_bank(fpc_ctx* ctx, int n, const int32_t* slot_dev, const int32_t* match_dev, const float* R_in_dev,
                          const float* t_in_dev, const fpc_refine_params* params, float* R_dev, float* t_dev,
                          int32_t* nfront_dev, float* xyz_dev, uint8_t* front_dev, float* stats_dev);
+
+/* --- local bundle adjustment: refine a key frame's landmarks over the frames that see them ---------------------------------
+ * Every landmark above comes from two views, and every pose against the map from one view with the landmarks held fixed.
+ * fpc_refine_window, fpc_refine_window_frames and fpc_refine_window_bank refine ONE key frame's landmarks and the poses of
+ * up to FPC_WINDOW_MAX_FRAMES frames that observe them, together, by damped Gauss-Newton steps (Levenberg-Marquardt) on the
+ * reprojection error in all views.  The inputs are what fpc_match_bank + fpc_pnp_bank leave on the device -- a match table
+ * per frame against the key and R, t per frame at the map's scale -- and xyz_dev, kind_dev go back into
+ * fpc_bank_store_landmarks(slot, xyz_dev, kind_dev) as they are: the chain improves its own map without a host call.
+ *  - Window: n frames of the last results, 1 <= n <= min(max_batch, FPC_WINDOW_MAX_FRAMES): the reduced system is at most
+ *    96 x 96 in fp64 and is solved in LDS.
+ *  - Landmarks: in the key camera's frame, as fpc_bank_store_landmarks defines them; valid by its rule (the flag is set and the
+ *    three coordinates are finite).  Explicit: key_xy_dev float32 [P][2], key_xyz_dev float32 [P][3], key_valid_dev uint8 [P]
+ *    or NULL, nkey_dev[0] (clamped to the capacity) <= P.  Frames: the key arguments of fpc_landmarks_frames.  Bank: slot
+ *    key_slot_dev[0], read on the device; a slot outside [0, slots) or a bank without landmark storage leaves the key without
+ *    rows, and the call fails as below.
+ *  - Poses: PnP's convention, Y = R_f X + t_f maps into frame f's camera; what fpc_pnp_* / fpc_p3p_* wrote goes in unchanged.
+ *  - Observations of frame f.  Frames and bank: query row i < count[f] with 0 <= j = match[f][i] < nkey and landmark j valid,
+ *    in ascending i; the pixel is xy[f][i] of the results.  Explicit: pair k < nobs_in[f] (clamped to [0, stride]) with
+ *    j = idx[f][k] and the pixel xy[f][k].  When several rows of one frame name the same j, the LOWEST one that passes the
+ *    member test is the observation (an integer minimum per (frame, landmark): independent of the execution order).
+ *    Bank: frame f takes part iff slot_dev is NULL or slot_dev[f] == key_slot_dev[0] -- fpc_match_bank's table of a frame is
+ *    against best[f], so a frame whose best is another slot stays out.
+ * The rule.  Everything is fp64 unless said otherwise.
+ *  - Live frames: a frame is dead if R_in is all zero, if R_in or t_in holds a non-finite entry, or if the bank variant's
+ *    slot test fails.  R is used as given; it is not orthonormalised.  The state is the fp32 inputs.
+ *  - Membership, fixed for the whole call and decided in one pass: landmark j is ELIGIBLE iff it is valid and passes the PnP
+ *    inlier test of the PnP section (c > 0, division-free) against its own key pixel under the key camera (t_*) with the
+ *    identity pose.  An observation is a MEMBER iff its frame is live, its landmark is eligible, R_f X_j + t_f passes that
+ *    test against the frame's pixel under the query camera (q_*), and it is the lowest such row of (f, j).  A live frame with
+ *    fewer than min_obs members is dropped and its observations stop being members; the others are KEPT.  A landmark is
+ *    ACTIVE iff it is eligible and at least one member observation is left.  If no frame is kept the call FAILS: every R, t
+ *    and nobs is zero, the stats are zero, the mask is zero and every valid landmark is copied out with kind 2 -- a failed
+ *    call never erases a map.
+ *  - Cost: C = sum over the active landmarks of |pi_key(X_j) - k_j|^2 + sum over the members of |pi_q(R_f X_j + t_f) - p|^2,
+ *    evaluated from the fp32 state; +inf where any depth is not > 0.  rms = sqrt(C / (members + active)).  A landmark's terms
+ *    are added key first, then its frames in ascending order; the landmarks of a chunk of 64 key rows in ascending order; the
+ *    chunks in ascending order.
+ *  - Unknowns: dX (three) per active landmark; per kept frame the six of the PnP refit's left perturbation (omega, upsilon);
+ *    the key camera is the origin.  The reduced system has D = 6 x (kept frames) <= 96 unknowns, in ascending frame order.
+ *  - Per observation, with Y = R_f X + t_f and J_p as in the refine section: J_X = J_p(Y) R_f, J_c = [-J_p(Y) [Y]x, J_p(Y)]
+ *    (2 x 6), r = pi_q(Y) - p.  Per landmark: U_j = J_k^T J_k + sum_f J_X^T J_X and g_j = J_k^T r_k + sum_f J_X^T r (key
+ *    first, then the frames in ascending order) with J_k = J_p(X_j) under the key camera and r_k = pi_key(X_j) - k_j;
+ *    W_fj = J_c^T J_X (6 x 3).  Per frame: A_f = sum J_c^T J_c, g_f = sum J_c^T r.
+ *  - Damping and reduction, as in the refine section: U* = U + lambda diag U, inverted as adjugate over determinant; a
+ *    determinant that is not > 0 or not finite, at any landmark, rejects the attempt.
+ *        S = A + lambda diag A - sum_j W_j U*^-1 W_j^T,      b = g_c - sum_j W_j U*^-1 g_j
+ *    with W_j the stack of the blocks of the frames that observe j.  Order of the sums: every entry of S (A without its
+ *    damping folded in per landmark: J_c^T J_c - Y W^T on the diagonal blocks, 0 - Y W^T elsewhere, Y = W U*^-1), of diag A and
+ *    of b is accumulated over the landmarks of a chunk of 64 key rows in ascending order, and the chunks' partial sums are
+ *    added in ascending order.  There are no floating-point atomics.
+ *  - Solve: S delta = -b by Gaussian elimination with partial pivoting (the first largest pivot); a pivot not above 1e-14 of
+ *    the largest diagonal entry of S rejects the attempt.  The gauge's null direction is left to the damping.
+ *  - Step: R_f' = E(omega_f) R_f and t_f' = E t_f + upsilon_f with E as in the PnP refit; X_j' = X_j - U*^-1 (g_j + sum_f
+ *    W_fj^T delta_f), the frames in ascending order.  SCALE GAUGE: with Z0 the sum, in ascending j, of the active landmarks'
+ *    third coordinates at the START state, s = Z0 / sum_j X_j'[2] (ascending j); s not finite or not > 0 rejects the attempt;
+ *    every t_f' and X_j' is multiplied by s (the cost is invariant under that scaling; fixing the scale by one frame's |t|
+ *    instead hands that frame's scale error to the points).  The state is then rounded to fp32 and C' is evaluated from it.
+ *  - Accept, reject, stop: exactly the refine section's rule -- accepted iff C' < C, then lambda <- max(lambda / 10, 1e-10);
+ *    otherwise the state is kept and lambda <- min(10 lambda, 1e6).  The call stops after `iterations` attempts, or after an
+ *    accepted step with C - C' <= 1e-6 C.
+ *  - Result: kept frames get their state, dropped and dead frames zeros.  An active landmark that passes the key-pixel test at
+ *    the final state gets kind 1; one that fails it gets kind 0 and zeros (culled); a valid landmark that is not active gets
+ *    kind 2 and is copied unchanged; everything else, and every row at or beyond nkey, is kind 0 with zeros.  nobs[f]: the
+ *    kept frame's member observations whose landmark has kind 1 and that pass the frame's reprojection test at the final
+ *    state; obs marks them.  The outputs never cost more than the inputs: a call without an accepted attempt returns the
+ *    inputs.  The three entry points give bit-identical outputs on equal observation lists.
+ * Outputs: xyz_dev float32 [capacity][3] and kind_dev uint8 [capacity], by key row, are REQUIRED: xyz_dev is the state of the
+ * iteration.  R_dev float32 [n][9] and t_dev float32 [n][3] may alias the inputs.  nobs_dev int32 [n].  obs_dev uint8
+ * [n][capacity] by query row, or [n][stride] by pair for the explicit variant (may be NULL).  stats_dev float32 [4] (may be
+ * NULL): rms before, rms after, attempts made, attempts accepted.  Every row of every output is written.
+ * fpc_window_reserve is the only call here that allocates or synchronises: the observation table, the partial sums and the
+ * pose state, in an allocation of its own, with guard zones under FPC_PLAN_GUARD_ZONES, freed by fpc_destroy; a second
+ * reserve is FPC_E_INVALID.  It carves nothing: the plan hash, the packed size and fpc_bank_get().bytes stay what they are.
+ * Execution: asynchronous on the ctx stream, no host synchronisation, no device-to-host copy; every count and slot is read
+ * on the device; a fixed sequence of launches per attempt, `iterations` times, which a device flag turns into no-ops once the
+ * call has stopped (no cooperative launch, no workgroup waits on another).  Repeated calls give bit-identical outputs.  It
+ * works on a FPC_BANK_BF16 bank: it reads xy, counts and landmarks only.  fpc_detect, fpc_match_bank, fpc_pnp_bank,
+ * fpc_refine_window_bank, fpc_bank_store_landmarks needs no host call in between.
+ *  - Not here: robust kernels, refining the intrinsics, larger windows (more than 16 frames), several key frames' landmarks
+ *    in one problem.
+ * FPC_E_INVALID (nothing is written): no fpc_window_reserve; what the refine twins refuse for the arguments they share (n,
+ * stride, a NULL observation array, match_dev, no bank); n > FPC_WINDOW_MAX_FRAMES; a NULL key_xy_dev, key_xyz_dev, nkey_dev,
+ * key_slot_dev, R_in_dev, t_in_dev, params, R_dev, t_dev, nobs_dev, xyz_dev or kind_dev; fx or fy not > 0 or any non-finite
+ * intrinsic; reproj_threshold not > 0 (or not below 1e18); iterations outside 1 .. 16; lambda0 not > 0 or not finite;
+ * min_obs < 3. */
+#define FPC_WINDOW_MAX_FRAMES 16
+typedef struct fpc_window_params {
+  float q_fx, q_fy, q_cx, q_cy;   /* camera of the n frames (pixels), fx, fy > 0                                          */
+  float t_fx, t_fy, t_cx, t_cy;   /* camera of the key frame                                                              */
+  float reproj_threshold;         /* px, > 0, below 1e18: membership and the final tests                                  */
+  int   iterations;               /* 1 .. 16 attempts                                                                     */
+  float lambda0;                  /* > 0, finite: the first damping                                                       */
+  int   min_obs;                  /* >= 3: fewer member observations drop a frame                                         */
+} fpc_window_params;
+/* fx = fy = 500, centre (320, 240) on both sides, reproj_threshold 3.0, iterations 8, lambda0 1e-3, min_obs 6 */
+int fpc_default_window_params(fpc_window_params* params);
+int fpc_window_reserve(fpc_ctx* ctx, size_t* bytes);
+int fpc_refine_window(fpc_ctx* ctx, int n, const float* xy_dev, const int32_t* idx_dev, const int32_t* nobs_in_dev, int stride,
+                      const float* key_xy_dev, const float* key_xyz_dev, const uint8_t* key_valid_dev, const int32_t* nkey_dev,
+                      const float* R_in_dev, const float* t_in_dev, const fpc_window_params* params, float* R_dev,
+                      float* t_dev, int32_t* nobs_dev, float* xyz_dev, uint8_t* kind_dev, uint8_t* obs_dev, float* stats_dev);
+int fpc_refine_window_frames(fpc_ctx* ctx, int n, const int32_t* key_xy_dev, const int32_t* nkey_dev, const float* key_xyz_dev,
+                             const uint8_t* key_valid_dev, const int32_t* match_dev, const float* R_in_dev,
+                             const float* t_in_dev, const fpc_window_params* params, float* R_dev, float* t_dev,
+                             int32_t* nobs_dev, float* xyz_dev, uint8_t* kind_dev, uint8_t* obs_dev, float* stats_dev);
+int fpc_refine_window_bank(fpc_ctx* ctx, int n, const int32_t* key_slot_dev, const int32_t* slot_dev, const int32_t* match_dev,
+                           const float* R_in_dev, const float* t_in_dev, const fpc_window_params* params, float* R_dev,
+                           float* t_dev, int32_t* nobs_dev, float* xyz_dev, uint8_t* kind_dev, uint8_t* obs_dev,
+                           float* stats_dev);
 
 /* --- Sim(3) alignment: RANSAC similarity between two frames' landmarks ----------------------------------------------------
  * Every key frame carries landmarks in its own camera frame, at the scale it inherited from the key frame it was localised
