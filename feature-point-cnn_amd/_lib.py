@@ -52,6 +52,8 @@ SYMBOLS = [
     "fpc_essential_bank_topk",
     "fpc_default_window_params", "fpc_window_reserve", "fpc_refine_window", "fpc_refine_window_frames",
     "fpc_refine_window_bank",
+    "fpc_default_graph_params", "fpc_graph_reserve", "fpc_graph_get", "fpc_graph_clear", "fpc_graph_set_nodes",
+    "fpc_graph_add_edges", "fpc_graph_optimise", "fpc_graph_apply_scale",
 ]
 
 ABI_VERSION = 4
@@ -155,6 +157,24 @@ class FpcWindowParams(ctypes.Structure):
 
 
 WINDOW_MAX_FRAMES = 16        # include/fpc.h FPC_WINDOW_MAX_FRAMES
+
+
+class FpcGraphParams(ctypes.Structure):
+    """fpc_graph_params (include/fpc.h)."""
+    _fields_ = [("iterations", ctypes.c_int), ("lambda0", ctypes.c_float), ("cg_iterations", ctypes.c_int),
+                ("cg_tol", ctypes.c_float), ("trans_unit", ctypes.c_float)]
+
+
+class FpcGraphView(ctypes.Structure):
+    """fpc_graph_view (include/fpc.h)."""
+    _fields_ = [("nodes", ctypes.c_int), ("edges", ctypes.c_int), ("node_s", ctypes.c_void_p), ("node_R", ctypes.c_void_p),
+                ("node_t", ctypes.c_void_p), ("edge_from", ctypes.c_void_p), ("edge_to", ctypes.c_void_p),
+                ("edge_s", ctypes.c_void_p), ("edge_R", ctypes.c_void_p), ("edge_t", ctypes.c_void_p),
+                ("edge_w", ctypes.c_void_p), ("count", ctypes.c_void_p), ("bytes", ctypes.c_size_t)]
+
+
+GRAPH_MAX_EDGES = 16384       # include/fpc.h FPC_GRAPH_MAX_EDGES
+GRAPH_INIT_TO = 1             # include/fpc.h FPC_GRAPH_INIT_TO
 
 
 class FpcSim3Params(ctypes.Structure):
@@ -331,6 +351,16 @@ def load():
     l.fpc_refine_window.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, wp] + [vp] * 7
     l.fpc_refine_window_frames.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, wp] + [vp] * 7
     l.fpc_refine_window_bank.argtypes = [vp, ci, vp, vp, vp, vp, vp, wp] + [vp] * 7
+    gp = ctypes.POINTER(FpcGraphParams)
+    l.fpc_default_graph_params.argtypes = [gp]
+    l.fpc_graph_reserve.argtypes = [vp, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
+    l.fpc_graph_get.argtypes = [vp, ctypes.POINTER(FpcGraphView)]
+    l.fpc_graph_clear.argtypes = [vp]
+    l.fpc_graph_set_nodes.argtypes = [vp, ci, ci, vp, vp, vp]
+    # (n, from_dev, to_dev, s_dev, R_dev, t_dev, ninliers_dev, min_inliers, flags)
+    l.fpc_graph_add_edges.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, ctypes.c_uint]
+    l.fpc_graph_optimise.argtypes = [vp, vp, gp, vp]
+    l.fpc_graph_apply_scale.argtypes = [vp]
     l.fpc_bank_topk_reserve.argtypes =[vp, ci, ctypes.POINTER(ctypes.c_size_t)]
     l.fpc_match_bank_topk.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp, vp]
     l.fpc_homography_bank_topk.argtypes = [vp, ci, ci, vp, vp, rp, vp, vp, vp, vp, vp]

@@ -53,6 +53,7 @@
 #include "landmarks.h"
 #include "refine_pose.h"
 #include "refine_window.h"
+#include "pose_graph.h"
 #include "homography.h"
 #include "weights.h"
 #include "plan_options.h"
@@ -519,7 +520,7 @@ struct Timing {
 };
 
 // One device allocation of a context: carved by a Carver, zeroed, its canary zones (offset, bytes) filled where the
-// context has them.  A context owns seven (fpc_ctx::slabs).
+// context has them.  A context owns eight (fpc_ctx::slabs).
 using GuardZones = std::vector<std::pair<size_t, size_t>>;
 struct Carver;
 struct Slab {
@@ -577,11 +578,11 @@ struct fpc_ctx {
   bool weights_loaded = false;
   bool plan_error = false;           // a layer asked for a kernel instance that does not exist (fpc_create -> FPC_E_INVALID)
 
-  // The seven device allocations a context can own: `slab` for all activations / results (build_plan), the others made
+  // The eight device allocations a context can own: `slab` for all activations / results (build_plan), the others made
   // by the call that reserves them.  bank_slab, topk_slab, pnp_topk_slab and lm_slab go with the bank; fpc_destroy frees
   // what is left.
-  Slab slab, bank_slab, topk_slab, pnp_slab, lm_slab, pnp_topk_slab, window_slab;
-  Slab* const slabs[7] = {&slab, &bank_slab, &topk_slab, &pnp_slab, &lm_slab, &pnp_topk_slab, &window_slab};
+  Slab slab, bank_slab, topk_slab, pnp_slab, lm_slab, pnp_topk_slab, window_slab, graph_slab;
+  Slab* const slabs[8] = {&slab, &bank_slab, &topk_slab, &pnp_slab, &lm_slab, &pnp_topk_slab, &window_slab, &graph_slab};
   float *stem_out, *x0, *h4, *x1, *x2, *h8, *x3, *cat, *dh, *dproj, *d0, *lg;
   float *h16, *y16a, *y16b, *lo_h, *lo0, *desc_map, *desc_in_nhwc;
   float* prob;
@@ -634,6 +635,9 @@ struct fpc_ctx {
   // observation table and pixels [16][cap], the key pixels, flags and stepped points [cap], the chunks' partial sums and
   // the pose state
   RwArgs rw{};
+  // pose graph (fpc_graph_reserve, pose_graph.h): an allocation of its own, freed by fpc_destroy -- the nodes, the edges and
+  // their counters, the stepped state, the adjacency, the linearisation and the solve's vectors
+  PgArgs pg{};
   int pts_n = 0;                     // frames of the last call that produced keypoints (fpc_detect*, fpc_get_points)
   bool pts_desc = false;             // ... and whether it sampled their descriptors
 
@@ -5127,6 +5131,125 @@ int fpc_refine_window_bank(fpc_ctx* c, int n, const int32_t* key_slot, const int
   const RwBank src{RwFrames{c->xy, c->count, match, c->cap}, key_slot, slot, c->bank.xy, c->bank.count, c->lm_xyzw, c->bank.rows,
                    c->bank.slots};
   return window_launch(c, n, src, R_in, t_in, p, R, t, nobs, xyz, kind, obs, stats, c->cap);
+}
+
+// ---- pose graph over the bank's slots (include/fpc.h; kernels in pose_graph.h) ---------------------------------------------------
+int fpc_default_graph_params(fpc_graph_params* p) {
+  if (!p) return FPC_E_INVALID;
+  p->iterations = 16;
+  p->lambda0 = 1e-3f;
+  p->cg_iterations = 256;
+  p->cg_tol = 1e-8f;
+  p->trans_unit = 1.0f;
+  return FPC_OK;
+}
+
+// The only call of the section that allocates or synchronises: an allocation of its own (nothing is carved: the plan hash,
+// the packed size and the bank's bytes are what they were).  Zeroed: every node unset, no edge.
+int fpc_graph_reserve(fpc_ctx* c, int nodes, int edges, size_t* bytes) {
+  if (!c || c->graph_slab || nodes < 1 || nodes > FPC_BANK_MAX_SLOTS || edges < 1 || edges > FPC_GRAPH_MAX_EDGES)
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const size_t N = nodes, E = edges, chunks = (E + PG_CHUNK - 1) / PG_CHUNK;
+  Carver cv(c);
+  PgArgs& g = c->pg;
+  cv.into(&g.ns, N); cv.into(&g.nR, N * 9); cv.into(&g.nt, N * 3);
+  cv.into(&g.efrom, E); cv.into(&g.eto, E); cv.into(&g.es, E); cv.into(&g.eR, E * 9); cv.into(&g.et, E * 3); cv.into(&g.ew, E);
+  cv.into(&g.count, 2); cv.into(&g.st, 1);
+  cv.into(&g.cs, N); cv.into(&g.cR, N * 9); cv.into(&g.ct, N * 3);
+  cv.into(&g.deg, N + 1); cv.into(&g.adj, 2 * E); cv.into(&g.member, N); cv.into(&g.bad, N);
+  cv.into(&g.lin, E * PG_LIN);
+  cv.into(&g.g, (size_t)7 * PG_MAX_NODES); cv.into(&g.dH, (size_t)7 * PG_MAX_NODES); cv.into(&g.delta, (size_t)7 * PG_MAX_NODES);
+  cv.into(&g.Minv, (size_t)49 * PG_MAX_NODES); cv.into(&g.cpart, chunks); cv.into(&g.eq, E * 8);
+  if (int rc = c->graph_slab.allocate(c->stream, cv)) return rc;
+  g.nodes = nodes; g.edges = edges;
+  if (bytes) *bytes = c->graph_slab.bytes;
+  return FPC_OK;
+}
+
+int fpc_graph_get(fpc_ctx* c, fpc_graph_view* v) {
+  if (!c || !v || !c->graph_slab) return FPC_E_INVALID;
+  const PgArgs& g = c->pg;
+  v->nodes = g.nodes; v->edges = g.edges;
+  v->node_s = g.ns; v->node_R = g.nR; v->node_t = g.nt;
+  v->edge_from = g.efrom; v->edge_to = g.eto; v->edge_s = g.es; v->edge_R = g.eR; v->edge_t = g.et; v->edge_w = g.ew;
+  v->count = g.count;
+  v->bytes = c->graph_slab.bytes;
+  return FPC_OK;
+}
+
+int fpc_graph_clear(fpc_ctx* c) {
+  if (!c || !c->graph_slab) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const PgArgs& g = c->pg;
+  HIPCHECK(hipMemsetAsync(g.ns, 0, sizeof(float) * g.nodes, c->stream));
+  HIPCHECK(hipMemsetAsync(g.nR, 0, sizeof(float) * g.nodes * 9, c->stream));
+  HIPCHECK(hipMemsetAsync(g.nt, 0, sizeof(float) * g.nodes * 3, c->stream));
+  HIPCHECK(hipMemsetAsync(g.count, 0, sizeof(int32_t) * 2, c->stream));
+  return FPC_OK;
+}
+
+int fpc_graph_set_nodes(fpc_ctx* c, int first, int count, const float* s, const float* R, const float* t) {
+  if (!c || !c->graph_slab || !R || !t || first < 0 || count < 1 || first > c->pg.nodes - count) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(pg_set_nodes_kernel, dim3((count + 255) / 256), dim3(256), 0, c->stream, c->pg, first, count, s, R, t);
+  return launched();
+}
+
+int fpc_graph_add_edges(fpc_ctx* c, int n, const int32_t* from, const int32_t* to, const float* s, const float* R, const float* t,
+                        const int32_t* ninliers, int min_inliers, unsigned flags) {
+  if (!c || !c->graph_slab || n < 1 || n > FPC_GRAPH_MAX_EDGES || !from || !to || !R || !t || (flags & ~FPC_GRAPH_INIT_TO))
+    return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(pg_add_edges_kernel, dim3(1), dim3(256), 0, c->stream, c->pg, n, from, to, s, R, t, ninliers, min_inliers,
+                     (flags & FPC_GRAPH_INIT_TO) ? 1 : 0);
+  return launched();
+}
+
+static bool graph_params_ok(const fpc_graph_params* p) {
+  return p && p->iterations >= 1 && p->iterations <= 16 && std::isfinite(p->lambda0) && p->lambda0 > 0.f &&
+         p->cg_iterations >= 1 && p->cg_iterations <= 1024 && std::isfinite(p->cg_tol) && p->cg_tol >= 0.f &&
+         std::isfinite(p->trans_unit) && p->trans_unit > 0.f;    // (a NaN fails its comparison)
+}
+
+// The launches: the problem (degrees, begin, adjacency), C of the start, `iterations` times the attempt's kernels (no-ops
+// once the call has stopped on the device).
+int fpc_graph_optimise(fpc_ctx* c, const int32_t* fixed, const fpc_graph_params* p, float* stats) {
+  if (!c || !c->graph_slab || !fixed || !stats || !graph_params_ok(p)) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  PgArgs a = c->pg;
+  a.iterations = p->iterations; a.cg_iterations = p->cg_iterations;
+  a.lambda0 = (double)p->lambda0; a.tol2 = (double)p->cg_tol * (double)p->cg_tol; a.iu = 1.0 / (double)p->trans_unit;
+  const int nchunks = (a.nodes + PG_CHUNK - 1) / PG_CHUNK, echunks = (a.edges + PG_CHUNK - 1) / PG_CHUNK;
+  int wg = 64;
+  while (wg < a.nodes) wg *= 2;                                  // the solve's workgroup: the power of two >= nodes
+  hipStream_t st = c->stream;
+  hipLaunchKernelGGL(pg_degree_kernel, dim3(nchunks), dim3(PG_CHUNK), 0, st, a);
+  hipLaunchKernelGGL(pg_begin_kernel, dim3(1), dim3(1024), 0, st, a, fixed, stats);
+  hipLaunchKernelGGL(pg_fill_kernel, dim3(nchunks), dim3(PG_CHUNK), 0, st, a);
+  hipLaunchKernelGGL(pg_edges_kernel<false>, dim3(echunks), dim3(PG_CHUNK), 0, st, a);
+  hipLaunchKernelGGL(pg_decide_kernel, dim3(1), dim3(1024), 0, st, a, 1, stats);
+  for (int it = 0; it < p->iterations; ++it) {
+    if (it) hipLaunchKernelGGL(pg_edges_kernel<false>, dim3(echunks), dim3(PG_CHUNK), 0, st, a);
+    hipLaunchKernelGGL(pg_blocks_kernel, dim3(nchunks), dim3(PG_CHUNK), 0, st, a);
+    hipLaunchKernelGGL(pg_solve_kernel, dim3(1), dim3(wg), 0, st, a);
+    hipLaunchKernelGGL(pg_retract_kernel, dim3(nchunks), dim3(PG_CHUNK), 0, st, a);
+    hipLaunchKernelGGL(pg_edges_kernel<true>, dim3(echunks), dim3(PG_CHUNK), 0, st, a);
+    hipLaunchKernelGGL(pg_decide_kernel, dim3(1), dim3(1024), 0, st, a, 0, stats);
+  }
+  return launched();
+}
+
+int fpc_graph_apply_scale(fpc_ctx* c) {
+  if (!c || !c->graph_slab || !c->bank_slab || !c->lm_slab || c->pg.nodes != c->bank.slots) return FPC_E_INVALID;
+  HIPCHECK(hipSetDevice(c->cfg.device));
+  const PgArgs& a = c->pg;
+  hipStream_t st = c->stream;
+  hipLaunchKernelGGL(pg_scale_edges_kernel, dim3((a.edges + 255) / 256), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(pg_scale_points_kernel, dim3((c->bank.rows + 255) / 256, c->bank.slots), dim3(256), 0, st, a, c->lm_xyzw,
+                     c->bank.count, c->bank.rows);
+  hipLaunchKernelGGL(pg_scale_nodes_kernel, dim3((a.nodes + 255) / 256), dim3(256), 0, st, a);
+  return launched();
 }
 
 int fpc_results(fpc_ctx* c, fpc_device_results* out) {

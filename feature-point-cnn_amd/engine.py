@@ -1109,6 +1109,115 @@ class Engine:
         """refine_window_bank_async, then host arrays."""
         return self._host(self.refine_window_bank_async(n, key_slot, match, R, t, slot, K_query, K_train, alias, **params))
 
+    # -- pose graph over the bank's slots (fpc_graph_reserve / _set_nodes / _clear / _get / _add_edges / _optimise / _apply_scale) --
+    def graph_reserve(self, nodes, edges):
+        """fpc_graph_reserve: Sim(3) nodes (one per bank slot) and room for `edges` edges, with the optimiser's workspace;
+        the only graph call that allocates.  Every node starts unset.  Freed with the engine.  Returns the bytes."""
+        nbytes = ctypes.c_size_t(0)
+        _lib.check(self._l.fpc_graph_reserve(self._ctx, int(nodes), int(edges), ctypes.byref(nbytes)), "fpc_graph_reserve")
+        return int(nbytes.value)
+
+    def _graph_view(self):
+        v = _lib.FpcGraphView()
+        _lib.check(self._l.fpc_graph_get(self._ctx, ctypes.byref(v)), "fpc_graph_get")
+        return v
+
+    def _graph_alias(self, ptr, dtype, *shape):
+        n = 4
+        for s in shape:
+            n *= s
+        return torch.as_tensor(_DevArray(ptr, n), device=self.torch_device).view(dtype).view(*shape)
+
+    def _dev_f32(self, name, t, *shape):
+        """`t` (device tensor or host array) as a contiguous float32 device tensor of `shape`."""
+        t = torch.as_tensor(t).to(self.torch_device, torch.float32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must be float32 %s" % (name, list(shape)))
+        return t
+
+    def graph_nodes(self):
+        """(s float32 [nodes], R float32 [nodes,3,3], t float32 [nodes,3]) aliasing the graph's node state (fpc_graph_get):
+        X_i = s_i R_i X_w + t_i; s = 0: the node is unset."""
+        v = self._graph_view()
+        return (self._graph_alias(v.node_s, torch.float32, v.nodes), self._graph_alias(v.node_R, torch.float32, v.nodes, 3, 3),
+                self._graph_alias(v.node_t, torch.float32, v.nodes, 3))
+
+    def graph_edges(self):
+        """(from int32 [edges], to int32 [edges], s [edges], R [edges,3,3], t [edges,3], w [edges], count int32 [2])
+        aliasing the graph's edge storage: count[0] edges are held, count[1] were dropped for want of room."""
+        v = self._graph_view()
+        f32, i32, e = torch.float32, torch.int32, v.edges
+        return (self._graph_alias(v.edge_from, i32, e), self._graph_alias(v.edge_to, i32, e), self._graph_alias(v.edge_s, f32, e),
+                self._graph_alias(v.edge_R, f32, e, 3, 3), self._graph_alias(v.edge_t, f32, e, 3),
+                self._graph_alias(v.edge_w, f32, e), self._graph_alias(v.count, i32, 2))
+
+    def graph_clear(self):
+        """fpc_graph_clear: every node unset, no edge, both counters zero.  Does not synchronise."""
+        self._call("fpc_graph_clear")
+
+    def graph_set_nodes(self, first, R, t, s=None):
+        """fpc_graph_set_nodes: nodes first .. first + count - 1 from R [count,3,3], t [count,3] and s [count] (None: 1) --
+        device tensors or host arrays.  Does not synchronise."""
+        R = torch.as_tensor(R).to(self.torch_device, torch.float32).contiguous()
+        if R.dim() != 3 or R.shape[1:] != (3, 3) or R.shape[0] < 1:
+            raise ValueError("R must be [count,3,3]")
+        count = int(R.shape[0])
+        t = self._dev_f32("t", t, count, 3)
+        if s is not None:
+            s = self._dev_f32("s", s, count)
+        self._call("fpc_graph_set_nodes", int(first), count, s, R, t, inputs=(s, R, t))
+
+    def graph_add_edges_async(self, frm, to, R, t, s=None, ninliers=None, min_inliers=0, init_to=False):
+        """fpc_graph_add_edges: candidate f measures X_to = s R X_from + t, exactly as pnp_bank_async (s=None) and
+        sim3_bank_async write it: frm = the train slot, to = the slot the query frame was or will be stored in (int32 [n],
+        device tensors or host arrays), R [n,3,3], t [n,3], s [n] or None, ninliers int32 [n] or None (weight 1).  Failed
+        RANSAC outputs (all-zero R), non-finite values, slots out of range and candidates under min_inliers are refused on
+        the device; init_to gives an unset `to` node its start from a set `from` node.  Does not synchronise."""
+        R = torch.as_tensor(R).to(self.torch_device, torch.float32).contiguous()
+        if R.dim() != 3 or R.shape[1:] != (3, 3) or R.shape[0] < 1:
+            raise ValueError("R must be [n,3,3]")
+        n = int(R.shape[0])
+        t = self._dev_f32("t", t, n, 3)
+        frm = self._dev_int32("from", torch.as_tensor(frm).to(self.torch_device, torch.int32), "[n]", n)
+        to = self._dev_int32("to", torch.as_tensor(to).to(self.torch_device, torch.int32), "[n]", n)
+        if s is not None:
+            s = self._dev_f32("s", s, n)
+        if ninliers is not None:
+            ninliers = self._dev_int32("ninliers", torch.as_tensor(ninliers).to(self.torch_device, torch.int32), "[n]", n)
+        self._call("fpc_graph_add_edges", n, frm, to, s, R, t, ninliers, int(min_inliers),
+                   _lib.GRAPH_INIT_TO if init_to else 0, inputs=(frm, to, s, R, t, ninliers))
+
+    def graph_add_edges(self, frm, to, R, t, s=None, ninliers=None, min_inliers=0, init_to=False):
+        """graph_add_edges_async, then (edges held, edges dropped) on the host."""
+        self.graph_add_edges_async(frm, to, R, t, s, ninliers, min_inliers, init_to)
+        self.sync()
+        held, dropped = self.graph_edges()[6].cpu().tolist()
+        return held, dropped
+
+    def graph_optimise_async(self, fixed=0, **params):
+        """fpc_graph_optimise: Levenberg-Marquardt over the set nodes that have an edge, node `fixed` (an int, or a device
+        tensor int32 [1], read on the device) held as the gauge -> stats float32 [4] on the device: cost before, cost after,
+        attempts made, attempts accepted; the nodes change in place (graph_nodes).  Parameters: iterations, lambda0,
+        cg_iterations, cg_tol, trans_unit.  Does not synchronise."""
+        p = self._params(_lib.FpcGraphParams, "fpc_default_graph_params",
+                         ("iterations", "lambda0", "cg_iterations", "cg_tol", "trans_unit"), "graph", params)
+        if not isinstance(fixed, torch.Tensor):
+            fixed = torch.tensor([int(fixed)], dtype=torch.int32, device=self.torch_device)
+        fixed = self._dev_int32("fixed", fixed, "[1]", 1)
+        stats = torch.empty((4,), dtype=torch.float32, device=self.torch_device)
+        self._call("fpc_graph_optimise", fixed, ctypes.byref(p), stats, inputs=(fixed,))
+        return stats
+
+    def graph_optimise(self, fixed=0, **params):
+        """graph_optimise_async, then the stats on the host."""
+        return self._host((self.graph_optimise_async(fixed, **params),))[0]
+
+    def graph_apply_scale(self):
+        """fpc_graph_apply_scale: every slot's landmarks, its node and the edges brought to scale 1 (a bank with landmark
+        storage and as many slots as the graph has nodes).  Does not synchronise."""
+        self._bank_info()
+        self._call("fpc_graph_apply_scale")
+
     # -- absolute pose from landmarks: RANSAC PnP (fpc_pnp_reserve / fpc_bank_*landmarks* / fpc_ransac_pnp / _frames / _bank) ----
     def pnp_reserve(self):
         """fpc_pnp_reserve: the PnP workspace (pair records, counts and best keys of max_batch problems); the only PnP call

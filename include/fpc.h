@@ -1827,6 +1827,129 @@ int fpc_sim3_bank(fpc_ctx* ctx, int n, const float* q_xyz_dev, const uint8_t* q_
                   const int32_t* match_dev, const fpc_sim3_params* params, float* s_dev, float* R_dev, float* t_dev,
                   int32_t* ninliers_dev, uint8_t* inlier_dev);
 
+/* --- pose graph over the bank's slots: spread a loop's error over the key frames ---------------------------------------------
+ * fpc_pnp_bank gives an odometry edge between a new key frame and the slot it was localised against, fpc_sim3_bank a loop
+ * edge with the drift of the scale.  The calls below keep one Sim(3) node per bank slot and those edges on the device, spread
+ * a loop's error over the nodes by Levenberg-Marquardt, and bring the bank's landmarks to one scale afterwards; nothing of it
+ * needs a host round trip.  The rule is pinned by planted ring scenes and by a float64 restatement (tests/test_pose_graph.py).
+ *  - Storage.  fpc_graph_reserve(ctx, nodes, edges, &bytes): 1 <= nodes <= FPC_BANK_MAX_SLOTS, 1 <= edges <=
+ *    FPC_GRAPH_MAX_EDGES; the only call here that allocates or synchronises; an allocation of its own, with guard zones under
+ *    FPC_PLAN_GUARD_ZONES, freed by fpc_destroy; a second reserve is FPC_E_INVALID.  It carves nothing: the plan hash, the
+ *    packed size and fpc_bank_get().bytes stay what they are.  It needs no bank.  After it every node is unset and there is no
+ *    edge.
+ *  - Nodes.  Node i is (s_i, R_i, t_i), fp32, with X_i = s_i R_i X_w + t_i: the PnP direction with a scale.  A node is SET iff
+ *    s_i > 0 (0, the cleared value, a negative or a NaN is unset: outside the problem).  fpc_graph_set_nodes writes nodes
+ *    first .. first + count - 1 from device arrays s_dev float32 [count] (NULL: every s = 1), R_dev float32 [count][9]
+ *    row-major, t_dev float32 [count][3], as given.  fpc_graph_clear unsets every node and empties the edges and both counters.
+ *    fpc_graph_get returns device pointers into the reservation: the nodes, the edges (from, to, s, R, t, w), and count_dev
+ *    int32 [2]: the edges held and the edges dropped for want of room.
+ *  - Edges.  The measurement of an edge is X_to = s R X_from + t, exactly as fpc_pnp_* (s = 1) and fpc_sim3_* write it: the
+ *    train slot is `from`, the slot the query frame was or will be stored in is `to`.  fpc_graph_add_edges looks at candidates
+ *    f = 0 .. n - 1 (1 <= n <= FPC_GRAPH_MAX_EDGES): from_dev, to_dev int32 [n], s_dev float32 [n] or NULL (s = 1), R_dev
+ *    float32 [n][9], t_dev float32 [n][3], ninliers_dev int32 [n] or NULL.  Candidate f is TAKEN iff from and to lie in
+ *    [0, nodes) and differ, every value of s, R, t is finite, s > 0, R is not all zero (nine zeros are the failure output of
+ *    the RANSAC calls), and ninliers_dev is NULL or ninliers[f] >= min_inliers.  Its weight w is 1 without ninliers_dev,
+ *    otherwise (float)ninliers[f].  Taken candidates are appended in ascending f at count + rank (the rank is a ballot /
+ *    popcount prefix: independent of the execution order); those that would land at or beyond the capacity are dropped and
+ *    counted in count_dev[1].  With FPC_GRAPH_INIT_TO one lane then walks the edges THIS call appended, in ascending order:
+ *    where `from` is set and `to` is not, node[to] = M o node[from] = (s s_a, R R_a, s R t_a + t), formed in fp64 and rounded
+ *    to fp32 (skipped if a value is not finite in fp32 or the scale is not > 0) -- a chain of odometry edges in one batch
+ *    gets its starting values without a host call.
+ * The optimiser, fpc_graph_optimise(ctx, fixed_dev, params, stats_dev).  Everything is fp64 unless said otherwise; no
+ * floating-point atomics; no contraction of a product and a sum.
+ *  - Problem.  The ACTIVE edges are those held whose two ends are both set.  The unknowns are the set nodes with at least one
+ *    active edge, except the gauge fixed_dev[0] (read on the device), which stays as it is.  A gauge outside [0, nodes) or
+ *    unset makes the call FAIL: no node is written and the stats are zero.  Set nodes without an active edge, and unset
+ *    nodes, never change.
+ *  - Residual of edge (a, b, M = (s, R, t)) from the fp32 state: Q = R_a R_b^T, k = s_a / s_b, u = t_a - k Q t_b,
+ *        E = M o S_a o S_b^-1 = (s_E, R_E, t_E) = (s k, R Q, s R u + t),
+ *        e = (log R_E, t_E iu, ln s_E),  iu = 1 / trans_unit,
+ *    with log R_E = (theta / |v|) v for v = vee(R_E - R_E^T) / 2 and theta = atan2(|v|, (tr R_E - 1) / 2) (v itself where
+ *    |v| < 1e-12; the residual rotation is assumed away from pi).  trans_unit > 0 puts the translation in the map's units.
+ *    Cost C = sum_e w_e |e|^2 (the seven squares added in order onto 0, then times w): the edges of a chunk of 64 edge
+ *    indices in ascending order (an edge that is not active is a +0 term), the chunks in ascending order.
+ *  - Perturbation: the PnP refit's left perturbation with a scale, S <- D(delta) S with delta = (omega, upsilon, sigma) and
+ *    D = (e^sigma, E(omega), upsilon): R' = E(omega) R, t' = e^sigma E(omega) t + upsilon, s' = e^sigma s, E as in the PnP
+ *    refit.
+ *  - Jacobians, first order, the SO(3) log's Jacobian taken as the identity.  With d = t - t_E ([t]x - [t_E]x = [d]x):
+ *        J_a = [ R          0        0    ]        J_b = [ -R_E    0            0 ]
+ *              [ [d]x R iu  s R iu  -d iu ]              [  0     -s_E R_E iu   0 ]
+ *              [ 0          0        1    ]              [  0      0           -1 ]
+ *  - Normal equations.  Node i's gradient g_i = sum w J^T e and block H_ii = sum w J^T J run over its active edges in
+ *    ascending edge index (J is J_a where i is the edge's `from`, J_b where it is its `to`).  The system is
+ *    (H + lambda diag H) delta = -g with H = sum_e w [J_a J_b]^T [J_a J_b] over the unknowns (the gauge's columns left out).
+ *  - Linear solve: block-Jacobi preconditioned conjugate gradients.  M_i = (H_ii + lambda diag H_ii)^-1 by Gauss-Jordan on
+ *    the 7 x 14 tableau with partial pivoting (the first largest pivot, the pivot row scaled by the pivot's reciprocal); a
+ *    pivot not above 1e-14 of the largest diagonal entry of the damped block, at any node, rejects the attempt.  x = 0,
+ *    r = -g, z = M r, p = z, rz = rz0 = r.z; rz0 not > 0 ends the solve with x = 0.  Then at most cg_iterations times:
+ *    q = A p; pq = p.q; pq not > 0 ends the solve; alpha = rz / pq; x += alpha p; r -= alpha q; z = M r; rz' = r.z;
+ *    rz' <= cg_tol^2 rz0 ends the solve; p = z + (rz' / rz) p; rz = rz'.  (A p)_i is the sum over node i's active edges, in
+ *    ascending edge index, of J_i^T (w (J_a p_a + J_b p_b)), plus lambda diag(H_ii) p_i.  A dot product: node i's seven products
+ *    added in order onto 0, then the FIXED TREE over node indices 0 .. 1023 (a node that is no unknown is a +0 leaf): for
+ *    h = 512, 256, .. 1: leaf[i] += leaf[i + h] for every i < h; the result is leaf[0].  A truncated solve is still a valid
+ *    attempt: the accept rule guards the cost.
+ *  - Step: S_i <- D(x_i) S_i for every unknown, rounded to fp32 (a value that is not finite in fp32 or a scale that is not > 0
+ *    rejects the attempt); C' is evaluated from the rounded state.
+ *  - Accept, reject, stop: the refine and window sections' rule -- accepted iff C' < C, then lambda <- max(lambda / 10, 1e-10);
+ *    otherwise the state is kept and lambda <- min(10 lambda, 1e6).  The call stops after `iterations` attempts, or after an
+ *    accepted step with C - C' <= 1e-6 C.
+ *  - Result: the nodes in place and stats_dev float32 [4]: cost before, cost after, attempts made, attempts accepted.  A call
+ *    never raises the cost; a call without an accepted attempt leaves the nodes bit for bit.
+ * fpc_graph_apply_scale needs a bank with a landmark reservation and nodes == the bank's slots.  With sigma_i = s_i for a set
+ * node and 1 otherwise: every held edge becomes (s sigma_a / sigma_b, R, t / sigma_b); every valid landmark row (row < the
+ * slot's count, w != 0) of a set node with s_i != 1 is multiplied by 1 / s_i (the reciprocal in fp64, products rounded to fp32,
+ * w kept); that node becomes (1, R_i, t_i (1 / s_i)).  Every world point R_i^T (X - t_i) / s_i of a slot is unchanged, and so
+ * are the e_omega and e_sigma of every edge; t_E becomes t_E / sigma_b, so an edge's translation residual is rescaled with its
+ * `to` node (zero stays zero; trans_unit is in the new units).  After it PnP against neighbouring slots returns poses at one
+ * scale.  It works on both bank formats: it reads counts and reads and writes landmarks only.
+ * Execution: fpc_graph_set_nodes, _clear, _add_edges, _optimise and _apply_scale are asynchronous on the ctx stream: no host
+ * synchronisation, no device-to-host copy, no allocation; every count is read on the device; the optimiser is a fixed
+ * sequence of launches per attempt, `iterations` times, which a device flag turns into no-ops once the call has stopped (no
+ * cooperative launch, no workgroup waits on another); the conjugate-gradient solve of an attempt runs inside one workgroup,
+ * a node per thread.  Repeated sequences give bit-identical results.  fpc_sim3_bank, fpc_graph_add_edges, fpc_graph_optimise,
+ * fpc_graph_apply_scale needs no host call in between.
+ *  - Not here: robust kernels on edges, 7 x 7 information matrices, more than FPC_BANK_MAX_SLOTS nodes, merging duplicate
+ *    landmarks across slots, global bundle adjustment.
+ * FPC_E_INVALID (nothing is written): every call but fpc_graph_reserve without a reservation; fpc_graph_reserve: nodes or
+ * edges outside their ranges, a second reserve; fpc_graph_get: a NULL view; fpc_graph_set_nodes: a NULL R_dev or t_dev, first
+ * < 0, count < 1, first + count > nodes; fpc_graph_add_edges: n outside 1 .. FPC_GRAPH_MAX_EDGES, a NULL from_dev, to_dev,
+ * R_dev or t_dev, a flag other than FPC_GRAPH_INIT_TO; fpc_graph_optimise: a NULL fixed_dev, params or stats_dev, iterations
+ * outside 1 .. 16, lambda0 not > 0 or not finite, cg_iterations outside 1 .. 1024, cg_tol < 0 or not finite, trans_unit not
+ * > 0 or not finite; fpc_graph_apply_scale: no bank, no landmark reservation, nodes != slots. */
+#define FPC_GRAPH_MAX_EDGES 16384
+#define FPC_GRAPH_INIT_TO 1u
+typedef struct fpc_graph_params {
+  int   iterations;               /* 1 .. 16 attempts                                                                     */
+  float lambda0;                  /* > 0, finite: the first damping                                                       */
+  int   cg_iterations;            /* 1 .. 1024 conjugate-gradient iterations per attempt                                  */
+  float cg_tol;                   /* >= 0, finite: the solve ends when r.z <= cg_tol^2 of its first value                 */
+  float trans_unit;               /* > 0, finite: the length that weighs like one radian and one e-fold of scale         */
+} fpc_graph_params;
+typedef struct fpc_graph_view {
+  int nodes, edges;               /* the capacities of the reservation                                                    */
+  float* node_s;                  /* [nodes]                                                                              */
+  float* node_R;                  /* [nodes][9]                                                                           */
+  float* node_t;                  /* [nodes][3]                                                                           */
+  int32_t* edge_from;             /* [edges]                                                                              */
+  int32_t* edge_to;               /* [edges]                                                                              */
+  float* edge_s;                  /* [edges]                                                                              */
+  float* edge_R;                  /* [edges][9]                                                                           */
+  float* edge_t;                  /* [edges][3]                                                                           */
+  float* edge_w;                  /* [edges]                                                                              */
+  int32_t* count;                 /* [2]: edges held, edges dropped                                                       */
+  size_t bytes;                   /* allocated                                                                            */
+} fpc_graph_view;
+/* iterations 16, lambda0 1e-3, cg_iterations 256, cg_tol 1e-8, trans_unit 1 */
+int fpc_default_graph_params(fpc_graph_params* params);
+int fpc_graph_reserve(fpc_ctx* ctx, int nodes, int edges, size_t* bytes);
+int fpc_graph_get(fpc_ctx* ctx, fpc_graph_view* view);
+int fpc_graph_clear(fpc_ctx* ctx);
+int fpc_graph_set_nodes(fpc_ctx* ctx, int first, int count, const float* s_dev, const float* R_dev, const float* t_dev);
+int fpc_graph_add_edges(fpc_ctx* ctx, int n, const int32_t* from_dev, const int32_t* to_dev, const float* s_dev,
+                        const float* R_dev, const float* t_dev, const int32_t* ninliers_dev, int min_inliers, unsigned flags);
+int fpc_graph_optimise(fpc_ctx* ctx, const int32_t* fixed_dev, const fpc_graph_params* params, float* stats_dev);
+int fpc_graph_apply_scale(fpc_ctx* ctx);
+
 int fpc_results(fpc_ctx* ctx, fpc_device_results* out);
 /* Synchronises, then copies the per-frame counts to the host.  FPC_E_NONFINITE (counts delivered all the same) when a
  * frame of the call held a NaN / Inf pixel: "Numerical contract" at the top of this header. */
